@@ -1,19 +1,24 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: MB/s of log bytes parsed per MI355X (512 B Apache-combined lines, 10-field
-regex, bit-exact capture offsets), with the HBM-roofline fraction and the host-CPU baseline next to it.
+regex, bit-exact capture offsets), with the HBM-roofline fraction (and, with --full, the host-CPU baseline) next to it.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full      # + cpu_baseline (with the parity gate), end_to_end, configs
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 Default (BASELINE configs[1]).  One "step" = one pass of the hot path (lc_regex_match_device: the replacement for the
 per-event BoostRegexMatch loop, core/plugin/processor/ProcessorParseRegexNative.cpp:115-124,194) over one batch of
-1 Mi synthetic lines already resident in HBM.  `value` is that kernel-side rate; the same line also carries
-`end_to_end` (the north-star path with the host in it: pinned staging + H2D || kernel || D2H through
+1 Mi synthetic lines already resident in HBM.  `value` is that kernel-side rate.  A plain run sets up, warms up, times the K
+steps and prints the line; with --full the same line also carries `cpu_baseline` (the oracle's parity gate on the timed batch and
+the host-CPU rates), `end_to_end` (the north-star path with the host in it: pinned staging + H2D || kernel || D2H through
 lc_regex_match_host, and the in-agent shape -- lc_processor_process on 1000-line event groups from 1 and N runner
-threads), measured in the same run, never inside the timed region.  Multi-GPU is an embarrassingly parallel line shard:
-each rank owns its own batch, there is no data-path collective; the per-GPU counters are all-gathered (RCCL) so that
-rank 0 can print the per-GPU table next to the aggregate.  Rank 0 prints ONE JSON line.
+threads) and `configs` (bounded runs of the other BASELINE configs), measured in the same run, never inside the timed region.
+--dump-outputs DIR writes what the last timed step computed (every line's status, a fixed sample of the capture table) as .npy.
+Multi-GPU is an embarrassingly parallel line shard: each rank owns its own batch, there is no data-path collective; the
+per-GPU counters are all-gathered (RCCL) so that rank 0 can print the per-GPU table next to the aggregate.  Rank 0 prints
+ONE JSON line.
 
     python bench.py --config 4     # BASELINE configs[3]: 64 pipelines, each its own regex, ~512 KB groups round-robin
     python bench.py --config 5     # BASELINE configs[4]: mixed nginx/JSON corpus fed FROM HOST in 64 MiB slabs per rank
@@ -552,6 +557,28 @@ def cpu_baseline(pattern, keys, data, off, length, sample, d_caps, d_status):
     return cpu, exp_caps
 
 
+# ------------------------------------------------------------------------------------------------- --dump-outputs
+DUMP_ROWS = 1 << 17  # capture-table rows written: 131 072 x 2G float64 = 21 MB for regex A (all 1 Mi rows would be 160 MB)
+DUMP_STATUS_ALL = 1 << 23  # status of every line up to 8 Mi lines (float32, 32 MB); above that, of the sampled lines only
+
+
+def dump_outputs(out_dir, d_caps, d_status, rank=0):
+    """What the caller of lc_regex_match_device receives from the last timed step, as .npy files in out_dir (at most ~56 MB):
+    status.npy (float32, 1 = matched, one per line), caps_sample.npy (float64 [rows, 2G]: the capture offsets of a fixed seeded
+    sample of lines, -1 = group did not participate) and sample_lines.npy (float64: the sampled line numbers, ascending).
+    Rank r > 0 adds _rank<r> to each name."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n = d_status.shape[0]
+    rows = np.arange(n) if n <= DUMP_ROWS else np.sort(np.random.default_rng(20261016).choice(n, DUMP_ROWS, replace=False))
+    d_rows = torch.from_numpy(rows).to(d_caps.device)
+    status = d_status if n <= DUMP_STATUS_ALL else d_status.index_select(0, d_rows)
+    sfx = "" if rank == 0 else "_rank%d" % rank
+    np.save(os.path.join(out_dir, "status%s.npy" % sfx), status.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "caps_sample%s.npy" % sfx), d_caps.index_select(0, d_rows).cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "sample_lines%s.npy" % sfx), rows.astype(np.float64))
+
+
 # ------------------------------------------------------------------------------------------------- configs[1]: the headline
 def run_headline(args):
     import ctypes
@@ -600,15 +627,15 @@ def run_headline(args):
     torch.cuda.synchronize()
     kernels = binding.launched_kernels()
 
-    # ---- parity gate on this rank's batch (the timed batch): GPU vs oracle on the CPU-baseline sample
+    # ---- (--full) parity gate on this rank's batch (the timed batch): GPU vs oracle on the CPU-baseline sample
     cpu, exp_caps = None, None
     sample = min(args.cpu_sample_lines, n)
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         cpu, exp_caps = cpu_baseline(pattern, keys, data, off, length, sample, d_caps, d_status)
 
-    # ---- the host-inclusive figures (rank 0 only, outside the timed region, bounded: a few seconds)
+    # ---- (--full) the host-inclusive figures (rank 0 only, outside the timed region, bounded: a few seconds)
     e2e = None
-    if rank == 0 and not args.no_e2e:
+    if rank == 0 and args.full and not args.no_e2e:
         ncores = os.cpu_count() or 1
         tc = [1] + ([min(16, ncores)] if ncores > 1 else []) + ([min(32, ncores)] if ncores > 16 else [])
         e2e = end_to_end(rx, pattern, keys, data, off, length, exp_caps, dev, tc)
@@ -643,10 +670,12 @@ def run_headline(args):
     kernel_ms = ev_start.elapsed_time(ev_end) / args.steps
 
     matched = int(d_status.sum().item())
-    # ---- the other BASELINE configs, bounded, AFTER the timed region (never inside it): so that the driver's one line is
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, d_caps, d_status, rank)
+    # ---- (--full) the other BASELINE configs, bounded, AFTER the timed region (never inside it): so that the driver's one line is
     # evidence for all five configs.  configs[4] is host-fed and collective (barriers + the counters' all-gather): every rank runs it.
     extra = {}
-    if not args.no_configs:
+    if args.full and not args.no_configs:
         import argparse as _ap
         sub = _ap.Namespace(**vars(args))
         # (4 GiB per rank = 64 slabs: a bounded run whose fill and drain are 10 % of it, not 40 %; ~0.1 s)
@@ -1121,6 +1150,13 @@ def main():
     ap.add_argument("--streams", type=int, default=4)
     ap.add_argument("--corpus-gb", type=float, default=10.0)
     ap.add_argument("--slab-mib", type=int, default=64)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: cpu_baseline (parity gate against the oracle "
+                         "and the host-CPU rates), end_to_end and the bounded runs of the other configs (each still subject to its --no-* "
+                         "flag); without it those fields of the line are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy: status of every line (float32), "
+                         "capture offsets of a fixed seeded sample of lines (float64)")
     ap.add_argument("--launch-check", action="store_true",
                     help="(tests) no device work: the ranks rendezvous over gloo, all-gather a fixed counter row and rank 0 prints the "
                          "line's launch fields -- what tests/test_bench_launch.py runs on a box without a GPU")

@@ -452,9 +452,10 @@ def test_generated_patterns_on_the_backtracking_engine_against_the_oracle(host_v
 
 
 @pytest.mark.gpu
-def test_generated_patterns_through_the_kernel_against_the_oracle(torch_dev):
+def test_generated_patterns_through_the_kernel_against_the_oracle(torch_dev, host_vm):
     """The generator of tools/fuzz_bt.py on the device: 250 patterns, full match and search, 48 subjects each (up to 40 bytes, so that the
-    eight-byte loads of the counted repeats and every alignment of a value's first byte are exercised), bt_match_kernel against the oracle."""
+    eight-byte loads of the counted repeats and every alignment of a value's first byte are exercised), bt_match_kernel against the oracle.
+    (host_vm builds tests/_build/libbt_host_check.so, which tools/fuzz_bt.py loads when it is imported.)"""
     import importlib.util
     from test_gpu_parity import pack, run_device
     spec = importlib.util.spec_from_file_location("fuzz_bt", os.path.join(ROOT, "tools", "fuzz_bt.py"))

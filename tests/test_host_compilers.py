@@ -296,14 +296,12 @@ def test_fixed_length_lookarounds_on_both_engines_tables(golden_dir):
     assert B.GpuRegex(rb"(?>a+|ab)(?=bc)\w+").info()["engine"] == B.LC_ENGINE_BT
 
 
-def test_every_pattern_of_the_example_library_compiles():
-    """example_config/processor_grok_patterns/*: every pattern of every file, as the one Match entry of a Grok processor (expansion,
-    parse, follow NFA -- AnchoredFirst off: no tagged-DFA construction, that is a matter of speed).  Through round 4 MONGO_QUERY and
-    MONGO_SLOWQUERY (mongodb:2-3) failed Init on their multi-byte look-arounds.  The reference tree is not on the GPU box: skipped there."""
+def test_every_pattern_of_the_example_library_compiles(golden_dir):
+    """example_config/processor_grok_patterns/* (stored as data in tests/golden/processor_grok_patterns): every pattern of every file,
+    as the one Match entry of a Grok processor (expansion, parse, follow NFA -- AnchoredFirst off: no tagged-DFA construction, that is a
+    matter of speed).  Through round 4 MONGO_QUERY and MONGO_SLOWQUERY (mongodb:2-3) failed Init on their multi-byte look-arounds."""
     from loongcollector_amd.grok import Grok
-    lib = "/root/reference/example_config/processor_grok_patterns"
-    if not os.path.isdir(lib):
-        pytest.skip("needs the reference tree (/root/reference)")
+    lib = os.path.join(golden_dir, "processor_grok_patterns")
     names = []
     for fn in sorted(os.listdir(lib)):
         with open(os.path.join(lib, fn), encoding="utf-8") as f:

@@ -2,14 +2,15 @@
 """Differential fuzz of the NFA tables (packNfaBlob: steady masks, doomed-spawn rows, suffix flag) and of the atomic-elision pass: fresh
 random patterns, plain and atomic / possessive, full match and search, walked by tests/helpers NfaInterp / AtomicNfaInterp (the kernels' walk
 restated) against the oracle.    python tools/fuzz_nfa.py FIRST_SEED LAST_SEED     (250 seeds: ~60 000 pattern x modes, ~1 min)"""
-import sys, random, importlib.util, time
-sys.path.insert(0, "/root/repo")
+import os, sys, random, importlib.util, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 from loongcollector_amd import binding as B
 from oracle.oracle import OracleRegex
 from tests.helpers.table_interp import NfaInterp
 from tests.helpers.nfa_atomic_interp import AtomicNfaInterp
-spec = importlib.util.spec_from_file_location("g", "/root/repo/tests/golden/gen_regex_golden.py"); gen = importlib.util.module_from_spec(spec); spec.loader.exec_module(gen)
-aspec = importlib.util.spec_from_file_location("a", "/root/repo/tests/golden/gen_atomic_golden.py"); agen = importlib.util.module_from_spec(aspec); aspec.loader.exec_module(agen)
+spec = importlib.util.spec_from_file_location("g", os.path.join(ROOT, "tests", "golden", "gen_regex_golden.py")); gen = importlib.util.module_from_spec(spec); spec.loader.exec_module(gen)
+aspec = importlib.util.spec_from_file_location("a", os.path.join(ROOT, "tests", "golden", "gen_atomic_golden.py")); agen = importlib.util.module_from_spec(aspec); aspec.loader.exec_module(agen)
 t0=time.time(); checked=pats=quasi=elided=0
 for seed in range(int(sys.argv[1]), int(sys.argv[2])):
     rng = random.Random(9000 + seed); g = gen.Gen(rng)

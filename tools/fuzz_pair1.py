@@ -7,12 +7,13 @@ import os
 os.environ["LC_TDFA_PAIR"] = "2"
 os.environ["LC_TDFA_COMPACT"] = "512"
 import sys, random, importlib.util, time
-sys.path.insert(0, "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 import numpy as np
 from loongcollector_amd import binding as B
 from oracle.oracle import OracleRegex
 from tests.helpers.table_interp import TdfaPair1Interp
-spec = importlib.util.spec_from_file_location("g", "/root/repo/tests/golden/gen_regex_golden.py"); gen = importlib.util.module_from_spec(spec); spec.loader.exec_module(gen)
+spec = importlib.util.spec_from_file_location("g", os.path.join(ROOT, "tests", "golden", "gen_regex_golden.py")); gen = importlib.util.module_from_spec(spec); spec.loader.exec_module(gen)
 t0 = time.time(); checked = pats = derived = doubles = 0
 for seed in range(int(sys.argv[1]), int(sys.argv[2])):
     rng = random.Random(9000 + seed); g = gen.Gen(rng)

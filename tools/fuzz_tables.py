@@ -4,12 +4,13 @@ look-around ones) in full-match, search and anchored-search mode; the logical ta
 global-memory kernel), i.e. after dead-store elimination, state minimisation and the pack-time fold, against the oracle.
     python tools/fuzz_tables.py FIRST_SEED LAST_SEED      (40 seeds: 14 000 (pattern, mode) pairs, 300 000 checks, ~5 min)"""
 import sys, random, importlib.util, os, time
-sys.path.insert(0, "/root/repo")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
 from loongcollector_amd import binding as B
 from oracle.oracle import OracleRegex
 from tests.helpers.table_interp import NfaInterp, TdfaInterp, packed_tdfa_interp
-spec = importlib.util.spec_from_file_location("g", "/root/repo/tests/golden/gen_regex_golden.py"); gen = importlib.util.module_from_spec(spec); spec.loader.exec_module(gen)
-aspec = importlib.util.spec_from_file_location("a", "/root/repo/tests/golden/gen_atomic_golden.py"); agen = importlib.util.module_from_spec(aspec); aspec.loader.exec_module(agen)
+spec = importlib.util.spec_from_file_location("g", os.path.join(ROOT, "tests", "golden", "gen_regex_golden.py")); gen = importlib.util.module_from_spec(spec); spec.loader.exec_module(gen)
+aspec = importlib.util.spec_from_file_location("a", os.path.join(ROOT, "tests", "golden", "gen_atomic_golden.py")); agen = importlib.util.module_from_spec(aspec); aspec.loader.exec_module(agen)
 t0 = time.time(); checked = pats = 0
 for seed in range(int(sys.argv[1]), int(sys.argv[2])):
     rng = random.Random(5000 + seed); g = gen.Gen(rng)

@@ -18,7 +18,7 @@ suite)
   timeout 150 python tools/grok_bench.py --lines 1000,16384 --steps 10 --warmup 3 > $O/grok.json 2> $O/grok.err
   cut -c1-330 $O/grok.json; tail -3 $O/grok.err | cut -c1-300 ;;
 agent)
-  timeout 150 python bench.py --lines 262144 --steps 3 --warmup 1 --no-cpu-baseline --no-configs > $O/bench_e2e.json 2> $O/bench_e2e.err
+  timeout 150 python bench.py --full --lines 262144 --steps 3 --warmup 1 --no-cpu-baseline --no-configs > $O/bench_e2e.json 2> $O/bench_e2e.err
   echo "bench rc $?"; tail -c 3000 $O/bench_e2e.json | tr ',' '\n' | grep -A4 '"in_agent' | head -24; tail -3 $O/bench_e2e.err | cut -c1-300
   timeout 60 python -m pytest tests/test_gpu_processor.py tests/test_gpu_pipeline.py -m gpu -q -x 2>&1 | tail -3 | cut -c1-200 | tee $O/pytest_processors.txt
   inagent ;;

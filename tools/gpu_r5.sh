@@ -21,7 +21,7 @@ multi) multi ;;
 second)
   timeout 500 python -m pytest tests -m gpu -q -x 2>&1 | tail -6 | cut -c1-300 | tee $O/pytest_gpu.txt
   multi
-  timeout 400 python bench.py --lines 262144 --steps 3 --warmup 1 --no-cpu-baseline --no-configs > $O/bench_e2e.json 2> $O/bench_e2e.err
+  timeout 400 python bench.py --full --lines 262144 --steps 3 --warmup 1 --no-cpu-baseline --no-configs > $O/bench_e2e.json 2> $O/bench_e2e.err
   echo "bench rc $?"; tail -c 6000 $O/bench_e2e.json | tr ',' '\n' | grep -A5 '"in_agent' | head -60; tail -3 $O/bench_e2e.err | cut -c1-300 ;;
 grok)
   timeout 120 python -m pytest tests/test_gpu_grok.py -m gpu -q -x 2>&1 | tail -3 | cut -c1-200 | tee $O/pytest_grok.txt
