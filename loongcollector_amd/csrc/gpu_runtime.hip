@@ -1,11 +1,11 @@
 // gpu_runtime.hip -- gfx950 kernels and the device half of the C ABI (include/lc_regex_gpu.h).
 //
 // Kernels (hand-written HIP for CDNA4, wave64):
-//   tdfa_match_kernel : one log line per lane.  The pattern's tagged-DFA tables are staged once per workgroup
-//                       into LDS; every lane walks its own line with aligned 16-byte global loads, one
-//                       class lookup + one transition lookup (both LDS) per byte, and the few capture-offset
-//                       register moves attached to a transition.  Registers live in LDS as [reg][lane] so that
-//                       data-dependent register numbers never spill to scratch and never bank-conflict.
+//   tdfa_stream_kernel : one log line per lane.  The pattern's tagged-DFA tables are staged once per workgroup
+//                        into LDS; every lane walks its own line with aligned 16-byte global loads, one
+//                        class lookup + one transition lookup (both LDS) per byte, and the few capture-offset
+//                        register moves attached to a transition.  Registers live in LDS as [reg][lane] so that
+//                        data-dependent register numbers never spill to scratch and never bank-conflict.
 //   nfa_match_kernel  : one log line per wavefront, one lane per live NFA thread (priority order == lane order);
 //                       follow lists in LDS, ballot/mbcnt compaction, ds_bpermute capture transfer.
 // Byte-scan work: no MFMA.  The bound that matters is LDS lookup throughput / latency, then HBM.
@@ -301,72 +301,65 @@ struct DoneRequest {
 static thread_local DoneRequest tlsDone;
 static thread_local bool tlsJobTableInPlace = false;  // lcSetJobTableInPlace (zero-copy trips of the processors, below)
 
+// hipFuncSetAttribute for a launch that asks for more than the default 64 KiB of LDS: once per (kernel, device) and size
+static int lcAllowLds(const void* kern, size_t lds) {
+    if (lds <= 64 * 1024) return LC_OK;
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    static thread_local std::map<std::pair<const void*, int>, size_t> set;  // the attribute belongs to (function, device)
+    size_t& have = set[{kern, dev}];
+    if (lds > have) {
+        HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
+        have = lds;
+    }
+    return LC_OK;
+}
+
 // The kernel behind a (workgroup size, table format) pair: the interleaved-issue kernel (tdfa_stream_kernel.hpp) for the
-// class-indexed tables with or without the byte-pair extension, the phase-separated one (tdfa_kernel.hpp) for byte-indexed
-// rows -- and for everything when LC_TDFA_STREAM=0 is set (A/B measurements).
-template <int BLOCK, bool PAIR, bool COMPACT = false, bool BYTEROWS = false>
+// class-indexed tables with or without the byte-pair extension.
+template <int BLOCK, bool PAIR, bool COMPACT = false>
 static int launchTdfaBlock(const void* dBlob, uint32_t blobBytes, uint32_t regBytes, size_t lds, const uint8_t* d_data,
                            const uint32_t* d_off, const uint32_t* d_len, uint32_t sep, uint32_t minLen, uint32_t n, const uint32_t* d_n, const uint32_t* d_order, const uint32_t* d_resume, uint32_t ngroups,
                            int32_t* d_caps, uint8_t* d_status, hipStream_t stream, uint32_t* longFlag = nullptr, uint32_t seq = 0,
                            uint32_t nregsWord = 0, bool pairOne = false) {
-    static const bool streamOff = [] {
-        const char* e = getenv("LC_TDFA_STREAM");
-        return e && e[0] == '0';
-    }();
     // tables without any general register program (TD_NREGS_NO_GENERAL: the usual case once multi-stamp programs are folded,
     // regex_handle.cpp) run the instantiation that neither tracks nor replays them; LC_TDFA_NOGEN=0 keeps the checking one
     static const bool noGenOff = [] {
         const char* e = getenv("LC_TDFA_NOGEN");
         return e && e[0] == '0';
     }();
-    const bool noGen = !PAIR && !BYTEROWS && !streamOff && !noGenOff && (nregsWord & TD_NREGS_NO_GENERAL) != 0;
-    // COMPACT tiles (rows of exactly 64 bytes) are filled by LDS-DMA: no staging VGPRs (113 -> 89: 20 instead of 16 waves per CU),
-    // no ds_write_b128 (tdfa_stream_kernel.hpp, kLabDmaStage; round 3: 0.217 -> 0.208 ms on the headline batch).  LC_TDFA_DMA=0:
-    // the register-staged original (A/B measurements).
-    static const bool dmaOff = [] {
-        const char* e = getenv("LC_TDFA_DMA");
-        return e && e[0] == '0';
-    }();
-    const bool dma = COMPACT && !PAIR && !BYTEROWS && !streamOff && !dmaOff;
-    bool cmapA8 = false;
-    auto kern = tdfa_match_kernel<BLOCK, PAIR, COMPACT, BYTEROWS>;
-    if constexpr (!BYTEROWS) {
-        if (!streamOff) kern = tdfa_stream_kernel<BLOCK, COMPACT, PAIR>;
-        if constexpr (!PAIR) {
-            if (noGen) kern = tdfa_stream_kernel<BLOCK, COMPACT, false, kTdfaNoGeneralPrograms>;
-            if constexpr (COMPACT) {
-                if (dma) kern = noGen ? tdfa_stream_kernel<BLOCK, true, false, kTdfaNoGeneralPrograms | kLabDmaStage>
-                                      : tdfa_stream_kernel<BLOCK, true, false, kLabDmaStage>;
-            }
+    const bool noGen = !PAIR && !noGenOff && (nregsWord & TD_NREGS_NO_GENERAL) != 0;
+    // the mop-up launch behind a COMPACT one: an instantiation whose workgroups take the line blocks in turn (tdfa_stream_kernel.hpp
+    // kLabMopUp) -- for the workgroup size such a launch has in practice
+    constexpr bool kCanMopUp = BLOCK == 256 && !COMPACT;
+    const bool mopUp = kCanMopUp && minLen != 0;
+    constexpr int kMopUp = kCanMopUp ? kLabMopUp : 0;
+    const void* kern;
+    const char* name;
+    if constexpr (PAIR) {
+        // a ONE-STAMP pair table (LC_TDFA_PAIR=2, device_tables.h TP_FORMAT 1) is only understood by the instantiation made for it
+        constexpr int kOne = kTdfaNoGeneralPrograms | kLabPairOne | (COMPACT ? kLabDmaStage : 0);
+        if (pairOne) {
+            kern = mopUp ? reinterpret_cast<const void*>(tdfa_stream_kernel<BLOCK, COMPACT, true, kOne | kMopUp>)
+                         : reinterpret_cast<const void*>(tdfa_stream_kernel<BLOCK, COMPACT, true, kOne>);
+            name = COMPACT ? "tdfa_stream_kernel<compact,nogeneral,pair1,dma>" : "tdfa_stream_kernel<nogeneral,pair1>";
         } else {
-            // a ONE-STAMP pair table (LC_TDFA_PAIR=2, device_tables.h TP_FORMAT 1) is only understood by the instantiation made for it
-            if (pairOne) {
-                if (streamOff) {
-                    tlsError = "one-stamp pair tables need the stream kernel (LC_TDFA_STREAM=0 is set)";
-                    return LC_ERR_UNSUPPORTED;
-                }
-                kern = tdfa_stream_kernel<BLOCK, COMPACT, true, kTdfaNoGeneralPrograms | kLabPairOne | (COMPACT ? kLabDmaStage : 0)>;
-                // (round 6) ... with the first byte's class from a u8 copy of cmapA that the workgroup builds behind its tiles (272 bytes):
-                // ASCII bytes then sit on 32 different banks, where the u16 table put b and b + 64 on one.  Only where the extra LDS does
-                // not cost a resident workgroup.  MEASURED AND LEFT OFF (LC_TDFA_CMAPA8=1 switches it on): 0.1753 against 0.1719 ms per 1 Mi
-                // lines -- the conflicts of the class map are not what the chain link waits for (profiles/round6_tdfa_why_not.md section 8).
-                const char* a8Env = getenv("LC_TDFA_CMAPA8");
-                const size_t half = kLcLdsPerCu / 2;
-                if (a8Env && a8Env[0] == '1' && (lds + kTdfaCmapA8Bytes <= half || lds > half) && lds + kTdfaCmapA8Bytes <= kLcLdsPerCu) {
-                    kern = tdfa_stream_kernel<BLOCK, COMPACT, true, kTdfaNoGeneralPrograms | kLabPairOne | kLabCmapA8 | (COMPACT ? kLabDmaStage : 0)>;
-                    lds += kTdfaCmapA8Bytes;
-                    cmapA8 = true;
-                }
-            }
+            kern = mopUp ? reinterpret_cast<const void*>(tdfa_stream_kernel<BLOCK, COMPACT, true, kMopUp>)
+                         : reinterpret_cast<const void*>(tdfa_stream_kernel<BLOCK, COMPACT, true>);
+            name = COMPACT ? "tdfa_stream_kernel<compact,pair>" : "tdfa_stream_kernel<pair>";
         }
-    }
-    static thread_local size_t ldsAttrSet[kLcMaxDevices][7] = {};  // the attribute belongs to (function, device)
-    const int which = cmapA8 ? 6 : (PAIR && pairOne) ? 5 : dma ? (noGen ? 4 : 3) : noGen ? 2 : (!BYTEROWS && !streamOff) ? 1 : 0;
-    int devNow = 0;
-    if (lds > 64 * 1024) HIP_TRY(hipGetDevice(&devNow));
-    if (lds > 64 * 1024 && devNow < kLcMaxDevices && lds > ldsAttrSet[devNow][which]) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-        ldsAttrSet[devNow][which] = lds;
+    } else if constexpr (COMPACT) {
+        // COMPACT tiles (rows of exactly 64 bytes) are filled by LDS-DMA: no staging VGPRs (113 -> 89: 20 instead of 16 waves per
+        // CU), no ds_write_b128 (tdfa_stream_kernel.hpp, kLabDmaStage; round 3: 0.217 -> 0.208 ms on the headline batch)
+        kern = noGen ? reinterpret_cast<const void*>(tdfa_stream_kernel<BLOCK, true, false, kTdfaNoGeneralPrograms | kLabDmaStage>)
+                     : reinterpret_cast<const void*>(tdfa_stream_kernel<BLOCK, true, false, kLabDmaStage>);
+        name = noGen ? "tdfa_stream_kernel<compact,nogeneral,dma>" : "tdfa_stream_kernel<compact,dma>";
+    } else {
+        if (noGen) kern = mopUp ? reinterpret_cast<const void*>(tdfa_stream_kernel<BLOCK, false, false, kTdfaNoGeneralPrograms | kMopUp>)
+                                : reinterpret_cast<const void*>(tdfa_stream_kernel<BLOCK, false, false, kTdfaNoGeneralPrograms>);
+        else kern = mopUp ? reinterpret_cast<const void*>(tdfa_stream_kernel<BLOCK, false, false, kMopUp>)
+                          : reinterpret_cast<const void*>(tdfa_stream_kernel<BLOCK, false, false>);
+        name = noGen ? "tdfa_stream_kernel<nogeneral>" : "tdfa_stream_kernel";
     }
     // (measurement knob: LC_TDFA_EXTRA_LDS=<bytes> of unused LDS per workgroup lowers the number of resident workgroups -- how the
     // kernel's time scales with the lines in flight per CU says whether it waits for latency or for a pipe)
@@ -374,63 +367,11 @@ static int launchTdfaBlock(const void* dBlob, uint32_t blobBytes, uint32_t regBy
         const char* e = getenv("LC_TDFA_EXTRA_LDS");
         return e ? size_t(atol(e)) : size_t(0);
     }();
-    if (extraLds) {
-        lds += extraLds;
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-    }
+    lds += extraLds;
+    if (const int rc = lcAllowLds(kern, lds); rc != LC_OK) return rc;
     uint32_t grid = (n + BLOCK - 1) / BLOCK;
-    bool persistSel = false;
-    // (round 6) PERSISTENT WAVEFRONTS for the one-stamp COMPACT kernel on batches of several rounds of workgroups: the launch holds as
-    // many workgroups as the chip does at once, each wavefront goes on with its lines of the next block (tdfa_stream_kernel.hpp
-    // kLabPersist).  MEASURED AND LEFT OFF (LC_TDFA_PERSIST=1 switches it on; the GPU parity suite runs it): 0.1825 against 0.1700 ms per
-    // 1 Mi lines, 0.344 against 0.316 ms per 2 Mi -- as with round 3's persistent workgroups, the dispatcher starting a new workgroup in
-    // the middle of the resident ones' loops beats 4 096 wavefronts that start together and stay in step through every block
-    // (profiles/round6_tdfa_why_not.md section 9).
-    if constexpr (COMPACT && PAIR && !BYTEROWS && BLOCK == 512) {
-        const char* pe = getenv("LC_TDFA_PERSIST");
-        const bool persistOn = pe && pe[0] == '1';
-        if (persistOn && pairOne && !streamOff && !cmapA8 && !extraLds && minLen == 0) {
-            static thread_local uint32_t resident[kLcMaxDevices] = {};  // workgroups the device holds at once (LDS-bound: per CU)
-            int devP = 0;
-            HIP_TRY(hipGetDevice(&devP));
-            if (devP < kLcMaxDevices && !resident[devP]) {
-                hipDeviceProp_t prop;
-                HIP_TRY(hipGetDeviceProperties(&prop, devP));
-                // (LDS-bound, and never more than the 32 wavefronts of a CU: four workgroups of 512)
-                resident[devP] = uint32_t(prop.multiProcessorCount) * uint32_t(std::min<size_t>(4, std::max<size_t>(1, kLcLdsPerCu / lds)));
-            }
-            const uint32_t slots = devP < kLcMaxDevices ? resident[devP] : 0u;
-            if (slots && grid > slots) {
-                kern = tdfa_stream_kernel<512, true, true, kTdfaNoGeneralPrograms | kLabPairOne | kLabDmaStage | kLabPersist>;
-                static thread_local size_t persistAttr[kLcMaxDevices] = {};
-                if (lds > 64 * 1024 && lds > persistAttr[devP]) {
-                    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-                    persistAttr[devP] = lds;
-                }
-                grid = slots;
-                persistSel = true;
-            }
-        }
-    }
-    // (the mop-up launch behind a COMPACT one: an instantiation whose workgroups take the line blocks in turn, tdfa_stream_kernel.hpp
-    // kLabMopUp -- for the workgroup size such a launch has in practice)
-    if constexpr (BLOCK == 256 && !COMPACT && !BYTEROWS) {
-        if (minLen && !streamOff && !cmapA8) {
-            if constexpr (PAIR) kern = pairOne ? tdfa_stream_kernel<256, false, true, kTdfaNoGeneralPrograms | kLabPairOne | kLabMopUp>
-                                               : tdfa_stream_kernel<256, false, true, kLabMopUp>;
-            else kern = noGen ? tdfa_stream_kernel<256, false, false, kTdfaNoGeneralPrograms | kLabMopUp> : tdfa_stream_kernel<256, false, false, kLabMopUp>;
-            grid = std::min(grid, 256u);
-            static thread_local size_t mopAttrSet[kLcMaxDevices][4] = {};  // (function, device), as above
-            const int mopWhich = PAIR ? (pairOne ? 0 : 1) : (noGen ? 2 : 3);
-            if (lds > 64 * 1024 && devNow < kLcMaxDevices && lds > mopAttrSet[devNow][mopWhich]) {
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-                mopAttrSet[devNow][mopWhich] = lds;
-            }
-        }
-    }
-    noteKernel(persistSel ? "tdfa_stream_kernel<compact,nogeneral,pair1,dma,persist>" : cmapA8 ? (COMPACT ? "tdfa_stream_kernel<compact,nogeneral,pair1,dma,a8>" : "tdfa_stream_kernel<nogeneral,pair1,a8>")
-               : (PAIR && pairOne) ? (COMPACT ? "tdfa_stream_kernel<compact,nogeneral,pair1,dma>" : "tdfa_stream_kernel<nogeneral,pair1>") : dma ? (noGen ? "tdfa_stream_kernel<compact,nogeneral,dma>" : "tdfa_stream_kernel<compact,dma>") : noGen ? (COMPACT ? "tdfa_stream_kernel<compact,nogeneral>" : "tdfa_stream_kernel<nogeneral>") : which ? (PAIR ? (COMPACT ? "tdfa_stream_kernel<compact,pair>" : "tdfa_stream_kernel<pair>") : (COMPACT ? "tdfa_stream_kernel<compact>" : "tdfa_stream_kernel"))
-                     : (BYTEROWS ? "tdfa_match_kernel<byterows>" : "tdfa_match_kernel"));
+    if (mopUp) grid = std::min(grid, 256u);
+    noteKernel(name);
     // (hipLaunchKernel reports the launch's own status: no second runtime call to fetch it)
     const uint32_t* blobArg = static_cast<const uint32_t*>(dBlob);
     // completion signal requested by the zero-copy host path (tlsDone, below): this launch carries it when it is the match's
@@ -451,7 +392,7 @@ static int launchTdfaBlock(const void* dBlob, uint32_t blobBytes, uint32_t regBy
     // prologue does.)
     void* args[] = {&d_data, &d_off, &d_len, &sep, &minLen, &n, &d_n, &d_order, &d_resume, &blobArg, &blobBytes, &regBytes, &ngroups,
                     &d_caps, &d_status, &longFlag, &seq, &doneCounter, &doneFlag, &doneSeq};
-    HIP_TRY(hipLaunchKernel(reinterpret_cast<const void*>(kern), dim3(grid), dim3(BLOCK), args, lds, stream));
+    HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(BLOCK), args, lds, stream));
     return LC_OK;
 }
 
@@ -491,34 +432,16 @@ static int launchTdfaL2Family(lc_regex* re, const uint32_t* hostBlob, const void
         if (!stageOffAll && n <= 32768 && progBytes <= 40 * 1024 && lds + progBytes <= 60 * 1024) stageBytes = progBytes;
     }
     if (perWave) {
-        // (round 5) a small automaton rides in LDS whole: transition table + register programs (tdfa_l2_kernel.hpp LT)
-        // MEASURED AND LEFT OFF (LC_TDFA_WAVE_LDS_TRANS=1 switches it on): once the walk's state lives in SGPRs the transition read is a
-        // scalar load through the scalar cache, as fast as the LDS read + readfirstlane, without staging up to 48 KB per four values
-        // (CISCOFW105003 on its 314 values: 0.389 ms from L2, 0.411 ms from LDS; profiles/round5_wave_step.txt)
-        const bool transOff = [] {  // (read per launch: the GPU tests run both forms)
-            const char* v = getenv("LC_TDFA_WAVE_LDS_TRANS");
-            return !(v && v[0] == '1');
-        }();
-        const uint32_t allBytes = (hostBlob[TL_OFF_FINALID] - hostBlob[TL_OFF_TRANS] + 3u) & ~3u;
-        const bool ldsTrans = !transOff && !stageOffAll && n <= 32768 && allBytes <= 48 * 1024 && lds + allBytes <= 60 * 1024;
-        if (ldsTrans) stageBytes = allBytes;
         lds += stageBytes;
-        static thread_local size_t waveLdsAttrSet[2][kLcMaxDevices] = {};
-        if (lds > 48 * 1024 && dev < kLcMaxDevices && lds > waveLdsAttrSet[ldsTrans][dev]) {
-            HIP_TRY(hipFuncSetAttribute(ldsTrans ? reinterpret_cast<const void*>(tdfa_wave_kernel<true>)
-                                                 : reinterpret_cast<const void*>(tdfa_wave_kernel<false>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-            waveLdsAttrSet[ldsTrans][dev] = lds;
+        static thread_local size_t waveLdsAttrSet[kLcMaxDevices] = {};
+        if (lds > 48 * 1024 && dev < kLcMaxDevices && lds > waveLdsAttrSet[dev]) {
+            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(tdfa_wave_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
+            waveLdsAttrSet[dev] = lds;
         }
-        noteKernel(pendingFlag ? "tdfa_l2_kernel:wave:lazy" : ldsTrans ? "tdfa_l2_kernel:wave:lds" : "tdfa_l2_kernel:wave");
-        if (ldsTrans)
-            hipLaunchKernelGGL(tdfa_wave_kernel<true>, dim3((n + kTdfaWaveValues - 1) / kTdfaWaveValues), dim3(kTdfaWaveBlock), lds, stream,
-                               d_data, d_off, d_len, sep, n, d_n, d_order, d_resume, static_cast<const uint32_t*>(dBlob), ngroups, d_caps,
-                               d_status, stageBytes, pendingFlag, seq);
-        else
-            hipLaunchKernelGGL(tdfa_wave_kernel<false>, dim3((n + kTdfaWaveValues - 1) / kTdfaWaveValues), dim3(kTdfaWaveBlock), lds, stream,
-                               d_data, d_off, d_len, sep, n, d_n, d_order, d_resume, static_cast<const uint32_t*>(dBlob), ngroups, d_caps,
-                               d_status, stageBytes, pendingFlag, seq);
+        noteKernel(pendingFlag ? "tdfa_l2_kernel:wave:lazy" : "tdfa_l2_kernel:wave");
+        hipLaunchKernelGGL(tdfa_wave_kernel, dim3((n + kTdfaWaveValues - 1) / kTdfaWaveValues), dim3(kTdfaWaveBlock), lds, stream,
+                           d_data, d_off, d_len, sep, n, d_n, d_order, d_resume, static_cast<const uint32_t*>(dBlob), ngroups, d_caps,
+                           d_status, stageBytes, pendingFlag, seq);
         HIP_TRY(hipGetLastError());
         return LC_OK;
     }
@@ -564,16 +487,14 @@ static int launchTdfa(lc_regex* re, int dev, const uint8_t* d_data, const uint32
         const int wb = re->tdfaWideBlock;
         const uint32_t wRegBytes = uint32_t(size_t(re->tdfaWidePackedRegs + 1) * size_t(wb) * 2);
         const size_t wLds = lcTdfaCompactLdsBytes(wideBytes, re->tdfaWidePackedRegs, wb);
-        if (wb == kLcTdfaWideBlock)
-            rc = launchTdfaBlock<kLcTdfaWideBlock, false, true, true>(dWide, wideBytes, wRegBytes, wLds, d_data, d_off, d_len, sep, 0, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, stream, longFlag, seq, re->tdfaWideBlob[TD_NREGS]);
-        else if (wb == 512 && re->tdfaWideBlob[TD_OFF_PAIR])
-            rc = launchTdfaBlock<512, true, true, false>(dWide, wideBytes, wRegBytes, wLds, d_data, d_off, d_len, sep, 0, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, stream, longFlag, seq, re->tdfaWideBlob[TD_NREGS], lcPairOneFormat(re->tdfaWideBlob));
+        if (wb == 512 && re->tdfaWideBlob[TD_OFF_PAIR])
+            rc = launchTdfaBlock<512, true, true>(dWide, wideBytes, wRegBytes, wLds, d_data, d_off, d_len, sep, 0, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, stream, longFlag, seq, re->tdfaWideBlob[TD_NREGS], lcPairOneFormat(re->tdfaWideBlob));
         else if (wb == 512)
-            rc = launchTdfaBlock<512, false, true, false>(dWide, wideBytes, wRegBytes, wLds, d_data, d_off, d_len, sep, 0, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, stream, longFlag, seq, re->tdfaWideBlob[TD_NREGS]);
+            rc = launchTdfaBlock<512, false, true>(dWide, wideBytes, wRegBytes, wLds, d_data, d_off, d_len, sep, 0, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, stream, longFlag, seq, re->tdfaWideBlob[TD_NREGS]);
         else if (re->tdfaWideBlob[TD_OFF_PAIR])
-            rc = launchTdfaBlock<256, true, true, false>(dWide, wideBytes, wRegBytes, wLds, d_data, d_off, d_len, sep, 0, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, stream, longFlag, seq, re->tdfaWideBlob[TD_NREGS], lcPairOneFormat(re->tdfaWideBlob));
+            rc = launchTdfaBlock<256, true, true>(dWide, wideBytes, wRegBytes, wLds, d_data, d_off, d_len, sep, 0, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, stream, longFlag, seq, re->tdfaWideBlob[TD_NREGS], lcPairOneFormat(re->tdfaWideBlob));
         else
-            rc = launchTdfaBlock<256, false, true, false>(dWide, wideBytes, wRegBytes, wLds, d_data, d_off, d_len, sep, 0, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, stream, longFlag, seq, re->tdfaWideBlob[TD_NREGS]);
+            rc = launchTdfaBlock<256, false, true>(dWide, wideBytes, wRegBytes, wLds, d_data, d_off, d_len, sep, 0, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, stream, longFlag, seq, re->tdfaWideBlob[TD_NREGS]);
         if (rc != LC_OK) return rc;
         minLen = kTdfaWideMaxLine + 1;
     }
@@ -713,16 +634,17 @@ enum { kNfaWholeChain = 0, kNfaFirstChance = 1, kNfaSecondChance = 2, kNfaWideFi
 static thread_local uint32_t* tlsWideNote = nullptr;  // lcSetWideNote: where the next wide launch reports "more than 64 threads were needed"
 void lcSetWideNote(uint32_t* note) { tlsWideNote = note; }
 
-template <int NS, bool ATOMIC, bool GLOBAL, int BLOCK = kNfaBlock>
+template <int NS, bool ATOMIC, bool GLOBAL>
 static int launchNfaSlots(const void* dBlob, uint32_t blobBytes, uint32_t nPos, size_t lds, const uint8_t* d_data,
                           const uint32_t* d_off, const uint32_t* d_len, uint32_t sep, uint32_t n, const uint32_t* d_n, const uint32_t* d_order, const uint32_t* d_resume, uint32_t ngroups,
                           int32_t* d_caps, uint8_t* d_status, hipStream_t stream, uint32_t* overflowFlag, uint32_t seq,
-                          const uint32_t* pendingFlag, int chance = 0, int wideLdsMode = 0) {
+                          const uint32_t* pendingFlag, int chance = 0) {
+    constexpr int BLOCK = kNfaBlock;
     static thread_local size_t ldsAttrSet[kLcMaxDevices] = {};  // the attribute belongs to (function, device)
     int devNow = 0;
     if (lds > 64 * 1024) HIP_TRY(hipGetDevice(&devNow));
     if (lds > 64 * 1024 && devNow < kLcMaxDevices && lds > ldsAttrSet[devNow]) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&nfa_match_kernel<NS, ATOMIC, GLOBAL, BLOCK>),
+        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&nfa_match_kernel<NS, ATOMIC, GLOBAL>),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
         ldsAttrSet[devNow] = lds;
     }
@@ -744,7 +666,7 @@ static int launchNfaSlots(const void* dBlob, uint32_t blobBytes, uint32_t nPos, 
     }
     if (chance != kNfaSecondChance && !wideFirst) {
         noteKernel(ATOMIC ? "nfa_match_kernel<atomic>" : "nfa_match_kernel");
-        hipLaunchKernelGGL((nfa_match_kernel<NS, ATOMIC, GLOBAL, BLOCK>), dim3(grid), dim3(BLOCK), lds, stream, d_data, d_off, d_len, sep, n,
+        hipLaunchKernelGGL((nfa_match_kernel<NS, ATOMIC, GLOBAL>), dim3(grid), dim3(BLOCK), lds, stream, d_data, d_off, d_len, sep, n,
                            d_n, d_order, d_resume, static_cast<const uint32_t*>(dBlob), blobBytes, ngroups, d_caps, d_status, overflowFlag,
                            seq, pendingFlag);
         HIP_TRY(hipGetLastError());
@@ -758,26 +680,9 @@ static int launchNfaSlots(const void* dBlob, uint32_t blobBytes, uint32_t nPos, 
         const size_t wideLds = (size_t((nPos + 3) & ~3u) + 3 * kNfaWideThreads + 64) * 4;
         if (!wideOff && overflowFlag && wideLds <= 64 * 1024) {
             noteKernel(wideFirst ? "nfa_wide_kernel:first" : "nfa_wide_kernel");
-            // (wideLdsMode: the batch is small and program + scratch fit the CU's LDS -- the program is staged, launchNfa decides)
-            if (wideLdsMode && wideLds + blobBytes <= kLcLdsPerCu) {
-                static thread_local size_t wideAttrSet[kLcMaxDevices] = {};
-                const size_t need = wideLds + blobBytes;
-                if (need > 64 * 1024) {
-                    HIP_TRY(hipGetDevice(&devNow));
-                    if (devNow < kLcMaxDevices && need > wideAttrSet[devNow]) {
-                        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&nfa_wide_kernel<NS, true>),
-                                                    hipFuncAttributeMaxDynamicSharedMemorySize, int(need)));
-                        wideAttrSet[devNow] = need;
-                    }
-                }
-                hipLaunchKernelGGL((nfa_wide_kernel<NS, true>), dim3(n), dim3(64), need, stream, d_data, d_off, d_len, sep, n, d_n, d_order,
-                                   d_resume, static_cast<const uint32_t*>(dBlob), blobBytes, ngroups, d_caps, d_status, overflowFlag, seq,
-                                   wideFirst ? 1u : 0u, wideNote);
-            } else {
-                hipLaunchKernelGGL((nfa_wide_kernel<NS, false>), dim3(n), dim3(64), wideLds, stream, d_data, d_off, d_len, sep, n, d_n, d_order,
-                                   d_resume, static_cast<const uint32_t*>(dBlob), blobBytes, ngroups, d_caps, d_status, overflowFlag, seq,
-                                   wideFirst ? 1u : 0u, wideNote);
-            }
+            hipLaunchKernelGGL((nfa_wide_kernel<NS>), dim3(n), dim3(64), wideLds, stream, d_data, d_off, d_len, sep, n, d_n, d_order,
+                               d_resume, static_cast<const uint32_t*>(dBlob), ngroups, d_caps, d_status, overflowFlag, seq,
+                               wideFirst ? 1u : 0u, wideNote);
             HIP_TRY(hipGetLastError());
         }
     }
@@ -799,7 +704,7 @@ static int launchNfa(lc_regex* re, int dev, const uint8_t* d_data, const uint32_
     int rc = ensureUploaded(re, dev, kBlobNfa, &dBlob);
     if (rc != LC_OK) return rc;
     const uint32_t blobBytes = uint32_t(re->nfaBlob.size() * 4);  // the whole upload: the overflow flag sits behind it
-    // what a kernel that keeps the program in LDS stages: everything in front of the class lists (device_tables.h NF_STAGE_BYTES)
+    // what a kernel that keeps the program in LDS stages (device_tables.h NF_STAGE_BYTES: the whole program)
     const uint32_t stageBytes = re->nfaBlob[NF_STAGE_BYTES] ? re->nfaBlob[NF_STAGE_BYTES] : blobBytes;
     const bool atomic = re->nfa.atomicCount > 0;
     size_t lds = lcNfaLdsBytes(stageBytes, uint32_t(re->nfa.positions.size()), atomic);
@@ -811,45 +716,9 @@ static int launchNfa(lc_regex* re, int dev, const uint8_t* d_data, const uint32_
         const char* e = getenv("LC_NFA_GLOBAL_KB");
         return size_t(e ? atoi(e) : 52) * 1024;
     }();
-    // (round 4) ... on LARGE batches.  A small batch -- a Grok entry's few hundred candidates, an event group -- does not fill the
-    // chip either way and waits for its longest value, i.e. for the latency of a byte-step: with the program in LDS a step's
-    // dependent table reads (follow list bounds, paths, masks) cost LDS latency instead of L2 latency.  LC_NFA_SMALL_BATCH: the
-    // largest batch that stages whatever fits the CU's 160 KiB (0 = never; A/B measurements).
-    static const uint32_t smallBatch = [] {
-        const char* e = getenv("LC_NFA_SMALL_BATCH");
-        return uint32_t(e ? atol(e) : 0);  // (measured on configs[2], round 4: 4.57 vs 4.84 ms at 1000 values, 8.16 vs 8.18 ms at 16 Ki -- staging
-                                           // 100+ KiB per workgroup of four values eats what the faster steps save: off by default)
-    }();
-    // (round 5) What kept the r4 experiment from paying: the entries that ARE the long poles of a Grok step (CISCOFW313005 and its
-    // kin: 3 200 positions, 127 KB of program) do not fit LDS next to FOUR waves' election marks (4 x 14 KB) and stayed in L2.  Two or
-    // one value per workgroup do fit.  A batch that the chip takes in ONE round of such workgroups stages its program: block 256 if
-    // that fits, else 128, else 64 lanes.  LC_NFA_STAGE_SMALL=0 switches it off (A/B measurements).
-    // Measured (profiles/round5_nfa_staging.txt): alone on the chip, CISCOFW313005's launch gains 7 % from the staged program (2.75 ->
-    // 2.56 ms) -- the step was not the table reads but the candidate-owner loop (nfa_kernel.hpp, fixed in the same round); inside a Grok
-    // step, where sixteen such entries run side by side, a 155 KB workgroup per CU serialises them (16 Ki values: 5.3 -> 6.2 ms).
-    // So: OFF by default, LC_NFA_STAGE_SMALL=1 switches it on (A/B measurements).
-    static const bool stageSmall = [] {
-        const char* e = getenv("LC_NFA_STAGE_SMALL");
-        return e && e[0] == '1';
-    }();
-    int block = kNfaBlock;
-    bool global = lds > kLcLdsPerCu || (lds > globalAbove && n > smallBatch);
-    const uint32_t nPosAll = uint32_t(re->nfa.positions.size());
-    if (global && stageSmall && !atomic && re->nfa.slotCount() <= 64) {
-        for (int waves : {4, 2, 1}) {
-            const size_t need = lcNfaLdsBytes(stageBytes, nPosAll, atomic, uint32_t(waves));
-            if (need > kLcLdsPerCu) continue;
-            const size_t perCu = kLcLdsPerCu / need;                   // workgroups a CU holds
-            const size_t oneRound = size_t(256) * perCu * size_t(waves);  // values the chip walks at once
-            if (n <= oneRound) {
-                block = 64 * waves;
-                lds = need;
-                global = false;
-            }
-            break;  // (fewer values per workgroup only where more do not fit)
-        }
-    }
-    const bool wideStage = stageSmall && n <= 4096;  // (the second chance walks one value per workgroup anyway)
+    // (Rounds 4 and 5 staged the program of a small batch -- whatever fits the CU's 160 KiB, in workgroups of 256, 128 or 64 lanes --
+    // and measured no gain: DESIGN.md section 5.7.)  The bound applies to non-empty batches, as it always has.
+    const bool global = lds > kLcLdsPerCu || (lds > globalAbove && n > 0);
     if (global) lds -= stageBytes;
     if (lds > 160 * 1024) {
         tlsError = "nfa tables exceed LDS";
@@ -953,16 +822,8 @@ static int launchNfa(lc_regex* re, int dev, const uint8_t* d_data, const uint32_
         constexpr int NS = decltype(ns)::value;
         auto go = [&](auto a, auto g) {
             constexpr bool A = decltype(a)::value, G = decltype(g)::value;
-            if constexpr (!G && !A && NS <= 64) {  // (staged programs without atomic groups only -- an opt-in experiment does not get 24 more instantiations)
-                if (block == 128)
-                    return launchNfaSlots<NS, A, G, 128>(dBlob, stageBytes, nPos, lds, d_data, d_off, d_len, sep, n, d_n, d_order, d_resume, ngroups,
-                                                         d_caps, d_status, stream, overflowFlag, seq, pendingFlag, chance, wideStage);
-                if (block == 64)
-                    return launchNfaSlots<NS, A, G, 64>(dBlob, stageBytes, nPos, lds, d_data, d_off, d_len, sep, n, d_n, d_order, d_resume, ngroups,
-                                                        d_caps, d_status, stream, overflowFlag, seq, pendingFlag, chance, wideStage);
-            }
             return launchNfaSlots<NS, A, G>(dBlob, stageBytes, nPos, lds, d_data, d_off, d_len, sep, n, d_n, d_order, d_resume, ngroups, d_caps,
-                                            d_status, stream, overflowFlag, seq, pendingFlag, chance, wideStage);
+                                            d_status, stream, overflowFlag, seq, pendingFlag, chance);
         };
         if (atomic && global) return go(std::true_type{}, std::true_type{});
         if (atomic) return go(std::true_type{}, std::false_type{});

@@ -75,8 +75,6 @@ struct GrokDeviceState {
     void* dScreens[kLcMaxDevices] = {};
     uint32_t nScreens[kLcMaxDevices] = {};
     uint32_t screenLdsBytes[kLcMaxDevices] = {};  // largest staged table
-    uint32_t nBigScreens[kLcMaxDevices] = {};     // the table's first entries: screens too large for that, see GrokScreenDev::bigBytes
-    uint32_t bigScreenLdsBytes[kLcMaxDevices] = {};
     std::vector<GrokScreenDev> hostScreens[kLcMaxDevices];  // the same table on the host (kernel arguments of the remainder screens)
     // lcGrokMatchHost: the groups of concurrent runner threads travel as ONE batch per device (group_combiner.hpp): a worker thread
     // per (processor, device) owns the plan, the streams and the pinned staging
@@ -337,7 +335,7 @@ static int grokMatchSequential(const std::vector<GrokDevicePattern>& patterns, G
 namespace {
 constexpr int kGrokMaxStreams = 16;  // (LC_GROK_STREAMS; the default stays opts.streams = 8)
 constexpr uint32_t kGrokScreenStageMax = 44 * 1024;  // a screen's accept flags + table are staged into LDS up to this size
-constexpr uint32_t kGrokScreenBigMax = 150 * 1024;   // ... and up to this size by a workgroup that has its CU's LDS to itself (small batches)
+constexpr uint32_t kGrokScreenBigMax = 150 * 1024;   // screens above the first size and up to this one lead the screen table (its order since round 5)
 constexpr uint32_t kGrokMaxRounds = GC_BOUND - GC_ROUND0 - 1;  // search rounds that can be queued ahead per entry
 constexpr uint32_t kGrokSmallBatch = 262144;  // up to here phase 1 takes the chunk-parallel literal pass and LDS-staged screens, one value per
                                               // lane (round 5: measured better than the lane-per-value passes at 64 Ki (9.3 -> 7.3 ms), 128 Ki
@@ -465,21 +463,8 @@ thread_local PlanThread tlsPlan;
 // the screen the merged launch walks for an entry: the relaxed whole-pattern screen when there is one (it rejects nearly
 // everything the prefix screen rejects), else the prefix screen
 lc_regex* planScreenOf(const GrokDevicePattern& gp) {
-    // (round 6) ... unless the relaxed screen is too big to be staged into LDS and the prefix screen is not: a table walked through L2
-    // costs 100 ns a byte -- CISCOFW106006_106007_106010's 2 115 states x 57 classes (243 KB) were the longest walk of the screen
-    // launch AND of the remainder screens, 0.42 + 0.44 ms of every batch for 345 candidates (profiles/round6_grok_screen_split.txt) --
-    // against 45 ns a byte in LDS.  Either screen is a necessary condition; the prefix screen lets more values through to round 0.
-    // LC_GROK_SCREEN_PREFIX: 0 (default) never, 1 whenever the relaxed screen is not LDS-staged, 2 only beyond kGrokScreenBigMax.
-    // MEASURED AND LEFT OFF: the prefix screen of that entry lets 5 % more (entry, value) pairs through, and those are long values that
-    // walk a whole automaton in round 0 -- 16 Ki values 2.31 -> 2.73 ms (mode 2), 2.60 ms (mode 1); profiles/round6_grok_steps.txt.
-    static const int prefixMode = [] {
-        const char* v = getenv("LC_GROK_SCREEN_PREFIX");
-        return v ? atoi(v) : 0;
-    }();
-    auto stageBytesOf = [](const lc_regex* r) { return r->screenBlob[SC_TOTAL_BYTES] - r->screenBlob[SC_OFF_ACCEPT]; };
-    if (prefixMode && gp.relaxed && !gp.relaxed->screenBlob.empty() && gp.screen && !gp.screen->screenBlob.empty() &&
-        stageBytesOf(gp.relaxed) > (prefixMode == 1 ? kGrokScreenStageMax : kGrokScreenBigMax) && stageBytesOf(gp.screen) <= kGrokScreenStageMax)
-        return gp.screen;
+    // (Round 6 measured the prefix screen in place of a relaxed screen too big for LDS and left it off: DESIGN.md,
+    // profiles/round6_grok_steps.txt.)
     if (gp.relaxed && !gp.relaxed->screenBlob.empty()) return gp.relaxed;
     if (gp.screen && !gp.screen->screenBlob.empty()) return gp.screen;
     return nullptr;
@@ -490,8 +475,9 @@ int grokScreenTable(const std::vector<GrokDevicePattern>& patterns, GrokDeviceSt
     std::lock_guard<std::mutex> g(state->m);
     if (!state->screensBuilt[dev]) {
         static const bool noStage = getenv("LC_GROK_SCREEN_NO_LDS") != nullptr;
-        std::vector<GrokScreenDev> host;
-        uint32_t maxStage = 0, maxBig = 0;
+        // (the screens of up to kGrokScreenBigMax that do not fit beside other workgroups go first: the order the table has always had)
+        std::vector<GrokScreenDev> host, rest;
+        uint32_t maxStage = 0;
         for (size_t p = 0; p < patterns.size(); ++p) {
             lc_regex* scr = planScreenOf(patterns[p]);
             if (!scr) continue;
@@ -501,21 +487,16 @@ int grokScreenTable(const std::vector<GrokDevicePattern>& patterns, GrokDeviceSt
             d.bit = uint32_t(p);
             const uint32_t stage = scr->screenBlob[SC_TOTAL_BYTES] - scr->screenBlob[SC_OFF_ACCEPT];
             d.ldsBytes = (!noStage && stage <= kGrokScreenStageMax) ? (stage + 3u) & ~3u : 0u;
-            d.bigBytes = (!noStage && !d.ldsBytes && stage <= kGrokScreenBigMax) ? (stage + 3u) & ~3u : 0u;
+            const bool big = !noStage && !d.ldsBytes && stage <= kGrokScreenBigMax;
             maxStage = std::max(maxStage, d.ldsBytes);
-            maxBig = std::max(maxBig, d.bigBytes);
             if (getenv("LC_GROK_TRACE"))
                 fprintf(stderr, "grok screen of entry %zu: %u states x %u classes, %u bytes (%s)%s; prefix screen %u states\n", p, scr->screenBlob[SC_NSTATES],
-                        scr->screenBlob[SC_NCLASSES], stage, d.ldsBytes ? "staged in LDS" : d.bigBytes ? "big: through L2" : "through L2",
+                        scr->screenBlob[SC_NCLASSES], stage, d.ldsBytes ? "staged in LDS" : "through L2",
                         scr == patterns[p].relaxed ? " relaxed" : " prefix",
                         (patterns[p].screen && !patterns[p].screen->screenBlob.empty()) ? patterns[p].screen->screenBlob[SC_NSTATES] : 0u);
-            host.push_back(d);
+            (big ? host : rest).push_back(d);
         }
-        std::stable_sort(host.begin(), host.end(), [](const GrokScreenDev& x, const GrokScreenDev& y) { return (x.bigBytes != 0) > (y.bigBytes != 0); });
-        uint32_t nBig = 0;
-        for (const GrokScreenDev& d : host) nBig += d.bigBytes != 0;
-        state->nBigScreens[dev] = nBig;
-        state->bigScreenLdsBytes[dev] = maxBig;
+        host.insert(host.end(), rest.begin(), rest.end());
         if (!host.empty()) {
             void* p = nullptr;
             HIP_TRY(hipMalloc(&p, host.size() * sizeof(GrokScreenDev)));
@@ -668,71 +649,30 @@ int grokMatchSpeculative(const std::vector<GrokDevicePattern>& patterns, GrokDev
         uint32_t sliceLen = ((n / 64 + 255) / 256) * 256;
         sliceLen = std::max(256u, std::min(small ? 4096u : 1024u, sliceLen));
         // (round 5) small batches: never more than one value per lane -- the slices are in length order, the first one holds the 4 KiB
-        // values, and a screen that half of them carry walked two of them per lane, one after the other (LC_GROK_SLICE: A/B)
-        static const uint32_t sliceEnv = [] {
-            const char* v = getenv("LC_GROK_SLICE");
-            return uint32_t(v ? atoi(v) : 0);
-        }();
-        if (small) sliceLen = sliceEnv ? std::max(256u, sliceEnv / 256 * 256) : 256u;
-        // (round 6) TRIED AND LEFT OFF (LC_GROK_SCREEN_WAVE=1 switches it on): one value per WAVEFRONT (grokScreenWalkWave: a run of bytes
-        // that keep the state is crossed 256 bytes at a time).  A relaxed screen takes 130-400 real steps and 80-130 run scans per value
-        // (mean 1.1 KB): 50-250 us of a wavefront -- fine for the screens whose literal leaves eight candidates per slice, hopeless for
-        // the five whose entries have no literal and see EVERY value: 64 values per wavefront one after the other, 31 ms for a
-        // 1000-value batch against 0.44 ms one value per lane (profiles/round6_grok_screen_wave_negative.txt).
-        const uint32_t screenWalk = [&] {
-            const char* v = getenv("LC_GROK_SCREEN_WAVE");
-            return (small && v && v[0] == '1') ? 16u : 0u;
-        }() | [&] {  // (round 6) staged tables are staged SCALED (grok_plan_kernel.hpp grokScreenWalkScaled); LC_GROK_SCREEN_SCALED=0: as before
+        // values, and a screen that half of them carry walked two of them per lane, one after the other
+        if (small) sliceLen = 256u;
+        // (round 6) staged tables are staged SCALED (grok_plan_kernel.hpp grokScreenWalkScaled); LC_GROK_SCREEN_SCALED=0: as before
+        const uint32_t screenWalk = [] {
             const char* v = getenv("LC_GROK_SCREEN_SCALED");
             return (v && v[0] == '0') ? 0u : 32u;
         }();
         const uint32_t slices = (n + sliceLen - 1) / sliceLen;
         lcNoteKernel("grok_screen_all_kernel");
-        // Round 5: a relaxed whole-pattern screen of 1 000-2 000 states (70-130 KB) does not fit beside other workgroups and walked its
-        // table through L2 -- 120 ns a byte, 0.5 ms for a 4 KiB value: the whole screen phase of a small batch waited for three such
-        // screens (profiles/round5_grok_timeline.txt).  They now run in a launch of their own, on a worker stream beside the other
-        // screens' launch, each workgroup with the table staged into a CU's whole LDS.  MEASURED AND LEFT OFF (LC_GROK_BIG_SCREENS=1
-        // switches it on): what the phase waited for was not the table reads of those three screens but the walk itself, in every
-        // screen (two values per lane of 4 KiB each); with the walk fixed (grokScreenWalk) a 106 KB workgroup per CU costs more than
-        // its faster table reads gain: 16 Ki values 3.92 ms without, 4.13 ms with (profiles/round5_grok_steps.txt).
-        const bool bigOff = [] {  // (measured and left off: see above; read per batch -- the GPU tests switch it on)
-            const char* v = getenv("LC_GROK_BIG_SCREENS");
-            return !(v && v[0] == '1');
-        }();
-        const uint32_t nBig = (small && !bigOff) ? state->nBigScreens[dev] : 0u;
-        if (nBig) {
-            const size_t bigLds = size_t(sliceLen) * 4 + state->bigScreenLdsBytes[dev];
-            static thread_local size_t attrSet[kLcMaxDevices] = {};
-            if (bigLds > 48 * 1024 && dev < kLcMaxDevices && bigLds > attrSet[dev]) {
-                HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(grok_screen_all_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            int(bigLds)));
-                attrSet[dev] = bigLds;
-            }
-            HIP_TRY(hipEventRecord(T.fork, st));
-            HIP_TRY(hipStreamWaitEvent(T.workers[0], T.fork, 0));
-            hipLaunchKernelGGL(grok_screen_all_kernel, dim3(slices, nBig), dim3(kGrokPlanBlock), bigLds, T.workers[0], d_data, d_off, d_len, n,
-                               sliceLen, screens, reinterpret_cast<unsigned long long*>(masks), static_cast<const uint32_t*>(order), 2u | screenWalk);
-            HIP_TRY(hipEventRecord(T.join[0], T.workers[0]));
-        }
         static const bool splitScreens = getenv("LC_GROK_SCREEN_SPLIT") != nullptr;  // diagnosis: one launch per screen (a kernel trace then times each)
         if (splitScreens) {
-            for (uint32_t k = nBig; k < nScreens; ++k)
+            for (uint32_t k = 0; k < nScreens; ++k)
                 hipLaunchKernelGGL(grok_screen_all_kernel, dim3(slices, 1), dim3(kGrokPlanBlock), size_t(sliceLen) * 4 + (small ? screenLds : 0), st,
                                    d_data, d_off, d_len, n, sliceLen, screens + k, reinterpret_cast<unsigned long long*>(masks),
                                    static_cast<const uint32_t*>(order), (small ? 1u : 0u) | screenWalk);
-        } else if (nScreens > nBig) {
+        } else {
             // (grid (screens, slices): the slices of the longest values first -- grok_plan_kernel.hpp; LC_GROK_SCREEN_TRANSPOSED=0: as before)
             const char* tv = getenv("LC_GROK_SCREEN_TRANSPOSED");
             const bool transposed = !(tv && tv[0] == '0') && slices <= 65535u;
-            hipLaunchKernelGGL(grok_screen_all_kernel, transposed ? dim3(nScreens - nBig, slices) : dim3(slices, nScreens - nBig), dim3(kGrokPlanBlock),
-                               size_t(sliceLen) * 4 + (small ? screenLds : 0), st, d_data, d_off, d_len, n, sliceLen, screens + nBig,
+            hipLaunchKernelGGL(grok_screen_all_kernel, transposed ? dim3(nScreens, slices) : dim3(slices, nScreens), dim3(kGrokPlanBlock),
+                               size_t(sliceLen) * 4 + (small ? screenLds : 0), st, d_data, d_off, d_len, n, sliceLen, screens,
                                reinterpret_cast<unsigned long long*>(masks), static_cast<const uint32_t*>(order),
                                (small ? 1u : 0u) | screenWalk | (transposed ? 128u : 0u));
         }
-        if (nBig) HIP_TRY(hipStreamWaitEvent(st, T.join[0], 0));
-        if (trace && nBig)
-            fprintf(stderr, "grok plan 1: %u big screens in a launch of their own (%u KB of LDS per workgroup)\n", nBig,
-                    unsigned((size_t(sliceLen) * 4 + state->bigScreenLdsBytes[dev]) >> 10));
     }
     uint32_t* firstOf = T.dPlanWords + 64;   // [64]
     uint32_t* shadowBy = T.dPlanWords + 128;  // [64][64]
@@ -875,7 +815,7 @@ int grokMatchSpeculative(const std::vector<GrokDevicePattern>& patterns, GrokDev
         e.dev.columns = e.columns;
         e.dev.anchored = patterns[e.p].anchored ? 1u : 0u;
         T.hostEntries[a] = e.dev;
-        T.hostRemScreens[a] = e.remainderScreen ? *e.remainderScreen : GrokScreenDev{nullptr, e.p, 0u, 0u, 0u};
+        T.hostRemScreens[a] = e.remainderScreen ? *e.remainderScreen : GrokScreenDev{nullptr, e.p, 0u};
         if (e.remainderScreen) {
             ++nRemScreens;
             remScreenLds = std::max(remScreenLds, e.remainderScreen->ldsBytes);
@@ -1021,9 +961,8 @@ int grokMatchSpeculative(const std::vector<GrokDevicePattern>& patterns, GrokDev
         const bool remainderLiteral = envInt("LC_GROK_REMAINDER_LITERAL", 1) != 0 && literalIndex != nullptr;
         const bool remainderWon = envInt("LC_GROK_REMAINDER_WON", 1) != 0;      // slots of values an earlier entry has won drop out in front of the screens
         const bool remainderInChain = envInt("LC_GROK_REMAINDER_INCHAIN", 1) != 0;  // the remainder screens per entry, at the end of its chain in phase 2c
-        const bool screenWave = small && envInt("LC_GROK_SCREEN_WAVE", 0) != 0;  // remainder screens: one slot per wavefront (grokScreenWalkWave; off: see phase 1)
-        const uint32_t remWalk = (screenWave ? 16u : 0u) | (envInt("LC_GROK_SCREEN_SCALED", 1) != 0 ? 32u : 0u);
-        auto remGrid = [&](uint32_t slots) { return screenWave ? (slots + kGrokRemWaveSlots - 1) / kGrokRemWaveSlots : (slots + kGrokPlanBlock - 1) / kGrokPlanBlock; };
+        const uint32_t remWalk = envInt("LC_GROK_SCREEN_SCALED", 1) != 0 ? 32u : 0u;
+        auto remGrid = [&](uint32_t slots) { return (slots + kGrokPlanBlock - 1) / kGrokPlanBlock; };
         // (round 5) the host reads the survivors of the remainder screens together with the finish of the batch (three synchronisations
         // instead of four: see the end of phase 2c).  Round 6: the screens count their survivors onto the gate word themselves.
         const bool lazy = envInt("LC_GROK_LAZY_SYNC3", 1) != 0;
@@ -1032,7 +971,6 @@ int grokMatchSpeculative(const std::vector<GrokDevicePattern>& patterns, GrokDev
         // counts, on a stream beside it (the kernels test the entry's overflow / unanchored counts themselves): see phase 2b
         const bool remainderAhead = remainderInChain && envInt("LC_GROK_REMAINDER_AHEAD", 1) != 0;
         const bool postInStream = envInt("LC_GROK_POST_IN_STREAM", 1) != 0;    // round 0's post step behind each entry's kernel, on its stream
-        const bool bigRemainder = envInt("LC_GROK_BIG_REMAINDER", 0) != 0;      // an entry with a BIG screen stages it for its remainder screen (measured: slower)
         // An entry whose values needed more than 64 threads in recent batches (GC_WIDE, noted behind the batch) goes WIDE FIRST: its
         // first chance is nfa_wide_kernel over every candidate, and what is left behind it are the decide kernels alone.  Round 4's
         // timeline: the longest entry's first chance 1.0 ms + its second chance (14 values restarted from byte 0) 1.1 ms, back to back
@@ -1447,21 +1385,9 @@ int grokMatchSpeculative(const std::vector<GrokDevicePattern>& patterns, GrokDev
                                            remainderLiteral ? literalIndex : static_cast<const uint32_t*>(nullptr), 0ull,
                                            remainderWon ? static_cast<const uint32_t*>(winner) : static_cast<const uint32_t*>(nullptr), 0u);
                     const GrokScreenDev* sc = e.remainderScreen;
-                    const bool big = small && bigRemainder && sc && sc->bigBytes;
-                    const uint32_t lds = big ? sc->bigBytes : (small && sc) ? sc->ldsBytes : 0u;
-                    if (big) {
-                        static thread_local size_t attrSet[kLcMaxDevices] = {};
-                        if (lds > 48 * 1024 && dev < kLcMaxDevices && lds > attrSet[dev]) {
-                            if (hipFuncSetAttribute(reinterpret_cast<const void*>(grok_remainder_all_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                    int(lds)) != hipSuccess) {
-                                rc = lcHipFail(hipGetLastError(), "hipFuncSetAttribute(grok_remainder_all_kernel)");
-                                return;
-                            }
-                            attrSet[dev] = lds;
-                        }
-                    }
+                    const uint32_t lds = (small && sc) ? sc->ldsBytes : 0u;
                     hipLaunchKernelGGL(grok_remainder_all_kernel, dim3(remGrid(e.cand), 1), dim3(kGrokPlanBlock), lds, ws,
-                                       d_data, mine, static_cast<const GrokScreenDev*>(T.dRemScreens) + a, (big ? 2u : small ? 1u : 0u) | remWalk, 0ull,
+                                       d_data, mine, static_cast<const GrokScreenDev*>(T.dRemScreens) + a, (small ? 1u : 0u) | remWalk, 0ull,
                                        remGate);
                 });
             }
@@ -1522,37 +1448,8 @@ int grokMatchSpeculative(const std::vector<GrokDevicePattern>& patterns, GrokDev
                                remainderWon ? static_cast<const uint32_t*>(winner) : static_cast<const uint32_t*>(nullptr), 0u);
         }
         lcNoteKernel("grok_remainder_all_kernel");
-        {
-            // (the entries whose screens are BIG -- phase 1 -- in a launch of their own beside the others', table in a CU's whole LDS)
-            unsigned long long bigMask = 0;
-            uint32_t bigLds = 0;
-            const bool bigOff = [] {
-                const char* v = getenv("LC_GROK_BIG_SCREENS");
-                return !(v && v[0] == '1');
-            }();
-            if (small && !bigOff)
-                for (size_t a = 0; a < nAct; ++a)
-                    if (act[a].remainderScreen && act[a].remainderScreen->bigBytes && !((earlyMask >> a) & 1ull)) {
-                        bigMask |= 1ull << a;
-                        bigLds = std::max(bigLds, act[a].remainderScreen->bigBytes);
-                    }
-            if (bigMask) {
-                static thread_local size_t attrSet[kLcMaxDevices] = {};
-                if (bigLds > 48 * 1024 && dev < kLcMaxDevices && bigLds > attrSet[dev]) {
-                    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(grok_remainder_all_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                int(bigLds)));
-                    attrSet[dev] = bigLds;
-                }
-                HIP_TRY(hipEventRecord(T.fork, st));
-                HIP_TRY(hipStreamWaitEvent(T.workers[0], T.fork, 0));
-                hipLaunchKernelGGL(grok_remainder_all_kernel, dim3(remGrid(maxCand), nAct), dim3(kGrokPlanBlock), bigLds, T.workers[0], d_data, T.dEntries,
-                                   static_cast<const GrokScreenDev*>(T.dRemScreens), 2u | remWalk, ~bigMask, remGate);
-                HIP_TRY(hipEventRecord(T.join[0], T.workers[0]));
-            }
-            hipLaunchKernelGGL(grok_remainder_all_kernel, dim3(remGrid(maxCand), nAct), dim3(kGrokPlanBlock), small ? remScreenLds : 0, st, d_data, T.dEntries,
-                               static_cast<const GrokScreenDev*>(T.dRemScreens), (small ? 1u : 0u) | remWalk, earlyMask | bigMask, remGate);
-            if (bigMask) HIP_TRY(hipStreamWaitEvent(st, T.join[0], 0));
-        }
+        hipLaunchKernelGGL(grok_remainder_all_kernel, dim3(remGrid(maxCand), nAct), dim3(kGrokPlanBlock), small ? remScreenLds : 0, st, d_data, T.dEntries,
+                           static_cast<const GrokScreenDev*>(T.dRemScreens), (small ? 1u : 0u) | remWalk, earlyMask, remGate);
         }
         HIP_TRY(hipGetLastError());
         // What is left of phase 2 needs the survivors of the remainder screens -- almost always none.  Round 5: the host no longer waits

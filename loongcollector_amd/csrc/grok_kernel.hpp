@@ -1,6 +1,6 @@
 // grok_kernel.hpp -- bookkeeping kernels of the Grok matcher (grok_device.hip: the sequential path of lcGrokMatchDevice).
 //
-// The matching itself is done by the regex kernels (tdfa_match_kernel / nfa_match_kernel) in their "subset of lines,
+// The matching itself is done by the regex kernels (tdfa_stream_kernel / nfa_match_kernel) in their "subset of lines,
 // resumed search" mode.  What is restated here is the control flow of ProcessorGrok.processGrok
 // (plugins/processor/grok/processor_grok.go:148-194) for a whole batch at once:
 //     for each Match pattern, in order:            <- host loop, one pass per pattern over the values still undecided

@@ -368,14 +368,9 @@ __device__ inline uint32_t nfaAtomicStep(const NfaAtomicCtx& c, uint32_t nThread
     return nKept;
 }
 
-// BLOCK: 256 (four values per workgroup share one LDS copy of the program: large batches) or 128 / 64 (round 5).  A SMALL batch -- a
-// Grok entry's few hundred candidates -- waits for its longest value, i.e. for the latency of a byte step, and a step is a chain of
-// dependent table reads (follow-list bounds -> path -> its conditions -> the target's class mask -> the tags): from L2 that chain is
-// most of the step (measured: 300 ns a byte for CISCOFW313005, 3 219 positions, 127 KB of program).  With fewer values per workgroup
-// the per-wave election marks shrink and programs up to ~145 KB fit the CU's 160 KB of LDS next to them: the launcher picks the
-// largest BLOCK whose LDS need fits (gpu_runtime.hip launchNfa).
-template <int NS, bool ATOMIC, bool GLOBAL, int BLOCK = kNfaBlock>
-__global__ __launch_bounds__(BLOCK) void nfa_match_kernel(const uint8_t* __restrict__ data,
+// kNfaBlock lanes: four values per workgroup share one LDS copy of the program
+template <int NS, bool ATOMIC, bool GLOBAL>
+__global__ __launch_bounds__(kNfaBlock) void nfa_match_kernel(const uint8_t* __restrict__ data,
                                                               const uint32_t* __restrict__ off,
                                                               const uint32_t* __restrict__ len, uint32_t sepBytes,
                                                               uint32_t nLines, const uint32_t* __restrict__ nLinesPtr,
@@ -387,6 +382,7 @@ __global__ __launch_bounds__(BLOCK) void nfa_match_kernel(const uint8_t* __restr
                                                               uint8_t* __restrict__ status,
                                                               uint32_t* __restrict__ overflowFlag, uint32_t launchSeq,
                                                               const uint32_t* __restrict__ pendingFlag) {
+    constexpr int BLOCK = kNfaBlock;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t tid = threadIdx.x;
     // behind nfa_dfs_kernel (nfa_decide_kernel.hpp): only the lines it left pending are this launch's business -- usually none
@@ -439,10 +435,6 @@ __global__ __launch_bounds__(BLOCK) void nfa_match_kernel(const uint8_t* __restr
     tb.maskShift = hdr[NF_MASK_WORDS] == 4 ? 2 : 1;
     const uint32_t maskShift = tb.maskShift;
     const uint32_t* followStart = tb.followStart;
-    // follow lists by byte class (device_tables.h NF_OFF_CSTART): in global memory also when the program is staged
-    const uint32_t* cstart = hdr[NF_OFF_CSTART] ? reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(blob) + hdr[NF_OFF_CSTART]) : nullptr;
-    const uint32_t* cpaths = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(blob) + hdr[NF_OFF_CPATHS]);
-    const uint32_t nClasses = hdr[NF_NCLASSES];
 
     // (round 5: what is wave-uniform is SAID to be -- readfirstlane -- or the compiler, for which anything derived from threadIdx or read
     // from LDS is divergent, keeps the line's offsets, the byte position and the loop conditions in VGPRs and steers the walk with exec masks)
@@ -674,12 +666,11 @@ __global__ __launch_bounds__(BLOCK) void nfa_match_kernel(const uint8_t* __restr
             }
         }
 
-        // (round 5) this thread's paths whose target takes THIS byte: the class list where the blob has one, else the whole follow list
+        // this thread's follow list: its candidate paths
         uint32_t fs = 0, cnt = 0;
         if (liveLane) {
-            const uint32_t* rowStart = cstart ? cstart + (myPos * nClasses + cls) : followStart + myPos;
-            fs = rowStart[0];
-            cnt = rowStart[1] - fs;
+            fs = followStart[myPos];
+            cnt = followStart[myPos + 1] - fs;
         }
         uint32_t totalCand;
         const uint32_t rankBase = waveExclusiveScan(cnt, lane, totalCand);
@@ -713,13 +704,8 @@ __global__ __launch_bounds__(BLOCK) void nfa_match_kernel(const uint8_t* __restr
             bool pass = false;
             uint4 p{0, 0, 0, 0};
             if (cand < totalCand) {
-                if (cstart) {  // (listed = the target takes the byte; MATCH paths are not listed)
-                    p = nfaPath(tb, cpaths[q]);
-                    pass = (p.y & ~ctrue) == 0;
-                } else {
-                    p = nfaPath(tb, q);
-                    if (p.x != NF_TARGET_MATCH && (p.y & ~ctrue) == 0) pass = nfaMaskBit(tb.posMask, maskShift, p.x, cw, cb);
-                }
+                p = nfaPath(tb, q);
+                if (p.x != NF_TARGET_MATCH && (p.y & ~ctrue) == 0) pass = nfaMaskBit(tb.posMask, maskShift, p.x, cw, cb);
                 if (pass) atomicMin(&best[p.x], cand);  // per target, the candidate of highest priority
             }
             waveLdsSync();

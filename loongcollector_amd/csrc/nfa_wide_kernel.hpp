@@ -29,16 +29,13 @@ __device__ __forceinline__ void nfaWideScan(uint32_t v0, uint32_t v1, uint32_t l
     total = t0 + t1;
 }
 
-// STAGE (round 5): the program is staged into LDS (blobBytes of it, in front of the scratch) -- a value comes here to be walked to its
-// end at the latency of a byte step, and from L2 the step's dependent table reads are most of that latency (nfa_kernel.hpp BLOCK).  The
-// launcher stages when program + scratch fit the CU's LDS and the batch is small.
-template <int NS, bool STAGE = false>
+template <int NS>
 __global__ __launch_bounds__(64) void nfa_wide_kernel(const uint8_t* __restrict__ data, const uint32_t* __restrict__ off,
                                                       const uint32_t* __restrict__ len, uint32_t sepBytes, uint32_t nLines,
                                                       const uint32_t* __restrict__ nLinesPtr,
                                                       const uint32_t* __restrict__ order,
                                                       const uint32_t* __restrict__ resume,
-                                                      const uint32_t* __restrict__ blob, uint32_t blobBytes, uint32_t nGroupsOut,
+                                                      const uint32_t* __restrict__ blob, uint32_t nGroupsOut,
                                                       int32_t* __restrict__ caps, uint8_t* __restrict__ status,
                                                       uint32_t* __restrict__ overflowFlag, uint32_t launchSeq, uint32_t first,
                                                       uint32_t* __restrict__ wideNote) {
@@ -59,24 +56,6 @@ __global__ __launch_bounds__(64) void nfa_wide_kernel(const uint8_t* __restrict_
     if (!first && status[line] != LC_OVERFLOW) return;
 
     const uint8_t* tbl = reinterpret_cast<const uint8_t*>(blob);
-    uint32_t scratchBase = 0;
-    if constexpr (STAGE) {  // (only the workgroups that have a value to decide get here)
-        const uint4* src = reinterpret_cast<const uint4*>(blob);
-        uint4* dst = reinterpret_cast<uint4*>(smem);
-        const uint32_t nQuads = blobBytes / 16;
-        uint32_t i = lane;
-        for (; i + 7 * 64 < nQuads; i += 8 * 64) {
-            uint4 q[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) q[k] = src[i + uint32_t(k) * 64];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) dst[i + uint32_t(k) * 64] = q[k];
-        }
-        for (; i < nQuads; i += 64) dst[i] = src[i];
-        waveLdsSync();
-        tbl = smem;
-        scratchBase = blobBytes;
-    }
     const uint32_t* hdr = reinterpret_cast<const uint32_t*>(tbl);
     const uint32_t nPos = hdr[NF_NPOS];
     const uint32_t nSlots = hdr[NF_NSLOTS];
@@ -92,13 +71,9 @@ __global__ __launch_bounds__(64) void nfa_wide_kernel(const uint8_t* __restrict_
     tb.auxShift = TW == 10 ? 4 : (TW == 4 ? 3 : 2);
     tb.posMask = reinterpret_cast<const uint32_t*>(tbl + hdr[NF_OFF_POSMASK]);
     tb.maskShift = hdr[NF_MASK_WORDS] == 4 ? 2 : 1;
-    // follow lists by byte class (device_tables.h NF_OFF_CSTART; nfa_kernel.hpp): always read from global memory
-    const uint32_t* cstart = hdr[NF_OFF_CSTART] ? reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(blob) + hdr[NF_OFF_CSTART]) : nullptr;
-    const uint32_t* cpaths = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(blob) + hdr[NF_OFF_CPATHS]);
-    const uint32_t nClasses = hdr[NF_NCLASSES];
 
     // LDS: best[nPos] then newPos / newSrc / newAux for 128 threads
-    uint32_t* best = reinterpret_cast<uint32_t*>(smem + scratchBase);
+    uint32_t* best = reinterpret_cast<uint32_t*>(smem);
     uint32_t* newPos = best + ((nPos + 3) & ~3u);
     uint32_t* newSrc = newPos + kNfaWideThreads;
     uint32_t* newAux = newSrc + kNfaWideThreads;
@@ -199,14 +174,12 @@ __global__ __launch_bounds__(64) void nfa_wide_kernel(const uint8_t* __restrict_
         const bool live0 = lane < nThreads, live1 = lane + 64 < nThreads;
         uint32_t fs0 = 0, fs1 = 0, cnt0 = 0, cnt1 = 0;
         if (live0) {
-            const uint32_t* r0 = cstart ? cstart + (pos[0] * nClasses + cls) : tb.followStart + pos[0];
-            fs0 = r0[0];
-            cnt0 = r0[1] - fs0;
+            fs0 = tb.followStart[pos[0]];
+            cnt0 = tb.followStart[pos[0] + 1] - fs0;
         }
         if (live1) {
-            const uint32_t* r1 = cstart ? cstart + (pos[1] * nClasses + cls) : tb.followStart + pos[1];
-            fs1 = r1[0];
-            cnt1 = r1[1] - fs1;
+            fs1 = tb.followStart[pos[1]];
+            cnt1 = tb.followStart[pos[1] + 1] - fs1;
         }
         uint32_t rank0, rank1, totalCand;
         nfaWideScan(cnt0, cnt1, lane, rank0, rank1, totalCand);
@@ -239,13 +212,8 @@ __global__ __launch_bounds__(64) void nfa_wide_kernel(const uint8_t* __restrict_
             bool pass = false;
             uint4 p{0, 0, 0, 0};
             if (cand < totalCand) {
-                if (cstart) {
-                    p = nfaPath(tb, cpaths[q]);
-                    pass = (p.y & ~ctrue) == 0;
-                } else {
-                    p = nfaPath(tb, q);
-                    if (p.x != NF_TARGET_MATCH && (p.y & ~ctrue) == 0) pass = nfaMaskBit(tb.posMask, tb.maskShift, p.x, cw, cb);
-                }
+                p = nfaPath(tb, q);
+                if (p.x != NF_TARGET_MATCH && (p.y & ~ctrue) == 0) pass = nfaMaskBit(tb.posMask, tb.maskShift, p.x, cw, cb);
                 if (pass) atomicMin(&best[p.x], cand);
             }
             waveLdsSync();

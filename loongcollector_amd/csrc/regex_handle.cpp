@@ -329,15 +329,9 @@ static void lcTryStandardPairTable(lc_regex* re, bool fold) {
         const char* e = getenv("LC_TDFA_STD_PAIR");
         return e && e[0] == '0';
     }();
-    // (LC_TDFA_STREAM=0, the A/B knob that sends every launch to the phase-separated kernel, cannot run one-stamp tables: the
-    // standard blob then keeps its single-byte tables instead of making default patterns fail)
-    static const bool streamOff = [] {
-        const char* e = getenv("LC_TDFA_STREAM");
-        return e && e[0] == '0';
-    }();
-    if (off || streamOff || getenv("LC_TDFA_PAIR") || !re->tdfa.startAfter.empty() || !re->tdfaBlock) return;
+    if (off || getenv("LC_TDFA_PAIR") || !re->tdfa.startAfter.empty() || !re->tdfaBlock) return;
     try {
-        std::vector<uint32_t> blob = lcregex::packTdfaBlob(re->tdfa, re->tdfaBlock, false, false, fold, 2);
+        std::vector<uint32_t> blob = lcregex::packTdfaBlob(re->tdfa, re->tdfaBlock, false, fold, 2);
         const uint32_t po = blob[TD_OFF_PAIR];
         if (!po || blob[po / 4 + TP_FORMAT] != 1) return;  // (general programs left, or the pair table is too large)
         if (lcTdfaLdsBytes(uint32_t(blob.size() * 4), re->tdfaPackedRegs, re->tdfaBlock) > kLcLdsPerCu / 2) return;
@@ -368,9 +362,7 @@ size_t tdfaBlobBytesEstimate(const TdfaTables& t) {
 // Tables for a COMPACT kernel variant (tdfa_kernel.hpp), chosen when the pattern is compiled.  By default the 256-lane
 // variant (class-indexed rows, 16-bit registers: 16 instead of 12 waves per CU on the headline regex, +4 % measured) is
 // packed and the launcher uses it for large batches.  LC_TDFA_COMPACT=0: none.  LC_TDFA_COMPACT=256 / 512: that workgroup
-// size, used for every batch.  LC_TDFA_COMPACT=1024: byte-indexed rows shared by one 1024-lane workgroup per CU, for
-// automata small enough to keep that table, the registers and the staging tiles in the CU's LDS (measured slower: the
-// wide rows quadruple the LDS bank conflicts).
+// size, used for every batch.
 std::vector<uint32_t> packTdfaWideBlob(const TdfaTables& t, int* blockOut, bool* forcedOut, uint32_t* packedRegsOut) {
     const char* env = getenv("LC_TDFA_COMPACT");
     const int want = env ? atoi(env) : 256;
@@ -392,7 +384,7 @@ std::vector<uint32_t> packTdfaWideBlob(const TdfaTables& t, int* blockOut, bool*
             const uint32_t packedRegs = t.nRegs + (fold ? foldRegs : 0u);
             try {
                 if (size_t(packedRegs + 1) * 512 * 2 > TD_MAX_REG_AREA) continue;
-                std::vector<uint32_t> blob = packTdfaBlob(t, 512, false, true, fold != 0, 2);
+                std::vector<uint32_t> blob = packTdfaBlob(t, 512, true, fold != 0, 2);
                 const uint32_t po = blob[TD_OFF_PAIR];
                 if (!po || blob[po / 4 + TP_FORMAT] != 1) break;  // (general programs, or the pair table is too large)
                 if (lcTdfaCompactLdsBytes(uint32_t(blob.size() * 4), packedRegs, 512) * 2 > kLcLdsPerCu) break;  // two workgroups per CU
@@ -419,23 +411,11 @@ std::vector<uint32_t> packTdfaWideBlob(const TdfaTables& t, int* blockOut, bool*
     for (int fold = foldRegs ? 1 : 0; fold >= 0; --fold) {
         const uint32_t packedRegs = t.nRegs + (fold ? foldRegs : 0u);
         try {
-            if (want == 256 || want == 512) {
-                if (size_t(packedRegs + 1) * size_t(want) * 2 > TD_MAX_REG_AREA) continue;
-                std::vector<uint32_t> blob = packTdfaBlob(t, want, false, true, fold != 0);
-                if (lcTdfaCompactLdsBytes(uint32_t(blob.size() * 4), packedRegs, want) > kLcLdsPerCu) continue;
-                *blockOut = want;
-                *packedRegsOut = packedRegs;
-                return blob;
-            }
-            if (want != kLcTdfaWideBlock) return {};
-            const uint64_t tableEnd = TD_TRANS_OFFSET + uint64_t(t.nStates) * 257 * 4;
-            if (tableEnd > TD_MAX_TABLE_END) return {};
-            if (lcTdfaWideRegBytes(packedRegs) > TD_MAX_REG_AREA) continue;
-            const size_t rest = tdfaBlobBytesEstimate(t) - size_t(t.nStates) * (t.nClasses + 1) * 4;  // everything but the rows
-            if (lcTdfaWideLdsBytes(uint32_t(size_t(t.nStates) * 257 * 4 + rest + 64), packedRegs) > kLcLdsPerCu) continue;
-            std::vector<uint32_t> blob = packTdfaBlob(t, kLcTdfaWideBlock, true, true, fold != 0);
-            if (lcTdfaWideLdsBytes(uint32_t(blob.size() * 4), packedRegs) > kLcLdsPerCu) continue;
-            *blockOut = kLcTdfaWideBlock;
+            if (want != 256 && want != 512) return {};
+            if (size_t(packedRegs + 1) * size_t(want) * 2 > TD_MAX_REG_AREA) continue;
+            std::vector<uint32_t> blob = packTdfaBlob(t, want, true, fold != 0);
+            if (lcTdfaCompactLdsBytes(uint32_t(blob.size() * 4), packedRegs, want) > kLcLdsPerCu) continue;
+            *blockOut = want;
             *packedRegsOut = packedRegs;
             return blob;
         } catch (const RegexError&) {
@@ -445,9 +425,9 @@ std::vector<uint32_t> packTdfaWideBlob(const TdfaTables& t, int* blockOut, bool*
     return {};
 }
 
-std::vector<uint32_t> packTdfaBlob(const TdfaTables& t, int block, bool wide, bool compact, bool foldPrograms, int pairMode) {
-    // wide: rows indexed by the byte itself (256 columns + identity); compact: 16-bit offset registers (tdfa_kernel.hpp)
-    const uint32_t cols = (wide ? 256 : t.nClasses) + 1;  // + identity column
+std::vector<uint32_t> packTdfaBlob(const TdfaTables& t, int block, bool compact, bool foldPrograms, int pairMode) {
+    // compact: 16-bit offset registers (tdfa_kernel.hpp)
+    const uint32_t cols = t.nClasses + 1;  // + identity column
     const uint32_t rowBytes = cols * 4;
     if (TD_TRANS_OFFSET + uint64_t(t.nStates) * rowBytes > TD_MAX_TABLE_END)
         throw RegexError("tdfa: transition table exceeds the 64 KiB LDS window");
@@ -482,7 +462,7 @@ std::vector<uint32_t> packTdfaBlob(const TdfaTables& t, int block, bool wide, bo
     auto rowAddr = [&](uint32_t state) { return TD_TRANS_OFFSET + state * rowBytes; };
     for (uint32_t s = 0; s < t.nStates; ++s) {
         for (uint32_t c = 0; c + 1 < cols; ++c) {
-            const uint32_t e = t.trans[size_t(s) * t.nClasses + (wide ? t.classMap[c] : c)];
+            const uint32_t e = t.trans[size_t(s) * t.nClasses + c];
             trans[size_t(s) * cols + c] = rowAddr(e & 0xFFFF) | (field[e >> 16] << 16);
         }
         trans[size_t(s) * cols + cols - 1] = rowAddr(s) | (field[0] << 16);  // identity column
@@ -533,7 +513,7 @@ std::vector<uint32_t> packTdfaBlob(const TdfaTables& t, int block, bool wide, bo
     const bool pairOne = pairMode == 2;  // ONE stamp per pair entry (device_tables.h TP1_*)
     bool anyGeneralList = false;
     for (size_t id = 1; id < nLists; ++id) anyGeneralList = anyGeneralList || (field[id] & TD_OP_GENERAL);
-    if (!wide && (pairMode == 1 || (pairOne && !anyGeneralList)) && pairBytes <= TP_MAX_TABLE_BYTES && dummyReg < TP_GENERAL) {
+    if ((pairMode == 1 || (pairOne && !anyGeneralList)) && pairBytes <= TP_MAX_TABLE_BYTES && dummyReg < TP_GENERAL) {
         std::vector<uint16_t> cmapA(256);
         for (int b = 0; b < 256; ++b) cmapA[size_t(b)] = uint16_t(t.classMap[size_t(b)] * cols * 4);
         const uint32_t cmapAOff = w.put(cmapA);
@@ -883,39 +863,8 @@ std::vector<uint32_t> packNfaBlob(const FollowNfa& nfa, std::vector<uint8_t>& cl
         hdr[NF_OFF_EVENTS] = w.put(events);
         hdr[NF_OFF_ATOMICPOS] = w.put(atomicPos);
     }
-    // ---- follow lists by byte class (device_tables.h NF_OFF_CSTART): behind everything the LDS kernels stage
+    // what a kernel that keeps the program in LDS stages: all of it (words 24 and 25 stay 0, device_tables.h)
     hdr[NF_STAGE_BYTES] = uint32_t((w.bytes.size() + 15) & ~size_t(15));
-    {
-        // MEASURED AND LEFT OFF (LC_NFA_CLASS_LISTS=1 packs them; read when a pattern is compiled): on the Grok entries that are the long
-        // poles of a batch a step has ~14 candidates in ONE election round either way -- what a step costs there is the latency of its
-        // own ~650 instructions, not the number of candidates (profiles/round5_grok_steps.txt); the lists add up to 1.6 MB per pattern.
-        const char* on = getenv("LC_NFA_CLASS_LISTS");
-        const bool off = !(on && on[0] == '1');
-        const size_t nc = rep.size();
-        std::vector<uint32_t> cstart, cpaths;
-        bool fits = !off;
-        if (fits) {
-            cstart.reserve(size_t(npos + 1) * nc + 1);
-            for (int p = 0; p <= npos && fits; ++p) {
-                const uint32_t base = followStart[size_t(p)];
-                for (size_t c = 0; c < nc; ++c) {
-                    cstart.push_back(uint32_t(cpaths.size()));
-                    uint32_t k = 0;
-                    for (const auto& path : nfa.follow[size_t(p)]) {
-                        if (path.target >= 0 && nfa.positions[size_t(path.target)].has(rep[c])) cpaths.push_back(base + k);
-                        ++k;
-                    }
-                }
-                fits = (cstart.size() + cpaths.size()) * 4 <= (size_t(16) << 20);
-            }
-            cstart.push_back(uint32_t(cpaths.size()));
-        }
-        if (fits) {
-            if (cpaths.empty()) cpaths.push_back(0);
-            hdr[NF_OFF_CSTART] = w.put(cstart);
-            hdr[NF_OFF_CPATHS] = w.put(cpaths);
-        }
-    }
     std::memcpy(w.bytes.data(), hdr, sizeof hdr);
     return w.finish(NF_TOTAL_BYTES);
 }
@@ -1114,7 +1063,7 @@ static lc_regex* compileScreenNode(std::unique_ptr<Node> node, uint32_t syntax_f
         if (tdfaBlobBytesEstimate(re->tdfa) > maxBlobBytes) return nullptr;
         const bool fold = lcPickTdfaBlockAndFold(&*re);
         if (!re->tdfaBlock) return nullptr;
-        re->tdfaBlob = packTdfaBlob(re->tdfa, re->tdfaBlock, false, false, fold);
+        re->tdfaBlob = packTdfaBlob(re->tdfa, re->tdfaBlock, false, fold);
         re->tdfaWideBlob = packTdfaWideBlob(re->tdfa, &re->tdfaWideBlock, &re->tdfaWideForced, &re->tdfaWidePackedRegs);
         re->hasTdfa = true;
         // the same automaton as a plain yes/no DFA: the merged screen launch of the Grok matcher (grok_plan_kernel.hpp) walks
@@ -1721,7 +1670,7 @@ extern "C" int lc_regex_compile(const char* pattern, size_t pattern_len, uint32_
                 re->tdfa = buildTdfa(re->nfa, lim);
                 const bool fold = lcPickTdfaBlockAndFold(&*re);
                 if (!re->tdfaBlock) throw RegexError("tdfa: tables + registers exceed the 160 KiB LDS of a CU");
-                re->tdfaBlob = packTdfaBlob(re->tdfa, re->tdfaBlock, false, false, fold);
+                re->tdfaBlob = packTdfaBlob(re->tdfa, re->tdfaBlock, false, fold);
                 lcTryStandardPairTable(&*re, fold);
                 re->tdfaWideBlob = packTdfaWideBlob(re->tdfa, &re->tdfaWideBlock, &re->tdfaWideForced, &re->tdfaWidePackedRegs);
                 re->hasTdfa = true;
@@ -1776,7 +1725,7 @@ extern "C" int lc_regex_compile(const char* pattern, size_t pattern_len, uint32_
                             try {
                                 const bool fold = lcPickTdfaBlockAndFold(&*re);
                                 if (re->tdfaBlock) {
-                                    re->tdfaBlob = packTdfaBlob(re->tdfa, re->tdfaBlock, false, false, fold);
+                                    re->tdfaBlob = packTdfaBlob(re->tdfa, re->tdfaBlock, false, fold);
                                     re->tdfaWideBlob =
                                         packTdfaWideBlob(re->tdfa, &re->tdfaWideBlock, &re->tdfaWideForced, &re->tdfaWidePackedRegs);
                                     re->hasTdfa = true;

@@ -52,7 +52,7 @@ struct lc_regex {
     uint32_t tdfaPackedRegs = 0;        // registers per line tdfaBlob uses: tdfa.nRegs + one per folded multi-stamp set
     uint32_t tdfaWidePackedRegs = 0;    // the same for tdfaWideBlob (each blob folds only if its register area allows)
     std::vector<uint32_t> tdfaWideBlob; // tables of the COMPACT kernel variant (16-bit offset registers), or empty
-    int tdfaWideBlock = 0;              // its workgroup size: 256 / 512 (class-indexed rows) or 1024 (byte-indexed rows)
+    int tdfaWideBlock = 0;              // its workgroup size: 256 or 512
     bool tdfaWideForced = false;        // LC_TDFA_COMPACT was set: use it for every batch, not only for large ones
     std::vector<uint32_t> tdfaL2Blob;   // tdfa_l2_layout.h: the tagged DFA with its tables in global memory, when `tdfa` is too large
                                         // for the LDS kernels (then hasTdfa is false and tdfaBlob empty) and small enough for L2
@@ -112,8 +112,8 @@ int elideRedundantAtomics(ParsedRegex& re);
 // foldPrograms: multi-stamp register programs become stamps of set registers when every program of the table allows it
 // pairMode: the byte-pair extension -- -1: what LC_TDFA_PAIR says (unset / 0: none, 1: two stamps per entry, 2: one stamp);
 // 0 / 1 / 2: that, whatever the environment says
-std::vector<uint32_t> packTdfaBlob(const TdfaTables& t, int block, bool wide = false, bool compact = false,
-                                   bool foldPrograms = true, int pairMode = -1);
+std::vector<uint32_t> packTdfaBlob(const TdfaTables& t, int block, bool compact = false, bool foldPrograms = true,
+                                   int pairMode = -1);
 uint32_t tdfaFoldRegs(const TdfaTables& t);  // registers that fold adds per line (0 = nothing to fold)
 // tables of the COMPACT kernel variant (LC_TDFA_COMPACT picks it; empty: switched off, or the automaton is too large)
 std::vector<uint32_t> packTdfaWideBlob(const TdfaTables& t, int* blockOut, bool* forcedOut, uint32_t* packedRegsOut);
@@ -137,13 +137,7 @@ inline size_t lcTdfaStageBytes(int block) { return size_t(block / 64) * 64 * (LC
 inline size_t lcTdfaLdsBytes(uint32_t blobBytes, uint32_t nRegs, int block) {
     return size_t(blobBytes) + lcTdfaRegBytes(nRegs, block) + lcTdfaStageBytes(block);
 }
-// COMPACT kernel variants (tdfa_kernel.hpp): 16-bit offset registers, unpadded staging tiles; the byte-indexed one runs as
-// one 1024-lane workgroup per CU
-constexpr int kLcTdfaWideBlock = 1024;
-inline size_t lcTdfaWideRegBytes(uint32_t nRegs) { return size_t(nRegs + 1) * kLcTdfaWideBlock * 2; }
-inline size_t lcTdfaWideLdsBytes(uint32_t blobBytes, uint32_t nRegs) {
-    return size_t(blobBytes) + lcTdfaWideRegBytes(nRegs) + size_t(kLcTdfaWideBlock / 64) * 64 * LC_TDFA_STAGE_BYTES;
-}
+// COMPACT kernel variants (tdfa_kernel.hpp): 16-bit offset registers, unpadded staging tiles
 inline size_t lcTdfaCompactLdsBytes(uint32_t blobBytes, uint32_t nRegs, int block) {
     return size_t(blobBytes) + size_t(nRegs + 1) * size_t(block) * 2 + size_t(block / 64) * 64 * LC_TDFA_STAGE_BYTES;
 }
@@ -158,9 +152,8 @@ inline int lcTdfaPickBlock(uint32_t blobBytes, uint32_t nRegs) {
     return 0;
 }
 // 4 waves x (best[nPos] + 4x64 words) [+ 4 x the atomic path's scratch, nfa_kernel.hpp kNfaAtomicScratchWords = 1344]
-// (waves: values per workgroup -- 4, or 2 / 1 for small batches whose program then fits LDS, nfa_kernel.hpp BLOCK)
-inline size_t lcNfaLdsBytes(uint32_t blobBytes, uint32_t nPos, bool atomic, uint32_t waves = 4) {
-    return size_t(blobBytes) + size_t(waves) * (((nPos + 3) & ~3u) + 256) * 4 + (atomic ? size_t(waves) * 1344 * 4 : 0);
+inline size_t lcNfaLdsBytes(uint32_t blobBytes, uint32_t nPos, bool atomic) {
+    return size_t(blobBytes) + size_t(4) * (((nPos + 3) & ~3u) + 256) * 4 + (atomic ? size_t(4) * 1344 * 4 : 0);
 }
 
 // regex_handle.cpp: TDFA-only handle for the longest prefix of the pattern's top-level concatenation whose automaton stays

@@ -3,7 +3,7 @@
 // One DFA state = ordered list of (NFA position, register map) items; order = backtracking priority.  Registers
 // hold byte offsets of capture-group boundaries.  Register names are canonicalised per state (first appearance),
 // so state identity is (positions, prev-byte context, register-sharing pattern) and the construction is finite.
-// The device kernel (kernels.hip: tdfa_match_kernel) steps one log line per lane through `trans`, running the
+// The device kernel (tdfa_stream_kernel.hpp) steps one log line per lane through `trans`, running the
 // few register moves attached to a transition, and finishes with the per-state final map.
 #pragma once
 

@@ -1,4 +1,5 @@
-// tdfa_kernel.hpp -- gfx950 kernel of the tagged-DFA engine (included by gpu_runtime.hip only).
+// tdfa_kernel.hpp -- device pieces of the tagged-DFA engine's LDS kernels (tdfa_stream_kernel.hpp): layout constants, the
+// general-program replay, the result epilogue, the completion signal.
 //
 // One log line per lane, 64 lines per wavefront, tables in LDS.
 //
@@ -33,9 +34,7 @@
 //
 // COMPACT variants (regex_handle.cpp packTdfaWideBlob: 256 lanes by default for large batches): 16-bit offset registers (lines of 64 KiB and more are left to a second launch
 // of the 32-bit kernel) and an unpadded, XOR-swizzled staging tile -- 106 instead of 164 bytes of LDS per line, i.e. more
-// lines in flight per CU.  With BYTEROWS on top (small automata, one 1024-lane workgroup per CU sharing a 37 KiB table) the
-// transition rows are indexed by the BYTE itself (256 columns + the identity column, device_tables.h): phase 0 becomes
-// one VALU op per byte and the class lookup -- one of the three LDS instructions per byte -- is gone.
+// lines in flight per CU.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -59,9 +58,6 @@ typedef const u32x4 __attribute__((address_space(1))) * GlobalQuadPtr;
 template <typename RegT>
 using LdsRegPtrT = RegT __attribute__((address_space(3))) *;
 constexpr uint32_t kTdfaWideMaxLine = 0xFFFFu;  // longest line the COMPACT variants take
-#ifndef LC_TDFA_CHUNK
-#define LC_TDFA_CHUNK 16  // bytes stepped per three-phase round (8 halves the live col/tt registers)
-#endif
 
 #ifndef LC_TDFA_STAGE_BYTES
 #define LC_TDFA_STAGE_BYTES 64
@@ -93,14 +89,8 @@ enum { kLabNoStamp = 1, kLabPreClass = 2, kLabGlobalClass = 4, kLabReplicated = 
        kLabDmaStage = 256 /* tdfa_stream_kernel, COMPACT: the staging tile is filled by global_load_lds_dwordx4 (no staging VGPRs) */,
        kLabWaves5 = 512 /* tdfa_stream_kernel: register budget of 5 waves per SIMD (96 VGPRs) */,
        kLabNoDmaWait = 1024 /* DMA staging without the wait for the stage (wrong bytes: timing only -- what the wave loses there) */,
-       kLabCmapA8 = 2048 /* one-stamp pair kernel: the first byte's class from a u8 copy of cmapA built in LDS (class INDEX, scaled on the
-                            VALU): 128 ASCII bytes = 32 dwords = 32 banks, where the u16 table puts byte b and b+64 on one bank (round 6) */,
        kLabPairOne = 4096 /* byte-pair chunks on a ONE-STAMP pair table (device_tables.h TP1_*, LC_TDFA_PAIR=2): exact */,
-       kLabMopUp = 8192 /* tdfa_stream_kernel: the launch behind a COMPACT one -- a small grid whose workgroups take the line blocks in turn */,
-       kLabPersist = 16384 /* tdfa_stream_kernel, one-stamp pair tables: the launch is sized to the workgroups the chip holds, and every
-                              WAVEFRONT goes on with the lines of its place in the next block (tables staged once, no wait for the slowest
-                              wave of a workgroup before the slot is used again) */ };
-constexpr uint32_t kTdfaCmapA8Bytes = 272;  // 256 class indices + the identity class's index (a byte outside the line) + padding
+       kLabMopUp = 8192 /* tdfa_stream_kernel: the launch behind a COMPACT one -- a small grid whose workgroups take the line blocks in turn */ };
 constexpr int kTdfaNoGeneralPrograms = kLabNoGeneral;  // the product's second instantiation (gpu_runtime.hip launchTdfaBlock)
 
 // general register program (a list of moves); rare for log regexes
@@ -151,7 +141,7 @@ __device__ __forceinline__ uint32_t addHighHalf(uint32_t a, uint32_t t) {
 
 // In-order replay of one chunk for wavefronts that met a general register program in it: re-walks the 16 bytes
 // from the chunk's entry state and applies every register program at its own byte.  Rolled up: it is rare.
-template <int BLOCK, typename TdfaReg, bool WIDE, int LAB = 0>
+template <int BLOCK, typename TdfaReg, int LAB = 0>
 __device__ __forceinline__ void tdfaReplayChunk(uint8_t* smem, u32x4 q, uint32_t t, uint32_t base, uint32_t L,
                                                 uint32_t idCol, uint32_t regsBase, uint32_t tid, uint32_t nBytes) {
     typedef LdsRegPtrT<TdfaReg> LdsRegPtr;
@@ -161,66 +151,12 @@ __device__ __forceinline__ void tdfaReplayChunk(uint8_t* smem, u32x4 q, uint32_t
     for (uint32_t j = 0; j < nBytes; ++j) {
         const uint32_t word = (j < 8) ? ((j < 4) ? q.x : q.y) : ((j < 12) ? q.z : q.w);
         const uint32_t b = (word >> ((j & 3) * 8)) & 0xFFu;
-        uint32_t col = (base + j < L) ? (WIDE ? b * 4u : ((LAB & kLabPreClass) ? b : uint32_t(cmap[b]))) : idCol;
+        uint32_t col = (base + j < L) ? ((LAB & kLabPreClass) ? b : uint32_t(cmap[b])) : idCol;
         if constexpr ((LAB & kLabReplicated) != 0) col = (col << 4) + ((tid & 15u) << 2);
         t = *reinterpret_cast<LdsWordPtr>(addLowHalf(col, t));
         if (t & (TD_OP_GENERAL << 16)) tdfaRunMoveList<BLOCK, TdfaReg>(smem, regsBase, t >> 17, base + j, tid);
         else *reinterpret_cast<LdsRegPtr>(addHighHalf(regAddr0, t)) = TdfaReg(base + j);
     }
-}
-
-// steps NB (8 or 16) consecutive bytes held in `words`; CHECKED=false is the mid-line fast path (all NB bytes belong
-// to the line)
-template <int BLOCK, bool CHECKED, int NB, typename TdfaReg = uint32_t, bool WIDE = false, int LAB = 0>
-__device__ __forceinline__ uint32_t tdfaStepBytes(uint8_t* smem, const uint32_t (&words)[NB / 4], uint32_t t,
-                                                  uint32_t base, uint32_t L, uint32_t idCol, uint32_t regsBase,
-                                                  uint32_t tid, const uint8_t* __restrict__ gcmap = nullptr) {
-    typedef LdsRegPtrT<TdfaReg> LdsRegPtr;
-    // the blob sits at LDS address 0, so table offsets are LDS addresses
-    const LdsBytePtr cmap = reinterpret_cast<LdsBytePtr>(TD_CMAP_OFFSET);
-    const uint32_t regAddr0 = regsBase + tdfaRegLane<TdfaReg>(tid) * sizeof(TdfaReg);  // LDS address of regs[0][lane]
-    const uint32_t entry = t;
-    uint32_t col[NB], tt[NB];
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {  // phase 0
-        uint32_t c4;
-        if constexpr (WIDE) {  // rows are indexed by the byte itself: column offset = byte * 4, no lookup
-            const uint32_t w = words[j >> 2];
-            c4 = (j & 3) == 0 ? (w << 2) & 0x3FCu : (w >> ((j & 3) * 8 - 2)) & 0x3FCu;
-        } else if constexpr ((LAB & kLabPreClass) != 0) {
-            c4 = (words[j >> 2] >> ((j & 3) * 8)) & 0xFFu;
-        } else if constexpr ((LAB & kLabGlobalClass) != 0) {
-            c4 = gcmap[(words[j >> 2] >> ((j & 3) * 8)) & 0xFFu];
-        } else {
-            c4 = cmap[(words[j >> 2] >> ((j & 3) * 8)) & 0xFFu];
-        }
-        col[j] = CHECKED ? ((base + j < L) ? c4 : idCol) : c4;
-        if constexpr ((LAB & kLabReplicated) != 0) col[j] = (col[j] << 4) + ((tid & 15u) << 2);
-    }
-    uint32_t seen = 0;
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {  // phase 1
-        t = *reinterpret_cast<LdsWordPtr>(addLowHalf(col[j], t));
-        tt[j] = t;
-        seen |= t;
-    }
-    if (!__any((seen & (TD_OP_GENERAL << 16)) != 0)) {
-        if constexpr ((LAB & kLabNoStamp) == 0) {
-#pragma unroll
-            for (int j = 0; j < NB; ++j)  // phase 2
-                *reinterpret_cast<LdsRegPtr>(addHighHalf(regAddr0, tt[j])) = TdfaReg(base + j);
-        }
-    } else {
-        u32x4 q = {0, 0, 0, 0};
-        q.x = words[0];
-        q.y = words[1];
-        if (NB == 16) {
-            q.z = words[2 % (NB / 4)];
-            q.w = words[3 % (NB / 4)];
-        }
-        tdfaReplayChunk<BLOCK, TdfaReg, WIDE, LAB>(smem, q, entry, base, L, idCol, regsBase, tid, NB);
-    }
-    return t;
 }
 
 // Tables whose multi-stamp register programs were folded into set registers (regex_handle.cpp, planTdfaFold; the fold words
@@ -409,260 +345,8 @@ __device__ __forceinline__ void tdfaSignalDone(uint32_t* doneCounter, uint32_t* 
 
 // Byte-PAIR stepping (device_tables.h TP_*): the state chain -- the only serial dependency, one LDS round trip per link --
 // has one link per TWO bytes: t = pair32[(t & 0xFFFF) + cmapA[byte 2k] + cmap8[byte 2k+1]].  The entry also names the
-// register each of the two bytes stamps.  Same phases as tdfaStepBytes; NB/2 dependent lookups instead of NB.
+// register each of the two bytes stamps.  Where the pair table sits in the staged blob:
 struct TdfaPairInfo {
     uint32_t base, rowBytes, cmapA, idA;
 };
 typedef const uint16_t __attribute__((address_space(3))) * LdsHalfPtr;
-
-template <int BLOCK, bool CHECKED, int NB, typename TdfaReg = uint32_t>
-__device__ __forceinline__ uint32_t tdfaStepPairs(uint8_t* smem, const uint32_t (&words)[NB / 4], uint32_t t,
-                                                  uint32_t base, uint32_t L, uint32_t idCol, uint32_t regsBase,
-                                                  uint32_t tid, const TdfaPairInfo& pi, uint32_t singleRowBytes) {
-    typedef LdsRegPtrT<TdfaReg> LdsRegPtr;
-    const LdsBytePtr cmap = reinterpret_cast<LdsBytePtr>(TD_CMAP_OFFSET);
-    const uint32_t regAddr0 = regsBase + tdfaRegLane<TdfaReg>(tid) * sizeof(TdfaReg);
-    static_assert((BLOCK & (BLOCK - 1)) == 0 && BLOCK >= 64 && BLOCK <= 1024, "register stride must be a power of two");
-    constexpr uint32_t kRegShift = (BLOCK == 1024 ? 12 : BLOCK == 512 ? 11 : BLOCK == 256 ? 10 : BLOCK == 128 ? 9 : 8) -
-                                   (sizeof(TdfaReg) == 2 ? 1 : 0);  // log2(BLOCK * sizeof(TdfaReg))
-    const uint32_t entry = t;
-    uint32_t col[NB / 2], tt[NB / 2];
-#pragma unroll
-    for (int p = 0; p < NB / 2; ++p) {  // phase 0: two class lookups per pair, independent
-        const int j = 2 * p;
-        const uint32_t b0 = (words[j >> 2] >> ((j & 3) * 8)) & 0xFFu;
-        const uint32_t b1 = (words[(j + 1) >> 2] >> (((j + 1) & 3) * 8)) & 0xFFu;
-        uint32_t a = *reinterpret_cast<LdsHalfPtr>(pi.cmapA + b0 * 2);
-        uint32_t c = cmap[b1];
-        if (CHECKED) {
-            a = (base + j < L) ? a : pi.idA;
-            c = (base + j + 1 < L) ? c : idCol;
-        }
-        col[p] = a + c;
-    }
-    uint32_t seen = 0;
-#pragma unroll
-    for (int p = 0; p < NB / 2; ++p) {  // phase 1: the state chain, one link per pair
-        t = *reinterpret_cast<LdsWordPtr>(addLowHalf(col[p], t));
-        tt[p] = t;
-        seen |= t;
-    }
-    if (!__any((seen & ((TP_GENERAL << 16) | (TP_GENERAL << 24))) != 0)) {
-#pragma unroll
-        for (int p = 0; p < NB / 2; ++p) {  // phase 2: capture writes, two per pair, independent
-            const uint32_t r0 = (tt[p] >> 16) & 0xFFu, r1 = tt[p] >> 24;
-            *reinterpret_cast<LdsRegPtr>(regAddr0 + (r0 << kRegShift)) = TdfaReg(base + 2 * p);
-            *reinterpret_cast<LdsRegPtr>(regAddr0 + (r1 << kRegShift)) = TdfaReg(base + 2 * p + 1);
-        }
-    } else {  // a general register program somewhere in the chunk: replay it byte by byte on the single-byte table
-        u32x4 q = {0, 0, 0, 0};
-        q.x = words[0];
-        q.y = words[1];
-        if (NB == 16) {
-            q.z = words[2 % (NB / 4)];
-            q.w = words[3 % (NB / 4)];
-        }
-        const uint32_t state = ((entry & 0xFFFFu) - pi.base) / pi.rowBytes;
-        tdfaReplayChunk<BLOCK, TdfaReg, false>(smem, q, TD_TRANS_OFFSET + state * singleRowBytes, base, L, idCol, regsBase, tid,
-                                               NB);
-    }
-    return t;
-}
-
-// minLen: lines shorter than this are not this launch's business (the 32-bit kernel mopping up behind a COMPACT one)
-template <int BLOCK, bool PAIR, bool COMPACT = false, bool BYTEROWS = false, int LAB = 0>
-__global__ __launch_bounds__(BLOCK, LC_TDFA_MIN_WAVES) void tdfa_match_kernel(const uint8_t* __restrict__ data,
-                                                           const uint32_t* __restrict__ off,
-                                                           const uint32_t* __restrict__ len, uint32_t sepBytes,
-                                                           uint32_t minLen,
-                                                           uint32_t nLines, const uint32_t* __restrict__ nLinesPtr,
-                                                           const uint32_t* __restrict__ order,
-                                                           const uint32_t* __restrict__ resume,
-                                                           const uint32_t* __restrict__ blob,
-                                                           uint32_t blobBytes, uint32_t regBytes, uint32_t nGroupsOut,
-                                                           int32_t* __restrict__ caps, uint8_t* __restrict__ status,
-                                                           uint32_t* __restrict__ longFlag, uint32_t launchSeq,
-                                                           uint32_t* __restrict__ doneCounter, uint32_t* __restrict__ doneFlag,
-                                                           uint32_t doneSeq) {
-    static_assert(!(BYTEROWS && PAIR) && (COMPACT || !BYTEROWS), "byte rows: compact only, and no pair extension");
-    constexpr bool WIDE = BYTEROWS;
-    typedef typename std::conditional<COMPACT, uint16_t, uint32_t>::type TdfaReg;
-    // staging rows: padded to 80 bytes (conflict-free b128 reads), or -- COMPACT -- 64 bytes with the 16-byte segments of
-    // row r stored at segment ^ ((r >> 1) & 3), which is conflict-free without the padding
-    constexpr uint32_t kRowStride = COMPACT ? kTdfaStageBytes : kTdfaRowStride;
-    constexpr uint32_t kStagePerWave = 64 * kRowStride;
-    static_assert(!COMPACT || kTdfaStageBytes == 64, "the swizzle is written for 4 segments per row");
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    const uint32_t tid = threadIdx.x;
-    if (nLinesPtr) {  // line count produced on the device (split kernels) -- no host round trip between the launches
-        const uint32_t dyn = *nLinesPtr;
-        nLines = dyn < nLines ? dyn : nLines;
-    }
-    // The COMPACT launch raises *longFlag to its sequence number when it meets a line it has to leave behind; the mop-up
-    // launch that follows it on the stream has nothing to do while the flag is older than that.
-    if (minLen && longFlag && __atomic_load_n(longFlag, __ATOMIC_RELAXED) < launchSeq) return;
-    if (minLen) {  // mop-up launch: usually no line of this workgroup is long enough -- leave before staging the tables
-        const uint32_t s0 = blockIdx.x * BLOCK + tid;
-        bool mine = false;
-        if (s0 < nLines) {
-            const uint32_t ln = order ? order[s0] : s0;
-            uint32_t l0 = len ? len[ln] : off[ln + 1] - off[ln] - sepBytes;
-            if (resume) {
-                const uint32_t f0 = resume[ln];
-                l0 -= f0 < l0 ? f0 : l0;
-            }
-            mine = l0 >= minLen;
-        }
-        // (not __syncthreads_or: its workgroup reduction brings static LDS of its own, and the tables must sit at LDS
-        // address 0)
-        volatile uint32_t* flag = reinterpret_cast<volatile uint32_t*>(smem);
-        if (tid == 0) *flag = 0;
-        __syncthreads();
-        if (mine) *flag = 1;
-        __syncthreads();
-        const bool any = *flag != 0;
-        __syncthreads();  // everybody has read the flag before the tables overwrite it
-        if (!any) return;
-    }
-    {  // stage the tables: 16-byte coalesced copies
-        const uint4* src = reinterpret_cast<const uint4*>(blob);
-        uint4* dst = reinterpret_cast<uint4*>(smem);
-        for (uint32_t i = tid; i < blobBytes / 16; i += BLOCK) dst[i] = src[i];
-        tdfaClearRegisters<BLOCK>(smem, blob, blobBytes, regBytes);
-    }
-    __syncthreads();
-    const uint32_t* hdr = reinterpret_cast<const uint32_t*>(smem);
-    const uint32_t rowBytes = hdr[TD_ROW_BYTES];
-    const uint32_t idCol = hdr[TD_ID_COL];
-    const uint32_t regsBase = blobBytes;
-    uint32_t t = hdr[TD_START_ROW];  // low 16 bits: LDS address of the current state's row
-    TdfaPairInfo pi{};
-    // single-byte row address -> the row the kernel actually walks (PAIR: the same state's row in the pair table)
-    auto walkRow = [&](uint32_t singleRow) {
-        return PAIR ? pi.base + ((singleRow & 0xFFFFu) - TD_TRANS_OFFSET) / rowBytes * pi.rowBytes : singleRow;
-    };
-    if constexpr (PAIR) {
-        const uint32_t* ph = reinterpret_cast<const uint32_t*>(smem + hdr[TD_OFF_PAIR]);
-        pi = TdfaPairInfo{ph[TP_BASE], ph[TP_ROW_BYTES], ph[TP_OFF_CMAPA], ph[TP_ID_A]};
-        t = walkRow(t);
-    }
-    const uint32_t deadRow = PAIR ? pi.base : TD_TRANS_OFFSET;
-    const uint8_t* gcmap = reinterpret_cast<const uint8_t*>(blob) + TD_CMAP_OFFSET;  // (LAB variants only)
-
-    const uint32_t lane = tid & 63, wave = tid >> 6;
-    const uint32_t stageBase = blobBytes + regBytes + wave * kStagePerWave;  // this wave's staging rows (LDS address)
-
-    const uint32_t slot = blockIdx.x * BLOCK + tid;
-    bool live = slot < nLines;
-    const uint32_t line = (live && order) ? order[slot] : slot;  // length-aware schedule (sched_kernel.hpp)
-    uint32_t o = 0, L = 0;
-    uint32_t from = 0;  // search patterns: offset inside the line where this search resumes (0 = a fresh search)
-    if (live) {
-        o = off[line];
-        L = len ? len[line] : off[line + 1] - o - sepBytes;
-        if (resume) {
-            from = resume[line];
-            from = from < L ? from : L;
-            if (from) {  // only the wrapper's prefix thread is alive; what it remembers is the class of the previous byte
-                const uint32_t* startAfter = reinterpret_cast<const uint32_t*>(smem + hdr[TD_OFF_STARTAFTER]);
-                t = walkRow(startAfter[smem[TD_CMAP_OFFSET + data[size_t(o) + from - 1]] >> 2]);
-                o += from;
-                L -= from;
-            }
-        }
-        if ((COMPACT && L > kTdfaWideMaxLine) || L < minLen) {  // another launch decides this line
-            if (COMPACT && L > kTdfaWideMaxLine && longFlag) atomicMax(longFlag, launchSeq);
-            live = false;
-            L = 0;
-        }
-    }
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(data) + o;
-    const uint32_t head = uint32_t(addr & 15);
-    const uintptr_t rowStart = addr - head;              // 16-byte aligned start of this lane's line
-    const uint32_t span = L ? head + L : 0;              // staged bytes [0, span) of the aligned run are needed
-    const uint32_t myStages = (span + kTdfaStageBytes - 1) / kTdfaStageBytes;
-    uint32_t maxStages = myStages;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t other = __shfl_xor(maxStages, d, 64);
-        maxStages = other > maxStages ? other : maxStages;
-    }
-
-    // cooperative load plan: kTdfaLoads lanes share one line; load i of a stage serves line r = (64/kTdfaLoads)*i +
-    // lane/kTdfaLoads, 16-byte segment lane%kTdfaLoads
-    const uint32_t seg = (lane % kTdfaLoads) * 16;
-    uintptr_t srcAddr[kTdfaLoads];
-    uint32_t srcSpan[kTdfaLoads], dstAddr[kTdfaLoads];
-#pragma unroll
-    for (int i = 0; i < kTdfaLoads; ++i) {
-        const int r = (64 / kTdfaLoads) * i + int(lane / kTdfaLoads);
-        const uint32_t lo = __shfl(uint32_t(rowStart), r, 64);
-        const uint32_t hi = __shfl(uint32_t(rowStart >> 32), r, 64);
-        srcAddr[i] = ((uintptr_t(hi) << 32) | lo) + seg;
-        srcSpan[i] = __shfl(span, r, 64);
-        dstAddr[i] = stageBase + uint32_t(r) * kRowStride + (COMPACT ? seg ^ (((uint32_t(r) >> 1) & 3u) << 4) : seg);
-    }
-    const uint32_t myRow = stageBase + lane * kRowStride;
-    const uint32_t mySwizzle = COMPACT ? ((lane >> 1) & 3u) << 4 : 0u;
-
-    u32x4 in[kTdfaLoads];
-#pragma unroll
-    for (int i = 0; i < kTdfaLoads; ++i) {  // stage 0
-        in[i] = u32x4{0, 0, 0, 0};
-        if (seg < srcSpan[i]) in[i] = *reinterpret_cast<GlobalQuadPtr>(srcAddr[i]);
-    }
-
-    for (uint32_t s = 0; s < maxStages; ++s) {
-        // publish stage s to LDS, then put stage s+1 in flight
-        tdfaWaveLdsSync();
-#pragma unroll
-        for (int i = 0; i < kTdfaLoads; ++i) *reinterpret_cast<LdsQuadPtr>(dstAddr[i]) = in[i];
-        tdfaWaveLdsSync();
-        const uint32_t nextOff = (s + 1) * kTdfaStageBytes;
-#pragma unroll
-        for (int i = 0; i < kTdfaLoads; ++i) {
-            in[i] = u32x4{0, 0, 0, 0};
-            if (nextOff + seg < srcSpan[i]) in[i] = *reinterpret_cast<GlobalQuadPtr>(srcAddr[i] + nextOff);
-        }
-#pragma unroll 1
-        for (uint32_t k = 0; k < kTdfaStageBytes / 16; ++k) {
-            const u32x4 q = *reinterpret_cast<LdsQuadPtr>(myRow + ((k * 16) ^ mySwizzle));
-            const uint32_t base = s * kTdfaStageBytes + k * 16 - head;  // line offset of byte 0 (wraps in the head)
-            const bool full = base < L && L - base >= 16;
-#if LC_TDFA_CHUNK == 16
-            const uint32_t w[4] = {q.x, q.y, q.z, q.w};
-            if constexpr (PAIR) {
-                if (__all(full)) t = tdfaStepPairs<BLOCK, false, 16, TdfaReg>(smem, w, t, base, L, idCol, regsBase, tid, pi, rowBytes);
-                else t = tdfaStepPairs<BLOCK, true, 16, TdfaReg>(smem, w, t, base, L, idCol, regsBase, tid, pi, rowBytes);
-            } else {
-                if (__all(full)) t = tdfaStepBytes<BLOCK, false, 16, TdfaReg, WIDE, LAB>(smem, w, t, base, L, idCol, regsBase, tid, gcmap);
-                else t = tdfaStepBytes<BLOCK, true, 16, TdfaReg, WIDE, LAB>(smem, w, t, base, L, idCol, regsBase, tid, gcmap);
-            }
-#else
-            const uint32_t w0[2] = {q.x, q.y}, w1[2] = {q.z, q.w};
-            if constexpr (PAIR) {
-                if (__all(full)) {
-                    t = tdfaStepPairs<BLOCK, false, 8, TdfaReg>(smem, w0, t, base, L, idCol, regsBase, tid, pi, rowBytes);
-                    t = tdfaStepPairs<BLOCK, false, 8, TdfaReg>(smem, w1, t, base + 8, L, idCol, regsBase, tid, pi, rowBytes);
-                } else {
-                    t = tdfaStepPairs<BLOCK, true, 8, TdfaReg>(smem, w0, t, base, L, idCol, regsBase, tid, pi, rowBytes);
-                    t = tdfaStepPairs<BLOCK, true, 8, TdfaReg>(smem, w1, t, base + 8, L, idCol, regsBase, tid, pi, rowBytes);
-                }
-            } else if (__all(full)) {
-                t = tdfaStepBytes<BLOCK, false, 8, TdfaReg, WIDE>(smem, w0, t, base, L, idCol, regsBase, tid);
-                t = tdfaStepBytes<BLOCK, false, 8, TdfaReg, WIDE>(smem, w1, t, base + 8, L, idCol, regsBase, tid);
-            } else {
-                t = tdfaStepBytes<BLOCK, true, 8, TdfaReg, WIDE>(smem, w0, t, base, L, idCol, regsBase, tid);
-                t = tdfaStepBytes<BLOCK, true, 8, TdfaReg, WIDE>(smem, w1, t, base + 8, L, idCol, regsBase, tid);
-            }
-#endif
-        }
-        // every lane dead (or past its end in the identity column): nothing left to decide for this wavefront
-        if (__all((t & 0xFFFFu) == deadRow || s + 1 >= myStages)) break;
-    }
-
-    const uint32_t state = PAIR ? ((t & 0xFFFFu) - pi.base) / pi.rowBytes : ((t & 0xFFFFu) - TD_TRANS_OFFSET) / rowBytes;
-    tdfaWriteResults<BLOCK, TdfaReg>(smem, stageBase, regsBase, state, live, line, L, from, order != nullptr, nGroupsOut, caps,
-                                     status);
-    tdfaSignalDone(doneCounter, doneFlag, doneSeq);
-}

@@ -130,11 +130,7 @@ __global__ __launch_bounds__(kTdfaL2Block) void tdfa_l2_kernel(const uint8_t* __
 // Semantics: exactly tdfa_l2_kernel's (same blob, same results -- tests/test_gpu_parity.py runs both on the same lines).
 // LDS: cmap[256] | per wave: registers [nRegs] | (stageBytes != 0) the register programs.
 
-// LT (round 5): the automaton is small (transition table + register programs <= 48 KB: the LDS-size automata of handles that ASK for
-// this kernel -- lcPreferWaveTdfa, the Grok matcher's entries): the transition table is staged too, and a byte that is not part of a
-// quiet run costs an LDS read instead of a read through L2 (a search wrapper's lazy prefix makes EVERY byte such a byte: 146 -> ~40 ns).
-// stageBytes then counts from TL_OFF_TRANS (trans, opsStart, ops are contiguous in the blob).
-// (round 6) scalar loads for the walk of tdfaWaveBody<false>: the table word of a wave-uniform (state, class) through the scalar cache
+// (round 6) scalar loads for the walk of tdfaWaveBody: the table word of a wave-uniform (state, class) through the scalar cache
 // into an SGPR.  The compiler's own choice for these reads -- the pointers come out of a job table, so their address space is unknown
 // to it -- was flat_load_dword + v_readfirstlane with the state and the position in VGPRs and every loop condition an exec mask:
 // 45 instructions per byte (profiles/round6_wave_walk_isa.md).  The tables are read-only for the kernel's lifetime.
@@ -159,7 +155,6 @@ __device__ __forceinline__ uint32_t lcScalarLoad16(const void* base, uint32_t in
     return (index & 1u) ? (w >> 16) : (w & 0xFFFFu);
 }
 
-template <bool LT>
 __device__ __forceinline__ void tdfaWaveBody(const uint8_t* __restrict__ data, const uint32_t* __restrict__ off,
                                              const uint32_t* __restrict__ len, uint32_t sepBytes, uint32_t nLines,
                                              const uint32_t* __restrict__ nLinesPtr, const uint32_t* __restrict__ order,
@@ -178,7 +173,7 @@ __device__ __forceinline__ void tdfaWaveBody(const uint8_t* __restrict__ data, c
     for (uint32_t r = lane; r < nRegs; r += 64) regs[r] = 0xFFFFFFFFu;  // unset = -1
     if (stageBytes) {
         uint32_t* dst = wregs + kTdfaWaveValues * nRegs;
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(blob) + blob[LT ? TL_OFF_TRANS : TL_OFF_OPSSTART]);
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(blob) + blob[TL_OFF_OPSSTART]);
         for (uint32_t i = tid; i < stageBytes / 4; i += kTdfaWaveBlock) dst[i] = src[i];
     }
     __syncthreads();
@@ -188,20 +183,7 @@ __device__ __forceinline__ void tdfaWaveBody(const uint8_t* __restrict__ data, c
     const uint32_t line = __builtin_amdgcn_readfirstlane(order ? order[slot] : slot);
     const uint8_t* base = reinterpret_cast<const uint8_t*>(blob);
     const uint2* quietTab = reinterpret_cast<const uint2*>(base + blob[TL_OFF_QUIET]);
-    const uint8_t* staged = reinterpret_cast<const uint8_t*>(wregs + kTdfaWaveValues * nRegs);
-    const uint32_t* trans;
-    const uint32_t* opsStart;
-    const uint16_t* ops;
-    if constexpr (LT) {
-        trans = reinterpret_cast<const uint32_t*>(staged);
-        opsStart = reinterpret_cast<const uint32_t*>(staged + (blob[TL_OFF_OPSSTART] - blob[TL_OFF_TRANS]));
-        ops = reinterpret_cast<const uint16_t*>(staged + (blob[TL_OFF_OPS] - blob[TL_OFF_TRANS]));
-    } else {
-        trans = reinterpret_cast<const uint32_t*>(base + blob[TL_OFF_TRANS]);
-        opsStart = stageBytes ? reinterpret_cast<const uint32_t*>(staged) : reinterpret_cast<const uint32_t*>(base + blob[TL_OFF_OPSSTART]);
-        ops = stageBytes ? reinterpret_cast<const uint16_t*>(staged + (blob[TL_OFF_OPS] - blob[TL_OFF_OPSSTART]))
-                         : reinterpret_cast<const uint16_t*>(base + blob[TL_OFF_OPS]);
-    }
+    const uint32_t* trans = reinterpret_cast<const uint32_t*>(base + blob[TL_OFF_TRANS]);
     const uint32_t o = __builtin_amdgcn_readfirstlane(off[line]);
     const uint32_t L = __builtin_amdgcn_readfirstlane(len ? len[line] : off[line + 1] - o - sepBytes);
     uint32_t state = blob[TL_START], from = 0;
@@ -234,8 +216,8 @@ __device__ __forceinline__ void tdfaWaveBody(const uint8_t* __restrict__ data, c
         curWord = classesOf((w < nWords) ? words[w] : 0);
     }
     uint32_t idx = head + from;  // position in the word-aligned view
-    if constexpr (!LT) {
-        // ---- the walk, every control value in an SGPR (round 6; see lcScalarLoad32).  Same steps as the loop below, byte for byte.
+    {
+        // ---- the walk, every control value in an SGPR (round 6; see lcScalarLoad32).
         const uint32_t uNcls = __builtin_amdgcn_readfirstlane(ncls), uAbsorb = __builtin_amdgcn_readfirstlane(absorb),
                        uMiss = __builtin_amdgcn_readfirstlane(miss), uEnd = __builtin_amdgcn_readfirstlane(end),
                        uHead = __builtin_amdgcn_readfirstlane(head), uWords = __builtin_amdgcn_readfirstlane(nWords);
@@ -361,57 +343,6 @@ __device__ __forceinline__ void tdfaWaveBody(const uint8_t* __restrict__ data, c
 #endif
         state = uState;
         idx = uIdx;
-    } else
-    while (idx < end && state != 0 && state != absorb && state != miss) {
-        if ((idx >> 8) != chunk) {
-            chunk = idx >> 8;
-            const uint32_t w = (chunk << 6) + lane;
-            curWord = classesOf((w < nWords) ? words[w] : 0);
-        }
-        const uint32_t wsel = __builtin_amdgcn_readlane(curWord, (idx >> 2) & 63u);
-        const uint32_t cls = (wsel >> ((idx & 3u) * 8)) & 0xFFu;
-        const uint32_t t = __builtin_amdgcn_readfirstlane(trans[state * ncls + cls]);
-        const uint32_t prog = t >> 16, next = t & 0xFFFFu;
-        if (prog) {
-            const uint32_t pos = idx - head;
-            uint32_t at = __builtin_amdgcn_readfirstlane(opsStart[prog]);
-            const uint32_t n = __builtin_amdgcn_readfirstlane(ops[at]);
-            for (uint32_t k = 0; k < n; ++k) {  // (every lane stores the same word: one LDS write)
-                const uint32_t op = __builtin_amdgcn_readfirstlane(ops[++at]);
-                const uint32_t src = op >> 8;
-                regs[op & 0xFFu] = src == TD_REG_POS ? pos : regs[src];
-            }
-        } else if (next == state) {
-            // a quiet byte: find the end of the run -- every lane tests its 4 bytes of the chunk, chunk after chunk
-            const uint2 q2 = quietTab[state];
-            const uint64_t quiet = (uint64_t(q2.y) << 32) | q2.x;
-            uint32_t stop = end;
-            for (;;) {
-                const uint32_t chunkBase = chunk << 8;
-                uint32_t firstHit = 4;
-#pragma unroll
-                for (int j = 3; j >= 0; --j) {
-                    const uint32_t bi = chunkBase + lane * 4 + uint32_t(j);
-                    const uint32_t c = (curWord >> (8 * j)) & 0xFFu;
-                    const bool isQuiet = c < 64 && ((quiet >> c) & 1ull);
-                    if (bi > idx && bi < end && !isQuiet) firstHit = uint32_t(j);
-                }
-                const uint64_t hit = __ballot(firstHit < 4);
-                if (hit) {
-                    const int l = __ffsll((long long)hit) - 1;
-                    stop = chunkBase + uint32_t(l) * 4 + uint32_t(__builtin_amdgcn_readlane(int(firstHit), l));
-                    break;
-                }
-                if (chunkBase + 256 >= end) break;  // the run reaches the end of the value
-                ++chunk;
-                const uint32_t w = (chunk << 6) + lane;
-                curWord = classesOf((w < nWords) ? words[w] : 0);
-            }
-            idx = stop;
-            continue;
-        }
-        state = next;
-        ++idx;
     }
     if (miss && state == miss) {
         if (lane == 0) {
@@ -437,7 +368,6 @@ __device__ __forceinline__ void tdfaWaveBody(const uint8_t* __restrict__ data, c
     if (lane == 0) status[line] = matched ? LC_MATCH : LC_NOMATCH;
 }
 
-template <bool LT>
 __global__ __launch_bounds__(kTdfaWaveBlock) void tdfa_wave_kernel(const uint8_t* __restrict__ data, const uint32_t* __restrict__ off,
                                                                   const uint32_t* __restrict__ len, uint32_t sepBytes, uint32_t nLines,
                                                                   const uint32_t* __restrict__ nLinesPtr, const uint32_t* __restrict__ order,
@@ -445,7 +375,7 @@ __global__ __launch_bounds__(kTdfaWaveBlock) void tdfa_wave_kernel(const uint8_t
                                                                   uint32_t nGroupsOut, int32_t* __restrict__ caps,
                                                                   uint8_t* __restrict__ status, uint32_t stageBytes,
                                                                   uint32_t* __restrict__ pendingFlag, uint32_t launchSeq) {
-    tdfaWaveBody<LT>(data, off, len, sepBytes, nLines, nLinesPtr, order, resume, blob, nGroupsOut, caps, status, stageBytes, pendingFlag,
+    tdfaWaveBody(data, off, len, sepBytes, nLines, nLinesPtr, order, resume, blob, nGroupsOut, caps, status, stageBytes, pendingFlag,
                      launchSeq, 4u /* LC_PENDING */, blockIdx.x);
 }
 
@@ -466,6 +396,6 @@ __global__ __launch_bounds__(kTdfaWaveBlock) void tdfa_wave_multi_kernel(const u
         else hi = mid;
     }
     const TdfaWaveJob j = reinterpret_cast<const TdfaWaveJob*>(jobTable + kTdfaWaveMaxJobs)[lo];  // (wave-uniform: scalar loads)
-    tdfaWaveBody<false>(data, j.off, j.len, 0u, j.n, nullptr, nullptr, j.resume, j.blob, j.nGroupsOut, j.caps, j.status, j.stageBytes, j.missFlag,
+    tdfaWaveBody(data, j.off, j.len, 0u, j.n, nullptr, nullptr, j.resume, j.blob, j.nGroupsOut, j.caps, j.status, j.stageBytes, j.missFlag,
                         j.seq, j.missStatus, b - j.firstBlock);
 }

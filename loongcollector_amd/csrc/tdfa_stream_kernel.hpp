@@ -1,9 +1,8 @@
 // tdfa_stream_kernel.hpp -- the tagged-DFA engine with its LDS instructions INTERLEAVED per byte (included by
-// gpu_runtime.hip only; tdfa_kernel.hpp holds the phase-separated original, which stays for the byte-pair and byte-row
-// table formats).
+// gpu_runtime.hip only; tdfa_kernel.hpp holds the pieces it shares with the tools).
 //
-// Why a second kernel.  tdfa_match_kernel steps a 16-byte chunk in three bursts: 16 class lookups, the 16 dependent chain
-// links, 16 capture stamps.  The CU's LDS serves the instructions of all its waves in arrival order, so a chain link -- the
+// Why interleaved.  The phase-separated original (removed) stepped a 16-byte chunk in three bursts: 16 class
+// lookups, the 16 dependent chain links, 16 capture stamps.  The CU's LDS serves the instructions of all its waves in arrival order, so a chain link -- the
 // only thing a wave ever waits for -- queues behind the 32..64 LDS cycles of whatever burst another wave has just issued:
 // measured, a link costs ~310 cycles in that kernel against ~115 for the same mix issued one-one-one
 // (tools/lds_chain_bench.hip mode 2), with the LDS only half busy (profiles/round1: SQ_LDS_IDX_ACTIVE 55 %).  Here every
@@ -142,7 +141,7 @@ __device__ __forceinline__ uint32_t tdfaStreamPairChunk(uint32_t t, const uint32
 // max(register, pos + 1) -- only in chunks in which some lane of the wavefront met a DOUBLE.  Positions only grow along a line
 // and registers start at 0, so "latest" is "largest" and the order of the two kinds of store among themselves does not matter:
 // tests/helpers/table_interp.py TdfaPair1Interp is this function, store for store.
-template <int BLOCK, int NB, bool CHECKED, typename TdfaReg, bool A8 = false>
+template <int BLOCK, int NB, bool CHECKED, typename TdfaReg>
 __device__ __forceinline__ uint32_t tdfaStreamPair1Chunk(uint32_t t, const uint32_t (&colp)[NB / 2], uint32_t (&na)[NB / 2],
                                                          uint32_t (&nc)[NB / 2], const uint32_t (&nwords)[NB / 4], uint32_t nbase,
                                                          uint32_t L, uint32_t cmapA, uint32_t idAAddr,
@@ -159,12 +158,10 @@ __device__ __forceinline__ uint32_t tdfaStreamPair1Chunk(uint32_t t, const uint3
         asm volatile("v_bfe_u32 %0, %1, %2, 8" : "=v"(b0) : "v"(nwords[p >> 1]), "n"((p & 1) * 16));
         asm volatile("v_bfe_u32 %0, %1, %2, 8" : "=v"(b1) : "v"(nwords[p >> 1]), "n"((p & 1) * 16 + 8));
         if constexpr (CHECKED) {
-            if constexpr (A8) na[p] = *reinterpret_cast<LdsBytePtr>((nbase + 2 * p < L) ? cmapA + b0 : idAAddr);  // (cmapA / idAAddr: the u8 copy, its 257th byte)
-            else na[p] = *reinterpret_cast<LdsHalfPtr>((nbase + 2 * p < L) ? cmapA + b0 * 2 : idAAddr);
+            na[p] = *reinterpret_cast<LdsHalfPtr>((nbase + 2 * p < L) ? cmapA + b0 * 2 : idAAddr);
             nc[p] = *reinterpret_cast<LdsBytePtr>((nbase + 2 * p + 1 < L) ? TD_CMAP_OFFSET + b1 : kTdfaIdColByteAddr);
         } else {
-            if constexpr (A8) na[p] = *reinterpret_cast<LdsBytePtr>(cmapA + b0);
-            else na[p] = *reinterpret_cast<LdsHalfPtr>(cmapA + b0 * 2);
+            na[p] = *reinterpret_cast<LdsHalfPtr>(cmapA + b0 * 2);
 #if LC_TDFA_GCLASS
             // Round 6 experiment: the SECOND byte's class from the table's copy in global memory (256 bytes: two cache lines that never
             // leave the vector L1) -- the texture path is idle in this kernel, the LDS queue is what the chain link waits in
@@ -253,7 +250,7 @@ __device__ __forceinline__ void tdfaStreamBody(
     static_assert(!PAIR || (LAB & kLabPreClass) == 0, "no pre-classified pairs");
     typedef typename std::conditional<COMPACT, uint16_t, uint32_t>::type TdfaReg;
     typedef LdsRegPtrT<TdfaReg> LdsRegPtr;
-    constexpr uint32_t kRowStride = COMPACT ? kTdfaStageBytes : kTdfaRowStride;  // (tdfa_match_kernel's two tile layouts)
+    constexpr uint32_t kRowStride = COMPACT ? kTdfaStageBytes : kTdfaRowStride;  // (the two tile layouts, tdfa_kernel.hpp)
     constexpr uint32_t kStagePerWave = 64 * kRowStride;
     constexpr bool DMA = COMPACT && (LAB & kLabDmaStage) != 0 && kTdfaStageBytes == 64;
     constexpr bool PAIR1 = PAIR && (LAB & kLabPairOne) != 0;  // the pair table is a ONE-STAMP table (the launcher checks TP_FORMAT)
@@ -265,7 +262,7 @@ __device__ __forceinline__ void tdfaStreamBody(
         nLines = dyn < nLines ? dyn : nLines;
     }
     if (minLen && longFlag && __atomic_load_n(longFlag, __ATOMIC_RELAXED) < launchSeq) return;
-    if (minLen) {  // mop-up launch behind a COMPACT one (see tdfa_match_kernel)
+    if (minLen) {  // mop-up launch behind a COMPACT one: usually no line of this workgroup is long enough
         const uint32_t s0 = blockId * BLOCK + tid;
         bool mine = false;
         if (s0 < nLines) {
@@ -277,6 +274,7 @@ __device__ __forceinline__ void tdfaStreamBody(
             }
             mine = l0 >= minLen;
         }
+        // (not __syncthreads_or: its workgroup reduction brings static LDS of its own, and the tables must sit at LDS address 0)
         volatile uint32_t* flag = reinterpret_cast<volatile uint32_t*>(smem);
         if (tid == 0) *flag = 0;
         __syncthreads();
@@ -291,16 +289,6 @@ __device__ __forceinline__ void tdfaStreamBody(
         uint4* dst = reinterpret_cast<uint4*>(smem);
         for (uint32_t i = tid; i < blobBytes / 16; i += BLOCK) dst[i] = src[i];
         tdfaClearRegisters<BLOCK>(smem, blob, blobBytes, regBytes);
-        if constexpr (PAIR1 && (LAB & kLabCmapA8) != 0) {
-            // the u8 copy of the first-byte class map, behind the tiles: class INDEX = cmapA[b] / (the first byte's stride); byte 256 = the
-            // identity class (a byte outside the line)
-            const uint32_t po = blob[TD_OFF_PAIR];
-            const uint32_t* gph = reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(blob) + po);
-            const uint16_t* gA = reinterpret_cast<const uint16_t*>(reinterpret_cast<const uint8_t*>(blob) + gph[TP_OFF_CMAPA]);
-            const uint32_t strideA = blob[TD_ID_COL] + 4;  // (classes + 1) * 4
-            uint8_t* a8 = smem + blobBytes + regBytes + (BLOCK / 64) * 64 * (COMPACT ? kTdfaStageBytes : kTdfaRowStride);
-            for (uint32_t i = tid; i < 257; i += BLOCK) a8[i] = uint8_t((i < 256 ? uint32_t(gA[i]) : gph[TP_ID_A]) / strideA);
-        }
         if constexpr (PAIR1) {  // ("latest stamp" = "largest offset" for the settled doubles: every register starts at 0)
             if (((blob[TD_NREGS] >> 16) & 0x1FFFu) == 0) {
                 uint32_t* regs = reinterpret_cast<uint32_t*>(smem + blobBytes);
@@ -332,12 +320,10 @@ __device__ __forceinline__ void tdfaStreamBody(
 
     const uint32_t lane = tid & 63, wave = tid >> 6;
     const uint32_t stageBase = blobBytes + regBytes + wave * kStagePerWave;
-    // (kLabCmapA8) LDS address of the u8 first-byte class map and the stride a class index scales by
-    const uint32_t cmapA8 = blobBytes + regBytes + (BLOCK / 64) * kStagePerWave;
-    const uint32_t strideA8 = idCol + 4;
 
     const uint32_t tStart = t;
-    // ---- one block of BLOCK lines (everything from here on is the wavefront's own: its tile, its lanes' register columns)
+    // ---- one block of BLOCK lines (everything from here on is the wavefront's own: its tile, its lanes' register columns).  A lambda
+    // called once: written inline, the compiler allocates the kernels' scalar registers differently (the ISA of round 6 is kept).
     auto walkBlock = [&](const uint32_t blockNow) {
     t = tStart;
     const uint32_t slot = blockNow * BLOCK + tid;
@@ -535,13 +521,11 @@ __device__ __forceinline__ void tdfaStreamBody(
             bool general;
             if constexpr (PAIR1) {
                 uint32_t na[NC], nc[NC];
-                constexpr bool A8 = (LAB & kLabCmapA8) != 0;
-                const uint32_t mapA = A8 ? cmapA8 : pi.cmapA, idA = A8 ? cmapA8 + 256u : idAAddr;
-                if (ALLFULL || waveFull || __all(fullNext)) t = tdfaStreamPair1Chunk<BLOCK, NB, false, TdfaReg, A8>(t, col, na, nc, nwords, nbase, L, mapA, idA, ptt, tt, pbase, regAddr0, reinterpret_cast<const uint8_t*>(blob) + TD_CMAP_OFFSET);
-                else t = tdfaStreamPair1Chunk<BLOCK, NB, true, TdfaReg, A8>(t, col, na, nc, nwords, nbase, L, mapA, idA, ptt, tt, pbase, regAddr0);
+                if (ALLFULL || waveFull || __all(fullNext)) t = tdfaStreamPair1Chunk<BLOCK, NB, false, TdfaReg>(t, col, na, nc, nwords, nbase, L, pi.cmapA, idAAddr, ptt, tt, pbase, regAddr0, reinterpret_cast<const uint8_t*>(blob) + TD_CMAP_OFFSET);
+                else t = tdfaStreamPair1Chunk<BLOCK, NB, true, TdfaReg>(t, col, na, nc, nwords, nbase, L, pi.cmapA, idAAddr, ptt, tt, pbase, regAddr0);
                 tdfaSettleDoubles<BLOCK, NC, TdfaReg>(ptt, pbase, regAddr0);
 #pragma unroll
-                for (int j = 0; j < NC; ++j) ncol[j] = A8 ? __umul24(na[j], strideA8) + nc[j] : na[j] + nc[j];
+                for (int j = 0; j < NC; ++j) ncol[j] = na[j] + nc[j];
                 seen = 0;
                 general = false;
             } else if constexpr (PAIR) {
@@ -561,7 +545,7 @@ __device__ __forceinline__ void tdfaStreamBody(
                 const u32x4 q = {cwords[0], cwords[1], cwords[2], cwords[3]};
                 uint32_t single = entry;
                 if constexpr (PAIR) single = TD_TRANS_OFFSET + ((entry & 0xFFFFu) - pi.base) / pi.rowBytes * rowBytes;
-                tdfaReplayChunk<BLOCK, TdfaReg, false, LAB>(smem, q, single, base, L, idCol, regsBase, tid, NB);
+                tdfaReplayChunk<BLOCK, TdfaReg, LAB>(smem, q, single, base, L, idCol, regsBase, tid, NB);
 #pragma unroll
                 for (int j = 0; j < NC; ++j) tt[j] = dummyT;
             }
@@ -646,29 +630,7 @@ __device__ __forceinline__ void tdfaStreamBody(
     tdfaWriteResults<BLOCK, TdfaReg, LAB>(smem, stageBase, regsBase, state, live, line, L, from, order != nullptr, nGroupsOut, caps,
                                      status);
     };  // walkBlock
-    if constexpr ((LAB & kLabPersist) != 0) {
-        // (round 6) PERSISTENT WAVEFRONTS.  The launch has as many workgroups as the chip holds (gpu_runtime.hip); workgroup b walks
-        // blocks b, b + grid, b + 2 grid, ... -- and since nothing below the table staging is shared between the wavefronts of a
-        // workgroup, every wavefront goes on with ITS 64 lines of the next block the moment it has written its results: no wait for
-        // the slowest of the eight before the slot is used again, tables staged once.  (Round 3 tried persistent WORKGROUPS on the
-        // kernel of that time and dropped them: 0.243 against 0.227 ms.)  Between blocks the wavefront zeroes its lanes' register
-        // columns ("every register starts at 0", above) behind its own LDS reads of the result tile.
-        static_assert(PAIR1 && COMPACT, "persistent wavefronts: the one-stamp COMPACT kernel only");
-        constexpr uint32_t kRegShift = (BLOCK == 1024 ? 12 : BLOCK == 512 ? 11 : BLOCK == 256 ? 10 : BLOCK == 128 ? 9 : 8) -
-                                       (sizeof(TdfaReg) == 2 ? 1 : 0);
-        const uint32_t nBlocks = (nLines + BLOCK - 1) / BLOCK;
-        const uint32_t regRows = regBytes / (uint32_t(BLOCK) * uint32_t(sizeof(TdfaReg)));
-        const uint32_t myRegs = regsBase + tdfaRegLane<TdfaReg>(tid) * uint32_t(sizeof(TdfaReg));
-        for (uint32_t b = blockId; b < nBlocks; b += gridDim.x) {
-            walkBlock(b);
-            if (b + gridDim.x < nBlocks) {
-                tdfaLdsDrain();
-                for (uint32_t r = 0; r < regRows; ++r) *reinterpret_cast<LdsRegPtr>(myRegs + (r << kRegShift)) = TdfaReg(0);
-            }
-        }
-    } else {
-        walkBlock(blockId);
-    }
+    walkBlock(blockId);
 }
 
 template <int BLOCK, bool COMPACT, bool PAIR = false, int LAB = 0>

@@ -185,8 +185,8 @@ class NfaInterp:
 class TdfaBlobInterp:
     """Walks the PACKED TDFA tables exactly as the kernel addresses them (device_tables.h): the low half of a transition
     entry is the LDS address of the next row, the high half the byte offset of the stamped register (or a move-list id);
-    `compact` = the tables of the opt-in COMPACT kernel variant the pattern was compiled for (LC_TDFA_COMPACT=256|512|1024:
-    16-bit registers; 1024 = byte-indexed rows), LC_TABLE_TDFA_WIDE_BLOB."""
+    `compact` = the tables of the opt-in COMPACT kernel variant the pattern was compiled for (LC_TDFA_COMPACT=256|512:
+    16-bit registers), LC_TABLE_TDFA_WIDE_BLOB."""
 
     def __init__(self, rx, compact=False):
         blob = rx.table(B.LC_TABLE_TDFA_WIDE_BLOB if compact else B.LC_TABLE_TDFA_BLOB, np.uint32)
@@ -200,8 +200,7 @@ class TdfaBlobInterp:
         self.nregs &= 0xFFFF
         self.fold = [int(w) for w in blob[fold_off // 4 + 1:fold_off // 4 + 1 + int(blob[fold_off // 4])]] if fold_off else None
         self.compact = compact
-        self.wide = self.row_bytes == 257 * 4            # rows indexed by the byte itself
-        assert not self.wide or (compact and self.block == 1024)
+        assert self.row_bytes == (self.ncls + 1) * 4       # class-indexed rows + the identity column
         self.reg_stride = self.block * (2 if compact else 4)
         self.cmap = self.raw[64:320]
         self.final_id = self.raw[off_finalid:off_finalid + 2 * self.nstates].view(np.uint16)
@@ -217,7 +216,7 @@ class TdfaBlobInterp:
         regs = {r: 0 for r in range(self.nregs)} if self.fold is not None else {}   # (fold words: registers start at 0)
         limit = 0xFFFF if self.compact else 0xFFFFFFFF
         for pos in range(start, len(s)):
-            col = s[pos] * 4 if self.wide else int(self.cmap[s[pos]])
+            col = int(self.cmap[s[pos]])
             e = int(self.blob[((t & 0xFFFF) + col) // 4])
             t, f = e & 0xFFFF, e >> 16
             if f & 1:                                       # general move list

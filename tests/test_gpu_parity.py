@@ -632,33 +632,6 @@ def test_long_lines_behind_the_first_256_blocks_of_a_large_batch(torch_dev):
     assert exp_status.sum() > n // 2
 
 
-def test_persistent_wavefronts_of_the_one_stamp_kernel(torch_dev, monkeypatch):
-    """Round 6, measured and left off (LC_TDFA_PERSIST=1): the COMPACT one-stamp kernel launched with as many workgroups as the chip
-    holds, every wavefront going on with its 64 lines of the next block.  600 000 ragged lines (the launch needs two rounds of resident
-    workgroups to take this form), failing lines, empty lines and lines of 64 KiB and more among them, against the oracle."""
-    from oracle.oracle import OracleRegex
-    monkeypatch.setenv("LC_TDFA_PERSIST", "1")
-    pattern = rb"(\w+) (\d+) (.*)\|(\w*)"
-    rx = B.GpuRegex(pattern)
-    n = 600000
-    rng = random.Random(5)
-    subs = []
-    for i in range(n):
-        k = rng.randrange(12)
-        if k == 0: subs.append(b"")
-        elif k == 1: subs.append(b"no separator %d" % i)
-        else: subs.append(b"k%d %d %s|e%d" % (i, i * 3, b"x" * rng.randrange(0, 90), i % 7))
-    for where, size in ((5, 65536), (300001, 70001), (599999, 66000)):
-        subs[where] = b"key 12345 " + b"y" * (size - 14) + b"|end"
-    data, off, length = pack(subs)
-    exp_caps, exp_status = OracleRegex(pattern).fullmatch_batch(data, off, length)
-    B.launched_kernels()
-    caps, status = run_device(torch_dev, rx, data, off, length, engine=B.LC_ENGINE_TDFA)
-    assert "persist" in str(B.launched_kernels())
-    assert np.array_equal(status, exp_status) and np.array_equal(caps, exp_caps)
-    assert exp_status.sum() > n // 2
-
-
 def test_resumed_searches_on_long_lines_both_kernels(torch_dev):
     """lc_regex_match_device_from: a subset of the lines, each search resumed at its own offset (also beyond the first
     256-byte chunk of the NFA kernel and across the TDFA kernel's 64-byte stages), against the oracle's search(start)."""
@@ -846,10 +819,10 @@ def test_run_captures_on_both_kernels(torch_dev):
     assert checked == 2 * len(RUN_CAPTURE_PATTERNS) * len(RUN_CAPTURE_SUBJECTS)
 
 
-@pytest.mark.parametrize("compact", ["256", "512", "1024"])
+@pytest.mark.parametrize("compact", ["256", "512"])
 def test_compact_kernels_and_their_long_line_second_pass(torch_dev, monkeypatch, compact):
-    """Opt-in COMPACT kernel variants (LC_TDFA_COMPACT when the pattern is compiled): 16-bit offsets, swizzled staging,
-    1024 = byte-indexed rows; lines of 64 KiB and more are left to a second launch of the 32-bit kernel.  Lengths around
+    """Opt-in COMPACT kernel variants (LC_TDFA_COMPACT when the pattern is compiled): 16-bit offsets, swizzled staging;
+    lines of 64 KiB and more are left to a second launch of the 32-bit kernel.  Lengths around
     the boundary, captures at both ends, resumed searches, and the bench corpus."""
     monkeypatch.setenv("LC_TDFA_COMPACT", compact)
     pattern = rb"(\w+) (\d+) (.*)\|(\w*)"
@@ -1026,13 +999,10 @@ def test_wide_kernel_as_the_first_chance(torch_dev, golden_dir, monkeypatch):
         assert int(d_status[0]) == 1 and d_caps.cpu().numpy()[0].tolist() == [v for be in o for v in be], (frm, o)
 
 
-@pytest.mark.parametrize("lds", ["0", "1"])
-def test_small_automata_on_the_wave_kernel(torch_dev, golden_dir, monkeypatch, lds):
+def test_small_automata_on_the_wave_kernel(torch_dev, golden_dir):
     """Round 5: a handle that asks for the wave-per-value kernel (lc_regex_prefer_wave_tdfa: the Grok matcher's entries) -- the walk
-    with its state in SGPRs and the classes of a chunk looked up once; and, LC_TDFA_WAVE_LDS_TRANS=1 (measured, left off), transition
-    table + register programs staged into LDS when they fit 48 KB (tdfa_wave_kernel<LT>).  Same results as the oracle on the bench
-    corpora (poisoned lines included), on the golden full-match vectors, and on resumed searches."""
-    monkeypatch.setenv("LC_TDFA_WAVE_LDS_TRANS", lds)
+    with its state in SGPRs and the classes of a chunk looked up once.  Same results as the oracle on the bench corpora (poisoned
+    lines included), on the golden full-match vectors, and on resumed searches."""
     for kind in ("A", "B"):
         pattern = corpus.REGEX_A if kind == "A" else corpus.REGEX_B
         rx = B.GpuRegex(pattern)
@@ -1041,7 +1011,7 @@ def test_small_automata_on_the_wave_kernel(torch_dev, golden_dir, monkeypatch, l
         exp_caps, exp_status = OracleRegex(pattern).fullmatch_batch(data, off[:-1], length)
         B.launched_kernels()
         caps, status = run_device(torch_dev, rx, data, off, None, sep=1, engine=B.LC_ENGINE_TDFA)
-        assert ("tdfa_l2_kernel:wave:lds" in B.launched_kernels()) == (lds == "1")
+        assert "tdfa_l2_kernel:wave" in B.launched_kernels()
         assert np.array_equal(status, exp_status) and np.array_equal(caps, exp_caps)
     with open(os.path.join(golden_dir, "regex_golden.json")) as f:
         golden = json.load(f)
@@ -1077,45 +1047,6 @@ def test_small_automata_on_the_wave_kernel(torch_dev, golden_dir, monkeypatch, l
             assert int(d_status[0]) == B.LC_NOMATCH, frm
         else:
             assert int(d_status[0]) == 1 and d_caps.cpu().numpy()[0].tolist() == [v for be in o for v in be], (frm, o)
-
-
-def test_thread_list_kernels_on_follow_lists_by_byte_class(torch_dev, golden_dir, monkeypatch):
-    """LC_NFA_CLASS_LISTS=1 (device_tables.h NF_OFF_CSTART: measured on configs[2], no gain, left off): a step's candidates come from
-    the lists of the paths whose target takes the byte instead of the whole follow lists -- the narrow kernel, the wide kernel
-    (second chance and first chance), atomic groups; all equal to the oracle."""
-    monkeypatch.setenv("LC_NFA_CLASS_LISTS", "1")
-    with open(os.path.join(golden_dir, "regex_golden.json")) as f:
-        golden = json.load(f)
-    bad, checked = [], 0
-    for c in golden["cases"][::4]:
-        rx = B.GpuRegex(c["p"].encode("latin-1"))
-        if not rx.has_nfa_program():
-            continue
-        assert int(rx.table(B.LC_TABLE_NFA_BLOB, np.uint32)[24]) != 0
-        subs = [s.encode("latin-1") for s, _ in c["subs"]]
-        data, off, length = pack(subs)
-        caps, status = run_device(torch_dev, rx, data, off, length, engine=B.LC_ENGINE_NFA)
-        for i, (_, flat) in enumerate(c["subs"]):
-            checked += 1
-            ok = (status[i] == B.LC_NOMATCH and (caps[i] == -1).all()) if flat is None else \
-                 (status[i] == B.LC_MATCH and list(caps[i]) == flat[2:])
-            if not ok:
-                bad.append((c["p"], subs[i], int(status[i]), list(caps[i]), flat))
-    assert checked > 1000 and not bad, bad[:5]
-    for wide_first in ("0", "1"):
-        monkeypatch.setenv("LC_NFA_WIDE_FIRST", wide_first)
-        for pattern, subs in ((r"(.*)a(.{70})", [b"a" * 100, b"b" * 10, b"a" + b"b" * 70, b"xa" * 80, b"a" * 71, b""]),
-                              (r"(.*)a.{140}", [b"a" * 200, b"a" + b"b" * 140, b"a" * 140, b"b"]),
-                              (r"(?>a+)(b|bc)+d", [b"aaabbcd", b"abcbcd", b"aab", b"d"])):
-            data, off, length = pack(subs)
-            exp_caps, exp_status = OracleRegex(pattern).fullmatch_batch(data, off, length)
-            rx = B.GpuRegex(pattern, engine=B.LC_ENGINE_NFA)
-            caps, status = run_device(torch_dev, rx, data, off, length, engine=B.LC_ENGINE_NFA)
-            assert np.array_equal(status, exp_status) and np.array_equal(caps, exp_caps), (pattern, wide_first)
-        data, off, length = corpus.apache_batch(2000, "A", poison_every=11)
-        exp_caps, exp_status = OracleRegex(corpus.REGEX_A).fullmatch_batch(data, off[:-1], length)
-        caps_n, status_n = run_device(torch_dev, B.GpuRegex(corpus.REGEX_A), data, off, None, sep=1, engine=B.LC_ENGINE_NFA)
-        assert np.array_equal(status_n, exp_status) and np.array_equal(caps_n, exp_caps)
 
 
 def test_atomic_lazy_loop_commits_on_the_thread_list_engine(torch_dev):

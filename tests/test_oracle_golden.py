@@ -85,7 +85,7 @@ def test_oracle_search_matches_every_search_vector(golden_dir):
     assert not bad, bad[:5]
 
 
-def test_oracle_matches_atomic_and_possessive_vectors(golden_dir):
+def test_oracle_on_atomic_and_possessive_vectors(golden_dir):
     """(?>X), X*+ ... : vectors on which the `regex` module and PCRE1 agree (tests/golden/gen_atomic_golden.py)."""
     with open(os.path.join(golden_dir, "regex_atomic_golden.json")) as f:
         d = json.load(f)

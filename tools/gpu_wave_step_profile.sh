@@ -1,15 +1,13 @@
 #!/bin/bash
 # tools/gpu_wave_step_profile.sh TAG [PATTERN]: tdfa_wave_kernel on ONE Grok entry (default %{CISCOFW105003}: a search with a GREEDYDATA in
 # front of a literal -- every space of the free text behind starts an attempt) over the values of the configs[2] corpus that carry its
-# literal: time per launch with the tables in L2 and in LDS, then SQ counter passes of the kernel  -> gpurun_out/TAG.txt
+# literal: time per launch, then SQ counter passes of the kernel  -> TAG.txt beside the output directory ($O.txt)
 R=${GRAFT_REPO_ROOT:-/root/repo}
 TAG=$1; PAT=${2:-%{CISCOFW105003\}}
 O=$R/gpurun_out/$TAG; mkdir -p $O; cd $R
 export LC_BENCH_PREFER_WAVE=1 LC_BENCH_REPS=5
 {
-echo "## time per launch, tables in LDS (LC_TDFA_WAVE_LDS_TRANS=1)"
-LC_TDFA_WAVE_LDS_TRANS=1 timeout 200 python tools/grok_pattern_bench.py "$PAT" 2>&1 | grep -v Warning | tail -7
-echo "## time per launch, tables in L2 (default)"
+echo "## time per launch"
 timeout 200 python tools/grok_pattern_bench.py "$PAT" 2>&1 | grep -v Warning | tail -7
 } > $O.txt
 cd /tmp && export TMPDIR=/tmp
@@ -28,7 +26,7 @@ for f in glob.glob("$O/p*/**/*counter_collection.csv", recursive=True):
         k = row.get("Kernel_Name", "")
         if "tdfa_wave" not in k: continue
         acc[k[:40] + " grid=" + row.get("Grid_Size", "?")][row["Counter_Name"]].append(float(row["Counter_Value"]))
-print("## SQ counters per dispatch (tables in L2: the default)")
+print("## SQ counters per dispatch")
 for k in sorted(acc):
     print(k)
     for c in sorted(acc[k]):

@@ -1,4 +1,4 @@
-// tdfa_lab.hip -- measurement bench for the tagged-DFA kernel: the REAL kernel (csrc/tdfa_kernel.hpp) instantiated with its
+// tdfa_lab.hip -- measurement bench for the tagged-DFA kernel: the REAL kernel (csrc/tdfa_stream_kernel.hpp) instantiated with its
 // LAB variants on the headline corpus, to see what each LDS instruction per byte costs and what a layout change buys
 // before it is built into the product.  Not part of the product; inputs come from tools/tdfa_lab_inputs.py.
 //
@@ -120,7 +120,7 @@ struct Dev {
 
 constexpr uint32_t kPoolLines = 2048;  // 1 MiB of lines: resident in every XCD's L2 (4 MiB)
 static size_t gPadLdsTo = 0;  // occupancy sweep: ask for at least this much LDS per workgroup
-template <int BLOCK, int LAB, bool POOL = false, bool STREAM = false, bool PAIR = false>
+template <int BLOCK, int LAB, bool POOL = false, bool PAIR = false>
 static double runVariant(const char* name, const Inputs& in, const Dev& d, std::vector<int32_t>* capsOut, std::vector<uint8_t>* statusOut,
                          int iters) {
     const bool repl = (LAB & kLabReplicated) != 0;
@@ -138,13 +138,6 @@ static double runVariant(const char* name, const Inputs& in, const Dev& d, std::
     size_t lds = size_t(blobBytes) + regBytes + size_t(BLOCK / 64) * 64 * kTdfaStageBytes;
     if (gPadLdsTo > lds) lds = gPadLdsTo;
     auto kern = tdfa_stream_kernel<BLOCK, true, PAIR, LAB>;
-    if constexpr (!STREAM) {
-        if constexpr (kTdfaStageBytes == 64) kern = tdfa_match_kernel<BLOCK, PAIR, true, false, LAB>;
-        else {
-            printf("%-34s  skipped: the phase-separated kernel stages 64 bytes\n", name);
-            return 0;
-        }
-    }
     if (lds > 160 * 1024) {
         printf("%-34s  skipped: %zu bytes of LDS\n", name, lds);
         return 0;
@@ -247,41 +240,36 @@ int main(int argc, char** argv) {
     }
     std::vector<int32_t> refCaps;
     std::vector<uint8_t> refStatus;
-#define RUN(B, L, NAME) runVariant<B, L>(NAME, in, d, &refCaps, &refStatus, iters)
-#define RUNP(B, L, NAME) runVariant<B, L, true>(NAME, in, d, &refCaps, &refStatus, iters)
-    if (kTdfaStageBytes == 64) RUN(256, 0, "compact 256 (product)");
-#define RUNS(B, L, NAME) runVariant<B, L, false, true>(NAME, in, d, &refCaps, &refStatus, iters)
-#define RUNSP(B, L, NAME) runVariant<B, L, true, true>(NAME, in, d, &refCaps, &refStatus, iters)
+#define RUNS(B, L, NAME) runVariant<B, L>(NAME, in, d, &refCaps, &refStatus, iters)
+#define RUNSP(B, L, NAME) runVariant<B, L, true>(NAME, in, d, &refCaps, &refStatus, iters)
     if (in.blob[TD_OFF_PAIR] && in.blob[in.blob[TD_OFF_PAIR] / 4 + TP_FORMAT] == 1) {  // a ONE-STAMP pair table (LC_TDFA_PAIR=2)
-        runVariant<512, kLabNoGeneral | kLabDmaStage, false, true, false>("stream 512 single, nogen, DMA", in, d, &refCaps, &refStatus, iters);
-        runVariant<512, kLabNoGeneral | kLabPairOne, false, true, true>("stream 512 PAIR1 (one stamp/pair)", in, d, &refCaps, &refStatus, iters);
-        runVariant<512, kLabNoGeneral | kLabPairOne | kLabDmaStage, false, true, true>("stream 512 PAIR1, DMA", in, d, &refCaps, &refStatus, iters);
-        runVariant<512, kLabNoGeneral | kLabPairOne | kLabDmaStage, false, true, true>("stream 512 PAIR1, DMA (again)", in, d, &refCaps, &refStatus, iters);
-        runVariant<512, kLabNoGeneral | kLabPairOne | kLabDmaStage | kLabNoOutput, false, true, true>("stream 512 PAIR1, DMA, no output", in, d, &refCaps, &refStatus, iters);
-        runVariant<512, kLabNoGeneral | kLabPairOne | kLabDmaStage, true, true, true>("stream 512 PAIR1, DMA, pool", in, d, &refCaps, &refStatus, iters);
+        runVariant<512, kLabNoGeneral | kLabDmaStage, false, false>("stream 512 single, nogen, DMA", in, d, &refCaps, &refStatus, iters);
+        runVariant<512, kLabNoGeneral | kLabPairOne, false, true>("stream 512 PAIR1 (one stamp/pair)", in, d, &refCaps, &refStatus, iters);
+        runVariant<512, kLabNoGeneral | kLabPairOne | kLabDmaStage, false, true>("stream 512 PAIR1, DMA", in, d, &refCaps, &refStatus, iters);
+        runVariant<512, kLabNoGeneral | kLabPairOne | kLabDmaStage, false, true>("stream 512 PAIR1, DMA (again)", in, d, &refCaps, &refStatus, iters);
+        runVariant<512, kLabNoGeneral | kLabPairOne | kLabDmaStage | kLabNoOutput, false, true>("stream 512 PAIR1, DMA, no output", in, d, &refCaps, &refStatus, iters);
+        runVariant<512, kLabNoGeneral | kLabPairOne | kLabDmaStage, true, true>("stream 512 PAIR1, DMA, pool", in, d, &refCaps, &refStatus, iters);
         return 0;
     }
     if (in.blob[TD_OFF_PAIR] && getenv("LAB_DMA")) {
-        runVariant<512, kLabNoGeneral, false, true, true>("stream 512 pairs, no general", in, d, &refCaps, &refStatus, iters);
-        runVariant<512, kLabNoGeneral | kLabDmaStage, false, true, true>("stream 512 pairs, nogen, DMA", in, d, &refCaps, &refStatus, iters);
-        runVariant<512, kLabNoGeneral | kLabOneStamp | kLabNoStamp, false, true, true>("stream 512 pairs, ONE stamp/pair", in, d, &refCaps, &refStatus, iters);
-        runVariant<512, kLabNoGeneral | kLabOneStamp | kLabNoStamp | kLabDmaStage, false, true, true>("stream 512 pairs, ONE stamp, DMA", in, d, &refCaps, &refStatus, iters);
-        runVariant<512, kLabNoGeneral | kLabOneStamp | kLabNoStamp | kLabDmaStage | kLabNoOutput, false, true, true>("512 pairs, ONE stamp, DMA, no out", in, d, &refCaps, &refStatus, iters);
-        runVariant<512, kLabNoGeneral | kLabOneStamp | kLabNoStamp | kLabDmaStage, true, true, true>("512 pairs, ONE stamp, DMA, pool", in, d, &refCaps, &refStatus, iters);
+        runVariant<512, kLabNoGeneral, false, true>("stream 512 pairs, no general", in, d, &refCaps, &refStatus, iters);
+        runVariant<512, kLabNoGeneral | kLabDmaStage, false, true>("stream 512 pairs, nogen, DMA", in, d, &refCaps, &refStatus, iters);
+        runVariant<512, kLabNoGeneral | kLabOneStamp | kLabNoStamp, false, true>("stream 512 pairs, ONE stamp/pair", in, d, &refCaps, &refStatus, iters);
+        runVariant<512, kLabNoGeneral | kLabOneStamp | kLabNoStamp | kLabDmaStage, false, true>("stream 512 pairs, ONE stamp, DMA", in, d, &refCaps, &refStatus, iters);
+        runVariant<512, kLabNoGeneral | kLabOneStamp | kLabNoStamp | kLabDmaStage | kLabNoOutput, false, true>("512 pairs, ONE stamp, DMA, no out", in, d, &refCaps, &refStatus, iters);
+        runVariant<512, kLabNoGeneral | kLabOneStamp | kLabNoStamp | kLabDmaStage, true, true>("512 pairs, ONE stamp, DMA, pool", in, d, &refCaps, &refStatus, iters);
         return 0;
     }
     if (in.blob[TD_OFF_PAIR]) {
-        runVariant<512, 0, false, false, false>("compact 512, single-byte table", in, d, &refCaps, &refStatus, iters);
-        runVariant<512, 0, false, false, true>("compact 512 pairs (old kernel)", in, d, &refCaps, &refStatus, iters);
-        runVariant<512, 0, false, true, false>("stream 512, single-byte table", in, d, &refCaps, &refStatus, iters);
-        runVariant<512, 0, false, true, true>("stream 512 pairs", in, d, &refCaps, &refStatus, iters);
-        runVariant<512, kLabNoGeneral, false, true, true>("stream 512 pairs, no general", in, d, &refCaps, &refStatus, iters);
-        runVariant<512, kLabNoGeneral | kLabOneStamp | kLabNoStamp, false, true, true>("stream 512 pairs, ONE stamp/pair", in, d, &refCaps, &refStatus, iters);
-        runVariant<512, kLabNoGeneral, false, true, false>("stream 512 single, no general", in, d, &refCaps, &refStatus, iters);
-        runVariant<512, kLabNoStamp, false, true, true>("stream 512 pairs, no stamps", in, d, &refCaps, &refStatus, iters);
-        runVariant<512, kLabNoOutput, false, true, true>("stream 512 pairs, no output", in, d, &refCaps, &refStatus, iters);
-        runVariant<512, 0, true, true, true>("stream 512 pairs, pool", in, d, &refCaps, &refStatus, iters);
-        runVariant<512, kLabNoOutput, true, true, true>("stream 512 pairs, no output, pool", in, d, &refCaps, &refStatus, iters);
+        runVariant<512, 0, false, false>("stream 512, single-byte table", in, d, &refCaps, &refStatus, iters);
+        runVariant<512, 0, false, true>("stream 512 pairs", in, d, &refCaps, &refStatus, iters);
+        runVariant<512, kLabNoGeneral, false, true>("stream 512 pairs, no general", in, d, &refCaps, &refStatus, iters);
+        runVariant<512, kLabNoGeneral | kLabOneStamp | kLabNoStamp, false, true>("stream 512 pairs, ONE stamp/pair", in, d, &refCaps, &refStatus, iters);
+        runVariant<512, kLabNoGeneral, false, false>("stream 512 single, no general", in, d, &refCaps, &refStatus, iters);
+        runVariant<512, kLabNoStamp, false, true>("stream 512 pairs, no stamps", in, d, &refCaps, &refStatus, iters);
+        runVariant<512, kLabNoOutput, false, true>("stream 512 pairs, no output", in, d, &refCaps, &refStatus, iters);
+        runVariant<512, 0, true, true>("stream 512 pairs, pool", in, d, &refCaps, &refStatus, iters);
+        runVariant<512, kLabNoOutput, true, true>("stream 512 pairs, no output, pool", in, d, &refCaps, &refStatus, iters);
         return 0;
     }
     RUNS(256, 0, "stream 256");
@@ -319,7 +307,6 @@ int main(int argc, char** argv) {
     RUNS(64, 0, "stream 64");
     RUNS(128, 0, "stream 128");
     RUNS(512, 0, "stream 512");
-    RUN(64, 0, "compact 64 (old kernel)");
     RUNS(256, kLabNoOutput, "stream 256 no output");
     RUNS(256, kLabNoLoop, "stream 256 no loop");
     RUNS(256, kLabNoLoop | kLabNoOutput, "stream 256 no loop, no output");
@@ -330,11 +317,11 @@ int main(int argc, char** argv) {
         gPadLdsTo = size_t(160 * 1024 / wgs) & ~size_t(255);
         char nm[64];
         snprintf(nm, sizeof nm, "product, %d WG/CU", wgs);
-        RUN(256, 0, nm);
+        RUNS(256, kLabNoGeneral | kLabDmaStage, nm);
         snprintf(nm, sizeof nm, "product, pool, %d WG/CU", wgs);
-        RUNP(256, 0, nm);
+        RUNSP(256, kLabNoGeneral | kLabDmaStage, nm);
         snprintf(nm, sizeof nm, "bare chain, pool, %d WG/CU", wgs);
-        RUNP(256, kLabPreClass | kLabNoStamp, nm);
+        RUNSP(256, kLabPreClass | kLabNoStamp, nm);
     }
     gPadLdsTo = 0;
     return 0;
