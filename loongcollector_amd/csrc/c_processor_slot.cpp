@@ -17,7 +17,16 @@
 using logtail::PipelineEventGroup;
 using logtail::ProcessorParseRegexGpu;
 
+// The delimiter processor's way through the slot (processor_parse_delimiter_gpu.cpp).  Weak: a build that links this file without that
+// one (the agent-form plugin of INTEGRATION.md section 2) still links, and refuses such a config.
+extern "C" {
+__attribute__((weak)) int lcDelimiterSlotInit(const char* config_text, void** state);
+__attribute__((weak)) void lcDelimiterSlotProcess(void* state, void* native_group);
+__attribute__((weak)) void lcDelimiterSlotFinalize(void* state);
+}
+
 struct lc_processor {
+    void* delimiter = nullptr;  // slot only: the instance was built from a config whose Type is processor_parse_delimiter_gpu
     ProcessorParseRegexGpu impl;
     // the part ProcessorInstance adds around every plugin (ProcessorInstance.cpp:46-63)
     std::atomic<uint64_t> inEvents{0}, outEvents{0}, inBytes{0}, outBytes{0}, processUs{0};
@@ -397,6 +406,24 @@ static int slotInit(processor_instance_t* ins, void* config, void* context) {
 #else
     const char* configText = static_cast<const char*>(config);
 #endif
+    // "Type": "processor_parse_delimiter_gpu" builds the delimiter parser; every other config builds the regex parser, as before
+    bool wantsDelimiter = false;
+    try {
+        const lcjson::Value cfg = lcjson::parse(configText);
+        const lcjson::Value* type = cfg.isObject() ? cfg.find("Type") : nullptr;
+        wantsDelimiter = type && type->isString() && type->str == "processor_parse_delimiter_gpu";
+    } catch (const std::exception&) {
+    }
+    if (wantsDelimiter) {
+        if (!lcDelimiterSlotInit) {
+            std::fprintf(stderr, "[processor_parse_delimiter_gpu] this build of the plugin does not hold the delimiter parser\n");
+            return -1;
+        }
+        auto holder = std::make_unique<lc_processor>();
+        if (lcDelimiterSlotInit(configText, &holder->delimiter) != 0) return -1;
+        ins->plugin_state = holder.release();
+        return 0;
+    }
     if (lc_processor_create(configText, &p, err, sizeof err) != LC_OK) {
         std::fprintf(stderr, "[processor_parse_regex_gpu] init failed: %s\n", err);
         return -1;
@@ -411,9 +438,17 @@ static int slotInit(processor_instance_t* ins, void* config, void* context) {
     ins->plugin_state = p;
     return 0;
 }
-static void slotFinalize(void* state) { lc_processor_destroy(static_cast<lc_processor_t*>(state)); }
+static void slotFinalize(void* state) {
+    lc_processor_t* p = static_cast<lc_processor_t*>(state);
+    if (p && p->delimiter) lcDelimiterSlotFinalize(p->delimiter);
+    lc_processor_destroy(p);
+}
 static void slotProcess(void* state, void* logGroup) {
     if (!state || !logGroup) return;
+    if (static_cast<lc_processor_t*>(state)->delimiter) {
+        lcDelimiterSlotProcess(static_cast<lc_processor_t*>(state)->delimiter, logGroup);
+        return;
+    }
     processGroup(static_cast<lc_processor_t*>(state), *static_cast<PipelineEventGroup*>(logGroup));
 }
 

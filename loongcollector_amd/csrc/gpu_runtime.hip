@@ -2082,6 +2082,7 @@ extern "C" void lc_thread_release(void) {
     lcPipelineThreadRelease();
     lcMultilineThreadRelease();
     lcFilterThreadRelease();
+    lcDelimThreadRelease();
 }
 
 extern "C" void lc_nfa_set_dfs(int on) { gNfaDfsMode.store(on < 0 ? -1 : (on ? 1 : 0), std::memory_order_relaxed); }

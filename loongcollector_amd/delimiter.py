@@ -1,0 +1,146 @@
+"""ctypes binding of the delimiter parser (include/lc_delimiter.h): GpuDelimiter is the engine (delim_split_kernel over lines in
+device or host memory), DelimiterProcessor the processor_parse_delimiter_gpu plugin over event groups (same shape as
+processor.Processor).  There is no CPU path: every split needs a HIP device and raises otherwise."""
+import ctypes
+import json
+
+import numpy as np
+
+from . import binding
+from .processor import COUNTER_NAMES, EventGroup, ProcessorInitError, _lib as _processor_lib
+
+LC_DELIM_FAIL, LC_DELIM_OK, LC_DELIM_BLANK = 0, 1, 2
+LC_DELIM_EXTEND, LC_DELIM_KEEP, LC_DELIM_DISCARD = 0, 1, 2
+LC_DELIM_DOUBLED = 0x80000000
+MODES = {"extend": LC_DELIM_EXTEND, "keep": LC_DELIM_KEEP, "discard": LC_DELIM_DISCARD}
+
+
+def _lib():
+    L = _processor_lib()
+    if not getattr(L, "_lc_delimiter_bound", False):
+        vp, cp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
+        L.lc_delim_create.restype = i32
+        L.lc_delim_create.argtypes = [cp, u32, ctypes.c_uint8, i32, u32, ctypes.POINTER(vp)]
+        L.lc_delim_destroy.argtypes = [vp]
+        L.lc_delim_uses_quote.argtypes = [vp]
+        L.lc_delim_split_device.restype = i32
+        L.lc_delim_split_device.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, vp]
+        L.lc_delim_split_host.restype = i32
+        L.lc_delim_split_host.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp]
+        L.lc_delimiter_processor_create.restype = i32
+        L.lc_delimiter_processor_create.argtypes = [cp, ctypes.POINTER(vp), cp, sz]
+        L.lc_delimiter_processor_destroy.argtypes = [vp]
+        L.lc_delimiter_processor_warnings.restype = vp
+        L.lc_delimiter_processor_warnings.argtypes = [vp]
+        L.lc_delimiter_processor_process.restype = i32
+        L.lc_delimiter_processor_process.argtypes = [vp, vp]
+        L.lc_delimiter_processor_set_first_trip_columns.restype = None
+        L.lc_delimiter_processor_set_first_trip_columns.argtypes = [vp, u32]
+        L.lc_delimiter_processor_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+        L.lc_delimiter_processor_set_alarm_sink.restype = None
+        L.lc_delimiter_processor_set_alarm_sink.argtypes = [vp, vp, vp]
+        L._lc_delimiter_bound = True
+    return L
+
+
+class GpuDelimiter:
+    """The engine: separator (1..4 bytes), quote (one byte), OverflowedFieldsTreatment mode and the number of keys."""
+
+    def __init__(self, separator, quote=b'"', mode="extend", n_keys=0):
+        self._L = _lib()
+        separator, quote = bytes(separator), bytes(quote)
+        h = ctypes.c_void_p()
+        rc = self._L.lc_delim_create(separator, len(separator), quote[0] if quote else 0x22, MODES[mode], n_keys, ctypes.byref(h))
+        if rc != binding.LC_OK:
+            raise ValueError("lc_delim_create rc=%d" % rc)
+        self.handle = h
+
+    @property
+    def uses_quote(self):
+        return bool(self._L.lc_delim_uses_quote(self.handle))
+
+    def split_device(self, d_data, d_off, n, W, d_status, d_ncols, d_spans, stream=None):
+        """torch device tensors: d_data u8[], d_off i32[n + 1], d_status u8[n], d_ncols i32[n], d_spans i32[n, W, 2]; asynchronous"""
+        binding._check(self._L.lc_delim_split_device(self.handle, d_data.data_ptr(), d_off.data_ptr(), n, W, d_status.data_ptr(),
+                                                     d_ncols.data_ptr(), d_spans.data_ptr() if W else None, ctypes.c_void_p(stream or 0)),
+                       "lc_delim_split_device")
+
+    def split_host(self, data, off, W):
+        """numpy: data u8[], off[n + 1] -> (status u8[n], ncols u32[n], spans i32[n, W, 2]); the lines go up as views, one per line"""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        off = np.asarray(off, dtype=np.int64)
+        n = len(off) - 1
+        base = data.ctypes.data
+        ptrs = (base + off[:-1]).astype(np.uint64)
+        lens = (off[1:] - off[:-1]).astype(np.uint32)
+        status = np.zeros(n, np.uint8)
+        ncols = np.zeros(n, np.uint32)
+        spans = np.full((n, W, 2), -1, np.int32)
+        binding._check(self._L.lc_delim_split_host(self.handle, ptrs.ctypes.data, lens.ctypes.data, n, W, status.ctypes.data, ncols.ctypes.data,
+                                                   spans.ctypes.data), "lc_delim_split_host")
+        return status, ncols, spans
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._L.lc_delim_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DelimiterProcessor:
+    """processor_parse_delimiter_gpu; same config keys as processor_parse_delimiter_native."""
+
+    def __init__(self, config, first_trip_columns=0):
+        text = config if isinstance(config, str) else json.dumps(config)
+        self._L = _lib()
+        h = ctypes.c_void_p()
+        err = ctypes.create_string_buffer(512)
+        rc = self._L.lc_delimiter_processor_create(text.encode("utf-8"), ctypes.byref(h), err, 512)
+        if rc != binding.LC_OK:
+            raise ProcessorInitError(err.value.decode())
+        self._h = h
+        if first_trip_columns:
+            self._L.lc_delimiter_processor_set_first_trip_columns(h, first_trip_columns)
+
+    def warnings(self):
+        p = self._L.lc_delimiter_processor_warnings(self._h)
+        try:
+            return [w for w in ctypes.string_at(p).decode("utf-8").split("\n") if w]
+        finally:
+            self._L.lc_free(p)
+
+    def process(self, group: EventGroup):
+        rc = self._L.lc_delimiter_processor_process(self._h, group._h)
+        if rc == binding.LC_ERR_NO_DEVICE:
+            raise binding.GpuUnavailableError("processor_parse_delimiter_gpu: no usable HIP device (no CPU path)")
+        if rc != binding.LC_OK:
+            raise RuntimeError("lc_delimiter_processor_process rc=%d" % rc)
+
+    def collect_alarms(self):
+        """-> the list that receives (kind, message bytes) for every PARSE_LOG_FAIL_ALARM the reference would raise"""
+        out = []
+        proto = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
+        self._alarm_cb = proto(lambda user, kind, msg, n: out.append((kind, ctypes.string_at(msg, n))))
+        self._L.lc_delimiter_processor_set_alarm_sink(self._h, ctypes.cast(self._alarm_cb, ctypes.c_void_p), None)
+        return out
+
+    def counters(self):
+        buf = (ctypes.c_uint64 * len(COUNTER_NAMES))()
+        self._L.lc_delimiter_processor_counters(self._h, buf)
+        return dict(zip(COUNTER_NAMES, [int(x) for x in buf]))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.lc_delimiter_processor_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

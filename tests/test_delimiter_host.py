@@ -1,0 +1,228 @@
+"""processor_parse_delimiter_gpu on a machine without a GPU: the product's HOST code (csrc/processor_parse_delimiter_gpu.cpp: Init, the
+gather, the mop-up rule, the stitch, the source-key rules, counters, alarms) and the product's PER-LINE ROUTINE (delimSplitLine of
+csrc/delim_vm.hpp, what delim_split_kernel runs per lane, compiled for the host) over every case of
+tests/golden/delimiter_reference_outputs.json -- the reference's own output.  tests/native/delimiter_double.cpp stands in for the device
+trip.  Events, contents, counters and alarm texts must equal the fixture's."""
+import ctypes
+import json
+import os
+import random
+import subprocess
+
+import pytest
+
+from helpers.delimiter_model import Engine
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_LIB = None
+CNT = 12
+
+
+def _double():
+    global _LIB
+    if _LIB is not None:
+        return _LIB
+    out_dir = os.path.join(ROOT, "tests", "_build")
+    os.makedirs(out_dir, exist_ok=True)
+    so = os.path.join(out_dir, "libdelimiter_double.so")
+    csrc = os.path.join(ROOT, "loongcollector_amd", "csrc")
+    srcs = [os.path.join(ROOT, "tests", "native", "delimiter_double.cpp")] + [os.path.join(csrc, f) for f in (
+        "processor_parse_delimiter_gpu.cpp", "processor_parse_regex_gpu.cpp", "event_model.cpp")]
+    deps = srcs + [os.path.join(csrc, h) for h in ("delim_vm.hpp", "processor_parse_delimiter_gpu.hpp", "processor_parse_regex_gpu.hpp",
+                                                   "event_model.hpp", "json_min.hpp")] + [os.path.join(ROOT, "include", "lc_delimiter.h")]
+    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
+        subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-w", "-I", os.path.join(ROOT, "include"), "-I", csrc,
+                               "-o", so] + srcs + ["-Wl,--no-undefined", "-Wl,-Bsymbolic"])
+    L = ctypes.CDLL(so)
+    vp, cp, sz, u32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32
+    L.lc_delimiter_processor_create.argtypes = [cp, ctypes.POINTER(vp), cp, sz]
+    L.lc_delimiter_processor_destroy.argtypes = [vp]
+    L.lc_delimiter_processor_warnings.restype = vp
+    L.lc_delimiter_processor_warnings.argtypes = [vp]
+    L.lc_delimiter_processor_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+    L.lc_delimiter_processor_set_alarm_sink.restype = None
+    L.lc_delimiter_processor_set_alarm_sink.argtypes = [vp, vp, vp]
+    L.lc_delimiter_processor_set_first_trip_columns.restype = None
+    L.lc_delimiter_processor_set_first_trip_columns.argtypes = [vp, u32]
+    L.dd_process_json.restype = vp
+    L.dd_process_json.argtypes = [vp, cp, cp, sz]
+    L.dd_free.argtypes = [vp]
+    L.lc_delim_create.argtypes = [cp, u32, ctypes.c_uint8, ctypes.c_int, u32, ctypes.POINTER(vp)]
+    L.lc_delim_destroy.argtypes = [vp]
+    L.dd_split_line.restype = None
+    L.dd_split_line.argtypes = [vp, cp, u32, u32, u32, vp, vp, vp]
+    L.dd_split_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
+    _LIB = L
+    return L
+
+
+class Product:
+    def __init__(self, config, first_trip_columns=0):
+        self.L = _double()
+        self.h = ctypes.c_void_p()
+        err = ctypes.create_string_buffer(512)
+        if self.L.lc_delimiter_processor_create(json.dumps(config).encode(), ctypes.byref(self.h), err, 512) != 0:
+            self.h = None
+            raise ValueError(err.value.decode("utf-8", "replace"))
+        if first_trip_columns:
+            self.L.lc_delimiter_processor_set_first_trip_columns(self.h, first_trip_columns)
+        self.alarms = []
+        proto = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
+        self._cb = proto(lambda user, kind, msg, n: self.alarms.append((kind, ctypes.string_at(msg, n).decode("latin-1"))))
+        self.L.lc_delimiter_processor_set_alarm_sink(self.h, ctypes.cast(self._cb, vp_t), None)
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.L.lc_delimiter_processor_destroy(self.h)
+            self.h = None
+
+    def warnings(self):
+        p = self.L.lc_delimiter_processor_warnings(self.h)
+        try:
+            return [w for w in ctypes.string_at(p).decode().split("\n") if w]
+        finally:
+            self.L.dd_free(p)
+
+    def process_group(self, group):
+        """fixture group in -> the events that are left, each a dict with its contents as an ordered list of pairs"""
+        err = ctypes.create_string_buffer(512)
+        p = self.L.dd_process_json(self.h, json.dumps(group, ensure_ascii=False).encode("latin-1"), err, 512)
+        assert p, err.value
+        try:
+            d = json.loads(ctypes.string_at(p).decode("latin-1"), object_pairs_hook=list)
+        finally:
+            self.L.dd_free(p)
+        out = []
+        for ev in dict(d or []).get("events", []):
+            ev = dict(ev)
+            ev["contents"] = [list(kv) for kv in ev.get("contents", [])]
+            out.append(ev)
+        return out
+
+    def process_lines(self, lines):
+        events = [{"contents": [["content", ln]], "timestamp": 1, "type": 1} for ln in lines]
+        events.append({"contents": [["other", "x"]], "timestamp": 1, "type": 1})
+        return [ev["contents"] for ev in self.process_group({"events": events})]
+
+    def counters(self):
+        c = (ctypes.c_uint64 * CNT)()
+        self.L.lc_delimiter_processor_counters(self.h, c)
+        return [int(x) for x in c]
+
+
+vp_t = ctypes.c_void_p
+
+
+def _cases(golden_dir):
+    with open(os.path.join(golden_dir, "delimiter_reference_outputs.json"), encoding="utf-8") as f:
+        return json.load(f)["cases"]
+
+
+def test_the_product_s_host_code_and_per_line_routine_equal_the_reference_on_every_case(golden_dir):
+    for k, case in enumerate(_cases(golden_dir)):
+        p = Product(case["config"])
+        assert p.process_lines(case["lines"]) == case["out"], (k, case["config"])
+        c = p.counters()
+        assert c[:4] == case["counters"], (k, case["config"])
+        assert c[4] == len(case["lines"]) + 1 and c[5] == len(case["out"]) and c[11] == 0
+        assert [m for _, m in p.alarms] == case["alarms"], (k, case["config"])
+        assert all(kind == (2 if m.startswith("keys count") else 0) for kind, m in p.alarms)
+
+
+def test_the_mop_up_rule_a_small_first_trip_gives_the_same_events_as_a_huge_one(golden_dir):
+    """a group whose widest line has more columns than the first trip kept: the lines that did not fit take ONE second trip"""
+    L = _double()
+    stats = (ctypes.c_uint64 * 2)()
+    for k, case in enumerate(_cases(golden_dir)):
+        widest = max(len(ln) for ln in case["lines"]) + 2
+        for w in (1, 2, 4):
+            small = Product(case["config"], first_trip_columns=w)
+            huge = Product(case["config"], first_trip_columns=widest)
+            L.dd_split_stats(stats)
+            calls0 = stats[0]
+            got = small.process_lines(case["lines"])
+            L.dd_split_stats(stats)
+            assert stats[0] - calls0 <= 2                      # one trip, and at most one mop-up
+            assert got == huge.process_lines(case["lines"]) == case["out"], (k, w, case["config"])
+            assert small.counters()[:4] == case["counters"] and [m for _, m in small.alarms] == case["alarms"]
+
+
+def _unit(golden_dir):
+    with open(os.path.join(golden_dir, "delimiter_unittest_vectors.json"), encoding="utf-8") as f:
+        return json.load(f)
+
+
+def same_events(got, expect):
+    """the unit test compares ToJsonString texts, whose contents are an object: keys and values, timestamps and type"""
+    def norm(ev):
+        return (dict(ev.get("contents", [])), ev.get("timestamp"), ev.get("timestampNanosecond", 0), ev.get("type"))
+    return [norm(e) for e in got] == [norm(e) for e in expect.get("events", [])]
+
+
+COUNTER_MEMBERS = {"mDiscardedEventsTotal": 0, "mOutFailedEventsTotal": 1, "mOutKeyNotFoundEventsTotal": 2, "mOutSuccessfulEventsTotal": 3,
+                   "mInEventsTotal": 4, "mOutEventsTotal": 5}
+
+
+def test_the_cases_of_the_reference_s_unit_test_through_the_product_s_host_code(golden_dir):
+    doc = _unit(golden_dir)
+    assert len({c["name"].split("/")[0] for c in doc["cases"]} | {c["name"] for c in doc["init_only"]}) == 14
+    for case in doc["cases"]:
+        assert case["reference_agrees"], case["name"]      # (the reference's own output equals its unit test's expectation)
+        for first_trip in (0, 1):
+            p = Product(case["config"], first_trip_columns=first_trip)
+            got = p.process_group(case["in"])
+            assert same_events(got, case["expect"]), (case["name"], got)
+            c = p.counters()
+            for member, value in case["asserted"].items():
+                assert c[COUNTER_MEMBERS[member]] == value, (case["name"], member)
+            assert c[:4] == case["reference_counters"], case["name"]
+            assert [m for _, m in p.alarms] == case["reference_alarms"], case["name"]
+    for case in doc["init_only"]:
+        Product(case["config"])
+
+
+def test_init_successes_failures_and_warnings_are_the_reference_s(golden_dir):
+    """the fixture holds what the reference's own Init answered for each config: accepted or not, and the alarm texts it raised
+    ("<message>: abort, module: ..." for a refusal, "<message>: use default value instead ..." / "<message>: ignore param ..." for
+    a warning); the product refuses the same configs with the same message and raises the same warnings in the same order"""
+    init = _unit(golden_dir)["init"]
+    assert sum(i["ok"] for i in init) >= 8 and sum(not i["ok"] for i in init) >= 10
+    for i in init:
+        messages = [a.split(": ")[0] for a in i["alarms"]]
+        if i["ok"]:
+            assert Product(i["config"]).warnings() == messages, i["config"]
+        else:
+            with pytest.raises(ValueError) as e:
+                Product(i["config"])
+            assert [str(e.value)] == messages[-1:], i["config"]
+
+
+def test_the_per_line_routine_against_the_model_on_random_lines_at_every_alignment():
+    """delimSplitLine through HostLineSource (junk outside the line) at all 16 positions of a line inside its 16-byte unit"""
+    L = _double()
+    rng = random.Random(20261016)
+    checked = 0
+    for sep, quote, mode, nk in ((b",", b'"', "extend", 3), (b"|", b"'", "keep", 2), (b"\t", b"\t", "discard", 2), (b"||", b'"', "keep", 3),
+                                 (b"@@@@", b'"', "extend", 2), (b",", b'"', "discard", 1)):
+        h = ctypes.c_void_p()
+        assert L.lc_delim_create(sep, len(sep), quote[0], {"extend": 0, "keep": 1, "discard": 2}[mode], nk, ctypes.byref(h)) == 0
+        model = Engine(sep, quote, mode, nk)
+        alphabet = [b"a", b"bc", b" ", sep, sep, quote, b"\r", sep[:1], quote + quote]
+        W = 6
+        for trial in range(1500):
+            n = rng.choice([0, 1, 2, 5, 15, 16, 17, 40, 63, 64, 65, 130, 300])
+            line = b"".join(rng.choice(alphabet) for _ in range(n))[: max(n, 0) * 2]
+            if trial % 5 == 0:
+                line = rng.choice([b"", b"  "]) + sep.join(quote + b"f" * rng.randint(0, 9) + quote if rng.random() < 0.3 else b"g" * rng.randint(0, 9)
+                                                          for _ in range(rng.randint(1, 12))) + rng.choice([b"", b" \r", b"\r"])
+            want = model.split_line(line)
+            status = ctypes.c_uint8(9)
+            ncols = ctypes.c_uint32(99)
+            spans = (ctypes.c_int32 * (2 * W))(*([-7] * (2 * W)))
+            L.dd_split_line(h, line, len(line), trial, W, ctypes.byref(status), ctypes.byref(ncols), spans)
+            assert (status.value, ncols.value) == want[:2], (sep, quote, mode, line)
+            for c, (b, e, doubled) in enumerate(want[2][:W]):
+                assert (spans[2 * c] & 0x7FFFFFFF, spans[2 * c + 1], spans[2 * c] < 0) == (b, e, doubled), (sep, quote, mode, line, c)
+            checked += 1
+        L.lc_delim_destroy(h)
+    assert checked == 9000
