@@ -108,6 +108,12 @@ def load(path=None):
     L.lc_split_scratch_bytes.argtypes = [ctypes.c_uint64]
     L.lc_split_lines_device.restype = i32
     L.lc_split_lines_device.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint8, vp, u32, vp, vp, sz, vp]
+    L.lc_regex_prepare_span_filter.restype = i32
+    L.lc_regex_prepare_span_filter.argtypes = [vp]
+    L.lc_span_filter_device.restype = i32
+    L.lc_span_filter_device.argtypes = [vp, u32, vp, vp, u32, vp, u32, u32, vp, vp, vp, u32, vp, vp]
+    L.lc_upload_pinned.restype = i32
+    L.lc_upload_pinned.argtypes = [vp, vp, sz, vp]
     L.lc_regex_match_host.restype = i32
     L.lc_regex_match_host.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp]
     L.lc_last_error.restype = cp
@@ -123,6 +129,10 @@ def _check(rc, what):
         raise GpuUnavailableError("%s: no usable HIP device (the engine has no CPU path)" % what)
     msg = load().lc_last_error()
     raise RuntimeError("%s failed: rc=%d %s" % (what, rc, msg.decode() if msg else ""))
+
+
+class LcSpanFilter(ctypes.Structure):
+    _fields_ = [("re", ctypes.c_void_p), ("group", ctypes.c_uint32)]
 
 
 class LcMatchJob(ctypes.Structure):
@@ -286,6 +296,13 @@ class GpuRegex:
         self._L.lc_regex_prefer_wave_tdfa.argtypes = [ctypes.c_void_p]
         return bool(self._L.lc_regex_prefer_wave_tdfa(self._h))
 
+    def prepare_span_filter(self, check=True):
+        """lc_regex_prepare_span_filter: the handle gets the yes/no automaton span_filter_device walks; -> the status code"""
+        rc = self._L.lc_regex_prepare_span_filter(self._h)
+        if check:
+            _check(rc, "lc_regex_prepare_span_filter")
+        return rc
+
     def required_literal(self):
         n = ctypes.c_size_t()
         p = self._L.lc_regex_required_literal(self._h, ctypes.byref(n))
@@ -341,13 +358,42 @@ class GpuRegex:
         return caps, status
 
 
-def split_lines_device(d_data, nbytes, d_off, d_nlines, d_scratch, split_char=10, stream=None):
-    """ProcessorSplitLogStringNative on the device; all arguments are torch tensors on the current HIP device."""
+def split_lines_device(d_data, nbytes, d_off, d_nlines, d_scratch, split_char=10, stream=None, off_capacity=None, check=True):
+    """ProcessorSplitLogStringNative on the device; all arguments are torch tensors on the current HIP device.
+    off_capacity: entries of d_off the library may write (default: all of them).  -> the status code (check=False: not raised)"""
     L = load()
-    rc = L.lc_split_lines_device(d_data.data_ptr(), nbytes, split_char, d_off.data_ptr(), d_off.numel(),
+    rc = L.lc_split_lines_device(d_data.data_ptr(), nbytes, split_char, d_off.data_ptr(),
+                                 d_off.numel() if off_capacity is None else off_capacity,
                                  d_nlines.data_ptr(), d_scratch.data_ptr(), d_scratch.numel() * d_scratch.element_size(),
                                  stream)
-    _check(rc, "lc_split_lines_device")
+    if check:
+        _check(rc, "lc_split_lines_device")
+    return rc
+
+
+def span_filter_device(rules, d_data, d_off, sep_bytes, d_nlines, max_lines, ngroups, d_caps, d_status, d_packed, packed_cap_rows,
+                       d_counts, stream=None, check=True):
+    """lc_span_filter_device on the output of a device parse; rules: list of (GpuRegex, 1-based group of the parse regex), each
+    regex after prepare_span_filter().  d_packed may be None when packed_cap_rows is 0.  -> the status code"""
+    L = load()
+    arr = (LcSpanFilter * max(len(rules), 1))()
+    for k, (rx, group) in enumerate(rules):
+        arr[k] = LcSpanFilter(rx.handle, group)
+    rc = L.lc_span_filter_device(ctypes.cast(arr, ctypes.c_void_p) if rules else None, len(rules), d_data.data_ptr(), d_off.data_ptr(),
+                                 sep_bytes, d_nlines.data_ptr(), max_lines, ngroups, d_caps.data_ptr(), d_status.data_ptr(),
+                                 d_packed.data_ptr() if d_packed is not None else None, packed_cap_rows, d_counts.data_ptr(), stream)
+    if check:
+        _check(rc, "lc_span_filter_device")
+    return rc
+
+
+def upload_pinned(h_src, d_dst, nbytes, stream=None, check=True):
+    """lc_upload_pinned: nbytes (rounded up to 16) from a pinned host tensor to a device tensor by a kernel; both 16-byte aligned.
+    -> the status code"""
+    rc = load().lc_upload_pinned(h_src.data_ptr(), d_dst.data_ptr(), nbytes, stream)
+    if check:
+        _check(rc, "lc_upload_pinned")
+    return rc
 
 
 def sched_scratch_bytes(n):

@@ -10,6 +10,7 @@ import itertools
 import numpy as np
 import pytest
 
+from helpers.pipeline_corpus import access_log_buffer as _buffer
 from loongcollector_amd import binding as B
 from loongcollector_amd import corpus
 from loongcollector_amd.processor import EventGroup, Pipeline
@@ -18,27 +19,6 @@ from oracle.processor_oracle import LogEventModel, ProcessorOracle
 from oracle.split_oracle import split_lines
 
 pytestmark = pytest.mark.gpu
-
-
-def _buffer(n_lines, seed=5, trailing_newline=True):
-    """n access-log lines for regex B; every 7th has the user agent the benchmark's filter keeps, every 11th is junk the parser
-    cannot match, every 13th is empty"""
-    rng = np.random.default_rng(seed)
-    data, off, length = corpus.apache_batch(n_lines, "B", line_bytes=200, seed=seed, pool_lines=min(n_lines, 512))
-    lines = [bytes(data[o:o + l]) for o, l in zip(off[:-1], length)]
-    out = []
-    for i, l in enumerate(lines):
-        if i % 13 == 12:
-            out.append(b"")
-        elif i % 11 == 10:
-            out.append(b"{\"level\": \"info\", \"msg\": \"not an access log %d\"}" % i)
-        elif i % 7 == 6:
-            head, _, _ = l.rpartition(b' "')
-            out.append(head + b' "no-agent"')
-        else:
-            out.append(l)
-    buf = b"\n".join(out)
-    return buf + (b"\n" if trailing_newline else b""), int(rng.integers(0, 1 << 40))
 
 
 def _oracle_chain(buf, parse_cfg, filter_cfg, file_offset, file_offset_key):
