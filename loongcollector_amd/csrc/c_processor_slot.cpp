@@ -23,10 +23,15 @@ extern "C" {
 __attribute__((weak)) int lcDelimiterSlotInit(const char* config_text, void** state);
 __attribute__((weak)) void lcDelimiterSlotProcess(void* state, void* native_group);
 __attribute__((weak)) void lcDelimiterSlotFinalize(void* state);
+// ... and the timestamp processor's (processor_parse_timestamp_gpu.cpp), on the same terms
+__attribute__((weak)) int lcTimestampSlotInit(const char* config_text, void** state);
+__attribute__((weak)) void lcTimestampSlotProcess(void* state, void* native_group);
+__attribute__((weak)) void lcTimestampSlotFinalize(void* state);
 }
 
 struct lc_processor {
     void* delimiter = nullptr;  // slot only: the instance was built from a config whose Type is processor_parse_delimiter_gpu
+    void* timestamp = nullptr;  // slot only: ... whose Type is processor_parse_timestamp_gpu
     ProcessorParseRegexGpu impl;
     // the part ProcessorInstance adds around every plugin (ProcessorInstance.cpp:46-63)
     std::atomic<uint64_t> inEvents{0}, outEvents{0}, inBytes{0}, outBytes{0}, processUs{0};
@@ -406,12 +411,14 @@ static int slotInit(processor_instance_t* ins, void* config, void* context) {
 #else
     const char* configText = static_cast<const char*>(config);
 #endif
-    // "Type": "processor_parse_delimiter_gpu" builds the delimiter parser; every other config builds the regex parser, as before
-    bool wantsDelimiter = false;
+    // "Type": "processor_parse_delimiter_gpu" builds the delimiter parser, "processor_parse_timestamp_gpu" the timestamp processor;
+    // every other config builds the regex parser, as before
+    bool wantsDelimiter = false, wantsTimestamp = false;
     try {
         const lcjson::Value cfg = lcjson::parse(configText);
         const lcjson::Value* type = cfg.isObject() ? cfg.find("Type") : nullptr;
         wantsDelimiter = type && type->isString() && type->str == "processor_parse_delimiter_gpu";
+        wantsTimestamp = type && type->isString() && type->str == "processor_parse_timestamp_gpu";
     } catch (const std::exception&) {
     }
     if (wantsDelimiter) {
@@ -421,6 +428,16 @@ static int slotInit(processor_instance_t* ins, void* config, void* context) {
         }
         auto holder = std::make_unique<lc_processor>();
         if (lcDelimiterSlotInit(configText, &holder->delimiter) != 0) return -1;
+        ins->plugin_state = holder.release();
+        return 0;
+    }
+    if (wantsTimestamp) {
+        if (!lcTimestampSlotInit) {
+            std::fprintf(stderr, "[processor_parse_timestamp_gpu] this build of the plugin does not hold the timestamp processor\n");
+            return -1;
+        }
+        auto holder = std::make_unique<lc_processor>();
+        if (lcTimestampSlotInit(configText, &holder->timestamp) != 0) return -1;
         ins->plugin_state = holder.release();
         return 0;
     }
@@ -441,12 +458,17 @@ static int slotInit(processor_instance_t* ins, void* config, void* context) {
 static void slotFinalize(void* state) {
     lc_processor_t* p = static_cast<lc_processor_t*>(state);
     if (p && p->delimiter) lcDelimiterSlotFinalize(p->delimiter);
+    if (p && p->timestamp) lcTimestampSlotFinalize(p->timestamp);
     lc_processor_destroy(p);
 }
 static void slotProcess(void* state, void* logGroup) {
     if (!state || !logGroup) return;
     if (static_cast<lc_processor_t*>(state)->delimiter) {
         lcDelimiterSlotProcess(static_cast<lc_processor_t*>(state)->delimiter, logGroup);
+        return;
+    }
+    if (static_cast<lc_processor_t*>(state)->timestamp) {
+        lcTimestampSlotProcess(static_cast<lc_processor_t*>(state)->timestamp, logGroup);
         return;
     }
     processGroup(static_cast<lc_processor_t*>(state), *static_cast<PipelineEventGroup*>(logGroup));

@@ -1,0 +1,197 @@
+"""ctypes binding of the timestamp parser (include/lc_timestamp.h): GpuStrptime is the engine (strptime_kernel over values in device or
+host memory, also straight from a parser's capture table), TimestampProcessor the processor_parse_timestamp_gpu plugin over event groups
+(same shape as processor.Processor).  There is no CPU path: every parse needs a HIP device and raises otherwise."""
+import ctypes
+import json
+
+import numpy as np
+
+from . import binding
+from .processor import COUNTER_NAMES, EventGroup, ProcessorInitError, _lib as _processor_lib
+
+LC_TS_OK, LC_TS_HAS_YEAR, LC_TS_DST, LC_TS_EPOCH, LC_TS_ABSENT = 1, 2, 4, 8, 0x80
+LC_TS_MAX_PROGRAM = 64
+CLOCK = ctypes.CFUNCTYPE(ctypes.c_int64, ctypes.c_void_p)
+
+
+class LcTsOut(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_void_p), ("secs", ctypes.c_void_p), ("nanos", ctypes.c_void_p), ("matched", ctypes.c_void_p),
+                ("frac_len", ctypes.c_void_p), ("same_as_prev", ctypes.c_void_p)]
+
+
+def _lib():
+    L = _processor_lib()
+    if not getattr(L, "_lc_timestamp_bound", False):
+        vp, cp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
+        out = ctypes.POINTER(LcTsOut)
+        L.lc_strptime_create.restype = i32
+        L.lc_strptime_create.argtypes = [cp, ctypes.POINTER(vp), cp, sz]
+        L.lc_strptime_destroy.argtypes = [vp]
+        L.lc_strptime_program.restype = u32
+        L.lc_strptime_program.argtypes = [vp, ctypes.POINTER(u32)]
+        L.lc_strptime_parse_spans_device.restype = i32
+        L.lc_strptime_parse_spans_device.argtypes = [vp, vp, vp, vp, u32, out, vp]
+        L.lc_strptime_parse_captures_device.restype = i32
+        L.lc_strptime_parse_captures_device.argtypes = [vp, vp, vp, vp, u32, u32, vp, u32, u32, out, vp]
+        L.lc_strptime_parse_host.restype = i32
+        L.lc_strptime_parse_host.argtypes = [vp, vp, vp, u32, out]
+        L.lc_timestamp_zone_seconds.restype = ctypes.c_int64
+        L.lc_timestamp_zone_seconds.argtypes = [ctypes.c_int64, i32]
+        L.lc_timestamp_zone_reset.restype = None
+        L.lc_timestamp_processor_create.restype = i32
+        L.lc_timestamp_processor_create.argtypes = [cp, ctypes.POINTER(vp), cp, sz]
+        L.lc_timestamp_processor_create_with_clock.restype = i32
+        L.lc_timestamp_processor_create_with_clock.argtypes = [cp, vp, vp, ctypes.POINTER(vp), cp, sz]
+        L.lc_timestamp_processor_destroy.argtypes = [vp]
+        L.lc_timestamp_processor_warnings.restype = vp
+        L.lc_timestamp_processor_warnings.argtypes = [vp]
+        L.lc_timestamp_processor_zone_offset.restype = ctypes.c_int32
+        L.lc_timestamp_processor_zone_offset.argtypes = [vp]
+        L.lc_timestamp_processor_process.restype = i32
+        L.lc_timestamp_processor_process.argtypes = [vp, vp]
+        L.lc_timestamp_processor_set_clock.restype = None
+        L.lc_timestamp_processor_set_clock.argtypes = [vp, vp, vp]
+        L.lc_timestamp_processor_set_discard.restype = None
+        L.lc_timestamp_processor_set_discard.argtypes = [vp, i32, ctypes.c_int32, i32]
+        L.lc_timestamp_processor_set_plain_walk.restype = None
+        L.lc_timestamp_processor_set_plain_walk.argtypes = [vp, i32]
+        L.lc_timestamp_processor_walk_stats.restype = None
+        L.lc_timestamp_processor_walk_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+        L.lc_timestamp_processor_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
+        L.lc_timestamp_processor_history_failures.restype = ctypes.c_uint64
+        L.lc_timestamp_processor_history_failures.argtypes = [vp]
+        L.lc_timestamp_processor_set_alarm_sink.restype = None
+        L.lc_timestamp_processor_set_alarm_sink.argtypes = [vp, vp, vp]
+        L._lc_timestamp_bound = True
+    return L
+
+
+class GpuStrptime:
+    """The engine: a SourceFormat compiled once.  Raises ValueError for a format beyond the kernel's program window."""
+
+    def __init__(self, fmt):
+        self._L = _lib()
+        h = ctypes.c_void_p()
+        err = ctypes.create_string_buffer(256)
+        fmt = fmt.encode("latin-1") if isinstance(fmt, str) else bytes(fmt)
+        rc = self._L.lc_strptime_create(fmt, ctypes.byref(h), err, 256)
+        if rc != binding.LC_OK:
+            raise ValueError(err.value.decode() or "lc_strptime_create rc=%d" % rc)
+        self.handle = h
+
+    def program(self):
+        w = (ctypes.c_uint32 * LC_TS_MAX_PROGRAM)()
+        return list(w)[:self._L.lc_strptime_program(self.handle, w)]
+
+    @staticmethod
+    def device_outputs(n, device):
+        """-> dict of torch tensors for one call: status u8, secs i64, nanos i32 (the bits of a u32), matched i32, frac_len i32,
+        same_as_prev u8"""
+        import torch
+        return {"status": torch.empty(n, dtype=torch.uint8, device=device), "secs": torch.empty(n, dtype=torch.int64, device=device),
+                "nanos": torch.empty(n, dtype=torch.int32, device=device), "matched": torch.empty(n, dtype=torch.int32, device=device),
+                "frac_len": torch.empty(n, dtype=torch.int32, device=device), "same_as_prev": torch.empty(n, dtype=torch.uint8, device=device)}
+
+    @staticmethod
+    def _out(t):
+        return LcTsOut(*(t[k].data_ptr() for k in ("status", "secs", "nanos", "matched", "frac_len", "same_as_prev")))
+
+    def parse_spans_device(self, d_data, d_off, d_spans, n, out, stream=None):
+        """torch device tensors: d_data u8[], d_off i32/u32[>= n], d_spans i32[n, 2]; out: device_outputs(); asynchronous"""
+        o = self._out(out)
+        binding._check(self._L.lc_strptime_parse_spans_device(self.handle, d_data.data_ptr(), d_off.data_ptr(), d_spans.data_ptr(), n,
+                                                              ctypes.byref(o), ctypes.c_void_p(stream or 0)), "lc_strptime_parse_spans_device")
+
+    def parse_captures_device(self, d_data, d_off, d_caps, ngroups, group, d_line_status, match_value, n, out, stream=None):
+        """the value is group `group` of a parser's capture table d_caps i32[n, 2 * ngroups], present where d_line_status == match_value"""
+        o = self._out(out)
+        binding._check(self._L.lc_strptime_parse_captures_device(
+            self.handle, d_data.data_ptr(), d_off.data_ptr(), d_caps.data_ptr(), ngroups, group,
+            d_line_status.data_ptr() if d_line_status is not None else None, match_value, n, ctypes.byref(o), ctypes.c_void_p(stream or 0)),
+            "lc_strptime_parse_captures_device")
+
+    def parse_host(self, values):
+        """list of bytes -> dict of numpy arrays (one device trip)"""
+        n = len(values)
+        blob = np.frombuffer(b"".join(values) + b"\0", np.uint8)
+        lens = np.array([len(v) for v in values], np.uint32)
+        off = np.zeros(n, np.int64)
+        if n > 1:
+            off[1:] = np.cumsum(lens[:-1])
+        ptrs = (blob.ctypes.data + off).astype(np.uint64)
+        res = {"status": np.zeros(n, np.uint8), "secs": np.zeros(n, np.int64), "nanos": np.zeros(n, np.uint32),
+               "matched": np.zeros(n, np.int32), "frac_len": np.zeros(n, np.int32), "same_as_prev": np.zeros(n, np.uint8)}
+        o = LcTsOut(*(res[k].ctypes.data for k in ("status", "secs", "nanos", "matched", "frac_len", "same_as_prev")))
+        binding._check(self._L.lc_strptime_parse_host(self.handle, ptrs.ctypes.data, lens.ctypes.data, n, ctypes.byref(o)), "lc_strptime_parse_host")
+        return res
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self._L.lc_strptime_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TimestampProcessor:
+    """processor_parse_timestamp_gpu; same config keys as processor_parse_timestamp_native.  clock: a callable returning epoch seconds
+    ("now" of the year deduction and of the discard rule); default time()."""
+
+    def __init__(self, config, clock=None):
+        text = config if isinstance(config, str) else json.dumps(config)
+        self._L = _lib()
+        h = ctypes.c_void_p()
+        err = ctypes.create_string_buffer(512)
+        self._clock = CLOCK(lambda user: int(clock())) if clock is not None else None
+        rc = self._L.lc_timestamp_processor_create_with_clock(
+            text.encode("utf-8"), ctypes.cast(self._clock, ctypes.c_void_p) if self._clock else None, None, ctypes.byref(h), err, 512)
+        if rc != binding.LC_OK:
+            raise ProcessorInitError(err.value.decode())
+        self._h = h
+
+    def warnings(self):
+        p = self._L.lc_timestamp_processor_warnings(self._h)
+        try:
+            return [w for w in ctypes.string_at(p).decode("utf-8").split("\n") if w]
+        finally:
+            self._L.lc_free(p)
+
+    def set_discard(self, enabled=True, interval=43200, onetime=False):
+        self._L.lc_timestamp_processor_set_discard(self._h, int(enabled), interval, int(onetime))
+
+    def process(self, group: EventGroup):
+        rc = self._L.lc_timestamp_processor_process(self._h, group._h)
+        if rc == binding.LC_ERR_NO_DEVICE:
+            raise binding.GpuUnavailableError("processor_parse_timestamp_gpu: no usable HIP device (no CPU path)")
+        if rc != binding.LC_OK:
+            raise RuntimeError("lc_timestamp_processor_process rc=%d" % rc)
+
+    def collect_alarms(self):
+        """-> the list that receives (kind, message bytes): kind 0 PARSE_TIME_FAIL_ALARM, kind 1 OUTDATED_LOG_ALARM"""
+        out = []
+        proto = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
+        self._alarm_cb = proto(lambda user, kind, msg, n: out.append((kind, ctypes.string_at(msg, n))))
+        self._L.lc_timestamp_processor_set_alarm_sink(self._h, ctypes.cast(self._alarm_cb, ctypes.c_void_p), None)
+        return out
+
+    def counters(self):
+        buf = (ctypes.c_uint64 * len(COUNTER_NAMES))()
+        self._L.lc_timestamp_processor_counters(self._h, buf)
+        d = dict(zip(COUNTER_NAMES, [int(x) for x in buf]))
+        d["history_failure_total"] = int(self._L.lc_timestamp_processor_history_failures(self._h))
+        return d
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.lc_timestamp_processor_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
