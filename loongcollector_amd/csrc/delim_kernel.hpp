@@ -18,81 +18,14 @@
 #include <hip/hip_runtime.h>
 
 #include "delim_vm.hpp"
+#include "wave_tile_source.hpp"
 
 namespace lcdelim {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef u32x4 __attribute__((address_space(3))) * LdsQuadPtr;
-typedef const u32x4 __attribute__((address_space(1))) * GlobalQuadPtr;
-
 constexpr int kBlock = 256;
-constexpr uint32_t kTileBytes = 64 * kDelimStageBytes;  // per wavefront
-
-__device__ __forceinline__ void waveLdsSync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-struct WaveTileSource {
-    uint32_t lane, tile;       // tile: LDS byte address of the wavefront's tile
-    uint32_t headBytes;
-    uintptr_t rowStart;        // global address of this lane's row (16-byte aligned)
-    uint32_t myRow, mySwizzle;
-    uintptr_t srcRow[4];       // row starts of the rows this lane fetches for
-    uint32_t srcEnd[4], dstAddr[4], seg;
-    u32x4 in[4];
-
-    __device__ __forceinline__ WaveTileSource(uint32_t lane_, uint32_t tile_, uintptr_t lineAddr)
-        : lane(lane_), tile(tile_), headBytes(uint32_t(lineAddr & 15u)), rowStart(lineAddr - (lineAddr & 15u)) {
-        myRow = tile + lane * kDelimStageBytes;
-        mySwizzle = ((lane >> 1) & 3u) << 4;
-        seg = (lane & 3u) * 16;
-    }
-    __device__ __forceinline__ uint32_t head() const { return headBytes; }
-    __device__ __forceinline__ void tailQuad(uint32_t p16, uint32_t q[4]) const {
-        const u32x4 v = *reinterpret_cast<GlobalQuadPtr>(rowStart + p16);
-        q[0] = v.x; q[1] = v.y; q[2] = v.z; q[3] = v.w;
-    }
-    __device__ __forceinline__ void fetch(uint32_t s) {  // stage s -> in[]
-        const uint32_t at = s * kDelimStageBytes + seg;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            in[i] = u32x4{0, 0, 0, 0};
-            if (at < srcEnd[i]) in[i] = *reinterpret_cast<GlobalQuadPtr>(srcRow[i] + at);
-        }
-    }
-    // end: this lane's trimmed end in tile coordinates (0: nothing to walk).  Every lane of the wavefront calls this together.
-    __device__ __forceinline__ uint32_t stageCount(uint32_t end) {
-        uint32_t stages = (end + kDelimStageBytes - 1) / kDelimStageBytes;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const uint32_t other = __shfl_xor(stages, d, 64);
-            stages = other > stages ? other : stages;
-        }
-        stages = __builtin_amdgcn_readfirstlane(stages);
-        const uint32_t lo = uint32_t(rowStart), hi = uint32_t(uint64_t(rowStart) >> 32);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int r = 16 * i + int(lane >> 2);
-            srcRow[i] = uintptr_t((uint64_t(__shfl(hi, r, 64)) << 32) | __shfl(lo, r, 64));
-            srcEnd[i] = __shfl(end, r, 64);
-            dstAddr[i] = tile + uint32_t(r) * kDelimStageBytes + (seg ^ (((uint32_t(r) >> 1) & 3u) << 4));
-        }
-        if (stages) fetch(0);
-        return stages;
-    }
-    __device__ __forceinline__ void stage(uint32_t s) {
-        waveLdsSync();  // every lane has read its row of the stage before
-#pragma unroll
-        for (int i = 0; i < 4; ++i) *reinterpret_cast<LdsQuadPtr>(dstAddr[i]) = in[i];
-        waveLdsSync();
-        fetch(s + 1);  // (past the longest line: no lane's guard passes, nothing is issued)
-    }
-    __device__ __forceinline__ void rowQuad(uint32_t k, uint32_t q[4]) const {
-        const u32x4 v = *reinterpret_cast<LdsQuadPtr>(myRow + ((k * 16) ^ mySwizzle));
-        q[0] = v.x; q[1] = v.y; q[2] = v.z; q[3] = v.w;
-    }
-};
+static_assert(kDelimStageBytes == lcwave::kWaveStageBytes, "delimSplitLine walks the stages WaveTileSource hands out");
+constexpr uint32_t kTileBytes = lcwave::kWaveTileBytes;  // per wavefront
+using lcwave::WaveTileSource;
 
 template <bool QUOTE>
 __global__ __launch_bounds__(kBlock) void delim_split_kernel(DelimConfig cfg, const uint8_t* __restrict__ data,

@@ -2084,6 +2084,7 @@ extern "C" void lc_thread_release(void) {
     lcFilterThreadRelease();
     lcDelimThreadRelease();
     lcTimestampThreadRelease();
+    lcJsonThreadRelease();
 }
 
 extern "C" void lc_nfa_set_dfs(int on) { gNfaDfsMode.store(on < 0 ? -1 : (on ? 1 : 0), std::memory_order_relaxed); }

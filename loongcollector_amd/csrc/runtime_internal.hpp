@@ -19,6 +19,7 @@ void lcMultilineThreadRelease();                       // multiline_device.hip: 
 void lcFilterThreadRelease();                          // processor_filter_gpu.cpp: the same for the filter
 void lcDelimThreadRelease();                           // delim_device.hip: the same for the delimiter parser's host entry
 void lcTimestampThreadRelease();                       // timestamp_device.hip: the same for the timestamp parser's host entry
+void lcJsonThreadRelease();                            // json_device.hip: the same for the JSON parser's host entry
 // The device a HOST entry point (processors, lc_*_match_host, multiline, filter, pipeline) runs on for the calling thread: the thread's
 // binding (lc_runtime_bind_thread; first call binds by the process-wide policy), made current for the thread.  LC_OK or an error code.
 int lcHostEntryDevice(int* dev);

@@ -1,0 +1,290 @@
+"""The JSON parser on the device (include/lc_json.h): json_walk_kernel against tests/helpers/json_model.py -- which
+tests/test_json_model.py holds to the hand-written contract vectors and to CPython's json -- and processor_parse_json_gpu against the
+vectors' literal members."""
+import json
+import os
+import random
+
+import numpy as np
+import pytest
+
+from helpers import json_cases as jc
+from helpers import json_model as jm
+
+pytestmark = pytest.mark.gpu
+
+
+def _walk_host(lines, W):
+    from loongcollector_amd import json_parse
+    data, off = jc.pack(lines)
+    return json_parse.GpuJson().walk_host(data, off, W) + (off,)
+
+
+def _check(lines, result, W):
+    st, nm, err, rec, shadow, moved, off = result
+    for i, ln in enumerate(lines):
+        why = jc.same_as_model(ln, st[i], nm[i], err[i], rec[i], shadow[off[i]:off[i + 1]], W)
+        assert why is None, (i, ln[:300], why)
+
+
+def _walk_device(lines, W, device="cuda:0"):
+    import torch
+    from loongcollector_amd import json_parse
+    dev = torch.device(device)
+    data, off = jc.pack(lines)
+    n = len(lines)
+    d_data = torch.from_numpy(data).to(dev)
+    d_off = torch.from_numpy(off.astype(np.int32)).to(dev)
+    d_st = torch.full((max(n, 1),), 77, dtype=torch.uint8, device=dev)
+    d_nm = torch.full((max(n, 1),), -5, dtype=torch.int32, device=dev)
+    d_err = torch.full((max(n, 1),), -5, dtype=torch.int32, device=dev)
+    d_rec = torch.zeros((max(n, 1), max(W, 1), 20), dtype=torch.uint8, device=dev)
+    d_sh = torch.full((len(data),), 0xEE, dtype=torch.uint8, device=dev)
+    json_parse.GpuJson().walk_device(d_data, d_off, n, W, d_st, d_nm, d_err, d_rec, d_sh, stream=torch.cuda.current_stream().cuda_stream)
+    torch.cuda.synchronize()
+    rec = d_rec.cpu().numpy().reshape(max(n, 1), max(W, 1) * 20).view(jc.MEMBER)
+    return d_st.cpu().numpy()[:n], d_nm.cpu().numpy()[:n].astype(np.int64), d_err.cpu().numpy()[:n].astype(np.int64), rec[:n], d_sh.cpu().numpy(), 0, off
+
+
+def test_vectors_both_files_through_walk_host():
+    cases = jc.contract_cases()
+    lines = [jc.expand(c["line"]) for c in cases]
+    for W in (8, 1):
+        result = _walk_host(lines, W)
+        _check(lines, result, W)
+        st, nm, err = result[:3]
+        for i, c in enumerate(cases):
+            assert st[i] == jc.STATUS_NAMES[c["status"]], c["name"]
+            if c["status"] == "fail":
+                assert err[i] == c["errpos"], c["name"]
+            if c["status"] == "ok":
+                assert nm[i] == len(c["members"]), c["name"]
+    doc = jc.unittest_doc()
+    lines = [jc.expand(v) for case in doc["cases"] for ev in case["in"] for k, v in ev.items() if k == case["config"]["SourceKey"]]
+    lines += [jc.expand(s) for s in doc["invalid_formats"]]
+    _check(lines, _walk_host(lines, 8), 8)
+
+
+def _group_contents(g):
+    return [ev.get("contents", {}) for ev in (g.to_dict() or {}).get("events", [])]      # (a group left without events prints null)
+
+
+def test_vectors_both_files_through_the_processor():
+    from loongcollector_amd import json_parse
+    from loongcollector_amd.processor import EventGroup
+    cases = [c for c in jc.contract_cases()]
+    lines = [jc.expand(c["line"]) for c in cases]
+    data, off = jc.pack(lines)
+    for first_trip in (0, 1):
+        p = json_parse.JsonProcessor({"SourceKey": "content"}, first_trip_members=first_trip)
+        alarms = p.collect_alarms()
+        g = EventGroup.from_lines(data, off[:-1], off[1:] - off[:-1])
+        p.process(g)
+        kept = [c for c in cases if c["status"] == "ok"]      # (failed and empty ones are left without a content and erased, :139)
+        got = _group_contents(g)
+        assert len(got) == len(kept)
+        for c, ev in zip(kept, got):
+            want = {}
+            for k, _, v in c["members"]:
+                want[jc.expand(k).decode("utf-8")] = jc.expand(v).decode("utf-8")
+            assert ev == want, c["name"]
+        n_fail = sum(c["status"] == "fail" for c in cases)
+        cnt = p.counters()
+        assert (cnt["discarded_events_total"], cnt["out_failed_events_total"], cnt["out_successful_events_total"]) == (len(cases) - len(kept), n_fail, len(kept))
+        assert cnt["device_failed_events_total"] == 0 and cnt["in_events_total"] == len(cases)
+        assert [m for _, m in alarms] == [b"parse json fail:" + jc.expand(c["line"]) for c in cases if c["status"] == "fail"]
+        g.close()
+        p.close()
+    doc = jc.unittest_doc()
+    text = lambda ev: {jc.expand(k).decode("utf-8"): jc.expand(v).decode("utf-8") for k, v in ev.items()}      # noqa: E731
+    for case in doc["cases"]:
+        for first_trip in (0, 1):
+            p = json_parse.JsonProcessor(case["config"], first_trip_members=first_trip)
+            g = EventGroup({"events": [{"contents": text(ev), "timestamp": 12345678901, "type": 1} for ev in case["in"]]})
+            p.process(g)
+            got = _group_contents(g)
+            assert got == [text(ev) for ev in case["expect"]], case["name"]
+            cnt = p.counters()
+            for name, value in case["counters"].items():
+                assert cnt[name] == value, (case["name"], name)
+            for probe in case.get("probe_substrings", []):
+                assert any(probe in k or probe in v for ev in got for k, v in ev.items()), (case["name"], probe)
+            g.close()
+            p.close()
+    for case in doc["init_only"]:
+        json_parse.JsonProcessor(case["config"]).close()
+    p = json_parse.JsonProcessor({"SourceKey": "content"})
+    g = EventGroup({"events": [{"contents": {"content": s}, "timestamp": 1, "type": 1} for s in doc["invalid_formats"]]})
+    p.process(g)
+    assert len(g) == 0 and p.counters()["out_failed_events_total"] == len(doc["invalid_formats"])
+
+
+TOKENS = [("escaped quote", b'{"k":"', b'\\"', b'"}'), ("u escape", b'{"k":"', b"\\u20AC", b'"}'), ("surrogate pair", b'{"k":"', b"\\uD83D\\uDE00", b'"}'),
+          ("utf-8 of 2", b'{"k":"', "é".encode(), b'"}'), ("utf-8 of 3", b'{"k":"', "€".encode(), b'"}'), ("utf-8 of 4", b'{"k":"', "😀".encode(), b'"}'),
+          ("20-digit integer", b'{"k":', b"18446744073709551615", b'}'), ("21-digit integer", b'{"k":', b"184467440737095516150", b'}'),
+          ("exponent", b'{"k":', b"-12.5e+17", b',"z":1}'), ("true", b'{"k":', b"true", b'}'), ("false", b'{"k":[', b"false", b']}'),
+          ("null", b'{"k":', b"null", b',"n":null}'), ("key colon value", b'{"k', b'":"', b'v"}'), ("closing brace and blanks", b'{"k":1', b"} \t\r\n ", b""),
+          ("escaped key", b'{"', b"a\\tb\\u00e9", b'":"v"}'), ("utf-8 cut by a quote", b'{"k":"', b'\xe2\x82"', b'}')]
+
+
+def test_every_token_across_the_stage_boundary_at_every_alignment():
+    """line i starts at alignment (offset mod 16) chosen by a filler line in front of it; the token's bytes are put across byte
+    63 | 64 of the line's row (counted from the 16-byte boundary below its first byte) at every split position"""
+    lines, at = [], 0
+    for name, before, token, after in TOKENS:
+        for head in range(16):
+            for split in range(1, len(token)):
+                fill = (16 - at % 16 + head) % 16
+                lines.append(b" " * fill)               # (a blank line: fails at its end, and moves the next line to `head`)
+                at += fill
+                # the token's byte `split` is byte 64 of the row: head + len(prefix) + split == 64
+                pad = 64 - head - split - len(before) - 7
+                assert pad >= 0
+                prefix = b'{"p":"' + b"x" * pad + b'",' + before[1:]
+                line = prefix + token + after
+                assert head + len(prefix) + split == 64
+                lines.append(line)
+                at += len(line)
+    assert 2000 < len(lines) < 8000
+    result = _walk_host(lines, 4)
+    off = result[-1]
+    assert {int(o) % 16 for o in off[1:-1:2]} == set(range(16))
+    _check(lines, result, 4)
+    _check(lines, _walk_device(lines, 4), 4)
+    st = result[0]
+    assert int((st == jm.OK).sum()) > len(lines) // 2 - 200
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 257])
+def test_batch_sizes(n):
+    rng = random.Random(n)
+    lines = [jc.gen_document(rng) for _ in range(n)]
+    _check(lines, _walk_host(lines, 8), 8)
+    _check(lines, _walk_device(lines, 8), 8)
+
+
+def test_a_wavefront_mixing_lengths_0_1_2_63_64_65_4096():
+    def doc(n):
+        if n < 2:
+            return b"{"[:n]
+        if n < 9:
+            return (b"{}" + b" " * n)[:n]
+        return b'{"k":"' + b"y" * (n - 8) + b'"}'
+    lengths = [0, 1, 2, 63, 64, 65, 4096]
+    lines = [doc(lengths[i % 7]) for i in range(64)] + [doc(4096)[:-1]]
+    assert sorted({len(ln) for ln in lines}) == [0, 1, 2, 63, 64, 65, 4095, 4096]
+    for result in (_walk_host(lines, 2), _walk_device(lines, 2)):
+        _check(lines, result, 2)
+        assert list(result[0][:7]) == [jm.EMPTY, jm.FAIL, jm.OK, jm.OK, jm.OK, jm.OK, jm.OK] and result[0][64] == jm.FAIL
+
+
+def test_member_counts_around_w_and_the_processor_s_mop_up():
+    from loongcollector_amd import json_parse
+    from loongcollector_amd.processor import EventGroup
+    W = 8
+    lines = [b"{" + b",".join(b'"k%d":%d' % (i, i) for i in range(m)) + b"}" for m in (W - 1, W, W + 1, 0, 40)]
+    result = _walk_host(lines, W)
+    _check(lines, result, W)
+    assert list(result[1]) == [W - 1, W, W + 1, 0, 40]
+    p = json_parse.JsonProcessor({"SourceKey": "content"}, first_trip_members=2)
+    data, off = jc.pack(lines)
+    g = EventGroup.from_lines(data, off[:-1], off[1:] - off[:-1])
+    p.process(g)
+    got = _group_contents(g)
+    assert got == [{"k%d" % i: str(i) for i in range(m)} for m in (W - 1, W, W + 1, 0, 40)]      # (the empty object leaves an empty event)
+
+
+def test_depth_64_65_1024_1025_and_a_group_mixing_them_with_shallow_lines():
+    def nest(d, tail=b""):
+        return b'{"a":' + b"[" * (d - 1) + b"]" * (d - 1) + tail + b"}"
+    deep = [nest(64), nest(65), nest(1024), nest(1025), nest(65, b',"e":"\\n"'), nest(300)[:-5]]
+    for result in (_walk_host(deep, 2), _walk_device(deep, 2)):
+        _check(deep, result, 2)
+        assert list(result[0]) == [jm.OK, jm.OK, jm.OK, jm.FAIL, jm.OK, jm.FAIL] and result[2][3] == 1028
+    rng = random.Random(3)
+    mixed = [jc.gen_document(rng) for _ in range(300)]
+    for i, d in zip((0, 63, 64, 130, 131, 299), deep):
+        mixed[i] = d
+    _check(mixed, _walk_host(mixed, 4), 4)
+    _check(mixed, _walk_device(mixed, 4), 4)
+
+
+def test_escapes_a_batch_without_them_moves_no_shadow_bytes_and_one_full_of_them_is_unescaped():
+    plain = [b'{"time":"2026-10-17T10:00:%02d","level":"info","n":%d,"msg":"request served"}' % (i % 60, i) for i in range(500)]
+    result = _walk_host(plain, 8)
+    _check(plain, result, 8)
+    assert result[5] == 0
+    escaped = [b'{"k\\t%d":"line\\n%d \\u00e9\\uD83D\\uDE00 \\"q\\"","p%d":"\\\\"}' % (i, i, i) for i in range(500)]
+    result = _walk_host(escaped, 8)
+    _check(escaped, result, 8)
+    assert result[5] > 0
+    some = plain[:100] + escaped[:3] + plain[100:]
+    result = _walk_host(some, 8)
+    _check(some, result, 8)
+    assert 0 < result[5] <= sum(len(e) for e in escaped[:3])
+
+
+def test_walk_device_on_torch_tensors():
+    rng = random.Random(11)
+    lines = [jc.gen_document(rng) for _ in range(1000)]
+    _check(lines, _walk_device(lines, 8), 8)
+
+
+def test_walk_device_refuses_a_tensor_of_another_device_with_lc_err_arg():
+    import torch
+    if torch.cuda.device_count() < 2:
+        pytest.skip("one device: nothing lives on another one")
+    from loongcollector_amd import binding
+    torch.cuda.set_device(0)
+    with pytest.raises(RuntimeError) as e:
+        _walk_device([b'{"a":1}'] * 4, 8, device="cuda:1")
+    assert "lc_json_walk_device failed: rc=%d " % binding.LC_ERR_ARG in str(e.value)
+
+
+def _host_routine(lines, W):
+    """jsonWalkLine compiled for the host (tests/native/json_host_check.cpp), in the shape _walk_host returns"""
+    from test_json_host import _double
+    L = _double()
+    data, off = jc.pack(lines)
+    n = len(lines)
+    st, nm, err = np.zeros(n, np.uint8), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+    rec = np.zeros((n, W), jc.MEMBER)
+    shadow = np.zeros(len(data), np.uint8)
+    L.jh_walk_batch(data.ctypes.data, off.ctypes.data, n, W, st.ctypes.data, nm.ctypes.data, err.ctypes.data, rec.ctypes.data, shadow.ctypes.data)
+    return st, nm, err, rec, shadow, 0, off
+
+
+def _same_reports(lines, a, b, W):
+    """two walks' reports, field for field: status, count, error offset, the records that count, the shadow bytes of escaped spans"""
+    assert np.array_equal(a[0], b[0]) and np.array_equal(np.asarray(a[1], np.int64), np.asarray(b[1], np.int64))
+    assert np.array_equal(np.asarray(a[2], np.int64), np.asarray(b[2], np.int64))
+    off = a[-1]
+    for i in range(len(lines)):
+        if a[0][i] != jm.OK:
+            continue
+        for k in range(min(int(a[1][i]), W)):
+            ra, rb = a[3][i][k], b[3][i][k]
+            assert [int(ra[f]) for f in ("kb", "ke", "vb", "ve", "type")] == [int(rb[f]) for f in ("kb", "ke", "vb", "ve", "type")], (i, k, lines[i])
+            for bname, ename in (("kb", "ke"), ("vb", "ve")):
+                if int(ra[bname]) & jc.ESCAPED and (bname == "kb" or int(ra["type"]) == jm.STRING):
+                    lo, hi = int(off[i]) + (int(ra[bname]) & ~jc.ESCAPED), int(off[i]) + int(ra[ename])
+                    assert bytes(a[4][lo:hi]) == bytes(b[4][lo:hi]), (i, k, lines[i])
+
+
+def test_differential_fuzz_host_routine_against_kernel():
+    """The product's per-line routine compiled for the host against the kernel, zero differences allowed; the Python model is asked as
+    well.  LC_FUZZ_JSON_SEED / LC_FUZZ_JSON_COUNT: longer runs by hand."""
+    seed = int(os.environ.get("LC_FUZZ_JSON_SEED", "20261017"))
+    count = int(os.environ.get("LC_FUZZ_JSON_COUNT", "4000"))
+    docs = jc.generated_set(seed, count)
+    host = _host_routine(docs, 8)
+    for kernel in (_walk_host(docs, 8), _walk_device(docs, 8)):
+        _same_reports(docs, host, kernel, 8)
+        _check(docs, kernel, 8)
+
+
+def test_launched_kernels_names_the_json_kernel():
+    from loongcollector_amd import binding
+    binding.launched_kernels()
+    _walk_host([b'{"a":1}', b"x"], 4)
+    assert "json_walk_kernel" in binding.launched_kernels()
