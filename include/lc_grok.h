@@ -56,6 +56,20 @@ char* lc_grok_denormalize(lc_grok_t* g, const char* pattern, char* err, size_t e
  * value contain".  *words = NULL when the list is not indexable (more than 64 entries, fewer than two literals).  The pointer
  * stays valid until lc_grok_free. */
 int lc_grok_literal_index(lc_grok_t* g, const uint32_t** words, size_t* nwords);
+/* Phase 1 of the default (speculative) path, on its own (introspection for tests).  The matcher decides in phase 1 which (Match
+ * entry, value) pairs it evaluates at all: a 64-bit mask per value from the literal index (bit p = "contains Match[p]'s literal",
+ * always set for an entry without one), bits cleared by the entries' screens, then the candidate counts.  This call runs the SAME
+ * function lc_grok_match_device runs for a batch of this n -- small / large batch, every LC_GROK_* knob -- and copies out
+ *   stage 1: d_masks uint64[n] as the literal pass leaves them;
+ *   stage 2: d_masks after the screens and, if d_counts is not NULL, uint32[64 + 64 + 64*64]: candidates per entry | values whose
+ *            FIRST candidate is the entry | [p][f] candidates of p whose value's first candidate is the earlier entry f.
+ * d_data / d_off / d_len / d_scratch as for lc_grok_match_device (below).  Returns after `stream` has drained.  Lists of more than 64
+ * entries have no such phase: LC_ERR_ARG. */
+int lc_grok_plan_masks_device(lc_grok_t* g, const uint8_t* d_data, const uint32_t* d_off, const uint32_t* d_len, uint32_t n, int stage,
+                              uint64_t* d_masks, uint32_t* d_counts, void* d_scratch, size_t scratch_bytes, void* stream);
+/* The yes/no DFA that phase 1 walks for Match[i] (csrc/screen_kernel_layout.h; introspection for tests): *words = NULL when the entry
+ * has no screen.  *lds_bytes = bytes of it a small batch stages into LDS (0: walked in global memory).  Valid until lc_grok_free. */
+int lc_grok_screen_blob(lc_grok_t* g, int i, const uint32_t** words, size_t* nwords, uint32_t* lds_bytes);
 int lc_grok_engine(const lc_grok_t* g, int i);                     /* LC_ENGINE_TDFA / LC_ENGINE_NFA chosen for Match[i] */
 /* diagnostics: how Match[i] is run -- out[0] engine of the search form, [1] states of its tagged DFA (0: none), [2] 1 = tables in
  * LDS / 2 = in global memory, [3] prefix-screen states, [4] relaxed-screen states, [5] anchored search present (they arrive behind

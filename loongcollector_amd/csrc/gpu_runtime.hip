@@ -66,7 +66,7 @@ static thread_local std::string tlsKernelLog;
 void lcNoteKernel(const char* name);
 static void noteKernel(const char* name) { lcNoteKernel(name); }
 void lcNoteKernel(const char* name) {
-    if (tlsKernelLog.size() > 512 || tlsKernelLog.find(name) != std::string::npos) return;
+    if (tlsKernelLog.size() > 896 || tlsKernelLog.find(name) != std::string::npos) return;
     if (!tlsKernelLog.empty()) tlsKernelLog += ", ";
     tlsKernelLog += name;
 }

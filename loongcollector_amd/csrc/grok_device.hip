@@ -469,6 +469,12 @@ lc_regex* planScreenOf(const GrokDevicePattern& gp) {
     if (gp.screen && !gp.screen->screenBlob.empty()) return gp.screen;
     return nullptr;
 }
+// bytes of (accept flags + table) the plan stages into LDS for a screen; 0: the table is walked in global memory
+uint32_t planScreenLdsBytes(const lc_regex* scr) {
+    static const bool noStage = getenv("LC_GROK_SCREEN_NO_LDS") != nullptr;
+    const uint32_t stage = scr->screenBlob[SC_TOTAL_BYTES] - scr->screenBlob[SC_OFF_ACCEPT];
+    return (!noStage && stage <= kGrokScreenStageMax) ? (stage + 3u) & ~3u : 0u;
+}
 
 int grokScreenTable(const std::vector<GrokDevicePattern>& patterns, GrokDeviceState* state, int dev, const GrokScreenDev** table,
                     uint32_t* count, uint32_t* ldsBytes) {
@@ -486,7 +492,7 @@ int grokScreenTable(const std::vector<GrokDevicePattern>& patterns, GrokDeviceSt
             if (rc != LC_OK) return rc;
             d.bit = uint32_t(p);
             const uint32_t stage = scr->screenBlob[SC_TOTAL_BYTES] - scr->screenBlob[SC_OFF_ACCEPT];
-            d.ldsBytes = (!noStage && stage <= kGrokScreenStageMax) ? (stage + 3u) & ~3u : 0u;
+            d.ldsBytes = planScreenLdsBytes(scr);
             const bool big = !noStage && !d.ldsBytes && stage <= kGrokScreenBigMax;
             maxStage = std::max(maxStage, d.ldsBytes);
             if (getenv("LC_GROK_TRACE"))
@@ -518,56 +524,30 @@ int grokScreenTable(const std::vector<GrokDevicePattern>& patterns, GrokDeviceSt
     return LC_OK;
 }
 
-// host view of one active entry of the batch
-struct PlanEntry {
-    uint32_t p = 0, cand = 0, capsRow = 0, columns = 0, rounds = 0, ran = 0;
-    bool second = false;  // level > 0
-    uint32_t level = 0;   // 0: evaluated at once; L > 0: most of its candidates have an EARLIER candidate entry (of level < L) -- it waits
-                          // for those and only looks at the values none of them has won (a general format behind specific ones)
-    bool queued = false;  // rounds behind the first match were queued for this entry
-    bool wideFirst = false;  // round 0 ran nfa_wide_kernel over every candidate (the entry's history says its values overflow 64 threads)
-    uint32_t seq0 = 0;    // launch sequence of round 0's first-chance kernel (lcMatchSecondChanceOnStream)
-    uint32_t seqS = 0;    // ... and of the search proper's (phase 2c)
-    const GrokScreenDev* remainderScreen = nullptr;  // the entry's screen (host copy), walked over what is left behind a first match
-    int stream = 0;
-    double cost = 0, cost0 = 0, cost1 = 0;  // heuristic; measured round 0 / leftovers (ns, 0 = unknown)
-    GrokEntryDev dev{};
-    uint32_t *listA = nullptr, *listB = nullptr, *unanchored = nullptr;
-    int32_t* caps = nullptr;
-    uint8_t* status = nullptr;
+// ---- phase 1 of the plan: the batch's buffers cleared, the length order, the literal index (or every bit set), all screens, the
+// candidate counts -- queued on `st`, nothing read back.  The matcher runs it with stage = 2; lcGrokPlanMasksDevice (introspection for
+// tests, include/lc_grok.h) runs the same code and may stop behind the literal pass (stage = 1).  d_first / d_nextra: the matcher's
+// outputs, cleared along with everything else (nullptr: none).
+struct GrokPhase1 {
+    uint32_t *winner = nullptr, *undecided = nullptr, *order = nullptr;  // in the caller's scratch
+    uint64_t* masks = nullptr;                                           // likewise
+    const uint32_t* literalIndex = nullptr;
+    uint32_t nScreens = 0;
+    bool small = false;
 };
-
-int grokMatchSpeculative(const std::vector<GrokDevicePattern>& patterns, GrokDeviceState* state, const GrokOptions& opts, uint32_t row,
-                         const uint8_t* d_data, const uint32_t* d_off, const uint32_t* d_len, uint32_t n, int32_t* d_pattern,
-                         int32_t* d_first, int32_t* d_extra, uint32_t extraCap, uint32_t* d_nextra, void* d_scratch, hipStream_t st,
-                         int dev) {
-    GrokBatchStats& stats = tlsStats;
+int grokPlanPhase1(const std::vector<GrokDevicePattern>& patterns, GrokDeviceState* state, PlanThread& T, uint32_t row, const uint8_t* d_data,
+                   const uint32_t* d_off, const uint32_t* d_len, uint32_t n, int32_t* d_first, uint32_t* d_nextra, void* d_scratch,
+                   hipStream_t st, int dev, int stage, GrokPhase1* out) {
     const uint32_t nP = uint32_t(patterns.size());
-    static const uint32_t envStreams = [] {  // LC_GROK_STREAMS overrides the handle's option (A/B measurements)
-        const char* e = getenv("LC_GROK_STREAMS");
-        return uint32_t(e ? atoi(e) : 0);
-    }();
-    const uint32_t nStreams = std::max(1u, std::min<uint32_t>(envStreams ? envStreams : opts.streams, kGrokMaxStreams));
-    PlanThread& T = tlsPlan;
-    {
-        int rc = T.ensure(dev, nStreams);
-        if (rc != LC_OK) return rc;
-    }
-    static const bool trace = getenv("LC_GROK_TRACE") != nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
-    auto msNow = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
-
     // scratch: winner u32[n] | undecided u32[n] from the head, tail words / perEntry / masks at their fixed places
     uint8_t* head = static_cast<uint8_t*>(d_scratch);
     uint32_t* winner = reinterpret_cast<uint32_t*>(head);
     uint32_t* undecided = winner + n;
     uint8_t* tailAt = head + alignUp(size_t(n) * row * 4, 256) + alignUp(n, 256) + 7 * alignUp(size_t(n) * 4, 256);
-    uint32_t* tail = T.dTail;                                        // TW_* (the entries' counters behind them: one block, one copy back)
     uint32_t* perEntry = T.dPlanWords;                               // [64] (then firstOf[64], shadow[64][64]: one block, one copy back)
     uint64_t* masks = reinterpret_cast<uint64_t*>(tailAt + 512);
 
     const uint32_t gridAll = (n + kGrokPlanBlock - 1) / kGrokPlanBlock;
-    // ---- phase 1: length order, literal index, all screens, candidate counts
     // Small batches wait for their LONGEST value (every kernel below is a dependent chain per value): chunk-parallel literal pass,
     // screen tables in LDS.  Large batches are about values in flight and equal work per wavefront: lane-per-value in length order.
     static const uint32_t smallBatch = [] {  // LC_GROK_SMALL_BATCH: A/B measurements
@@ -588,8 +568,8 @@ int grokMatchSpeculative(const std::vector<GrokDevicePattern>& patterns, GrokDev
         fill(T.dTail, size_t(64 + 64 * GC_WORDS) * 4, 0u);
         fill(T.dPlanWords, size_t(kPlanWords) * 4, 0u);
         fill(winner, size_t(n) * 8, 0xFFFFFFFFu);
-        fill(d_first, size_t(n) * row * 4, 0xFFFFFFFFu);
-        fill(d_nextra, 4, 0u);
+        if (d_first) fill(d_first, size_t(n) * row * 4, 0xFFFFFFFFu);
+        if (d_nextra) fill(d_nextra, 4, 0u);
         const uint32_t most = uint32_t(std::max(size_t(n) * 2, size_t(n) * row));
         hipLaunchKernelGGL(grok_init_kernel, dim3(std::min(2048u, (most + kGrokPlanBlock - 1) / kGrokPlanBlock)), dim3(kGrokPlanBlock), 0, st, J);
     }
@@ -635,8 +615,19 @@ int grokMatchSpeculative(const std::vector<GrokDevicePattern>& patterns, GrokDev
         hipLaunchKernelGGL(grok_literal_index_kernel, dim3(gridAll), dim3(kGrokBlock), 0, st, d_data, d_off, d_len, n, literalIndex, masks,
                            nP, static_cast<uint32_t*>(nullptr), static_cast<const uint32_t*>(order));
     } else {
+        lcNoteKernel("grok_mask_fill_kernel");
         hipLaunchKernelGGL(grok_mask_fill_kernel, dim3(gridAll), dim3(kGrokPlanBlock), 0, st, masks, n,
                            nP >= 64 ? ~0ull : ((1ull << nP) - 1ull));
+    }
+    out->winner = winner;
+    out->undecided = undecided;
+    out->order = order;
+    out->masks = masks;
+    out->literalIndex = literalIndex;
+    out->small = small;
+    if (stage == 1) {
+        HIP_TRY(hipGetLastError());
+        return LC_OK;
     }
     const GrokScreenDev* screens = nullptr;
     uint32_t nScreens = 0, screenLds = 0;
@@ -676,8 +667,67 @@ int grokMatchSpeculative(const std::vector<GrokDevicePattern>& patterns, GrokDev
     }
     uint32_t* firstOf = T.dPlanWords + 64;   // [64]
     uint32_t* shadowBy = T.dPlanWords + 128;  // [64][64]
+    lcNoteKernel("grok_count_kernel");
     hipLaunchKernelGGL(grok_count_kernel, dim3(gridAll), dim3(kGrokPlanBlock), 0, st, masks, n, nP, perEntry, firstOf, shadowBy);
     HIP_TRY(hipGetLastError());
+    out->nScreens = nScreens;
+    return LC_OK;
+}
+
+// host view of one active entry of the batch
+struct PlanEntry {
+    uint32_t p = 0, cand = 0, capsRow = 0, columns = 0, rounds = 0, ran = 0;
+    bool second = false;  // level > 0
+    uint32_t level = 0;   // 0: evaluated at once; L > 0: most of its candidates have an EARLIER candidate entry (of level < L) -- it waits
+                          // for those and only looks at the values none of them has won (a general format behind specific ones)
+    bool queued = false;  // rounds behind the first match were queued for this entry
+    bool wideFirst = false;  // round 0 ran nfa_wide_kernel over every candidate (the entry's history says its values overflow 64 threads)
+    uint32_t seq0 = 0;    // launch sequence of round 0's first-chance kernel (lcMatchSecondChanceOnStream)
+    uint32_t seqS = 0;    // ... and of the search proper's (phase 2c)
+    const GrokScreenDev* remainderScreen = nullptr;  // the entry's screen (host copy), walked over what is left behind a first match
+    int stream = 0;
+    double cost = 0, cost0 = 0, cost1 = 0;  // heuristic; measured round 0 / leftovers (ns, 0 = unknown)
+    GrokEntryDev dev{};
+    uint32_t *listA = nullptr, *listB = nullptr, *unanchored = nullptr;
+    int32_t* caps = nullptr;
+    uint8_t* status = nullptr;
+};
+
+int grokMatchSpeculative(const std::vector<GrokDevicePattern>& patterns, GrokDeviceState* state, const GrokOptions& opts, uint32_t row,
+                         const uint8_t* d_data, const uint32_t* d_off, const uint32_t* d_len, uint32_t n, int32_t* d_pattern,
+                         int32_t* d_first, int32_t* d_extra, uint32_t extraCap, uint32_t* d_nextra, void* d_scratch, hipStream_t st,
+                         int dev) {
+    GrokBatchStats& stats = tlsStats;
+    const uint32_t nP = uint32_t(patterns.size());
+    static const uint32_t envStreams = [] {  // LC_GROK_STREAMS overrides the handle's option (A/B measurements)
+        const char* e = getenv("LC_GROK_STREAMS");
+        return uint32_t(e ? atoi(e) : 0);
+    }();
+    const uint32_t nStreams = std::max(1u, std::min<uint32_t>(envStreams ? envStreams : opts.streams, kGrokMaxStreams));
+    PlanThread& T = tlsPlan;
+    {
+        int rc = T.ensure(dev, nStreams);
+        if (rc != LC_OK) return rc;
+    }
+    static const bool trace = getenv("LC_GROK_TRACE") != nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto msNow = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
+
+    // ---- phase 1: length order, literal index, all screens, candidate counts (grokPlanPhase1)
+    GrokPhase1 P1;
+    {
+        int rc = grokPlanPhase1(patterns, state, T, row, d_data, d_off, d_len, n, d_first, d_nextra, d_scratch, st, dev, 2, &P1);
+        if (rc != LC_OK) return rc;
+    }
+    uint32_t* const winner = P1.winner;
+    uint32_t* const undecided = P1.undecided;
+    uint32_t* const order = P1.order;
+    uint64_t* const masks = P1.masks;
+    const uint32_t* const literalIndex = P1.literalIndex;
+    const uint32_t nScreens = P1.nScreens;
+    const bool small = P1.small;
+    uint32_t* tail = T.dTail;                                        // TW_* (the entries' counters behind them: one block, one copy back)
+    const uint32_t gridAll = (n + kGrokPlanBlock - 1) / kGrokPlanBlock;
     HIP_TRY(hipMemcpyAsync(T.hostWords + HW_CAND, T.dPlanWords, size_t(kPlanWords) * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(syncCounted(st));  // sync 1: candidates per entry
     const double tPhase1 = msNow();
@@ -1161,6 +1211,8 @@ int grokMatchSpeculative(const std::vector<GrokDevicePattern>& patterns, GrokDev
                 for (uint32_t a1 = 0; a1 < (splitRem ? nAct : 1u); ++a1) {
                     const unsigned long long skip1 = splitRem ? ~(1ull << a1) : skip;
                     if (splitRem && ((skip >> a1) & 1ull)) continue;
+                    if (remainderLiteral || remainderWon) lcNoteKernel("grok_remainder_literal_kernel");
+                    lcNoteKernel("grok_remainder_all_kernel");
                     if (remainderLiteral || remainderWon)
                         hipLaunchKernelGGL(grok_remainder_literal_kernel, dim3((most + kGrokPlanBlock / 64 - 1) / (kGrokPlanBlock / 64), nAct),
                                            dim3(kGrokPlanBlock), 0, gs, d_data, T.dEntries,
@@ -1379,6 +1431,8 @@ int grokMatchSpeculative(const std::vector<GrokDevicePattern>& patterns, GrokDev
                     hipStream_t ws = W(e.stream);
                     // (grid.y = 1 over a table that begins at this entry)
                     const GrokEntryDev* mine = static_cast<const GrokEntryDev*>(T.dEntries) + a;
+                    if (remainderLiteral || remainderWon) lcNoteKernel("grok_remainder_literal_kernel");
+                    lcNoteKernel("grok_remainder_all_kernel");
                     if (remainderLiteral || remainderWon)
                         hipLaunchKernelGGL(grok_remainder_literal_kernel, dim3((e.cand + kGrokPlanBlock / 64 - 1) / (kGrokPlanBlock / 64), 1),
                                            dim3(kGrokPlanBlock), 0, ws, d_data, mine,
@@ -1412,6 +1466,8 @@ int grokMatchSpeculative(const std::vector<GrokDevicePattern>& patterns, GrokDev
                 forked = true;
                 if (groupMask && !aheadLaunched) {  // the entries that only have remainders to screen: one launch pair, beside the chains
                     hipStream_t gs = W(int(used) - 1);
+                    if (remainderLiteral || remainderWon) lcNoteKernel("grok_remainder_literal_kernel");
+                    lcNoteKernel("grok_remainder_all_kernel");
                     if (remainderLiteral || remainderWon)
                         hipLaunchKernelGGL(grok_remainder_literal_kernel, dim3((maxCand + kGrokPlanBlock / 64 - 1) / (kGrokPlanBlock / 64), nAct),
                                            dim3(kGrokPlanBlock), 0, gs, d_data, T.dEntries,
@@ -1644,6 +1700,52 @@ int lcGrokMatchDevice(const std::vector<GrokDevicePattern>& patterns, GrokDevice
                                     d_scratch, st, dev);
     return grokMatchSequential(patterns, state, opts, row, d_data, d_off, d_len, n, d_pattern, d_first, d_extra, extraCap, d_nextra,
                                d_scratch, st, dev);
+}
+
+// include/lc_grok.h: lc_grok_plan_masks_device (introspection for tests) -- phase 1 of the plan path as the matcher runs it for a batch
+// of this n, then the masks (and the count words) copied out
+int lcGrokPlanMasksDevice(const std::vector<GrokDevicePattern>& patterns, GrokDeviceState* state, uint32_t row, const uint8_t* d_data,
+                          const uint32_t* d_off, const uint32_t* d_len, uint32_t n, int stage, uint64_t* d_masks, uint32_t* d_counts,
+                          void* d_scratch, size_t scratchBytes, void* streamPtr) {
+    if (n == 0) return LC_OK;
+    if (!state || !d_data || !d_off || !d_len || !d_masks || !d_scratch || (stage != 1 && stage != 2) || patterns.size() > 64) return LC_ERR_ARG;
+    if (scratchBytes < lcGrokScratchBytes(n, row)) {
+        lcSetLastError("grok: scratch buffer too small");
+        return LC_ERR_ARG;
+    }
+    if (lc_device_count() <= 0) {
+        lcSetLastError("no HIP device");
+        return LC_ERR_NO_DEVICE;
+    }
+    int dev = 0;
+    {
+        const int rcDev = lcDeviceEntryDevice(d_data, &dev);
+        if (rcDev != LC_OK) return rcDev;
+    }
+    hipStream_t st = static_cast<hipStream_t>(streamPtr);
+    PlanThread& T = tlsPlan;
+    {
+        int rc = T.ensure(dev, 0);
+        if (rc != LC_OK) return rc;
+    }
+    GrokPhase1 P1;
+    {
+        int rc = grokPlanPhase1(patterns, state, T, row, d_data, d_off, d_len, n, nullptr, nullptr, d_scratch, st, dev, stage, &P1);
+        if (rc != LC_OK) return rc;
+    }
+    HIP_TRY(hipMemcpyAsync(d_masks, P1.masks, size_t(n) * 8, hipMemcpyDeviceToDevice, st));
+    if (stage == 2 && d_counts) HIP_TRY(hipMemcpyAsync(d_counts, T.dPlanWords, size_t(kPlanWords) * 4, hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipGetLastError());
+    return LC_OK;
+}
+
+// include/lc_grok.h: lc_grok_screen_blob -- the screen grok_screen_all_kernel walks for an entry and what the plan stages of it
+const std::vector<uint32_t>* lcGrokPlanScreenBlob(const GrokDevicePattern& gp, uint32_t* ldsBytes) {
+    const lc_regex* scr = planScreenOf(gp);
+    if (!scr) return nullptr;
+    if (ldsBytes) *ldsBytes = planScreenLdsBytes(scr);
+    return &scr->screenBlob;
 }
 
 int lcGrokSampleDevice(const uint8_t* d_data, const uint32_t* d_off, const uint32_t* d_len, uint32_t n, uint32_t maxValues, void* streamPtr,

@@ -60,6 +60,13 @@ int lcGrokMatchDevice(const std::vector<GrokDevicePattern>& patterns, GrokDevice
                       int32_t* d_pattern, int32_t* d_first, int32_t* d_extra, uint32_t extraCap, uint32_t* d_nextra, void* d_scratch,
                       size_t scratchBytes, void* stream);
 
+// See include/lc_grok.h: lc_grok_plan_masks_device / lc_grok_screen_blob (introspection for tests).  The first runs phase 1 of the plan
+// path -- the very function lcGrokMatchDevice runs -- and copies the masks (stage 2: and the count words) out.
+int lcGrokPlanMasksDevice(const std::vector<GrokDevicePattern>& patterns, GrokDeviceState* state, uint32_t rowInts, const uint8_t* d_data,
+                          const uint32_t* d_off, const uint32_t* d_len, uint32_t n, int stage, uint64_t* d_masks, uint32_t* d_counts,
+                          void* d_scratch, size_t scratchBytes, void* stream);
+const std::vector<uint32_t>* lcGrokPlanScreenBlob(const GrokDevicePattern& gp, uint32_t* ldsBytes);
+
 // pinned-host convenience used by lc_grok_match_host: copies in (one block, the calling thread's own stream), runs
 // lcGrokMatchDevice, copies out.  *firstRows = int32[n][rowInts] in the thread's pinned staging, valid until the thread's next call;
 // extraRows receives [line, seq, row...] records sorted by (line, seq).

@@ -581,6 +581,27 @@ extern "C" int lc_grok_literal_index(lc_grok_t* g, const uint32_t** words, size_
     return LC_OK;
 }
 
+extern "C" int lc_grok_screen_blob(lc_grok_t* g, int i, const uint32_t** words, size_t* nwords, uint32_t* lds_bytes) {
+    if (!g || !words || !nwords || i < 0) return LC_ERR_ARG;
+    *words = nullptr;
+    *nwords = 0;
+    if (lds_bytes) *lds_bytes = 0;
+    const auto& patterns = g->p.compiledPatterns();  // (the screens are compiled with the entries: they do not wait for the warm-up thread)
+    if (size_t(i) >= patterns.size()) return LC_ERR_ARG;
+    if (const std::vector<uint32_t>* blob = lcGrokPlanScreenBlob(patterns[size_t(i)], lds_bytes)) {
+        *words = blob->data();
+        *nwords = blob->size();
+    }
+    return LC_OK;
+}
+extern "C" int lc_grok_plan_masks_device(lc_grok_t* g, const uint8_t* d_data, const uint32_t* d_off, const uint32_t* d_len, uint32_t n,
+                                         int stage, uint64_t* d_masks, uint32_t* d_counts, void* d_scratch, size_t scratch_bytes,
+                                         void* stream) {
+    if (!g || !g->p.deviceState()) return LC_ERR_ARG;
+    return lcGrokPlanMasksDevice(g->p.devicePatterns(), g->p.deviceState(), g->p.rowInts(), d_data, d_off, d_len, n, stage, d_masks,
+                                 d_counts, d_scratch, scratch_bytes, stream);
+}
+
 extern "C" void lc_grok_wait_ready(lc_grok_t* g) {
     if (g) g->p.WaitReady();
 }

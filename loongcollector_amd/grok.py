@@ -49,6 +49,10 @@ def _lib():
         L.lc_grok_process_logs_json.restype = i32
         L.lc_grok_process_logs_json.argtypes = [vp, cp, sz, ctypes.POINTER(vp)]
         L.lc_grok_free_string.argtypes = [vp]
+        L.lc_grok_plan_masks_device.restype = i32
+        L.lc_grok_plan_masks_device.argtypes = [vp, vp, vp, vp, u32, i32, vp, vp, vp, sz, vp]
+        L.lc_grok_screen_blob.restype = i32
+        L.lc_grok_screen_blob.argtypes = [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(u32)]
         L.lc_grok_last_batch_stats.restype = None
         L.lc_grok_last_batch_stats.argtypes = [vp]
         L._lc_grok_bound = True
@@ -87,6 +91,27 @@ class Grok:
         if rc != 0 or not words.value:
             return None
         return np.ctypeslib.as_array(ctypes.cast(words.value, ctypes.POINTER(ctypes.c_uint32)), shape=(n.value,)).copy()
+
+    def screen_blob(self, i):
+        """lc_grok_screen_blob: (uint32 words of the yes/no DFA the plan path walks for Match[i], bytes of it staged into LDS),
+        or None when the entry has no screen"""
+        words = ctypes.c_void_p()
+        n = ctypes.c_size_t()
+        lds = ctypes.c_uint32()
+        rc = self._L.lc_grok_screen_blob(self._h, i, ctypes.byref(words), ctypes.byref(n), ctypes.byref(lds))
+        binding._check(rc, "lc_grok_screen_blob")
+        if not words.value:
+            return None
+        blob = np.ctypeslib.as_array(ctypes.cast(words.value, ctypes.POINTER(ctypes.c_uint32)), shape=(n.value,)).copy()
+        return blob, int(lds.value)
+
+    def plan_masks_device(self, d_data, d_off, d_len, n, stage, d_masks, d_counts, d_scratch, stream=None):
+        """lc_grok_plan_masks_device: phase 1 of the default path on a resident batch -- d_masks int64[>= n] after the literal pass
+        (stage 1) or after the screens (stage 2, with d_counts int32[>= 64 + 64 + 64 * 64] or None: grok_count_kernel's words)"""
+        rc = self._L.lc_grok_plan_masks_device(self._h, d_data.data_ptr(), d_off.data_ptr(), d_len.data_ptr(), n, stage,
+                                               d_masks.data_ptr(), None if d_counts is None else d_counts.data_ptr(),
+                                               d_scratch.data_ptr(), d_scratch.numel() * d_scratch.element_size(), stream)
+        binding._check(rc, "lc_grok_plan_masks_device")
 
     def wait_ready(self):
         """lc_grok_wait_ready: block until the warm-up thread has compiled the anchored searches (speed only, never results)"""

@@ -11,6 +11,7 @@ import pytest
 from loongcollector_amd import binding as B
 from loongcollector_amd.grok import Grok, GrokInitError
 from oracle.grok_oracle import GrokOracle
+from tests.helpers.grok_device_rows import device_rows as _device_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -356,42 +357,6 @@ def test_values_that_need_more_than_64_threads_are_decided(torch_dev, golden_dir
         assert [(k, bytes(x)) for k, x in f] == [(k, bytes(x)) for k, x in want], v
         hit += bool(want)
     assert hit >= 500
-
-
-def _device_rows(torch, g, values, extra_cap=None):
-    """lc_grok_match_device on a resident batch -> (pattern, first, extra sorted by (line, seq), stats)"""
-    dev = torch.device("cuda:0")
-    n = len(values)
-    data = np.frombuffer(b"".join(values) + b"\0" * 16, dtype=np.uint8)
-    length = np.array([len(v) for v in values], dtype=np.uint32)
-    off = np.zeros(n, dtype=np.uint32)
-    off[1:] = np.cumsum(length[:-1], dtype=np.uint64).astype(np.uint32)
-    d_data = torch.from_numpy(data.copy()).to(dev)
-    d_off = torch.from_numpy(off.view(np.int32).copy()).to(dev)
-    d_len = torch.from_numpy(length.view(np.int32).copy()).to(dev)
-    row = g.row_ints
-    d_pattern = torch.empty(n, dtype=torch.int32, device=dev)
-    d_first = torch.empty((n, row), dtype=torch.int32, device=dev)
-    d_extra = torch.empty((extra_cap if extra_cap is not None else 6 * n + 1024, row + 2), dtype=torch.int32, device=dev)
-    d_nextra = torch.zeros(1, dtype=torch.int32, device=dev)
-    d_scratch = torch.empty(g.scratch_bytes(n), dtype=torch.uint8, device=dev)
-    try:
-        g.match_device(d_data, d_off, d_len, n, d_pattern, d_first, d_extra, d_nextra, d_scratch)
-    except RuntimeError:
-        # LC_ERR_OVERFLOW: d_nextra says how many rows are needed (the speculative path keeps the further matches of EVERY candidate
-        # entry until the winner is known, so its temporary rows can run out where the final rows would have fitted)
-        need = int(d_nextra.cpu()[0])
-        assert need > d_extra.shape[0]
-        d_extra = torch.empty((need, row + 2), dtype=torch.int32, device=dev)
-        g.match_device(d_data, d_off, d_len, n, d_pattern, d_first, d_extra, d_nextra, d_scratch)
-    stats = g.last_batch_stats()
-    nx = int(d_nextra.cpu()[0])
-    extra = d_extra[:nx].cpu().numpy()
-    if nx:
-        extra = extra[np.lexsort((extra[:, 1], extra[:, 0]))]
-    pattern, first = d_pattern.cpu().numpy(), d_first.cpu().numpy()
-    first[pattern < 0] = -1   # (rows of values nobody won are unspecified on the sequential path)
-    return pattern, first, extra, stats
 
 
 @pytest.mark.parametrize("match", [
