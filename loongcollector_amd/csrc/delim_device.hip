@@ -54,60 +54,32 @@ extern "C" int lc_delim_split_device(lc_delim_t* d, const uint8_t* d_data, const
 // ------------------------------------------------------------------------------------------------ host lines
 namespace {
 // per runner thread: a stream, one pinned and one device block each way, the pinned completion word; grow-only
-struct DelimThread {
-    hipStream_t stream = nullptr;
-    int device = -1;
-    TripBuf hIn, hOut, hFlag, dIn, dOut;
-    uint32_t seq = 0;
-    DelimThread() { hIn.pinned = hOut.pinned = hFlag.pinned = true; }
+struct DelimThread : TripThread<DelimThread> {
+    TripBuf hIn, hOut, dIn, dOut;
+    DelimThread() : TripThread(true) { hIn.pinned = hOut.pinned = true; }
     ~DelimThread() {
-        if (lcRuntimeUsable() && (stream || hIn.p || dIn.p)) lcDelimThreadRelease();
+        if (live()) release();
     }
+    void release() { releaseWith({&hIn, &hOut, &dIn, &dOut}); }
 };
 thread_local DelimThread tlsDelim;
 
 constexpr size_t kChunkBytes = 32u << 20;    // payload bytes per trip
 constexpr uint32_t kChunkLines = 1u << 18;   // and at most this many lines
 constexpr size_t kChunkSpanBytes = 64u << 20;
-
-inline size_t roundUp(size_t v, size_t a) { return (v + a - 1) / a * a; }
 }  // namespace
 
-void lcDelimThreadRelease() {
-    DelimThread& T = tlsDelim;
-    if (T.stream) {
-        (void)hipStreamSynchronize(T.stream);
-        (void)hipStreamDestroy(T.stream);
-        T.stream = nullptr;
-    }
-    for (TripBuf* b : {&T.hIn, &T.hOut, &T.hFlag, &T.dIn, &T.dOut}) b->release();
-    T.device = -1;
-}
+void lcDelimThreadRelease() { tlsDelim.release(); }
 
 extern "C" int lc_delim_split_host(lc_delim_t* d, const uint8_t* const* lines, const uint32_t* len, uint32_t n, uint32_t W, uint8_t* status,
                                    uint32_t* ncols, int32_t* spans) {
     if (!d) return LC_ERR_ARG;
     if (n == 0) return LC_OK;
     if (!lines || !len || !status || !ncols || (W && !spans)) return LC_ERR_ARG;
-    if (lc_device_count() <= 0) {
-        lcSetLastError("no HIP device: the delimiter parser has no CPU path");
-        return LC_ERR_NO_DEVICE;
-    }
-    int dev = 0;
-    {
-        const int rcDev = lcHostEntryDevice(&dev);  // the thread's binding
-        if (rcDev != LC_OK) return rcDev;
-    }
     DelimThread& T = tlsDelim;
-    if (T.stream && T.device != dev) lcDelimThreadRelease();
-    if (!T.stream) {
-        LC_HIP_TRY(hipStreamCreateWithFlags(&T.stream, hipStreamNonBlocking));
-        T.device = dev;
-        lcRegisterExitHook();
-        LC_HIP_TRY(T.hFlag.ensure(64));
-        *static_cast<uint32_t*>(T.hFlag.p) = 0;
-        T.seq = 0;
-    }
+    int dev = 0;
+    const int rcBegin = lcTripBegin(T, &dev, "no HIP device: the delimiter parser has no CPU path");
+    if (rcBegin != LC_OK) return rcBegin;
     const size_t lineSpanBytes = size_t(W) * 8;
     uint32_t next = 0;
     while (next < n) {
@@ -115,33 +87,21 @@ extern "C" int lc_delim_split_host(lc_delim_t* d, const uint8_t* const* lines, c
         // in one device block -- ONE copy down
         uint32_t cnt = 0;
         size_t bytes = 0;
-        while (next + cnt < n && cnt < kChunkLines && (cnt == 0 || (bytes + len[next + cnt] <= kChunkBytes && (cnt + 1) * lineSpanBytes <= kChunkSpanBytes))) {
-            bytes += len[next + cnt];
-            ++cnt;
-        }
-        if (bytes >= (size_t(1) << 31)) {
+        if (!tripCarve(len, next, n, kChunkLines, kChunkBytes, lineSpanBytes, kChunkSpanBytes, &cnt, &bytes)) {
             lcSetLastError("lc_delim_split_host: a line of 2 GiB or more");
             return LC_ERR_ARG;
         }
-        const size_t offAt = roundUp(bytes + 16, 64);
+        const size_t offAt = tripOffAt(bytes);
         const size_t inBytes = offAt + (size_t(cnt) + 1) * 4;
-        const size_t ncolsAt = roundUp(size_t(cnt) * lineSpanBytes, 64);
-        const size_t statusAt = ncolsAt + roundUp(size_t(cnt) * 4, 64);
-        const size_t outBytes = statusAt + roundUp(cnt, 64);
+        const size_t ncolsAt = tripRoundUp(size_t(cnt) * lineSpanBytes, 64);
+        const size_t statusAt = ncolsAt + tripRoundUp(size_t(cnt) * 4, 64);
+        const size_t outBytes = statusAt + tripRoundUp(cnt, 64);
         LC_HIP_TRY(T.hIn.ensure(inBytes));
         LC_HIP_TRY(T.dIn.ensure(inBytes));
         LC_HIP_TRY(T.hOut.ensure(outBytes));
         LC_HIP_TRY(T.dOut.ensure(outBytes));
         uint8_t* hIn = static_cast<uint8_t*>(T.hIn.p);
-        int32_t* hOff = reinterpret_cast<int32_t*>(hIn + offAt);
-        size_t at = 0;
-        for (uint32_t i = 0; i < cnt; ++i) {
-            hOff[i] = int32_t(at);
-            if (len[next + i]) std::memcpy(hIn + at, lines[next + i], len[next + i]);
-            at += len[next + i];
-        }
-        hOff[cnt] = int32_t(at);
-        std::memset(hIn + at, 0, offAt - at);
+        reinterpret_cast<int32_t*>(hIn + offAt)[cnt] = int32_t(tripPackLines(hIn, offAt, lines, len, next, cnt));
         uint8_t* dIn = static_cast<uint8_t*>(T.dIn.p);
         uint8_t* dOut = static_cast<uint8_t*>(T.dOut.p);
         LC_HIP_TRY(hipMemcpyAsync(dIn, hIn, inBytes, hipMemcpyHostToDevice, T.stream));
@@ -151,16 +111,8 @@ extern "C" int lc_delim_split_host(lc_delim_t* d, const uint8_t* const* lines, c
             const hipError_t e = hipMemcpyAsync(T.hOut.p, dOut, outBytes, hipMemcpyDeviceToHost, T.stream);
             if (e != hipSuccess) rc = lcHipFail(e, "hipMemcpyAsync(delimiter results)");
         }
-        // the trip's end: the pinned word is stored by a one-lane kernel behind the copy down
-        uint32_t* hFlag = static_cast<uint32_t*>(T.hFlag.p);
-        const uint32_t seq = ++T.seq;
-        if (rc == LC_OK) rc = lcQueueTripSignal(hFlag, seq, T.stream);
-        if (rc == LC_OK) rc = lcAwaitTripSignal(hFlag, seq, T.stream);
-        if (rc != LC_OK) {
-            (void)hipStreamSynchronize(T.stream);  // nothing queued here may still touch the staging when the next call reuses it
-            (void)hipGetLastError();
-            return rc;
-        }
+        rc = T.end(rc);
+        if (rc != LC_OK) return rc;
         const uint8_t* hOut = static_cast<const uint8_t*>(T.hOut.p);
         if (W) std::memcpy(spans + size_t(next) * W * 2, hOut, size_t(cnt) * lineSpanBytes);
         std::memcpy(ncols + next, hOut + ncolsAt, size_t(cnt) * 4);

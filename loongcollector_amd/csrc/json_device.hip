@@ -93,14 +93,18 @@ extern "C" int lc_json_walk_device(const uint8_t* d_data, const int32_t* d_off, 
 // ------------------------------------------------------------------------------------------------ host lines
 namespace {
 // per runner thread: a stream, pinned and device blocks each way, the pinned completion word; grow-only
-struct JsonThread {
-    hipStream_t stream = nullptr;
-    int device = -1;
-    TripBuf hIn, hOut, hShadow, hFlag, dIn, dOut, dShadow;
-    uint32_t seq = 0;
-    JsonThread() { hIn.pinned = hOut.pinned = hShadow.pinned = hFlag.pinned = true; }
+struct JsonThread : TripThread<JsonThread> {
+    TripBuf hIn, hOut, hShadow, dIn, dOut, dShadow;
+    JsonThread() : TripThread(true) { hIn.pinned = hOut.pinned = hShadow.pinned = true; }
     ~JsonThread() {
-        if (lcRuntimeUsable() && (stream || hIn.p || dIn.p)) lcJsonThreadRelease();
+        if (live()) release();
+    }
+    void release() {
+        if (stream) {
+            (void)hipStreamSynchronize(stream);
+            deepScratchForget(device, stream);  // (before the stream is destroyed: the block is found by it)
+        }
+        releaseWith({&hIn, &hOut, &hShadow, &dIn, &dOut, &dShadow});
     }
 };
 thread_local JsonThread tlsJson;
@@ -109,58 +113,19 @@ constexpr size_t kChunkBytes = 32u << 20;    // payload bytes per trip
 constexpr uint32_t kChunkLines = 1u << 18;   // and at most this many lines
 constexpr size_t kChunkRecordBytes = 64u << 20;
 constexpr uint32_t kShadowGap = 4096;        // two escaped spans closer than this come down in one copy
-
-inline size_t roundUp(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-int tripEnd(JsonThread& T, int rc) {
-    uint32_t* hFlag = static_cast<uint32_t*>(T.hFlag.p);
-    const uint32_t seq = ++T.seq;
-    if (rc == LC_OK) rc = lcQueueTripSignal(hFlag, seq, T.stream);
-    if (rc == LC_OK) rc = lcAwaitTripSignal(hFlag, seq, T.stream);
-    if (rc != LC_OK) {
-        (void)hipStreamSynchronize(T.stream);  // nothing queued here may still touch the staging when the next call reuses it
-        (void)hipGetLastError();
-    }
-    return rc;
-}
 }  // namespace
 
-void lcJsonThreadRelease() {
-    JsonThread& T = tlsJson;
-    if (T.stream) {
-        (void)hipStreamSynchronize(T.stream);
-        deepScratchForget(T.device, T.stream);
-        (void)hipStreamDestroy(T.stream);
-        T.stream = nullptr;
-    }
-    for (TripBuf* b : {&T.hIn, &T.hOut, &T.hShadow, &T.hFlag, &T.dIn, &T.dOut, &T.dShadow}) b->release();
-    T.device = -1;
-}
+void lcJsonThreadRelease() { tlsJson.release(); }
 
 extern "C" int lc_json_walk_host(const uint8_t* const* lines, const uint32_t* len, uint32_t n, uint32_t W, uint8_t* status, uint32_t* nmembers,
                                  uint32_t* errpos, lc_json_member_t* records, uint8_t* shadow, uint64_t* shadow_bytes_moved) {
     if (shadow_bytes_moved) *shadow_bytes_moved = 0;
     if (n == 0) return LC_OK;
     if (!lines || !len || !status || !nmembers || !errpos || !shadow || (W && !records)) return LC_ERR_ARG;
-    if (lc_device_count() <= 0) {
-        lcSetLastError("no HIP device: the JSON parser has no CPU path");
-        return LC_ERR_NO_DEVICE;
-    }
-    int dev = 0;
-    {
-        const int rcDev = lcHostEntryDevice(&dev);  // the thread's binding
-        if (rcDev != LC_OK) return rcDev;
-    }
     JsonThread& T = tlsJson;
-    if (T.stream && T.device != dev) lcJsonThreadRelease();
-    if (!T.stream) {
-        LC_HIP_TRY(hipStreamCreateWithFlags(&T.stream, hipStreamNonBlocking));
-        T.device = dev;
-        lcRegisterExitHook();
-        LC_HIP_TRY(T.hFlag.ensure(64));
-        *static_cast<uint32_t*>(T.hFlag.p) = 0;
-        T.seq = 0;
-    }
+    int dev = 0;
+    const int rcBegin = lcTripBegin(T, &dev, "no HIP device: the JSON parser has no CPU path");
+    if (rcBegin != LC_OK) return rcBegin;
     const size_t lineRecordBytes = size_t(W) * sizeof(lc_json_member_t);
     uint32_t next = 0;
     size_t shadowAt = 0;  // where line `next`'s part of the caller's shadow begins
@@ -170,20 +135,16 @@ extern "C" int lc_json_walk_host(const uint8_t* const* lines, const uint32_t* le
         // status bytes in one device block -- ONE copy down
         uint32_t cnt = 0;
         size_t bytes = 0;
-        while (next + cnt < n && cnt < kChunkLines && (cnt == 0 || (bytes + len[next + cnt] <= kChunkBytes && (cnt + 1) * lineRecordBytes <= kChunkRecordBytes))) {
-            bytes += len[next + cnt];
-            ++cnt;
-        }
-        if (bytes >= (size_t(1) << 31)) {
+        if (!tripCarve(len, next, n, kChunkLines, kChunkBytes, lineRecordBytes, kChunkRecordBytes, &cnt, &bytes)) {
             lcSetLastError("lc_json_walk_host: a line of 2 GiB or more");
             return LC_ERR_ARG;
         }
-        const size_t offAt = roundUp(bytes + 16, 64);
+        const size_t offAt = tripOffAt(bytes);
         const size_t inBytes = offAt + (size_t(cnt) + 1) * 4;
-        const size_t countAt = roundUp(size_t(cnt) * lineRecordBytes, 64);
-        const size_t errAt = countAt + roundUp(size_t(cnt) * 4, 64);
-        const size_t statusAt = errAt + roundUp(size_t(cnt) * 4, 64);
-        const size_t outBytes = statusAt + roundUp(cnt, 64);
+        const size_t countAt = tripRoundUp(size_t(cnt) * lineRecordBytes, 64);
+        const size_t errAt = countAt + tripRoundUp(size_t(cnt) * 4, 64);
+        const size_t statusAt = errAt + tripRoundUp(size_t(cnt) * 4, 64);
+        const size_t outBytes = statusAt + tripRoundUp(cnt, 64);
         LC_HIP_TRY(T.hIn.ensure(inBytes));
         LC_HIP_TRY(T.dIn.ensure(inBytes));
         LC_HIP_TRY(T.hOut.ensure(outBytes));
@@ -191,14 +152,7 @@ extern "C" int lc_json_walk_host(const uint8_t* const* lines, const uint32_t* le
         LC_HIP_TRY(T.dShadow.ensure(offAt));
         uint8_t* hIn = static_cast<uint8_t*>(T.hIn.p);
         int32_t* hOff = reinterpret_cast<int32_t*>(hIn + offAt);
-        size_t at = 0;
-        for (uint32_t i = 0; i < cnt; ++i) {
-            hOff[i] = int32_t(at);
-            if (len[next + i]) std::memcpy(hIn + at, lines[next + i], len[next + i]);
-            at += len[next + i];
-        }
-        hOff[cnt] = int32_t(at);
-        std::memset(hIn + at, 0, offAt - at);
+        hOff[cnt] = int32_t(tripPackLines(hIn, offAt, lines, len, next, cnt));
         uint8_t* dIn = static_cast<uint8_t*>(T.dIn.p);
         uint8_t* dOut = static_cast<uint8_t*>(T.dOut.p);
         uint8_t* dShadow = static_cast<uint8_t*>(T.dShadow.p);
@@ -213,7 +167,7 @@ extern "C" int lc_json_walk_host(const uint8_t* const* lines, const uint32_t* le
             const hipError_t e = hipMemcpyAsync(T.hOut.p, dOut, outBytes, hipMemcpyDeviceToHost, T.stream);
             if (e != hipSuccess) rc = lcHipFail(e, "hipMemcpyAsync(JSON results)");
         }
-        rc = tripEnd(T, rc);
+        rc = T.end(rc);
         if (rc != LC_OK) return rc;
         const uint8_t* hOut = static_cast<const uint8_t*>(T.hOut.p);
         // lines nested deeper than the first launch's registers reach: the second launch, over the chunk that still lies on the device
@@ -223,7 +177,7 @@ extern "C" int lc_json_walk_host(const uint8_t* const* lines, const uint32_t* le
                 const hipError_t e = hipMemcpyAsync(T.hOut.p, dOut, outBytes, hipMemcpyDeviceToHost, T.stream);
                 if (e != hipSuccess) rc = lcHipFail(e, "hipMemcpyAsync(JSON results, second launch)");
             }
-            rc = tripEnd(T, rc);
+            rc = T.end(rc);
             if (rc != LC_OK) return rc;
         }
         if (W) std::memcpy(records + size_t(next) * W, hOut, size_t(cnt) * lineRecordBytes);
@@ -264,7 +218,7 @@ extern "C" int lc_json_walk_host(const uint8_t* const* lines, const uint32_t* le
                 moved += c.e - c.b;
             }
             if (!copies.empty()) {
-                rc = tripEnd(T, rc);
+                rc = T.end(rc);
                 if (rc != LC_OK) return rc;
             }
             for (const Range& r : spans)

@@ -50,38 +50,20 @@ extern "C" int lc_multiline_bounds_device(uint32_t mode, const uint8_t* d_start,
 
 namespace {
 
-// per runner thread: a stream, pinned staging, device buffers; grow-only
-typedef TripBuf MlBuf;
-struct MlThread {
-    hipStream_t stream = nullptr;
-    int device = -1;
-    MlBuf hIn, hOut;                                             // pinned
-    MlBuf dData, dOff, dStatus, dFlags, dScratch, dSmall;        // device
+// per runner thread: a stream, pinned staging, device buffers; grow-only (the trips end with hipStreamSynchronize, not the signal)
+struct MlThread : TripThread<MlThread> {
+    TripBuf hIn, hOut;                                             // pinned
+    TripBuf dData, dOff, dStatus, dFlags, dScratch, dSmall;        // device
     uint32_t recordGuess = 1024;
-    MlThread() { hIn.pinned = hOut.pinned = true; }
+    MlThread() : TripThread(false) { hIn.pinned = hOut.pinned = true; }
     ~MlThread() {
-        if (lcRuntimeUsable() && (stream || hIn.p || dData.p)) lcMultilineThreadRelease();
+        if (live()) release();
     }
+    void release() { releaseWith({&hIn, &hOut, &dData, &dOff, &dStatus, &dFlags, &dScratch, &dSmall}); }
 };
 thread_local MlThread tlsMl;
 
-int prepare(MlThread& T, int& dev) {
-    if (lc_device_count() <= 0) {
-        lcSetLastError("no HIP device: the multiline processors have no CPU path");
-        return LC_ERR_NO_DEVICE;
-    }
-    {
-        const int rcDev = lcHostEntryDevice(&dev);  // the thread's binding (runtime_internal.hpp)
-        if (rcDev != LC_OK) return rcDev;
-    }
-    if (T.stream && T.device != dev) lcMultilineThreadRelease();  // (another device: old stream and buffers go)
-    if (!T.stream) {
-        LC_HIP_TRY(hipStreamCreateWithFlags(&T.stream, hipStreamNonBlocking));
-        T.device = dev;
-        lcRegisterExitHook();
-    }
-    return LC_OK;
-}
+int prepare(MlThread& T, int& dev) { return lcTripBegin(T, &dev, "no HIP device: the multiline processors have no CPU path"); }
 
 uint32_t modeOf(const lc_multiline& m, bool flush) {
     return (m.start ? ML_HAS_START : 0u) | (m.cont ? ML_HAS_CONT : 0u) | (m.end ? ML_HAS_END : 0u) | (m.discardUnmatched ? ML_DISCARD : 0u) |
@@ -128,16 +110,7 @@ int checkUndecided(const uint32_t counts[ML_CNT_WORDS]) {
 
 }  // namespace
 
-void lcMultilineThreadRelease() {
-    MlThread& T = tlsMl;
-    if (T.stream) {
-        (void)hipStreamSynchronize(T.stream);
-        (void)hipStreamDestroy(T.stream);
-        T.stream = nullptr;
-    }
-    for (MlBuf* b : {&T.hIn, &T.hOut, &T.dData, &T.dOff, &T.dStatus, &T.dFlags, &T.dScratch, &T.dSmall}) b->release();
-    T.device = -1;
-}
+void lcMultilineThreadRelease() { tlsMl.release(); }
 
 int lcMultilineSplitTrip(lc_multiline* m, const uint8_t* data, uint32_t nbytes, std::vector<lc_ml_record_t>& out,
                          uint32_t counts[ML_CNT_WORDS]) {

@@ -8,47 +8,24 @@
 #include "../../include/lc_processor.h"
 #include "../../include/lc_regex_gpu.h"
 #include "regex_handle.hpp"
-#include <hip/hip_runtime_api.h>
-
 #include "trip_buffers.hpp"
-
-void lcFilterThreadRelease();  // (runtime_internal.hpp; that header is for the device translation units)
 
 namespace {
 // per runner thread: a stream, pinned staging, device buffers; grow-only
-struct FilterThread {
-    hipStream_t stream = nullptr;
-    int device = -1;
+struct FilterThread : TripThread<FilterThread> {
     TripBuf hIn, hStatus;  // pinned: staging (values, offsets, lengths); status bytes + the trip's completion word
     TripBuf dIn, dStatus;  // device (dStatus: the kernels' capture scratch; dIn: only with LC_FILTER_COPY_TRIP)
     uint32_t tripSeq = 0;
-    FilterThread() { hIn.pinned = hStatus.pinned = true; }
-    ~FilterThread();
+    FilterThread() : TripThread(false) { hIn.pinned = hStatus.pinned = true; }  // (the word lives in hStatus: kFlagBytes)
+    ~FilterThread() {
+        if (live()) release();
+    }
+    void release() { releaseWith({&hIn, &hStatus, &dIn, &dStatus}); }
 };
 thread_local FilterThread tlsFilter;
 constexpr size_t kFlagBytes = 64;  // hStatus: [completion word, one cache line][status bytes]
 }  // namespace
-void lcRegisterExitHook();
-bool lcRuntimeUsable();  // gpu_runtime.hip
-int lcHostEntryDevice(int* dev);  // gpu_runtime.hip: the calling thread's device binding
-int lcQueueTripSignal(uint32_t* hFlag, uint32_t seq, hipStream_t stream);
-int lcAwaitTripSignal(const uint32_t* hFlag, uint32_t seq, hipStream_t stream);
-void lcSetJobTableInPlace(bool on);
-void lcFilterThreadRelease() {
-    FilterThread& T = tlsFilter;
-    if (T.stream) {
-        (void)hipStreamSynchronize(T.stream);
-        (void)hipStreamDestroy(T.stream);
-        T.stream = nullptr;
-    }
-    for (TripBuf* b : {&T.hIn, &T.hStatus, &T.dIn, &T.dStatus}) b->release();
-    T.device = -1;
-}
-namespace {
-FilterThread::~FilterThread() {
-    if (lcRuntimeUsable() && (stream || hIn.p || dIn.p)) lcFilterThreadRelease();
-}
-}  // namespace
+void lcFilterThreadRelease() { tlsFilter.release(); }
 
 namespace logtail {
 
@@ -315,22 +292,18 @@ bool ProcessorFilterGpu::Process(PipelineEventGroup& logGroup, std::string& erro
         return false;
     };
     if (totalVals) {
-        if (lc_device_count() <= 0) return fail("no HIP device: the filter has no CPU path");
-        if (totalBytes >= 0xFFFFFFF0ull) return fail("filter: more than 4 GiB of values in one group");
         FilterThread& T = tlsFilter;
         int dev = 0;
+        TripBeginFail why;
+        if (T.begin(&dev, &why) != LC_OK)
+            return fail(why.noDevice ? "no HIP device: the filter has no CPU path"
+                        : why.hipCall ? std::string(why.hipCall) + ": " + hipGetErrorString(why.hip) : std::string("filter: ") + lc_last_error());
+        if (totalBytes >= 0xFFFFFFF0ull) return fail("filter: more than 4 GiB of values in one group");
 #define FILTER_TRY(expr)                                                                  \
     do {                                                                                  \
         const hipError_t e_ = (expr);                                                     \
         if (e_ != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(e_)); \
     } while (0)
-        if (lcHostEntryDevice(&dev) != LC_OK) return fail(std::string("filter: ") + lc_last_error());  // the thread's binding
-        if (T.stream && T.device != dev) lcFilterThreadRelease();  // (another device: old stream and buffers go, see PipeThread)
-        if (!T.stream) {
-        lcRegisterExitHook();
-            FILTER_TRY(hipStreamCreateWithFlags(&T.stream, hipStreamNonBlocking));
-            T.device = dev;
-        }
         // staging: [value bytes, back to back][off: one word per value][len: one word per value]
         const size_t dataBytes = (size_t(totalBytes) + 31) & ~size_t(15);
         const size_t upBytes = dataBytes + totalVals * 8 + 16;

@@ -1,13 +1,12 @@
 // processor_pipeline_gpu.cpp -- see processor_pipeline_gpu.hpp and include/lc_processor.h (lc_pipeline_*).
 #include "processor_pipeline_gpu.hpp"
 
-#include <hip/hip_runtime_api.h>
-
 #include <algorithm>
 #include <cstring>
 
 #include "../../include/lc_regex_gpu.h"
 #include "regex_handle.hpp"
+#include "trip_buffers.hpp"
 
 namespace logtail {
 
@@ -135,57 +134,25 @@ void ProcessorPipelineGpu::SplitEvents(PipelineEventGroup& logGroup) const {
 }
 
 namespace {
-// per runner thread: a stream, pinned staging, device buffers; grow-only
-struct PipeBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    bool pinned = false;
-    void release() {
-        if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
-        p = nullptr;
-        cap = 0;
-    }
-    hipError_t ensure(size_t bytes) {
-        if (p && cap >= bytes) return hipSuccess;
-        release();
-        const size_t want = bytes + (bytes >> 2) + 256;
-        const hipError_t e = pinned ? hipHostMalloc(&p, want, hipHostMallocDefault) : hipMalloc(&p, want);
-        if (e == hipSuccess) cap = want;
-        return e;
-    }
-};
-struct PipeThread {
-    hipStream_t stream = nullptr;
-    int device = -1;
-    PipeBuf hIn, hOut;                                             // pinned
-    PipeBuf dData, dOff, dCaps, dStatus, dPacked, dCounts, dScratch;  // device
+// per runner thread: a stream, pinned staging, device buffers; grow-only (the trips end with hipStreamSynchronize, not the signal).
+// A runner thread that ends without lc_thread_release() does not leak its stream and buffers.
+struct PipeThread : TripThread<PipeThread> {
+    TripBuf hIn, hOut;                                             // pinned
+    TripBuf dData, dOff, dCaps, dStatus, dPacked, dCounts, dScratch;  // device
     uint32_t survivorGuess = 64;
-    PipeThread() { hIn.pinned = hOut.pinned = true; }
-    ~PipeThread();  // a runner thread that ends without lc_thread_release() does not leak its stream and buffers
+    PipeThread() : TripThread(false) { hIn.pinned = hOut.pinned = true; }
+    ~PipeThread() {
+        if (live()) release();
+    }
+    void release() { releaseWith({&hIn, &hOut, &dData, &dOff, &dCaps, &dStatus, &dPacked, &dCounts, &dScratch}); }
 };
 thread_local PipeThread tlsPipe;
 }  // namespace
 }  // namespace logtail
-void lcRegisterExitHook();
-bool lcRuntimeUsable();  // gpu_runtime.hip: false once the process is exiting (the HIP runtime may be gone)
-int lcHostEntryDevice(int* dev);  // gpu_runtime.hip: the calling thread's device binding
 // lc_thread_release(): the calling thread's staging and stream
-void lcPipelineThreadRelease() {
-    logtail::PipeThread& T = logtail::tlsPipe;
-    if (T.stream) {
-        (void)hipStreamSynchronize(T.stream);
-        (void)hipStreamDestroy(T.stream);
-        T.stream = nullptr;
-    }
-    for (logtail::PipeBuf* b : {&T.hIn, &T.hOut, &T.dData, &T.dOff, &T.dCaps, &T.dStatus, &T.dPacked, &T.dCounts, &T.dScratch}) b->release();
-    T.device = -1;
-}
+void lcPipelineThreadRelease() { logtail::tlsPipe.release(); }
 namespace logtail {
 namespace {
-PipeThread::~PipeThread() {
-    if (lcRuntimeUsable() && (stream || hIn.p || dData.p)) lcPipelineThreadRelease();
-}
-
 struct Trip {
     uint32_t lines = 0, survivors = 0, failed = 0, undecided = 0;
     std::vector<int32_t> rows;  // survivors sorted by line: [line, off, len, caps...]
@@ -219,23 +186,13 @@ bool ProcessorPipelineGpu::ProcessFused(PipelineEventGroup& logGroup, std::strin
         fellBack = true;
         return true;
     }
-    if (lc_device_count() <= 0) {
-        error = "no HIP device: the pipeline has no CPU path";
-        return false;
-    }
     PipeThread& T = tlsPipe;
     int dev = 0;
-    if (lcHostEntryDevice(&dev) != LC_OK) {  // the thread's binding
-        error = std::string("pipeline: ") + lc_last_error();
+    TripBeginFail why;
+    if (T.begin(&dev, &why) != LC_OK) {
+        error = why.noDevice ? "no HIP device: the pipeline has no CPU path"
+                : why.hipCall ? std::string(why.hipCall) + ": " + hipGetErrorString(why.hip) : std::string("pipeline: ") + lc_last_error();
         return false;
-    }
-    // (a thread that moved to another device starts over: its stream is destroyed, its grow-only buffers -- allocated on the old
-    // device -- are released; they used to be kept and handed to kernels of the new device)
-    if (T.stream && T.device != dev) lcPipelineThreadRelease();
-    if (!T.stream) {
-        lcRegisterExitHook();
-        PIPE_TRY(hipStreamCreateWithFlags(&T.stream, hipStreamNonBlocking));
-        T.device = dev;
     }
     const uint32_t G = uint32_t(mParse.mMarkCount);
     const uint32_t rowInts = 3 + 2 * G;

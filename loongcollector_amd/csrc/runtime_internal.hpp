@@ -6,13 +6,13 @@
 #include <cstdint>
 #include <string>
 
+#include "trip_buffers.hpp"  // lcHostEntryDevice, the exit hook, the trip signal: what the host translation units share too
+
 struct lc_regex;
 
 void lcSetLastError(const std::string& msg);           // the thread's lc_last_error() text
 int lcHipFail(hipError_t e, const char* what);         // sets the error text, returns LC_ERR_HIP
 void lcNoteKernel(const char* name);                   // lc_launched_kernels() log
-void lcRegisterExitHook();                             // thread_local device resources: see gpu_runtime.hip
-bool lcRuntimeUsable();
 void lcGrokThreadRelease();                            // grok_device.hip: the calling thread's Grok buffers
 void lcPipelineThreadRelease();                        // processor_pipeline_gpu.cpp: the calling thread's staging and stream
 void lcMultilineThreadRelease();                       // multiline_device.hip: the same for the multiline processors
@@ -20,17 +20,8 @@ void lcFilterThreadRelease();                          // processor_filter_gpu.c
 void lcDelimThreadRelease();                           // delim_device.hip: the same for the delimiter parser's host entry
 void lcTimestampThreadRelease();                       // timestamp_device.hip: the same for the timestamp parser's host entry
 void lcJsonThreadRelease();                            // json_device.hip: the same for the JSON parser's host entry
-// The device a HOST entry point (processors, lc_*_match_host, multiline, filter, pipeline) runs on for the calling thread: the thread's
-// binding (lc_runtime_bind_thread; first call binds by the process-wide policy), made current for the thread.  LC_OK or an error code.
-int lcHostEntryDevice(int* dev);
 // The device a DEVICE-pointer entry point runs on: the caller's current HIP device; LC_ERR_ARG when d_ptr lives on another device.
 int lcDeviceEntryDevice(const void* d_ptr, int* dev);
-// the ending of a zero-copy device trip (gpu_runtime.hip): a one-lane kernel behind everything on `stream` stores seq into the pinned word;
-// the host spins on it (few waiters) or blocks in the runtime (many)
-int lcQueueTripSignal(uint32_t* hFlag, uint32_t seq, hipStream_t stream);
-int lcAwaitTripSignal(const uint32_t* hFlag, uint32_t seq, hipStream_t stream);
-// the calling thread's next lc_regex_match_device_multi calls let the kernel read their (small) job tables from pinned memory
-void lcSetJobTableInPlace(bool on);
 // the decide pool the calling thread's next NFA launches use (0 = default; 1.. = worker streams of the Grok matcher)
 void lcSetDecideSlot(int slot);
 // where the calling thread's NEXT wide-kernel launch reports that it had work (a device word set to 1; nullptr = nowhere)
@@ -56,6 +47,16 @@ int lcLaunchWaveJobs(const uint8_t* d_data, const TdfaWaveJob* jobs, uint32_t nJ
 // order[] = the lines 0..n-1 sorted by length bucket (32 bytes), longest first (sched_kernel.hpp); work: 512 words
 int lcLengthOrderOnStream(const uint32_t* d_off, const uint32_t* d_len, uint32_t sep_bytes, uint32_t n, uint32_t* work, uint32_t* order,
                           hipStream_t st);
+
+// TripThread::begin (trip_buffers.hpp) for a device translation unit: its failure worded into lc_last_error()
+template <class Thread>
+int lcTripBegin(Thread& T, int* dev, const char* noDeviceText) {
+    TripBeginFail why;
+    const int rc = T.begin(dev, &why);
+    if (why.noDevice) lcSetLastError(noDeviceText);
+    else if (why.hipCall) return lcHipFail(why.hip, why.hipCall);
+    return rc;
+}
 
 #define LC_HIP_TRY(expr)                                    \
     do {                                                    \

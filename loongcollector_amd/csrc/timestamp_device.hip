@@ -78,58 +78,30 @@ extern "C" int lc_strptime_parse_captures_device(lc_strptime_t* t, const uint8_t
 
 // ------------------------------------------------------------------------------------------------ host values
 namespace {
-struct TimestampThread {
-    hipStream_t stream = nullptr;
-    int device = -1;
-    TripBuf hIn, hOut, hFlag, dIn, dOut;
-    uint32_t seq = 0;
-    TimestampThread() { hIn.pinned = hOut.pinned = hFlag.pinned = true; }
+struct TimestampThread : TripThread<TimestampThread> {
+    TripBuf hIn, hOut, dIn, dOut;
+    TimestampThread() : TripThread(true) { hIn.pinned = hOut.pinned = true; }
     ~TimestampThread() {
-        if (lcRuntimeUsable() && (stream || hIn.p || dIn.p)) lcTimestampThreadRelease();
+        if (live()) release();
     }
+    void release() { releaseWith({&hIn, &hOut, &dIn, &dOut}); }
 };
 thread_local TimestampThread tlsTimestamp;
 
 constexpr size_t kChunkBytes = 32u << 20;   // value bytes per trip
 constexpr uint32_t kChunkValues = 1u << 20;  // and at most this many values
-
-inline size_t roundUp(size_t v, size_t a) { return (v + a - 1) / a * a; }
 }  // namespace
 
-void lcTimestampThreadRelease() {
-    TimestampThread& T = tlsTimestamp;
-    if (T.stream) {
-        (void)hipStreamSynchronize(T.stream);
-        (void)hipStreamDestroy(T.stream);
-        T.stream = nullptr;
-    }
-    for (TripBuf* b : {&T.hIn, &T.hOut, &T.hFlag, &T.dIn, &T.dOut}) b->release();
-    T.device = -1;
-}
+void lcTimestampThreadRelease() { tlsTimestamp.release(); }
 
 extern "C" int lc_strptime_parse_host(lc_strptime_t* t, const uint8_t* const* vals, const uint32_t* len, uint32_t n, const lc_ts_out_t* out) {
     if (!t) return LC_ERR_ARG;
     if (n == 0) return LC_OK;
     if (!vals || !len || !outComplete(out)) return LC_ERR_ARG;
-    if (lc_device_count() <= 0) {
-        lcSetLastError("no HIP device: the timestamp parser has no CPU path");
-        return LC_ERR_NO_DEVICE;
-    }
-    int dev = 0;
-    {
-        const int rcDev = lcHostEntryDevice(&dev);  // the thread's binding
-        if (rcDev != LC_OK) return rcDev;
-    }
     TimestampThread& T = tlsTimestamp;
-    if (T.stream && T.device != dev) lcTimestampThreadRelease();
-    if (!T.stream) {
-        LC_HIP_TRY(hipStreamCreateWithFlags(&T.stream, hipStreamNonBlocking));
-        T.device = dev;
-        lcRegisterExitHook();
-        LC_HIP_TRY(T.hFlag.ensure(64));
-        *static_cast<uint32_t*>(T.hFlag.p) = 0;
-        T.seq = 0;
-    }
+    int dev = 0;
+    const int rcBegin = lcTripBegin(T, &dev, "no HIP device: the timestamp parser has no CPU path");
+    if (rcBegin != LC_OK) return rcBegin;
     uint32_t next = 0;
     while (next < n) {
         // a chunk up: the values back to back, then (64-byte aligned) their offsets and (begin, end) pairs -- ONE copy; down: the six
@@ -139,39 +111,30 @@ extern "C" int lc_strptime_parse_host(lc_strptime_t* t, const uint8_t* const* va
         const uint32_t first = next - lead;
         uint32_t cnt = lead;
         size_t bytes = lead ? len[first] : 0;
-        while (first + cnt < n && cnt < kChunkValues && (cnt == lead || bytes + len[first + cnt] <= kChunkBytes)) {
-            bytes += len[first + cnt];
-            ++cnt;
-        }
-        if (bytes >= (size_t(1) << 31)) {
+        if (!tripCarve(len, next, n, kChunkValues, kChunkBytes, 0, 0, &cnt, &bytes)) {
             lcSetLastError("lc_strptime_parse_host: a value of 2 GiB or more");
             return LC_ERR_ARG;
         }
-        const size_t offAt = roundUp(bytes + 16, 64);
-        const size_t spanAt = offAt + roundUp(size_t(cnt) * 4, 64);
+        const size_t offAt = tripOffAt(bytes);
+        const size_t spanAt = offAt + tripRoundUp(size_t(cnt) * 4, 64);
         const size_t inBytes = spanAt + size_t(cnt) * 8;
-        const size_t nanosAt = roundUp(size_t(cnt) * 8, 64);
-        const size_t matchedAt = nanosAt + roundUp(size_t(cnt) * 4, 64);
-        const size_t fracAt = matchedAt + roundUp(size_t(cnt) * 4, 64);
-        const size_t statusAt = fracAt + roundUp(size_t(cnt) * 4, 64);
-        const size_t sameAt = statusAt + roundUp(cnt, 64);
-        const size_t outBytes = sameAt + roundUp(cnt, 64);
+        const size_t nanosAt = tripRoundUp(size_t(cnt) * 8, 64);
+        const size_t matchedAt = nanosAt + tripRoundUp(size_t(cnt) * 4, 64);
+        const size_t fracAt = matchedAt + tripRoundUp(size_t(cnt) * 4, 64);
+        const size_t statusAt = fracAt + tripRoundUp(size_t(cnt) * 4, 64);
+        const size_t sameAt = statusAt + tripRoundUp(cnt, 64);
+        const size_t outBytes = sameAt + tripRoundUp(cnt, 64);
         LC_HIP_TRY(T.hIn.ensure(inBytes));
         LC_HIP_TRY(T.dIn.ensure(inBytes));
         LC_HIP_TRY(T.hOut.ensure(outBytes));
         LC_HIP_TRY(T.dOut.ensure(outBytes));
         uint8_t* hIn = static_cast<uint8_t*>(T.hIn.p);
-        uint32_t* hOff = reinterpret_cast<uint32_t*>(hIn + offAt);
+        tripPackLines(hIn, offAt, vals, len, first, cnt);
         int32_t* hSpan = reinterpret_cast<int32_t*>(hIn + spanAt);
-        size_t at = 0;
         for (uint32_t i = 0; i < cnt; ++i) {
-            hOff[i] = uint32_t(at);
             hSpan[2 * i] = 0;
             hSpan[2 * i + 1] = int32_t(len[first + i]);
-            if (len[first + i]) std::memcpy(hIn + at, vals[first + i], len[first + i]);
-            at += len[first + i];
         }
-        std::memset(hIn + at, 0, offAt - at);
         uint8_t* dIn = static_cast<uint8_t*>(T.dIn.p);
         uint8_t* dOut = static_cast<uint8_t*>(T.dOut.p);
         LC_HIP_TRY(hipMemcpyAsync(dIn, hIn, inBytes, hipMemcpyHostToDevice, T.stream));
@@ -183,15 +146,8 @@ extern "C" int lc_strptime_parse_host(lc_strptime_t* t, const uint8_t* const* va
             const hipError_t e = hipMemcpyAsync(T.hOut.p, dOut, outBytes, hipMemcpyDeviceToHost, T.stream);
             if (e != hipSuccess) rc = lcHipFail(e, "hipMemcpyAsync(timestamp results)");
         }
-        uint32_t* hFlag = static_cast<uint32_t*>(T.hFlag.p);
-        const uint32_t seq = ++T.seq;
-        if (rc == LC_OK) rc = lcQueueTripSignal(hFlag, seq, T.stream);
-        if (rc == LC_OK) rc = lcAwaitTripSignal(hFlag, seq, T.stream);
-        if (rc != LC_OK) {
-            (void)hipStreamSynchronize(T.stream);  // nothing queued here may still touch the staging when the next call reuses it
-            (void)hipGetLastError();
-            return rc;
-        }
+        rc = T.end(rc);
+        if (rc != LC_OK) return rc;
         const uint8_t* hOut = static_cast<const uint8_t*>(T.hOut.p);
         const uint32_t got = cnt - lead;
         std::memcpy(out->secs + next, hOut + size_t(lead) * 8, size_t(got) * 8);

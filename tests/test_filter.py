@@ -9,6 +9,7 @@ import random
 
 import pytest
 
+from helpers import fresh_thread
 from loongcollector_amd import binding as B
 from loongcollector_amd import processor as P
 from loongcollector_amd.processor import EventGroup, Filter, ProcessorInitError
@@ -155,3 +156,22 @@ def test_groups_of_alternating_sizes_over_more_than_257_trips():
             d = g.to_dict()
             got = [e["contents"]["k"] for e in d["events"]] if d else []
             assert got == ["yes%d" % i for i, fl in enumerate(flags_now) if fl], trip
+
+
+@pytest.mark.gpu
+def test_process_after_thread_release_gives_the_same_answer():
+    f = Filter({"Include": {"k": "yes.*"}})
+    events = [{"k": "yes1"}, {"k": "no"}, {"other": "yes"}, {"k": "yes"}]
+
+    def body():
+        answers = []
+        for _ in range(2):
+            g = _group(events)
+            f.process(g)
+            answers.append([e["contents"] for e in g.to_dict()["events"]])
+            B.load().lc_thread_release()
+        return answers, B.load().lc_last_error()
+
+    answers, error = fresh_thread.run(body)
+    assert answers[0] == answers[1] == [{"k": "yes1"}, {"k": "yes"}]
+    assert not error

@@ -9,6 +9,7 @@ import threading
 import numpy as np
 import pytest
 
+from helpers import fresh_thread
 from helpers.delimiter_model import Engine
 
 pytestmark = pytest.mark.gpu
@@ -254,3 +255,60 @@ def test_the_plugin_slot_builds_the_delimiter_parser_for_its_type_name():
     iface.finalize(ins.plugin_state)
     bad = Instance()
     assert iface.init(ctypes.addressof(bad), json.dumps(dict(config, Separator="12345")).encode(), None) != 0 and not bad.plugin_state
+
+
+# ---------------------------------------------------------------------------------------------- the host entry's chunk limits
+def _host_equals_device(dl, lines, W):
+    """lc_delim_split_host against lc_delim_split_device over the same packed lines: status, counts and the spans that count"""
+    st, nc, sp = _device_split(dl, lines, W)
+    data, off = _pack(lines)
+    hst, hnc, hsp = dl.split_host(data, off, W)
+    assert np.array_equal(hst, st) and np.array_equal(hnc.astype(np.int64), nc)
+    kmax = int(min(nc.max(), W))
+    live = np.arange(kmax)[None, :] < np.minimum(nc, W)[:, None]
+    assert np.array_equal(hsp[:, :kmax][live], sp[:, :kmax][live])
+    return hst, hnc, hsp
+
+
+def test_split_host_second_chunk_behind_two_to_the_18_lines():
+    from loongcollector_amd import delimiter
+    dl = delimiter.GpuDelimiter(b",", b'"', "extend", 3)
+    n = (1 << 18) + 1
+    lines = [b"%d,b" % (i % 1000) if i % 7 else b'"q,%d",x,y' % (i % 10) for i in range(n)]
+    hst, hnc, hsp = _host_equals_device(dl, lines, 4)
+    assert (int(hnc[n - 1]), int(hnc[n - 2])) == (2, 3) and list(hsp[n - 1, 0]) == [0, len(lines[n - 1]) - 2]
+
+
+def test_split_host_forty_lines_of_one_mib_cross_the_payload_limit():
+    from loongcollector_amd import delimiter
+    dl = delimiter.GpuDelimiter(b",", b'"', "extend", 3)
+    lines = []
+    for i in range(40):
+        body = b"abcdefg," * (1 << 17) if i % 2 else b"k," + b"v" * ((1 << 20) - 4) + b",z"
+        assert len(body) == 1 << 20
+        lines += [body, b"s%d,t" % i, b""]
+    hst, hnc, hsp = _host_equals_device(dl, lines, 4)
+    assert [int(c) for c in hnc[:6]] == [3, 2, 0, (1 << 17) + 1, 2, 0]
+
+
+def test_split_host_64_mib_of_spans_per_chunk_at_w_8192():
+    from loongcollector_amd import delimiter
+    dl = delimiter.GpuDelimiter(b",", b'"', "extend", 3)
+    lines = [b",".join(b"c%d" % (i + c) for c in range(1 + i % 5)) for i in range(1100)]      # (1023 lines fill a chunk)
+    hst, hnc, hsp = _host_equals_device(dl, lines, 8192)
+    assert [int(c) for c in hnc[1020:1030]] == [1 + i % 5 for i in range(1020, 1030)]
+
+
+def test_split_host_after_thread_release_gives_the_same_answer():
+    from loongcollector_amd import binding, delimiter
+    dl = delimiter.GpuDelimiter(b",", b'"', "extend", 3)
+    data, off = _pack([b"a,b", b'"x,y",z', b"", b"k"])
+
+    def body():
+        first = dl.split_host(data, off, 4)
+        binding.load().lc_thread_release()
+        return first, dl.split_host(data, off, 4), binding.load().lc_last_error()
+
+    first, second, error = fresh_thread.run(body)
+    assert all(np.array_equal(a, b) for a, b in zip(first, second)) and list(first[1]) == [2, 2, 0, 1]
+    assert not error

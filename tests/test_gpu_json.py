@@ -8,6 +8,7 @@ import random
 import numpy as np
 import pytest
 
+from helpers import fresh_thread
 from helpers import json_cases as jc
 from helpers import json_model as jm
 
@@ -288,3 +289,72 @@ def test_launched_kernels_names_the_json_kernel():
     binding.launched_kernels()
     _walk_host([b'{"a":1}', b"x"], 4)
     assert "json_walk_kernel" in binding.launched_kernels()
+
+
+# ---------------------------------------------------------------------------------------------- the host entry's chunk limits
+def _host_equals_device(lines, W):
+    """lc_json_walk_host against lc_json_walk_device over the same packed lines: status, counts, error offsets, the records that count
+    and the unescaped bytes of escaped spans"""
+    host, dev = _walk_host(lines, W), _walk_device(lines, W)
+    st, nm = host[0], np.asarray(host[1], np.int64)
+    assert np.array_equal(st, dev[0]) and np.array_equal(nm, dev[1]) and np.array_equal(np.asarray(host[2], np.int64), dev[2])
+    escaped = np.zeros(len(lines), bool)
+    for k in range(min(W, int(nm.max()))):
+        live = (st == jm.OK) & (nm > k)
+        a, b = host[3][live, k], dev[3][live, k]
+        for f in ("kb", "ke", "vb", "ve", "type"):
+            assert np.array_equal(a[f], b[f]), (k, f)
+        escaped[live] |= ((a["kb"] | a["vb"]) & jc.ESCAPED) != 0
+    some = [int(i) for i in np.nonzero(escaped)[0]]
+    off = host[6]
+    for i in some:
+        for r in host[3][i][:min(W, int(nm[i]))]:
+            for b, e in (("kb", "ke"), ("vb", "ve")):
+                if int(r[b]) & jc.ESCAPED and (b == "kb" or int(r["type"]) == jm.STRING):
+                    lo, hi = int(off[i]) + (int(r[b]) & ~jc.ESCAPED), int(off[i]) + int(r[e])
+                    assert bytes(host[4][lo:hi]) == bytes(dev[4][lo:hi]), (i, lines[i][:100])
+    return host, some
+
+
+def test_walk_host_second_chunk_behind_two_to_the_18_lines():
+    n = (1 << 18) + 1
+    lines = [b'{"a":%d}' % (i % 1000) if i % 3001 and i != n - 1 else b'{"e\\t%d":"x\\n\\u00e9"}' % (i % 10) for i in range(n)]
+    host, some = _host_equals_device(lines, 2)
+    assert len(some) == len(range(0, n, 3001)) + 1 and some[-1] == 1 << 18 and host[5] > 0      # (the second chunk is one escaped line)
+    off, last = host[6], some[-1]
+    assert bytes(host[4][off[last] + 2:off[last] + 5]) == b"e\t%d" % (last % 10)
+
+
+def test_walk_host_forty_lines_of_one_mib_cross_the_payload_limit():
+    lines = []
+    for i in range(40):
+        body = b'{"k":"' + b"y" * ((1 << 20) - 8 - 8 * (i % 2)) + (b"\\n\\t\\r\\b" if i % 2 else b"") + b'"}'
+        assert len(body) == 1 << 20
+        lines += [body, b'{"s":%d}' % i, b""]
+    host, some = _host_equals_device(lines, 2)
+    assert list(host[0][:3]) == [jm.OK, jm.OK, jm.EMPTY] and some == list(range(3, 120, 6))
+
+
+def test_walk_host_64_mib_of_records_per_chunk_at_w_4096_with_deep_and_escaped_lines_in_the_second_chunk():
+    lines = [b"{" + b",".join(b'"k%d":%d' % (c, i) for c in range(1 + i % 4)) + b"}" for i in range(900)]      # (819 lines fill a chunk)
+    for i in (5, 400, 830, 870):
+        lines[i] = b'{"e":"a\\"b\\u20AC","n":%d}' % i
+    for i in (100, 850, 899):
+        lines[i] = b'{"a":' + b"[" * 99 + b"]" * 99 + b',"t":"\\t"}'
+    host, some = _host_equals_device(lines, 4096)
+    assert some == [5, 100, 400, 830, 850, 870, 899] and list(host[1][[818, 819, 820, 850]]) == [3, 4, 1, 2] and np.all(host[0] == jm.OK)
+    _check(lines, host, 4096)
+
+
+def test_walk_host_after_thread_release_gives_the_same_answer():
+    from loongcollector_amd import binding
+    lines = [b'{"a":1}', b'{"e":"x\\ny"}', b"", b'{"a":' + b"[" * 99 + b"]" * 99 + b"}", b"{x"]
+
+    def body():
+        first = _walk_host(lines, 4)
+        binding.load().lc_thread_release()
+        return first, _walk_host(lines, 4), binding.load().lc_last_error()
+
+    first, second, error = fresh_thread.run(body)
+    assert all(np.array_equal(a, b) for a, b in zip(first, second)) and list(first[0]) == [jm.OK, jm.OK, jm.EMPTY, jm.OK, jm.FAIL]
+    assert not error

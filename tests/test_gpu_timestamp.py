@@ -11,6 +11,7 @@ import time
 import numpy as np
 import pytest
 
+from helpers import fresh_thread
 from helpers import timestamp_model as model
 from helpers.timestamp_double import INT_MIN, LC_TS_ABSENT, LC_TS_EPOCH, LC_TS_HAS_YEAR, LC_TS_OK, Product, bind_processor, check_vector
 
@@ -285,3 +286,54 @@ def test_slot_builds_the_timestamp_processor():
     iface.process(ins.plugin_state, L.lc_group_native(g._h))
     assert json.loads(g.to_json())["events"][0]["timestamp"] == now - 5
     iface.finalize(ins.plugin_state)
+
+
+# ---------------------------------------------------------------------------------------------- the host entry's chunk limits
+def _host_equals_device(torch, fmt, values):
+    """lc_strptime_parse_host against lc_strptime_parse_spans_device over the same packed values, all six arrays"""
+    from loongcollector_amd import timestamp
+    t = timestamp.GpuStrptime(fmt)
+    d_data, d_off, d_spans = _upload(torch, values)
+    out = t.device_outputs(len(values), d_data.device)
+    t.parse_spans_device(d_data, d_off, d_spans, len(values), out)
+    torch.cuda.synchronize()
+    host = t.parse_host(values)
+    for k in KEYS:
+        assert np.array_equal(out[k].cpu().numpy().view(host[k].dtype), host[k]), k
+    return host
+
+
+def test_parse_host_second_chunk_behind_two_to_the_20_values_starts_one_value_early():
+    torch = _torch()
+    n = (1 << 20) + 1
+    values = [b"%d" % (1700000000 + (i + 1) // 2) for i in range(n)]      # equal pairs (1, 2), (3, 4) .. (2^20 - 1, 2^20)
+    assert values[n - 1] == values[n - 2] != values[n - 3]
+    host = _host_equals_device(torch, "%s", values)
+    assert host["same_as_prev"][n - 1] == 1 and host["same_as_prev"][n - 2] == 0 and host["same_as_prev"][:5].tolist() == [0, 0, 1, 0, 1]
+    assert int(host["secs"][n - 1]) == 1700000000 + (1 << 19) and np.all(host["status"] & LC_TS_OK)
+
+
+def test_parse_host_forty_values_of_one_mib_cross_the_payload_limit():
+    torch = _torch()
+    values = []
+    for i in range(40):
+        values += [b"%d" % (1700000000 + i // 2) + b"x" * ((1 << 20) - 10), b"%d" % (1700000000 + i), b"%d" % (1700000000 + i)]
+    host = _host_equals_device(torch, "%s", values)
+    assert host["secs"][:6].tolist() == [1700000000, 1700000000, 1700000000, 1700000000, 1700000001, 1700000001]
+    assert host["matched"][:3].tolist() == [10, 10, 10] and host["same_as_prev"][:6].tolist() == [0, 1, 1, 1, 0, 1]
+
+
+def test_parse_host_after_thread_release_gives_the_same_answer():
+    _torch()
+    from loongcollector_amd import binding, timestamp
+    t = timestamp.GpuStrptime("%Y-%m-%d %H:%M:%S")
+    values = [b"2023-12-25 01:02:03", b"2023-12-25 01:02:03", b"x", b""]
+
+    def body():
+        first = t.parse_host(values)
+        binding.load().lc_thread_release()
+        return first, t.parse_host(values), binding.load().lc_last_error()
+
+    first, second, error = fresh_thread.run(body)
+    assert all(np.array_equal(first[k], second[k]) for k in KEYS) and first["secs"][:2].tolist() == [1703466123] * 2
+    assert first["same_as_prev"].tolist() == [0, 1, 0, 0] and not error

@@ -7,6 +7,7 @@ import random
 
 import pytest
 
+from helpers import fresh_thread
 from loongcollector_amd import binding as B
 from loongcollector_amd.multiline import Multiline, MultilineInitError
 from oracle.multiline_oracle import MultilineOracle
@@ -99,6 +100,21 @@ def test_random_buffers_against_the_oracle(config):
         if rng.random() < 0.2:
             val += b"\n"
         assert m.split(val) == o.split(val), (config, val)
+
+
+@pytest.mark.gpu
+def test_split_after_thread_release_gives_the_same_answer():
+    m = Multiline(StartPattern="BEGIN", EndPattern=r"END\d*$")
+    val = b"noise\nBEGIN tx\nstmt;\nEND7\nEND7x\nBEGIN"
+
+    def body():
+        first = m.split(val)
+        B.load().lc_thread_release()
+        return first, m.split(val), B.load().lc_last_error()
+
+    first, second, error = fresh_thread.run(body)
+    assert second == first == MultilineOracle(StartPattern="BEGIN", EndPattern=r"END\d*$").split(val)
+    assert not error
 
 
 # ---------------------------------------------------------------------------------------------- the processors on whole event groups
