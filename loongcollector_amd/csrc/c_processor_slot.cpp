@@ -8,7 +8,7 @@
 #include <memory>
 
 #include "../../include/lc_processor.h"
-#include "processor_parse_regex_gpu.hpp"
+#include "parse_processor_shell.hpp"
 #include "processor_pipeline_gpu.hpp"
 #ifdef LC_USE_REFERENCE_HEADERS
 #include "json/json.h"  // the agent hands init() a Json::Value* (DynamicCProcessorProxy.cpp:30-32)
@@ -17,24 +17,35 @@
 using logtail::PipelineEventGroup;
 using logtail::ProcessorParseRegexGpu;
 
-// The delimiter processor's way through the slot (processor_parse_delimiter_gpu.cpp).  Weak: a build that links this file without that
-// one (the agent-form plugin of INTEGRATION.md section 2) still links, and refuses such a config.
+// The other processor types the slot builds, by the Type of the config.  Their entries are weak: a build that links this file without
+// the processor's own (the agent-form plugin of INTEGRATION.md section 2) still links, and refuses such a config.
 extern "C" {
-__attribute__((weak)) int lcDelimiterSlotInit(const char* config_text, void** state);
+__attribute__((weak)) int lcDelimiterSlotInit(const char* config_text, void** state);  // processor_parse_delimiter_gpu.cpp
 __attribute__((weak)) void lcDelimiterSlotProcess(void* state, void* native_group);
 __attribute__((weak)) void lcDelimiterSlotFinalize(void* state);
-// ... and the timestamp processor's (processor_parse_timestamp_gpu.cpp), on the same terms
-__attribute__((weak)) int lcTimestampSlotInit(const char* config_text, void** state);
+__attribute__((weak)) int lcTimestampSlotInit(const char* config_text, void** state);  // processor_parse_timestamp_gpu.cpp
 __attribute__((weak)) void lcTimestampSlotProcess(void* state, void* native_group);
 __attribute__((weak)) void lcTimestampSlotFinalize(void* state);
 }
+namespace {
+struct SlotEntry {
+    const char* type;   // the config's Type
+    const char* label;  // what a build without the processor says it does not hold
+    int (*init)(const char* config_text, void** state);
+    void (*process)(void* state, void* native_group);
+    void (*finalize)(void* state);
+};
+const SlotEntry kSlotTable[] = {
+    {"processor_parse_delimiter_gpu", "delimiter parser", lcDelimiterSlotInit, lcDelimiterSlotProcess, lcDelimiterSlotFinalize},
+    {"processor_parse_timestamp_gpu", "timestamp processor", lcTimestampSlotInit, lcTimestampSlotProcess, lcTimestampSlotFinalize},
+};
+}  // namespace
 
-struct lc_processor {
-    void* delimiter = nullptr;  // slot only: the instance was built from a config whose Type is processor_parse_delimiter_gpu
-    void* timestamp = nullptr;  // slot only: ... whose Type is processor_parse_timestamp_gpu
-    ProcessorParseRegexGpu impl;
-    // the part ProcessorInstance adds around every plugin (ProcessorInstance.cpp:46-63)
-    std::atomic<uint64_t> inEvents{0}, outEvents{0}, inBytes{0}, outBytes{0}, processUs{0};
+struct lc_processor : logtail::ProcessorHandle<ProcessorParseRegexGpu> {
+    std::atomic<uint64_t> processUs{0};
+    // slot only: the instance was built from a config whose Type names an entry of kSlotTable; `other` is that processor
+    const SlotEntry* entry = nullptr;
+    void* other = nullptr;
 };
 
 #ifndef LC_USE_REFERENCE_HEADERS
@@ -44,9 +55,7 @@ struct lc_event_group {
 };
 #endif
 
-static void setErr(char* err, size_t cap, const std::string& msg) {
-    if (err && cap) std::snprintf(err, cap, "%s", msg.c_str());
-}
+using logtail::setErrorText;
 
 static int processGroup(lc_processor* p, PipelineEventGroup& group) {
     p->inEvents += group.GetEvents().size();
@@ -71,28 +80,13 @@ static int processGroup(lc_processor* p, PipelineEventGroup& group) {
 }
 
 extern "C" int lc_processor_create(const char* config_json, lc_processor_t** out, char* err, size_t errcap) {
-    if (!config_json || !out) return LC_ERR_ARG;
-    *out = nullptr;
-    lcjson::Value cfg;
-    try {
-        cfg = lcjson::parse(config_json);
-    } catch (const std::exception& e) {
-        setErr(err, errcap, e.what());
-        return LC_ERR_ARG;
-    }
-    auto p = std::make_unique<lc_processor>();
-    if (const lcjson::Value* eng = cfg.find("_Engine")) {  // test hook: "tdfa" | "nfa"
-        if (eng->str == "tdfa") p->impl.mEngineChoice = LC_ENGINE_TDFA;
-        if (eng->str == "nfa") p->impl.mEngineChoice = LC_ENGINE_NFA;
-    }
-    std::string error;
-    if (!p->impl.Init(cfg, error)) {
-        setErr(err, errcap, error);
-        return LC_ERR_SYNTAX;
-    }
-    setErr(err, errcap, "");
-    *out = p.release();
-    return LC_OK;
+    return logtail::createHandle(config_json, out, err, errcap, [](lc_processor& h, const lcjson::Value& cfg, std::string& error) {
+        if (const lcjson::Value* eng = cfg.find("_Engine")) {  // test hook: "tdfa" | "nfa"
+            if (eng->str == "tdfa") h.impl.mEngineChoice = LC_ENGINE_TDFA;
+            if (eng->str == "nfa") h.impl.mEngineChoice = LC_ENGINE_NFA;
+        }
+        return logtail::initHandle(h, cfg, error);
+    });
 }
 
 extern "C" void lc_processor_destroy(lc_processor_t* p) { delete p; }
@@ -123,19 +117,10 @@ extern "C" void lc_processor_set_alarm_sink(lc_processor_t* p, lc_alarm_sink_t s
 }
 
 extern "C" int lc_processor_counters(const lc_processor_t* p, uint64_t out[LC_CNT_COUNT]) {
-    if (!p || !out) return LC_ERR_ARG;
-    out[LC_CNT_DISCARDED_EVENTS] = p->impl.mDiscardedEventsTotal;
-    out[LC_CNT_OUT_FAILED_EVENTS] = p->impl.mOutFailedEventsTotal;
-    out[LC_CNT_OUT_KEY_NOT_FOUND] = p->impl.mOutKeyNotFoundEventsTotal;
-    out[LC_CNT_OUT_SUCCESSFUL_EVENTS] = p->impl.mOutSuccessfulEventsTotal;
-    out[LC_CNT_IN_EVENTS] = p->inEvents;
-    out[LC_CNT_OUT_EVENTS] = p->outEvents;
-    out[LC_CNT_IN_SIZE_BYTES] = p->inBytes;
-    out[LC_CNT_OUT_SIZE_BYTES] = p->outBytes;
+    if (logtail::fillCounters(p, out, false) != LC_OK) return LC_ERR_ARG;
     out[LC_CNT_PROCESS_TIME_US] = p->processUs;
     out[LC_CNT_COMPLEXITY_EXCEEDED] = p->impl.mComplexityExceededEventsTotal;
     out[LC_CNT_UNDECIDED_EVENTS] = p->impl.mUndecidedEventsTotal;
-    out[LC_CNT_DEVICE_FAILED_EVENTS] = p->impl.mDeviceFailedEventsTotal;
     return LC_OK;
 }
 
@@ -145,10 +130,10 @@ extern "C" lc_event_group_t* lc_group_from_json(const char* json, char* err, siz
     auto g = std::make_unique<lc_event_group>();
     std::string error;
     if (!g->group.FromJsonString(json, &error)) {
-        setErr(err, errcap, error);
+        setErrorText(err, errcap, error);
         return nullptr;
     }
-    setErr(err, errcap, "");
+    setErrorText(err, errcap, "");
     return g.release();
 }
 
@@ -198,24 +183,7 @@ struct lc_pipeline {
     logtail::ProcessorPipelineGpu impl;
 };
 extern "C" int lc_pipeline_create(const char* config_json, lc_pipeline_t** out, char* err, size_t errcap) {
-    if (!config_json || !out) return LC_ERR_ARG;
-    *out = nullptr;
-    lcjson::Value cfg;
-    try {
-        cfg = lcjson::parse(config_json);
-    } catch (const std::exception& e) {
-        setErr(err, errcap, e.what());
-        return LC_ERR_ARG;
-    }
-    auto p = std::make_unique<lc_pipeline>();
-    std::string error;
-    if (!p->impl.Init(cfg, error)) {
-        setErr(err, errcap, error);
-        return LC_ERR_SYNTAX;
-    }
-    setErr(err, errcap, "");
-    *out = p.release();
-    return LC_OK;
+    return logtail::createHandle(config_json, out, err, errcap);
 }
 extern "C" void lc_pipeline_destroy(lc_pipeline_t* p) { delete p; }
 extern "C" int lc_pipeline_is_fused(const lc_pipeline_t* p) { return p && p->impl.IsFused(); }
@@ -411,33 +379,23 @@ static int slotInit(processor_instance_t* ins, void* config, void* context) {
 #else
     const char* configText = static_cast<const char*>(config);
 #endif
-    // "Type": "processor_parse_delimiter_gpu" builds the delimiter parser, "processor_parse_timestamp_gpu" the timestamp processor;
-    // every other config builds the regex parser, as before
-    bool wantsDelimiter = false, wantsTimestamp = false;
+    // a config whose Type names an entry of kSlotTable builds that processor; every other config builds the regex parser, as before
+    std::string typeName;
     try {
         const lcjson::Value cfg = lcjson::parse(configText);
         const lcjson::Value* type = cfg.isObject() ? cfg.find("Type") : nullptr;
-        wantsDelimiter = type && type->isString() && type->str == "processor_parse_delimiter_gpu";
-        wantsTimestamp = type && type->isString() && type->str == "processor_parse_timestamp_gpu";
+        if (type && type->isString()) typeName = type->str;
     } catch (const std::exception&) {
     }
-    if (wantsDelimiter) {
-        if (!lcDelimiterSlotInit) {
-            std::fprintf(stderr, "[processor_parse_delimiter_gpu] this build of the plugin does not hold the delimiter parser\n");
+    for (const SlotEntry& entry : kSlotTable) {
+        if (typeName != entry.type) continue;
+        if (!entry.init) {
+            std::fprintf(stderr, "[%s] this build of the plugin does not hold the %s\n", entry.type, entry.label);
             return -1;
         }
         auto holder = std::make_unique<lc_processor>();
-        if (lcDelimiterSlotInit(configText, &holder->delimiter) != 0) return -1;
-        ins->plugin_state = holder.release();
-        return 0;
-    }
-    if (wantsTimestamp) {
-        if (!lcTimestampSlotInit) {
-            std::fprintf(stderr, "[processor_parse_timestamp_gpu] this build of the plugin does not hold the timestamp processor\n");
-            return -1;
-        }
-        auto holder = std::make_unique<lc_processor>();
-        if (lcTimestampSlotInit(configText, &holder->timestamp) != 0) return -1;
+        if (entry.init(configText, &holder->other) != 0) return -1;
+        holder->entry = &entry;
         ins->plugin_state = holder.release();
         return 0;
     }
@@ -457,21 +415,14 @@ static int slotInit(processor_instance_t* ins, void* config, void* context) {
 }
 static void slotFinalize(void* state) {
     lc_processor_t* p = static_cast<lc_processor_t*>(state);
-    if (p && p->delimiter) lcDelimiterSlotFinalize(p->delimiter);
-    if (p && p->timestamp) lcTimestampSlotFinalize(p->timestamp);
+    if (p && p->entry) p->entry->finalize(p->other);
     lc_processor_destroy(p);
 }
 static void slotProcess(void* state, void* logGroup) {
     if (!state || !logGroup) return;
-    if (static_cast<lc_processor_t*>(state)->delimiter) {
-        lcDelimiterSlotProcess(static_cast<lc_processor_t*>(state)->delimiter, logGroup);
-        return;
-    }
-    if (static_cast<lc_processor_t*>(state)->timestamp) {
-        lcTimestampSlotProcess(static_cast<lc_processor_t*>(state)->timestamp, logGroup);
-        return;
-    }
-    processGroup(static_cast<lc_processor_t*>(state), *static_cast<PipelineEventGroup*>(logGroup));
+    lc_processor_t* p = static_cast<lc_processor_t*>(state);
+    if (p->entry) p->entry->process(p->other, logGroup);
+    else processGroup(p, *static_cast<PipelineEventGroup*>(logGroup));
 }
 
 extern "C" {

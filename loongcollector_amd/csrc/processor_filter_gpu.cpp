@@ -7,6 +7,7 @@
 
 #include "../../include/lc_processor.h"
 #include "../../include/lc_regex_gpu.h"
+#include "parse_processor_shell.hpp"  // createHandle
 #include "regex_handle.hpp"
 #include "trip_buffers.hpp"
 
@@ -422,27 +423,7 @@ struct lc_filter {
 };
 
 extern "C" int lc_filter_create(const char* config_json, lc_filter_t** out, char* err, size_t errcap) {
-    if (!config_json || !out) return LC_ERR_ARG;
-    *out = nullptr;
-    auto set = [&](const std::string& m) {
-        if (err && errcap) std::snprintf(err, errcap, "%s", m.c_str());
-    };
-    lcjson::Value cfg;
-    try {
-        cfg = lcjson::parse(config_json);
-    } catch (const std::exception& e) {
-        set(e.what());
-        return LC_ERR_ARG;
-    }
-    auto f = std::make_unique<lc_filter>();
-    std::string error;
-    if (!f->impl.Init(cfg, error)) {
-        set(error);
-        return LC_ERR_SYNTAX;
-    }
-    set("");
-    *out = f.release();
-    return LC_OK;
+    return logtail::createHandle(config_json, out, err, errcap);
 }
 extern "C" void lc_filter_destroy(lc_filter_t* f) { delete f; }
 extern "C" int lc_filter_mode(const lc_filter_t* f) { return f ? int(f->impl.mFilterMode) : -1; }

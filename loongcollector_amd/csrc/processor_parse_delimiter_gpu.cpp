@@ -4,7 +4,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <memory>
 
 namespace logtail {
 
@@ -12,54 +11,13 @@ const std::string ProcessorParseDelimiterGpu::sName = "processor_parse_delimiter
 const std::string ProcessorParseDelimiterGpu::s_mDiscardedFieldKey = "_";
 
 namespace {
-// GetMandatoryStringParam / GetOptional*Param / GetMandatoryListParam (core/common/ParamExtractor.cpp:31-43,101-113,174-188,
-// ParamExtractor.h:162-342)
-bool mandatoryString(const lcjson::Value& cfg, const std::string& key, std::string& out, std::string& err) {
-    const lcjson::Value* v = cfg.find(key);
-    if (!v) {
-        err = "mandatory param " + key + " is missing";
-        return false;
-    }
-    if (!v->isString()) {
-        err = "param " + key + " is not of type string";
-        return false;
-    }
-    out = v->str;
-    if (out.empty()) {
-        err = "mandatory string param " + key + " is empty";
-        return false;
-    }
-    return true;
-}
-bool optionalString(const lcjson::Value& cfg, const std::string& key, std::string& out, std::string& err) {
-    const lcjson::Value* v = cfg.find(key);
-    if (v) {
-        if (!v->isString()) {
-            err = "param " + key + " is not of type string";
-            return false;
-        }
-        out = v->str;
-    }
-    return true;
-}
-bool optionalBool(const lcjson::Value& cfg, const std::string& key, bool& out, std::string& err) {
-    const lcjson::Value* v = cfg.find(key);
-    if (v) {
-        if (!v->isBool()) {
-            err = "param " + key + " is not of type bool";
-            return false;
-        }
-        out = v->b;
-    }
-    return true;
-}
-
 // one runner thread's scratch for Process()
 struct ProcessScratch {
     std::vector<uint8_t> kind, status, status2;
-    std::vector<const uint8_t*> linePtr, linePtr2;
-    std::vector<uint32_t> lineLen, lineLen2, ncols, ncols2, second;
+    std::vector<const uint8_t*> linePtr;
+    std::vector<uint32_t> lineLen, ncols, ncols2;
     std::vector<int32_t> spans, spans2;
+    SecondTrip mopUp;
 };
 }  // namespace
 
@@ -97,30 +55,7 @@ bool ProcessorParseDelimiterGpu::Init(const lcjson::Value& config, std::string& 
     } else if (!quoteStr.empty()) {
         mInitWarnings.push_back("string param Quote is not allowed when param Separator is not a single char");
     }
-    // Keys :111-126
-    {
-        const lcjson::Value* keys = config.find("Keys");
-        if (!keys) {
-            error = "mandatory param Keys is missing";
-            return false;
-        }
-        if (!keys->isArray()) {
-            error = "param Keys is not of type list";
-            return false;
-        }
-        mKeys.clear();
-        for (const auto& k : keys->arr) {
-            if (!k.isString()) {
-                error = "element in list param Keys is not of type string";
-                return false;
-            }
-            mKeys.push_back(k.str);
-        }
-        if (mKeys.empty()) {
-            error = "mandatory list param Keys is empty";
-            return false;
-        }
-    }
+    if (!mandatoryStringList(config, "Keys", "element in list param Keys is not of type string", mKeys, error)) return false;  // :111-126
     mSourceKeyOverwritten = false;
     for (const auto& key : mKeys)
         if (key == mSourceKey) mSourceKeyOverwritten = true;
@@ -148,16 +83,6 @@ bool ProcessorParseDelimiterGpu::Init(const lcjson::Value& config, std::string& 
         return false;
     }
     return true;
-}
-
-// :411-419
-void ProcessorParseDelimiterGpu::AddLog(const StringView& key, const StringView& value, LogEvent& targetEvent, bool overwritten) {
-    if (!overwritten && targetEvent.HasContent(key)) return;
-    targetEvent.SetContentNoCopy(key, value);
-}
-
-void ProcessorParseDelimiterGpu::RaiseAlarm(int kind, const std::string& message) const {
-    if (mAlarmSink) mAlarmSink(mAlarmUser, kind, message.data(), message.size());
 }
 
 StringView ProcessorParseDelimiterGpu::ColumnValue(LogEvent& ev, StringView raw, int32_t begin, int32_t end) const {
@@ -236,16 +161,7 @@ bool ProcessorParseDelimiterGpu::FinishEvent(LogEvent& ev, StringView raw, uint8
     } else {
         ++tally.outFailed;
     }
-    // :350-363
-    if (!parseSuccess || !mSourceKeyOverwritten) ev.DelContent(mSourceKey);
-    if (mCommonParserOptions.ShouldAddSourceContent(parseSuccess)) AddLog(mCommonParserOptions.mRenamedSourceKey, raw, ev, false);
-    if (mCommonParserOptions.ShouldAddLegacyUnmatchedRawLog(parseSuccess))
-        AddLog(GpuCommonParserOptions::legacyUnmatchedRawLogKey, raw, ev, false);
-    if (mCommonParserOptions.ShouldEraseEvent(parseSuccess, ev, metadata)) {
-        ++tally.discarded;
-        return false;
-    }
-    return true;
+    return FinishSourceKey(ev, raw, parseSuccess, mSourceKeyOverwritten, mCommonParserOptions, metadata, tally);  // :350-363
 }
 
 // Process :186-204 + ProcessEvent :206-282, restructured as gather -> device trip(s) -> stitch
@@ -253,30 +169,13 @@ int ProcessorParseDelimiterGpu::Process(PipelineEventGroup& logGroup) {
     if (logGroup.GetEvents().empty()) return LC_OK;
     EventsContainer& events = logGroup.MutableEvents();
     const GroupMetadata& metadata = logGroup.GetAllMetadata();
-    const size_t nEvents = events.size();
-    enum Kind : uint8_t { Keep, Parse };
     static thread_local ProcessScratch tScratch;
     ProcessScratch& S = tScratch;
-    S.kind.assign(nEvents, Keep);
-    S.linePtr.clear();
-    S.lineLen.clear();
+    SecondTrip& T = S.mopUp;
     Tally tally;
-    for (size_t i = 0; i < nEvents; ++i) {
-        PipelineEventPtr& e = events[i];
-        if (!e.Is<LogEvent>()) {  // :209-212
-            ++tally.outFailed;
-            continue;
-        }
-        LogEvent& ev = e.Cast<LogEvent>();
-        if (!ev.HasContent(mSourceKey)) {  // :214-217
-            ++tally.keyNotFound;
-            continue;
-        }
-        const StringView raw = ev.GetContent(mSourceKey);
-        S.kind[i] = Parse;
-        S.linePtr.push_back(reinterpret_cast<const uint8_t*>(raw.data()));
-        S.lineLen.push_back(uint32_t(raw.size()));
-    }
+    const Gathered gathered = gatherSourceValues(events, mSourceKey, S.kind, S.linePtr, S.lineLen);  // :209-217
+    tally.outFailed = gathered.notLogEvent;
+    tally.keyNotFound = gathered.noSourceKey;
     const uint32_t nLines = uint32_t(S.linePtr.size());
     const size_t K = mKeys.size();
     const bool extend = mOverflowedFieldsTreatment == OverflowedFieldsTreatment::EXTEND;
@@ -284,75 +183,44 @@ int ProcessorParseDelimiterGpu::Process(PipelineEventGroup& logGroup) {
     const uint32_t W = mFirstTripColumns ? mFirstTripColumns : uint32_t(extend ? K + 10 : K + 1);
     // what the stitch reads of a line with n columns: all of them, except in discard mode (the keys' columns only, :335-337)
     const bool discard = mOverflowedFieldsTreatment == OverflowedFieldsTreatment::DISCARD;
-    uint32_t W2 = 0;
     if (nLines) {
         S.status.resize(nLines);
         S.ncols.resize(nLines);
         S.spans.resize(size_t(nLines) * W * 2);
         int rc = lc_delim_split_host(mDelim, S.linePtr.data(), S.lineLen.data(), nLines, W, S.status.data(), S.ncols.data(), S.spans.data());
-        S.second.assign(nLines, UINT32_MAX);
-        if (rc == LC_OK) {
-            // the mop-up: the kernel always reports the TRUE count, so the lines that did not fit take ONE second trip with room for
-            // the widest of them
-            S.linePtr2.clear();
-            S.lineLen2.clear();
-            for (uint32_t li = 0; li < nLines; ++li) {
-                const uint32_t needed = discard && S.ncols[li] > K ? uint32_t(K) : S.ncols[li];
-                if (S.status[li] == LC_DELIM_OK && needed > W) {
-                    S.second[li] = uint32_t(S.linePtr2.size());
-                    S.linePtr2.push_back(S.linePtr[li]);
-                    S.lineLen2.push_back(S.lineLen[li]);
-                    W2 = S.ncols[li] > W2 ? S.ncols[li] : W2;
-                }
-            }
-            if (!S.linePtr2.empty()) {
-                const uint32_t n2 = uint32_t(S.linePtr2.size());
-                S.status2.resize(n2);
-                S.ncols2.resize(n2);
-                S.spans2.resize(size_t(n2) * W2 * 2);
-                rc = lc_delim_split_host(mDelim, S.linePtr2.data(), S.lineLen2.data(), n2, W2, S.status2.data(), S.ncols2.data(), S.spans2.data());
-                mMopUpLinesTotal += n2;
-            }
-        }
+        if (rc == LC_OK)
+            rc = runSecondTrip(S.linePtr, S.lineLen, S.status.data(), LC_DELIM_OK, S.ncols.data(), W,
+                               [&](uint32_t li) { return discard && S.ncols[li] > K ? uint32_t(K) : S.ncols[li]; }, T, mMopUpLinesTotal,
+                               [&](const SecondTrip& t) {
+                                   const uint32_t n2 = uint32_t(t.linePtr.size());
+                                   S.status2.resize(n2);
+                                   S.ncols2.resize(n2);
+                                   S.spans2.resize(size_t(n2) * t.W * 2);
+                                   return lc_delim_split_host(mDelim, t.linePtr.data(), t.lineLen.data(), n2, t.W, S.status2.data(),
+                                                              S.ncols2.data(), S.spans2.data());
+                               });
         if (rc != LC_OK) {
-            // no CPU path: the events stay exactly as they came in, and the failure is said loudly
-            const std::string message = "GPU split failed (rc=" + std::to_string(rc) + ": " + lc_last_error() + "); " + std::to_string(nLines) +
-                                        " events left unparsed";
-            if (mAlarmSink) RaiseAlarm(3, message);
-            else std::fprintf(stderr, "[%s] %s\n", sName.c_str(), message.c_str());
-            mDeviceFailedEventsTotal += nLines;
             mOutFailedEventsTotal += tally.outFailed;
             mOutKeyNotFoundEventsTotal += tally.keyNotFound;
-            return rc;
+            return ReportFailedTrip(sName, "split", "unparsed", rc, nLines);
         }
     }
     // stitch + in-place compaction (:193-202)
-    size_t wIdx = 0, line = 0;
-    for (size_t rIdx = 0; rIdx < nEvents; ++rIdx) {
-        bool keep = true;
-        if (S.kind[rIdx] == Parse) {
-            const size_t li = line++;
-            LogEvent& ev = events[rIdx].Cast<LogEvent>();
-            const StringView raw(reinterpret_cast<const char*>(S.linePtr[li]), S.lineLen[li]);
-            if (S.status[li] == LC_DELIM_BLANK) {
-                ++tally.outFailed;  // :220-224, :239-242: nothing behind the trim -- counted, and the event goes on as it came
-            } else if (S.second[li] != UINT32_MAX) {
-                const uint32_t l2 = S.second[li];
-                keep = FinishEvent(ev, raw, S.status2[l2], S.ncols2[l2], &S.spans2[size_t(l2) * W2 * 2], metadata, tally);
-            } else {
-                keep = FinishEvent(ev, raw, S.status[li], S.ncols[li], &S.spans[li * W * 2], metadata, tally);
-            }
+    size_t line = 0;
+    compactEvents(events, [&](size_t i) {
+        if (S.kind[i] != kToParse) return true;
+        const size_t li = line++;
+        LogEvent& ev = events[i].Cast<LogEvent>();
+        const StringView raw(reinterpret_cast<const char*>(S.linePtr[li]), S.lineLen[li]);
+        if (S.status[li] == LC_DELIM_BLANK) {
+            ++tally.outFailed;  // :220-224, :239-242: nothing behind the trim -- counted, and the event goes on as it came
+            return true;
         }
-        if (keep) {
-            if (wIdx != rIdx) events[wIdx] = std::move(events[rIdx]);
-            ++wIdx;
-        }
-    }
-    events.resize(wIdx);
-    if (tally.discarded) mDiscardedEventsTotal += tally.discarded;
-    if (tally.outFailed) mOutFailedEventsTotal += tally.outFailed;
-    if (tally.keyNotFound) mOutKeyNotFoundEventsTotal += tally.keyNotFound;
-    if (tally.outSuccessful) mOutSuccessfulEventsTotal += tally.outSuccessful;
+        const uint32_t l2 = T.second[li];
+        if (l2 != UINT32_MAX) return FinishEvent(ev, raw, S.status2[l2], S.ncols2[l2], &S.spans2[size_t(l2) * T.W * 2], metadata, tally);
+        return FinishEvent(ev, raw, S.status[li], S.ncols[li], &S.spans[li * W * 2], metadata, tally);
+    });
+    AddTally(tally);
     return LC_OK;
 }
 
@@ -362,77 +230,27 @@ int ProcessorParseDelimiterGpu::Process(PipelineEventGroup& logGroup) {
 using logtail::PipelineEventGroup;
 using logtail::ProcessorParseDelimiterGpu;
 
-struct lc_delimiter_processor {
-    ProcessorParseDelimiterGpu impl;
-    // what ProcessorInstance adds around every plugin (ProcessorInstance.cpp:46-63)
-    std::atomic<uint64_t> inEvents{0}, outEvents{0}, inBytes{0}, outBytes{0};
-};
+struct lc_delimiter_processor : logtail::ProcessorHandle<ProcessorParseDelimiterGpu> {};
 
 extern "C" int lc_delimiter_processor_create(const char* config_json, lc_delimiter_processor_t** out, char* err, size_t errcap) {
-    if (!config_json || !out) return LC_ERR_ARG;
-    *out = nullptr;
-    auto setErr = [&](const std::string& m) {
-        if (err && errcap) std::snprintf(err, errcap, "%s", m.c_str());
-    };
-    lcjson::Value cfg;
-    try {
-        cfg = lcjson::parse(config_json);
-    } catch (const std::exception& e) {
-        setErr(e.what());
-        return LC_ERR_ARG;
-    }
-    auto p = std::make_unique<lc_delimiter_processor>();
-    std::string error;
-    if (!p->impl.Init(cfg, error)) {
-        setErr(error);
-        return LC_ERR_SYNTAX;
-    }
-    setErr("");
-    *out = p.release();
-    return LC_OK;
+    return logtail::createHandle(config_json, out, err, errcap);
 }
 extern "C" void lc_delimiter_processor_destroy(lc_delimiter_processor_t* p) { delete p; }
-extern "C" char* lc_delimiter_processor_warnings(const lc_delimiter_processor_t* p) {
-    std::string s;
-    if (p)
-        for (const std::string& w : p->impl.mInitWarnings) s += w + "\n";
-    char* out = static_cast<char*>(std::malloc(s.size() + 1));
-    if (out) std::memcpy(out, s.c_str(), s.size() + 1);
-    return out;
-}
+extern "C" char* lc_delimiter_processor_warnings(const lc_delimiter_processor_t* p) { return logtail::warningsText(p); }
 extern "C" int lc_delimiter_processor_process_native(lc_delimiter_processor_t* p, void* native_group) {
-    if (!p || !native_group) return LC_ERR_ARG;
-    PipelineEventGroup& group = *static_cast<PipelineEventGroup*>(native_group);
-    p->inEvents += group.GetEvents().size();
-    p->inBytes += group.DataSize();
-    const int rc = p->impl.Process(group);
-    p->outEvents += group.GetEvents().size();
-    p->outBytes += group.DataSize();
-    return rc;
+    return logtail::processNative(p, native_group);
 }
 #ifndef LC_USE_REFERENCE_HEADERS
 extern "C" void* lc_group_native(lc_event_group_t* g);
 extern "C" int lc_delimiter_processor_process(lc_delimiter_processor_t* p, lc_event_group_t* group) {
-    if (!p || !group) return LC_ERR_ARG;
-    return lc_delimiter_processor_process_native(p, lc_group_native(group));
+    return p && group ? logtail::processNative(p, lc_group_native(group)) : LC_ERR_ARG;
 }
 #endif
 extern "C" void lc_delimiter_processor_set_first_trip_columns(lc_delimiter_processor_t* p, uint32_t columns) {
     if (p) p->impl.mFirstTripColumns = columns;
 }
 extern "C" int lc_delimiter_processor_counters(const lc_delimiter_processor_t* p, uint64_t out[LC_CNT_COUNT]) {
-    if (!p || !out) return LC_ERR_ARG;
-    for (int i = 0; i < LC_CNT_COUNT; ++i) out[i] = 0;
-    out[LC_CNT_DISCARDED_EVENTS] = p->impl.mDiscardedEventsTotal;
-    out[LC_CNT_OUT_FAILED_EVENTS] = p->impl.mOutFailedEventsTotal;
-    out[LC_CNT_OUT_KEY_NOT_FOUND] = p->impl.mOutKeyNotFoundEventsTotal;
-    out[LC_CNT_OUT_SUCCESSFUL_EVENTS] = p->impl.mOutSuccessfulEventsTotal;
-    out[LC_CNT_IN_EVENTS] = p->inEvents;
-    out[LC_CNT_OUT_EVENTS] = p->outEvents;
-    out[LC_CNT_IN_SIZE_BYTES] = p->inBytes;
-    out[LC_CNT_OUT_SIZE_BYTES] = p->outBytes;
-    out[LC_CNT_DEVICE_FAILED_EVENTS] = p->impl.mDeviceFailedEventsTotal;
-    return LC_OK;
+    return logtail::fillCounters(p, out, true);
 }
 extern "C" void lc_delimiter_processor_set_alarm_sink(lc_delimiter_processor_t* p, lc_alarm_sink_t sink, void* user) {
     if (p) p->impl.SetAlarmSink(sink, user);
@@ -440,16 +258,9 @@ extern "C" void lc_delimiter_processor_set_alarm_sink(lc_delimiter_processor_t* 
 
 // ---- the plugin slot's way to this processor (c_processor_slot.cpp: a config whose Type is processor_parse_delimiter_gpu)
 extern "C" int lcDelimiterSlotInit(const char* config_text, void** state) {
-    lc_delimiter_processor_t* p = nullptr;
-    char err[256];
-    if (lc_delimiter_processor_create(config_text, &p, err, sizeof err) != LC_OK) {
-        std::fprintf(stderr, "[processor_parse_delimiter_gpu] init failed: %s\n", err);
-        return -1;
-    }
-    *state = p;
-    return 0;
+    return logtail::slotInitHandle(&lc_delimiter_processor_create, ProcessorParseDelimiterGpu::sName, config_text, state);
 }
 extern "C" void lcDelimiterSlotProcess(void* state, void* native_group) {
-    (void)lc_delimiter_processor_process_native(static_cast<lc_delimiter_processor_t*>(state), native_group);
+    (void)logtail::processNative(static_cast<lc_delimiter_processor_t*>(state), native_group);
 }
-extern "C" void lcDelimiterSlotFinalize(void* state) { lc_delimiter_processor_destroy(static_cast<lc_delimiter_processor_t*>(state)); }
+extern "C" void lcDelimiterSlotFinalize(void* state) { delete static_cast<lc_delimiter_processor_t*>(state); }

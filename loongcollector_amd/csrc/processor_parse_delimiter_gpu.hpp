@@ -15,11 +15,11 @@
 #include <vector>
 
 #include "../../include/lc_delimiter.h"
-#include "processor_parse_regex_gpu.hpp"  // the event model, json_min, GpuCommonParserOptions
+#include "parse_processor_shell.hpp"  // the event model, json_min, GpuCommonParserOptions, ParseProcessorBase
 
 namespace logtail {
 
-class ProcessorParseDelimiterGpu {
+class ProcessorParseDelimiterGpu : public ParseProcessorBase {
 public:
     static const std::string sName;                 // "processor_parse_delimiter_gpu"
     static const std::string s_mDiscardedFieldKey;  // "_"
@@ -32,7 +32,6 @@ public:
     // LC_OK, or the LC_ERR_* code of a failed device trip (the group is then untouched)
     int Process(PipelineEventGroup& logGroup);
 
-    std::string mSourceKey;
     std::string mSeparator;
     char mSeparatorChar = '\0';
     char mQuote = '"';
@@ -42,37 +41,22 @@ public:
     bool mExtractingPartialFields = false;
     GpuCommonParserOptions mCommonParserOptions;
 
-    // plugin counters (:178-181)
-    std::atomic<uint64_t> mDiscardedEventsTotal{0}, mOutFailedEventsTotal{0}, mOutKeyNotFoundEventsTotal{0}, mOutSuccessfulEventsTotal{0};
-    std::atomic<uint64_t> mDeviceFailedEventsTotal{0};  // no reference counterpart: events passed on unparsed behind a failed trip
-    std::atomic<uint64_t> mMopUpLinesTotal{0};          // no reference counterpart: lines that took the second trip
-    std::vector<std::string> mInitWarnings;
+    // (the plugin counters of :178-181 are ParseProcessorBase's)
+    std::atomic<uint64_t> mMopUpLinesTotal{0};  // no reference counterpart: lines that took the second trip
     // W of the first trip; 0 = the reference's reserve (:244-245).  Not a config key: lc_delimiter_processor_set_first_trip_columns
     // (set before the first Process; results do not depend on it, only how many lines take the second trip)
     uint32_t mFirstTripColumns = 0;
 
-    // kind 0 "parse delimiter log fail, logs:<line>" (:303-309), kind 2 "keys count unmatch columns count :<n>, required:<k>,
-    // logs:<line>" (:292-299), kind 4 "no column keys defined" (:313-318), kind 3: a failed device trip
-    using AlarmSink = void (*)(void* user, int kind, const char* message, size_t len);
-    void SetAlarmSink(AlarmSink sink, void* user) {
-        mAlarmSink = sink;
-        mAlarmUser = user;
-    }
+    // alarms (SetAlarmSink): kind 0 "parse delimiter log fail, logs:<line>" (:303-309), kind 2 "keys count unmatch columns count :<n>,
+    // required:<k>, logs:<line>" (:292-299), kind 4 "no column keys defined" (:313-318), kind 3: a failed device trip
 
 private:
-    struct Tally {
-        uint64_t discarded = 0, outFailed = 0, keyNotFound = 0, outSuccessful = 0;
-    };
-    void AddLog(const StringView& key, const StringView& value, LogEvent& targetEvent, bool overwritten = true);
     // one column's value: a view of the line, or its un-doubled copy in the group's SourceBuffer (AddFieldWithUnQuote :83-113)
     StringView ColumnValue(LogEvent& ev, StringView raw, int32_t begin, int32_t end) const;
     // :284-363 for one event whose line the device has split; false: the event is erased
     bool FinishEvent(LogEvent& ev, StringView raw, uint8_t status, uint32_t ncols, const int32_t* spans, const GroupMetadata& metadata,
                      Tally& tally);
-    void RaiseAlarm(int kind, const std::string& message) const;
 
-    AlarmSink mAlarmSink = nullptr;
-    void* mAlarmUser = nullptr;
     bool mSourceKeyOverwritten = false;
     bool mUseQuote = false;
     lc_delim_t* mDelim = nullptr;

@@ -4,7 +4,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <memory>
 
 namespace logtail {
 
@@ -14,44 +13,22 @@ namespace {
 // one runner thread's scratch for Process()
 struct ProcessScratch {
     std::vector<uint8_t> kind, status, status2, shadow, shadow2;
-    std::vector<const uint8_t*> linePtr, linePtr2;
-    std::vector<uint32_t> lineLen, lineLen2, nmembers, nmembers2, errpos, errpos2, second;
+    std::vector<const uint8_t*> linePtr;
+    std::vector<uint32_t> lineLen, nmembers, nmembers2, errpos, errpos2;
     std::vector<size_t> shadowAt, shadowAt2;
     std::vector<lc_json_member_t> records, records2;
+    SecondTrip mopUp;
 };
 }  // namespace
 
-// ProcessorParseJsonNative::Init :44-84; GetMandatoryStringParam core/common/ParamExtractor.cpp:174-188
+// ProcessorParseJsonNative::Init :44-84
 bool ProcessorParseJsonGpu::Init(const lcjson::Value& config, std::string& error) {
     if (!config.isObject()) {
         error = "plugin config is not an object";
         return false;
     }
-    const lcjson::Value* v = config.find("SourceKey");  // :48-57
-    if (!v) {
-        error = "mandatory param SourceKey is missing";
-        return false;
-    }
-    if (!v->isString()) {
-        error = "param SourceKey is not of type string";
-        return false;
-    }
-    mSourceKey = v->str;
-    if (mSourceKey.empty()) {
-        error = "mandatory string param SourceKey is empty";
-        return false;
-    }
-    return mCommonParserOptions.Init(config, mInitWarnings);  // :59-61
-}
-
-// :469-477
-void ProcessorParseJsonGpu::AddLog(const StringView& key, const StringView& value, LogEvent& targetEvent, bool overwritten) {
-    if (!overwritten && targetEvent.HasContent(key)) return;
-    targetEvent.SetContentNoCopy(key, value);
-}
-
-void ProcessorParseJsonGpu::RaiseAlarm(int kind, const std::string& message) const {
-    if (mAlarmSink) mAlarmSink(mAlarmUser, kind, message.data(), message.size());
+    if (!mandatoryString(config, "SourceKey", mSourceKey, error)) return false;  // :48-57
+    return mCommonParserOptions.Init(config, mInitWarnings);                     // :59-61
 }
 
 // ProcessEvent :122-144 behind the parse; shadow: the line's own unescaped bytes
@@ -104,15 +81,7 @@ bool ProcessorParseJsonGpu::FinishEvent(LogEvent& ev, StringView raw, uint8_t st
         RaiseAlarm(0, "parse json fail:" + std::string(raw.data(), raw.size()));
         ++tally.outFailed;
     }
-    // :130-144
-    if (!parseSuccess || !sourceKeyOverwritten) ev.DelContent(mSourceKey);
-    if (mCommonParserOptions.ShouldAddSourceContent(parseSuccess)) AddLog(mCommonParserOptions.mRenamedSourceKey, raw, ev, false);
-    if (mCommonParserOptions.ShouldAddLegacyUnmatchedRawLog(parseSuccess))
-        AddLog(GpuCommonParserOptions::legacyUnmatchedRawLogKey, raw, ev, false);
-    if (mCommonParserOptions.ShouldEraseEvent(parseSuccess, ev, metadata)) {
-        ++tally.discarded;
-        return false;
-    }
+    if (!FinishSourceKey(ev, raw, parseSuccess, sourceKeyOverwritten, mCommonParserOptions, metadata, tally)) return false;  // :130-144
     ++tally.outSuccessful;  // (:143: every event that goes on, parsed or not)
     return true;
 }
@@ -122,114 +91,56 @@ int ProcessorParseJsonGpu::Process(PipelineEventGroup& logGroup) {
     if (logGroup.GetEvents().empty()) return LC_OK;
     EventsContainer& events = logGroup.MutableEvents();
     const GroupMetadata& metadata = logGroup.GetAllMetadata();
-    const size_t nEvents = events.size();
-    enum Kind : uint8_t { Keep, Parse };
     static thread_local ProcessScratch tScratch;
     ProcessScratch& S = tScratch;
-    S.kind.assign(nEvents, Keep);
-    S.linePtr.clear();
-    S.lineLen.clear();
-    S.shadowAt.clear();
+    SecondTrip& T = S.mopUp;
     Tally tally;
-    size_t totalBytes = 0;
-    for (size_t i = 0; i < nEvents; ++i) {
-        PipelineEventPtr& e = events[i];
-        if (!e.Is<LogEvent>()) {  // :110-113
-            ++tally.outFailed;
-            continue;
-        }
-        LogEvent& ev = e.Cast<LogEvent>();
-        if (!ev.HasContent(mSourceKey)) {  // :115-118
-            ++tally.keyNotFound;
-            continue;
-        }
-        const StringView raw = ev.GetContent(mSourceKey);
-        S.kind[i] = Parse;
-        S.linePtr.push_back(reinterpret_cast<const uint8_t*>(raw.data()));
-        S.lineLen.push_back(uint32_t(raw.size()));
-        S.shadowAt.push_back(totalBytes);
-        totalBytes += raw.size();
-    }
+    const Gathered gathered = gatherSourceValues(events, mSourceKey, S.kind, S.linePtr, S.lineLen);  // :110-118
+    tally.outFailed = gathered.notLogEvent;
+    tally.keyNotFound = gathered.noSourceKey;
     const uint32_t nLines = uint32_t(S.linePtr.size());
     const uint32_t W = mFirstTripMembers ? mFirstTripMembers : 32u;  // :309
-    uint32_t W2 = 0;
     if (nLines) {
         S.status.resize(nLines);
         S.nmembers.resize(nLines);
         S.errpos.resize(nLines);
         S.records.resize(size_t(nLines) * W);
-        S.shadow.resize(totalBytes + 1);
+        S.shadow.resize(prefixSums(S.lineLen, S.shadowAt) + 1);
         uint64_t moved = 0, moved2 = 0;
         int rc = lc_json_walk_host(S.linePtr.data(), S.lineLen.data(), nLines, W, S.status.data(), S.nmembers.data(), S.errpos.data(),
                                    S.records.data(), S.shadow.data(), &moved);
-        S.second.assign(nLines, UINT32_MAX);
-        if (rc == LC_OK) {
-            // the mop-up: the kernel always reports the TRUE count, so the lines that did not fit take ONE second trip with room for
-            // the one with the most members
-            S.linePtr2.clear();
-            S.lineLen2.clear();
-            S.shadowAt2.clear();
-            size_t bytes2 = 0;
-            for (uint32_t li = 0; li < nLines; ++li) {
-                if (S.status[li] == LC_JSON_OK && S.nmembers[li] > W) {
-                    S.second[li] = uint32_t(S.linePtr2.size());
-                    S.linePtr2.push_back(S.linePtr[li]);
-                    S.lineLen2.push_back(S.lineLen[li]);
-                    S.shadowAt2.push_back(bytes2);
-                    bytes2 += S.lineLen[li];
-                    W2 = S.nmembers[li] > W2 ? S.nmembers[li] : W2;
-                }
-            }
-            if (!S.linePtr2.empty()) {
-                const uint32_t n2 = uint32_t(S.linePtr2.size());
-                S.status2.resize(n2);
-                S.nmembers2.resize(n2);
-                S.errpos2.resize(n2);
-                S.records2.resize(size_t(n2) * W2);
-                S.shadow2.resize(bytes2 + 1);
-                rc = lc_json_walk_host(S.linePtr2.data(), S.lineLen2.data(), n2, W2, S.status2.data(), S.nmembers2.data(), S.errpos2.data(),
-                                       S.records2.data(), S.shadow2.data(), &moved2);
-                mMopUpLinesTotal += n2;
-            }
-        }
+        if (rc == LC_OK)
+            rc = runSecondTrip(S.linePtr, S.lineLen, S.status.data(), LC_JSON_OK, S.nmembers.data(), W, [&](uint32_t li) { return S.nmembers[li]; },
+                               T, mMopUpLinesTotal, [&](const SecondTrip& t) {
+                                   const uint32_t n2 = uint32_t(t.linePtr.size());
+                                   S.status2.resize(n2);
+                                   S.nmembers2.resize(n2);
+                                   S.errpos2.resize(n2);
+                                   S.records2.resize(size_t(n2) * t.W);
+                                   S.shadow2.resize(prefixSums(t.lineLen, S.shadowAt2) + 1);
+                                   return lc_json_walk_host(t.linePtr.data(), t.lineLen.data(), n2, t.W, S.status2.data(), S.nmembers2.data(),
+                                                            S.errpos2.data(), S.records2.data(), S.shadow2.data(), &moved2);
+                               });
         if (rc != LC_OK) {
-            // no CPU path: the events stay exactly as they came in, and the failure is said loudly
-            const std::string message = "GPU JSON walk failed (rc=" + std::to_string(rc) + ": " + lc_last_error() + "); " + std::to_string(nLines) +
-                                        " events left unparsed";
-            if (mAlarmSink) RaiseAlarm(3, message);
-            else std::fprintf(stderr, "[%s] %s\n", sName.c_str(), message.c_str());
-            mDeviceFailedEventsTotal += nLines;
             mOutFailedEventsTotal += tally.outFailed;
             mOutKeyNotFoundEventsTotal += tally.keyNotFound;
-            return rc;
+            return ReportFailedTrip(sName, "JSON walk", "unparsed", rc, nLines);
         }
         mShadowBytesTotal += moved + moved2;
     }
     // stitch + in-place compaction (:95-104)
-    size_t wIdx = 0, line = 0;
-    for (size_t rIdx = 0; rIdx < nEvents; ++rIdx) {
-        bool keep = true;
-        if (S.kind[rIdx] == Parse) {
-            const size_t li = line++;
-            LogEvent& ev = events[rIdx].Cast<LogEvent>();
-            const StringView raw(reinterpret_cast<const char*>(S.linePtr[li]), S.lineLen[li]);
-            if (S.second[li] != UINT32_MAX) {
-                const uint32_t l2 = S.second[li];
-                keep = FinishEvent(ev, raw, S.status2[l2], S.nmembers2[l2], &S.records2[size_t(l2) * W2], S.shadow2.data() + S.shadowAt2[l2], metadata, tally);
-            } else {
-                keep = FinishEvent(ev, raw, S.status[li], S.nmembers[li], &S.records[li * W], S.shadow.data() + S.shadowAt[li], metadata, tally);
-            }
-        }
-        if (keep) {
-            if (wIdx != rIdx) events[wIdx] = std::move(events[rIdx]);
-            ++wIdx;
-        }
-    }
-    events.resize(wIdx);
-    if (tally.discarded) mDiscardedEventsTotal += tally.discarded;
-    if (tally.outFailed) mOutFailedEventsTotal += tally.outFailed;
-    if (tally.keyNotFound) mOutKeyNotFoundEventsTotal += tally.keyNotFound;
-    if (tally.outSuccessful) mOutSuccessfulEventsTotal += tally.outSuccessful;
+    size_t line = 0;
+    compactEvents(events, [&](size_t i) {
+        if (S.kind[i] != kToParse) return true;
+        const size_t li = line++;
+        LogEvent& ev = events[i].Cast<LogEvent>();
+        const StringView raw(reinterpret_cast<const char*>(S.linePtr[li]), S.lineLen[li]);
+        const uint32_t l2 = T.second[li];
+        if (l2 != UINT32_MAX)
+            return FinishEvent(ev, raw, S.status2[l2], S.nmembers2[l2], &S.records2[size_t(l2) * T.W], S.shadow2.data() + S.shadowAt2[l2], metadata, tally);
+        return FinishEvent(ev, raw, S.status[li], S.nmembers[li], &S.records[li * W], S.shadow.data() + S.shadowAt[li], metadata, tally);
+    });
+    AddTally(tally);
     return LC_OK;
 }
 
@@ -239,78 +150,24 @@ int ProcessorParseJsonGpu::Process(PipelineEventGroup& logGroup) {
 using logtail::PipelineEventGroup;
 using logtail::ProcessorParseJsonGpu;
 
-struct lc_json_processor {
-    ProcessorParseJsonGpu impl;
-    // what ProcessorInstance adds around every plugin (ProcessorInstance.cpp:46-63)
-    std::atomic<uint64_t> inEvents{0}, outEvents{0}, inBytes{0}, outBytes{0};
-};
+struct lc_json_processor : logtail::ProcessorHandle<ProcessorParseJsonGpu> {};
 
 extern "C" int lc_json_processor_create(const char* config_json, lc_json_processor_t** out, char* err, size_t errcap) {
-    if (!config_json || !out) return LC_ERR_ARG;
-    *out = nullptr;
-    auto setErr = [&](const std::string& m) {
-        if (err && errcap) std::snprintf(err, errcap, "%s", m.c_str());
-    };
-    lcjson::Value cfg;
-    try {
-        cfg = lcjson::parse(config_json);
-    } catch (const std::exception& e) {
-        setErr(e.what());
-        return LC_ERR_ARG;
-    }
-    auto p = std::make_unique<lc_json_processor>();
-    std::string error;
-    if (!p->impl.Init(cfg, error)) {
-        setErr(error);
-        return LC_ERR_SYNTAX;
-    }
-    setErr("");
-    *out = p.release();
-    return LC_OK;
+    return logtail::createHandle(config_json, out, err, errcap);
 }
 extern "C" void lc_json_processor_destroy(lc_json_processor_t* p) { delete p; }
-extern "C" char* lc_json_processor_warnings(const lc_json_processor_t* p) {
-    std::string s;
-    if (p)
-        for (const std::string& w : p->impl.mInitWarnings) s += w + "\n";
-    char* out = static_cast<char*>(std::malloc(s.size() + 1));
-    if (out) std::memcpy(out, s.c_str(), s.size() + 1);
-    return out;
-}
-extern "C" int lc_json_processor_process_native(lc_json_processor_t* p, void* native_group) {
-    if (!p || !native_group) return LC_ERR_ARG;
-    PipelineEventGroup& group = *static_cast<PipelineEventGroup*>(native_group);
-    p->inEvents += group.GetEvents().size();
-    p->inBytes += group.DataSize();
-    const int rc = p->impl.Process(group);
-    p->outEvents += group.GetEvents().size();
-    p->outBytes += group.DataSize();
-    return rc;
-}
+extern "C" char* lc_json_processor_warnings(const lc_json_processor_t* p) { return logtail::warningsText(p); }
+extern "C" int lc_json_processor_process_native(lc_json_processor_t* p, void* native_group) { return logtail::processNative(p, native_group); }
 #ifndef LC_USE_REFERENCE_HEADERS
 extern "C" void* lc_group_native(lc_event_group_t* g);
 extern "C" int lc_json_processor_process(lc_json_processor_t* p, lc_event_group_t* group) {
-    if (!p || !group) return LC_ERR_ARG;
-    return lc_json_processor_process_native(p, lc_group_native(group));
+    return p && group ? logtail::processNative(p, lc_group_native(group)) : LC_ERR_ARG;
 }
 #endif
 extern "C" void lc_json_processor_set_first_trip_members(lc_json_processor_t* p, uint32_t members) {
     if (p) p->impl.mFirstTripMembers = members;
 }
-extern "C" int lc_json_processor_counters(const lc_json_processor_t* p, uint64_t out[LC_CNT_COUNT]) {
-    if (!p || !out) return LC_ERR_ARG;
-    for (int i = 0; i < LC_CNT_COUNT; ++i) out[i] = 0;
-    out[LC_CNT_DISCARDED_EVENTS] = p->impl.mDiscardedEventsTotal;
-    out[LC_CNT_OUT_FAILED_EVENTS] = p->impl.mOutFailedEventsTotal;
-    out[LC_CNT_OUT_KEY_NOT_FOUND] = p->impl.mOutKeyNotFoundEventsTotal;
-    out[LC_CNT_OUT_SUCCESSFUL_EVENTS] = p->impl.mOutSuccessfulEventsTotal;
-    out[LC_CNT_IN_EVENTS] = p->inEvents;
-    out[LC_CNT_OUT_EVENTS] = p->outEvents;
-    out[LC_CNT_IN_SIZE_BYTES] = p->inBytes;
-    out[LC_CNT_OUT_SIZE_BYTES] = p->outBytes;
-    out[LC_CNT_DEVICE_FAILED_EVENTS] = p->impl.mDeviceFailedEventsTotal;
-    return LC_OK;
-}
+extern "C" int lc_json_processor_counters(const lc_json_processor_t* p, uint64_t out[LC_CNT_COUNT]) { return logtail::fillCounters(p, out, true); }
 extern "C" void lc_json_processor_set_alarm_sink(lc_json_processor_t* p, lc_alarm_sink_t sink, void* user) {
     if (p) p->impl.SetAlarmSink(sink, user);
 }

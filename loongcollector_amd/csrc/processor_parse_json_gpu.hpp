@@ -16,11 +16,11 @@
 #include <vector>
 
 #include "../../include/lc_json.h"
-#include "processor_parse_regex_gpu.hpp"  // the event model, json_min, GpuCommonParserOptions
+#include "parse_processor_shell.hpp"  // the event model, json_min, GpuCommonParserOptions, ParseProcessorBase
 
 namespace logtail {
 
-class ProcessorParseJsonGpu {
+class ProcessorParseJsonGpu : public ParseProcessorBase {
 public:
     static const std::string sName;  // "processor_parse_json_gpu"
 
@@ -30,38 +30,21 @@ public:
     // LC_OK, or the LC_ERR_* code of a failed device trip (the group is then untouched)
     int Process(PipelineEventGroup& logGroup);
 
-    std::string mSourceKey;
     GpuCommonParserOptions mCommonParserOptions;
 
-    // plugin counters (:78-81)
-    std::atomic<uint64_t> mDiscardedEventsTotal{0}, mOutFailedEventsTotal{0}, mOutKeyNotFoundEventsTotal{0}, mOutSuccessfulEventsTotal{0};
-    std::atomic<uint64_t> mDeviceFailedEventsTotal{0};  // no reference counterpart: events passed on unparsed behind a failed trip
-    std::atomic<uint64_t> mMopUpLinesTotal{0};          // no reference counterpart: lines that took the second trip
-    std::atomic<uint64_t> mShadowBytesTotal{0};         // no reference counterpart: unescaped bytes that came back from the device
-    std::vector<std::string> mInitWarnings;
+    // (the plugin counters of :78-81 are ParseProcessorBase's)
+    std::atomic<uint64_t> mMopUpLinesTotal{0};   // no reference counterpart: lines that took the second trip
+    std::atomic<uint64_t> mShadowBytesTotal{0};  // no reference counterpart: unescaped bytes that came back from the device
     // W of the first trip; 0 = 32, the reference's tempFields.reserve(32) (:309).  Not a config key:
     // lc_json_processor_set_first_trip_members (results do not depend on it, only how many lines take the second trip)
     uint32_t mFirstTripMembers = 0;
 
-    // kind 0 "parse json fail:<line>" (:278-283), kind 3: a failed device trip
-    using AlarmSink = void (*)(void* user, int kind, const char* message, size_t len);
-    void SetAlarmSink(AlarmSink sink, void* user) {
-        mAlarmSink = sink;
-        mAlarmUser = user;
-    }
+    // alarms (SetAlarmSink): kind 0 "parse json fail:<line>" (:278-283), kind 3: a failed device trip
 
 private:
-    struct Tally {
-        uint64_t discarded = 0, outFailed = 0, keyNotFound = 0, outSuccessful = 0;
-    };
-    void AddLog(const StringView& key, const StringView& value, LogEvent& targetEvent, bool overwritten = true);
     // :122-144 for one event whose line the device has walked; false: the event is erased
     bool FinishEvent(LogEvent& ev, StringView raw, uint8_t status, uint32_t nmembers, const lc_json_member_t* members, const uint8_t* shadow,
                      const GroupMetadata& metadata, Tally& tally);
-    void RaiseAlarm(int kind, const std::string& message) const;
-
-    AlarmSink mAlarmSink = nullptr;
-    void* mAlarmUser = nullptr;
 };
 
 }  // namespace logtail

@@ -3,6 +3,8 @@
 
 #include <cstdio>
 
+#include "parse_processor_shell.hpp"  // the config readers
+
 namespace logtail {
 
 const std::string ProcessorParseRegexGpu::sName = "processor_parse_regex_gpu";
@@ -12,47 +14,6 @@ namespace {
 const std::string kDefaultContentKey = "content";      // DEFAULT_CONTENT_KEY, core/constants/Constants.cpp:25
 const std::string kContainerTimeKey = "_time_";        // ProcessorParseContainerLogNative.cpp:41
 const std::string kContainerSourceKey = "_source_";    // ProcessorParseContainerLogNative.cpp:42
-
-// GetMandatoryStringParam / GetOptional*Param (core/common/ParamExtractor.cpp:31-43,101-113,174-188)
-bool mandatoryString(const lcjson::Value& cfg, const std::string& key, std::string& out, std::string& err) {
-    const lcjson::Value* v = cfg.find(key);
-    if (!v) {
-        err = "mandatory param " + key + " is missing";
-        return false;
-    }
-    if (!v->isString()) {
-        err = "param " + key + " is not of type string";
-        return false;
-    }
-    out = v->str;
-    if (out.empty()) {
-        err = "mandatory string param " + key + " is empty";
-        return false;
-    }
-    return true;
-}
-bool optionalBool(const lcjson::Value& cfg, const std::string& key, bool& out, std::string& err) {
-    const lcjson::Value* v = cfg.find(key);
-    if (v) {
-        if (!v->isBool()) {
-            err = "param " + key + " is not of type bool";
-            return false;
-        }
-        out = v->b;
-    }
-    return true;
-}
-bool optionalString(const lcjson::Value& cfg, const std::string& key, std::string& out, std::string& err) {
-    const lcjson::Value* v = cfg.find(key);
-    if (v) {
-        if (!v->isString()) {
-            err = "param " + key + " is not of type string";
-            return false;
-        }
-        out = v->str;
-    }
-    return true;
-}
 
 // One runner thread's scratch for Process(), reached with ONE thread-local lookup per call (a function-scope thread_local of class
 // type goes through an init-check wrapper at every use; inside the per-event loops that was measurable).
@@ -157,27 +118,7 @@ bool ProcessorParseRegexGpu::Init(const lcjson::Value& config, std::string& erro
     }
     // Keys :71-88 (mandatory, non-empty list of strings; legacy ["k1,k2"] form is split on ',')
     {
-        const lcjson::Value* keys = config.find("Keys");
-        if (!keys) {
-            error = "mandatory param Keys is missing";
-            return false;
-        }
-        if (!keys->isArray()) {
-            error = "param Keys is not of type list";
-            return false;
-        }
-        mKeys.clear();
-        for (const auto& k : keys->arr) {
-            if (!k.isString()) {
-                error = "param Keys is not of type string list";
-                return false;
-            }
-            mKeys.push_back(k.str);
-        }
-        if (mKeys.empty()) {
-            error = "mandatory list param Keys is empty";
-            return false;
-        }
+        if (!mandatoryStringList(config, "Keys", "param Keys is not of type string list", mKeys, error)) return false;
         if (mKeys.size() == 1 && mKeys[0].find(',') != std::string::npos) {
             std::vector<std::string> parts;
             size_t at = 0;

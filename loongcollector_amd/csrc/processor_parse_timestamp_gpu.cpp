@@ -6,7 +6,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
-#include <memory>
 
 #include "strptime_vm.hpp"
 
@@ -89,24 +88,6 @@ namespace logtail {
 const std::string ProcessorParseTimestampGpu::sName = "processor_parse_timestamp_gpu";
 
 namespace {
-// GetMandatoryStringParam / GetOptionalStringParam / GetOptionalIntParam (core/common/ParamExtractor.cpp)
-bool mandatoryString(const lcjson::Value& cfg, const std::string& key, std::string& out, std::string& err) {
-    const lcjson::Value* v = cfg.find(key);
-    if (!v) {
-        err = "mandatory param " + key + " is missing";
-        return false;
-    }
-    if (!v->isString()) {
-        err = "param " + key + " is not of type string";
-        return false;
-    }
-    out = v->str;
-    if (out.empty()) {
-        err = "mandatory string param " + key + " is empty";
-        return false;
-    }
-    return true;
-}
 // std::from_chars<int> over exactly two bytes (StringTo of core/common/StringTools.h)
 bool twoCharInt(const char* s, int& out) {
     const bool neg = s[0] == '-';
@@ -199,10 +180,6 @@ bool ProcessorParseTimestampGpu::Init(const lcjson::Value& config, std::string& 
     return true;
 }
 
-void ProcessorParseTimestampGpu::RaiseAlarm(int kind, const std::string& message) const {
-    if (mAlarmSink) mAlarmSink(mAlarmUser, kind, message.data(), message.size());
-}
-
 // Strptime() behind strptime_ns (TimeUtil.cpp:141-190)
 int64_t ProcessorParseTimestampGpu::LocalSeconds(uint8_t status, int64_t secs, int64_t now) const {
     if (status & LC_TS_EPOCH) return secs;  // mktime(localtime(t)) = t
@@ -250,26 +227,9 @@ int64_t ProcessorParseTimestampGpu::LocalSeconds(uint8_t status, int64_t secs, i
 int ProcessorParseTimestampGpu::Process(PipelineEventGroup& logGroup) {
     if (logGroup.GetEvents().empty() || mSourceFormat.empty() || mSourceKey.empty()) return LC_OK;
     EventsContainer& events = logGroup.MutableEvents();
-    const size_t nEvents = events.size();
-    enum Kind : uint8_t { Unsupported, NoKey, Parse };
     static thread_local ProcessScratch tScratch;
     ProcessScratch& S = tScratch;
-    S.kind.assign(nEvents, Unsupported);
-    S.ptr.clear();
-    S.len.clear();
-    for (size_t i = 0; i < nEvents; ++i) {
-        PipelineEventPtr& e = events[i];
-        if (!e.Is<LogEvent>()) continue;
-        LogEvent& ev = e.Cast<LogEvent>();
-        if (!ev.HasContent(mSourceKey)) {
-            S.kind[i] = NoKey;
-            continue;
-        }
-        const StringView v = ev.GetContent(mSourceKey);
-        S.kind[i] = Parse;
-        S.ptr.push_back(reinterpret_cast<const uint8_t*>(v.data()));
-        S.len.push_back(uint32_t(v.size()));
-    }
+    gatherSourceValues(events, mSourceKey, S.kind, S.ptr, S.len);  // (the walk below counts the events without a value as it meets them)
     const uint32_t nValues = uint32_t(S.ptr.size());
     if (nValues) {
         S.status.resize(nValues);
@@ -280,14 +240,7 @@ int ProcessorParseTimestampGpu::Process(PipelineEventGroup& logGroup) {
         S.fracLen.resize(nValues);
         const lc_ts_out_t out{S.status.data(), S.secs.data(), S.nanos.data(), S.matched.data(), S.fracLen.data(), S.same.data()};
         const int rc = lc_strptime_parse_host(mStrptime, S.ptr.data(), S.len.data(), nValues, &out);
-        if (rc != LC_OK) {
-            const std::string message = "GPU timestamp parse failed (rc=" + std::to_string(rc) + ": " + lc_last_error() + "); " +
-                                        std::to_string(nValues) + " events left without a parsed time";
-            if (mAlarmSink) RaiseAlarm(3, message);
-            else std::fprintf(stderr, "[%s] %s\n", sName.c_str(), message.c_str());
-            mDeviceFailedEventsTotal += nValues;
-            return rc;
-        }
+        if (rc != LC_OK) return ReportFailedTrip(sName, "timestamp parse", "without a parsed time", rc, nValues);
     }
     const int64_t now = Now();
     const bool cacheInUse = !mHaveNanosecond || mEndWithNanosecond;
@@ -296,14 +249,15 @@ int ProcessorParseTimestampGpu::Process(PipelineEventGroup& logGroup) {
     uint32_t cacheLen = 0;
     int64_t tvSec = 0;
     bool cacheIsPrevPrefix = false;  // the cache holds exactly the matched prefix of the value before, which parsed
-    uint64_t discarded = 0, outFailed = 0, keyNotFound = 0, outSuccessful = 0, walked = 0, inRun = 0;
-    size_t wIdx = 0, vi = 0;
-    for (size_t rIdx = 0; rIdx < nEvents; ++rIdx) {
+    Tally tally;
+    uint64_t walked = 0, inRun = 0;
+    size_t vi = 0;
+    compactEvents(events, [&](size_t rIdx) {
         bool keep = true;
-        if (S.kind[rIdx] == Unsupported) {
-            ++outFailed;
-        } else if (S.kind[rIdx] == NoKey) {
-            ++keyNotFound;
+        if (S.kind[rIdx] == kNotLogEvent) {
+            ++tally.outFailed;
+        } else if (S.kind[rIdx] == kNoSourceKey) {
+            ++tally.keyNotFound;
         } else {
             const size_t i = vi++;
             const uint8_t* val = S.ptr[i];
@@ -347,29 +301,20 @@ int ProcessorParseTimestampGpu::Process(PipelineEventGroup& logGroup) {
             }
             if (!parsed) {
                 RaiseAlarm(0, std::string(reinterpret_cast<const char*>(val), len) + " " + mSourceFormat);  // :223-228
-                ++outFailed;
+                ++tally.outFailed;
             } else if (tvSec <= 0 || (mDiscardOldData && (now - tvSec) > mDiscardInterval && !mOnetime)) {  // :146-170
                 RaiseAlarm(1, "logTime: " + std::to_string(tvSec));
-                ++discarded;
+                ++tally.discarded;
                 keep = false;
             } else {
                 events[rIdx].Cast<LogEvent>().SetTimestamp(time_t(tvSec), nsec);
-                ++outSuccessful;
+                ++tally.outSuccessful;
             }
         }
-        if (keep) {
-            if (wIdx != rIdx) events[wIdx] = std::move(events[rIdx]);
-            ++wIdx;
-        }
-    }
-    events.resize(wIdx);
-    if (discarded) {
-        mDiscardedEventsTotal += discarded;
-        mHistoryFailureTotal += discarded;
-    }
-    if (outFailed) mOutFailedEventsTotal += outFailed;
-    if (keyNotFound) mOutKeyNotFoundEventsTotal += keyNotFound;
-    if (outSuccessful) mOutSuccessfulEventsTotal += outSuccessful;
+        return keep;
+    });
+    AddTally(tally);
+    if (tally.discarded) mHistoryFailureTotal += tally.discarded;
     mWalkedValues += walked;
     mRunValues += inRun;
     return LC_OK;
@@ -381,66 +326,30 @@ int ProcessorParseTimestampGpu::Process(PipelineEventGroup& logGroup) {
 using logtail::PipelineEventGroup;
 using logtail::ProcessorParseTimestampGpu;
 
-struct lc_timestamp_processor {
-    ProcessorParseTimestampGpu impl;
-    // what ProcessorInstance adds around every plugin (ProcessorInstance.cpp:46-63)
-    std::atomic<uint64_t> inEvents{0}, outEvents{0}, inBytes{0}, outBytes{0};
-};
+struct lc_timestamp_processor : logtail::ProcessorHandle<ProcessorParseTimestampGpu> {};
 
 extern "C" int lc_timestamp_processor_create(const char* config_json, lc_timestamp_processor_t** out, char* err, size_t errcap) {
     return lc_timestamp_processor_create_with_clock(config_json, nullptr, nullptr, out, err, errcap);
 }
 extern "C" int lc_timestamp_processor_create_with_clock(const char* config_json, lc_clock_t clock, void* clock_user,
                                                         lc_timestamp_processor_t** out, char* err, size_t errcap) {
-    if (!config_json || !out) return LC_ERR_ARG;
-    *out = nullptr;
-    auto setErr = [&](const std::string& m) {
-        if (err && errcap) std::snprintf(err, errcap, "%s", m.c_str());
-    };
-    lcjson::Value cfg;
-    try {
-        cfg = lcjson::parse(config_json);
-    } catch (const std::exception& e) {
-        setErr(e.what());
-        return LC_ERR_ARG;
-    }
-    auto p = std::make_unique<lc_timestamp_processor>();
-    p->impl.SetClock(clock, clock_user);  // Init resolves SourceTimezone against it
-    std::string error;
-    bool unsupported = false;
-    if (!p->impl.Init(cfg, error, &unsupported)) {
-        setErr(error);
-        return unsupported ? LC_ERR_UNSUPPORTED : LC_ERR_SYNTAX;
-    }
-    setErr("");
-    *out = p.release();
-    return LC_OK;
+    return logtail::createHandle(config_json, out, err, errcap, [&](lc_timestamp_processor& h, const lcjson::Value& cfg, std::string& error) {
+        h.impl.SetClock(clock, clock_user);  // Init resolves SourceTimezone against it
+        bool unsupported = false;
+        if (h.impl.Init(cfg, error, &unsupported)) return int(LC_OK);
+        return int(unsupported ? LC_ERR_UNSUPPORTED : LC_ERR_SYNTAX);
+    });
 }
 extern "C" void lc_timestamp_processor_destroy(lc_timestamp_processor_t* p) { delete p; }
-extern "C" char* lc_timestamp_processor_warnings(const lc_timestamp_processor_t* p) {
-    std::string s;
-    if (p)
-        for (const std::string& w : p->impl.mInitWarnings) s += w + "\n";
-    char* out = static_cast<char*>(std::malloc(s.size() + 1));
-    if (out) std::memcpy(out, s.c_str(), s.size() + 1);
-    return out;
-}
+extern "C" char* lc_timestamp_processor_warnings(const lc_timestamp_processor_t* p) { return logtail::warningsText(p); }
 extern "C" int32_t lc_timestamp_processor_zone_offset(const lc_timestamp_processor_t* p) { return p ? p->impl.mLogTimeZoneOffsetSecond : 0; }
 extern "C" int lc_timestamp_processor_process_native(lc_timestamp_processor_t* p, void* native_group) {
-    if (!p || !native_group) return LC_ERR_ARG;
-    PipelineEventGroup& group = *static_cast<PipelineEventGroup*>(native_group);
-    p->inEvents += group.GetEvents().size();
-    p->inBytes += group.DataSize();
-    const int rc = p->impl.Process(group);
-    p->outEvents += group.GetEvents().size();
-    p->outBytes += group.DataSize();
-    return rc;
+    return logtail::processNative(p, native_group);
 }
 #ifndef LC_USE_REFERENCE_HEADERS
 extern "C" void* lc_group_native(lc_event_group_t* g);
 extern "C" int lc_timestamp_processor_process(lc_timestamp_processor_t* p, lc_event_group_t* group) {
-    if (!p || !group) return LC_ERR_ARG;
-    return lc_timestamp_processor_process_native(p, lc_group_native(group));
+    return p && group ? logtail::processNative(p, lc_group_native(group)) : LC_ERR_ARG;
 }
 #endif
 extern "C" void lc_timestamp_processor_set_clock(lc_timestamp_processor_t* p, lc_clock_t clock, void* user) {
@@ -461,18 +370,7 @@ extern "C" void lc_timestamp_processor_walk_stats(const lc_timestamp_processor_t
     out[1] = p->impl.mRunValues;
 }
 extern "C" int lc_timestamp_processor_counters(const lc_timestamp_processor_t* p, uint64_t out[LC_CNT_COUNT]) {
-    if (!p || !out) return LC_ERR_ARG;
-    for (int i = 0; i < LC_CNT_COUNT; ++i) out[i] = 0;
-    out[LC_CNT_DISCARDED_EVENTS] = p->impl.mDiscardedEventsTotal;
-    out[LC_CNT_OUT_FAILED_EVENTS] = p->impl.mOutFailedEventsTotal;
-    out[LC_CNT_OUT_KEY_NOT_FOUND] = p->impl.mOutKeyNotFoundEventsTotal;
-    out[LC_CNT_OUT_SUCCESSFUL_EVENTS] = p->impl.mOutSuccessfulEventsTotal;
-    out[LC_CNT_IN_EVENTS] = p->inEvents;
-    out[LC_CNT_OUT_EVENTS] = p->outEvents;
-    out[LC_CNT_IN_SIZE_BYTES] = p->inBytes;
-    out[LC_CNT_OUT_SIZE_BYTES] = p->outBytes;
-    out[LC_CNT_DEVICE_FAILED_EVENTS] = p->impl.mDeviceFailedEventsTotal;
-    return LC_OK;
+    return logtail::fillCounters(p, out, true);
 }
 extern "C" uint64_t lc_timestamp_processor_history_failures(const lc_timestamp_processor_t* p) { return p ? uint64_t(p->impl.mHistoryFailureTotal) : 0; }
 extern "C" void lc_timestamp_processor_set_alarm_sink(lc_timestamp_processor_t* p, lc_alarm_sink_t sink, void* user) {
@@ -481,16 +379,9 @@ extern "C" void lc_timestamp_processor_set_alarm_sink(lc_timestamp_processor_t* 
 
 // ---- the plugin slot's way to this processor (c_processor_slot.cpp: a config whose Type is processor_parse_timestamp_gpu)
 extern "C" int lcTimestampSlotInit(const char* config_text, void** state) {
-    lc_timestamp_processor_t* p = nullptr;
-    char err[256];
-    if (lc_timestamp_processor_create(config_text, &p, err, sizeof err) != LC_OK) {
-        std::fprintf(stderr, "[processor_parse_timestamp_gpu] init failed: %s\n", err);
-        return -1;
-    }
-    *state = p;
-    return 0;
+    return logtail::slotInitHandle(&lc_timestamp_processor_create, ProcessorParseTimestampGpu::sName, config_text, state);
 }
 extern "C" void lcTimestampSlotProcess(void* state, void* native_group) {
-    (void)lc_timestamp_processor_process_native(static_cast<lc_timestamp_processor_t*>(state), native_group);
+    (void)logtail::processNative(static_cast<lc_timestamp_processor_t*>(state), native_group);
 }
-extern "C" void lcTimestampSlotFinalize(void* state) { lc_timestamp_processor_destroy(static_cast<lc_timestamp_processor_t*>(state)); }
+extern "C" void lcTimestampSlotFinalize(void* state) { delete static_cast<lc_timestamp_processor_t*>(state); }

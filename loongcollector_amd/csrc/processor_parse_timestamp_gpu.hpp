@@ -19,11 +19,11 @@
 #include <vector>
 
 #include "../../include/lc_timestamp.h"
-#include "processor_parse_regex_gpu.hpp"  // the event model, json_min
+#include "parse_processor_shell.hpp"  // the event model, json_min, ParseProcessorBase
 
 namespace logtail {
 
-class ProcessorParseTimestampGpu {
+class ProcessorParseTimestampGpu : public ParseProcessorBase {
 public:
     static const std::string sName;  // "processor_parse_timestamp_gpu"
     ~ProcessorParseTimestampGpu();
@@ -33,7 +33,6 @@ public:
     // LC_OK, or the LC_ERR_* code of a failed device trip (the group is then untouched)
     int Process(PipelineEventGroup& logGroup);
 
-    std::string mSourceKey;
     std::string mSourceFormat;
     std::string mSourceTimezone;
     int32_t mSourceYear = -1;
@@ -45,17 +44,9 @@ public:
     bool mOnetime = false;
     bool mPlainWalk = false;  // walk every value (the tests compare it with the run-head walk)
 
-    std::atomic<uint64_t> mDiscardedEventsTotal{0}, mOutFailedEventsTotal{0}, mOutKeyNotFoundEventsTotal{0}, mOutSuccessfulEventsTotal{0},
-        mHistoryFailureTotal{0};
-    std::atomic<uint64_t> mDeviceFailedEventsTotal{0};  // no reference counterpart
+    std::atomic<uint64_t> mHistoryFailureTotal{0};  // (beside ParseProcessorBase's counters: every discarded event counts here too)
     std::atomic<uint64_t> mWalkedValues{0}, mRunValues{0};
-    std::vector<std::string> mInitWarnings;
 
-    using AlarmSink = void (*)(void* user, int kind, const char* message, size_t len);
-    void SetAlarmSink(AlarmSink sink, void* user) {
-        mAlarmSink = sink;
-        mAlarmUser = user;
-    }
     void SetClock(lc_clock_t clock, void* user) {
         mClock = clock;
         mClockUser = user;
@@ -63,12 +54,9 @@ public:
     int64_t Now() const;
 
 private:
-    void RaiseAlarm(int kind, const std::string& message) const;
     // tv_sec as Strptime() leaves it for one device result (mktime, the year modes); no SourceTimezone yet
     int64_t LocalSeconds(uint8_t status, int64_t secs, int64_t now) const;
 
-    AlarmSink mAlarmSink = nullptr;
-    void* mAlarmUser = nullptr;
     lc_clock_t mClock = nullptr;
     void* mClockUser = nullptr;
     bool mHaveNanosecond = false, mEndWithNanosecond = false, mFormatIsEpoch = false, mFormatIsFraction = false;

@@ -58,7 +58,7 @@ def double():
     srcs = [os.path.join(ROOT, "tests", "native", "timestamp_double.cpp")] + [os.path.join(csrc, f) for f in (
         "processor_parse_timestamp_gpu.cpp", "strptime_program.cpp", "event_model.cpp")]
     deps = srcs + [os.path.join(csrc, h) for h in ("strptime_vm.hpp", "strptime_program.hpp", "processor_parse_timestamp_gpu.hpp",
-                                                   "processor_parse_regex_gpu.hpp", "event_model.hpp", "json_min.hpp")]
+                                                   "processor_parse_regex_gpu.hpp", "parse_processor_shell.hpp", "event_model.hpp", "json_min.hpp")]
     deps.append(os.path.join(ROOT, "include", "lc_timestamp.h"))
     if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
         subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-w", "-I", os.path.join(ROOT, "include"), "-I", csrc,
@@ -68,6 +68,10 @@ def double():
     vp, cp, sz, u32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32
     L.td_process_json.restype = vp
     L.td_process_json.argtypes = [vp, cp, cp, sz]
+    L.td_process_json_rc.restype = vp
+    L.td_process_json_rc.argtypes = [vp, cp, ctypes.POINTER(ctypes.c_int), cp, sz]
+    L.td_fail_next_trips.argtypes = [ctypes.c_int]
+    L.td_fail_after.argtypes = [ctypes.c_int]
     L.td_free.argtypes = [vp]
     L.td_parse_one.restype = None
     L.td_parse_one.argtypes = [vp, cp, u32, vp, vp, vp, vp, vp]
@@ -161,6 +165,17 @@ class Product:
             finally:
                 self.L.td_free(p)
         return (d or {}).get("events", [])
+
+    def process_group_rc(self, group):
+        """the double only: (the processor's return code, the events that are left)"""
+        err = ctypes.create_string_buffer(512)
+        rc = ctypes.c_int(0)
+        p = self.L.td_process_json_rc(self.h, json.dumps(group, ensure_ascii=False).encode("latin-1"), ctypes.byref(rc), err, 512)
+        assert p, err.value
+        try:
+            return rc.value, (json.loads(ctypes.string_at(p).decode("latin-1")) or {}).get("events", [])
+        finally:
+            self.L.td_free(p)
 
     def process_values(self, values, key="time"):
         """-> per event left: (value, timestamp, nanoseconds or None)"""

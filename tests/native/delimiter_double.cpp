@@ -20,6 +20,16 @@ struct lc_delim {
     DelimConfig cfg;
 };
 static uint64_t gSplitCalls = 0, gSplitLines = 0;
+// what the processor does behind a failed device trip: dd_fail_next_trips(n) fails the next n engine calls, dd_fail_after(k) lets
+// k calls through and fails the one behind them (the mop-up alone, for k = 1)
+static int gFailNext = 0, gFailAfter = -1;
+static bool tripFails() {
+    if (gFailNext) {
+        --gFailNext;
+        return true;
+    }
+    return gFailAfter >= 0 && gFailAfter-- == 0;
+}
 
 extern "C" {
 const char* lc_last_error(void) { return "the delimiter double has no device"; }
@@ -53,31 +63,41 @@ void dd_split_line(const lc_delim_t* d, const uint8_t* line, uint32_t len, uint3
 int lc_delim_split_host(lc_delim_t* d, const uint8_t* const* lines, const uint32_t* len, uint32_t n, uint32_t W, uint8_t* status,
                         uint32_t* ncols, int32_t* spans) {
     if (!d || (n && (!lines || !len || !status || !ncols || (W && !spans)))) return LC_ERR_ARG;
+    if (tripFails()) return LC_ERR_HIP;
     ++gSplitCalls;
     gSplitLines += n;
     for (uint32_t i = 0; i < n; ++i)
         dd_split_line(d, lines[i], len[i], uint32_t(i * 7u), W, status + i, ncols + i, spans + size_t(i) * W * 2);
     return LC_OK;
 }
+void dd_fail_next_trips(int n) { gFailNext = n; }
+void dd_fail_after(int k) { gFailAfter = k; }
 void dd_split_stats(uint64_t out[2]) {
     out[0] = gSplitCalls;
     out[1] = gSplitLines;
 }
 
-// fixture JSON in -> lc_delimiter_processor_process_native -> fixture JSON out (malloc'ed; dd_free)
-char* dd_process_json(lc_delimiter_processor_t* p, const char* groupJson, char* err, size_t errcap) {
+// fixture JSON in -> lc_delimiter_processor_process_native -> fixture JSON out (malloc'ed; dd_free).  rc_out: the processor's return code
+char* dd_process_json_rc(lc_delimiter_processor_t* p, const char* groupJson, int* rc_out, char* err, size_t errcap) {
     logtail::PipelineEventGroup group(std::make_shared<logtail::SourceBuffer>());
     std::string error;
     if (!group.FromJsonString(groupJson, &error)) {
         std::snprintf(err, errcap, "%s", error.c_str());
         return nullptr;
     }
-    const int rc = lc_delimiter_processor_process_native(p, &group);
-    if (rc != LC_OK) {
+    *rc_out = lc_delimiter_processor_process_native(p, &group);
+    return strdup(group.ToJsonString().c_str());
+}
+// the same; a failed trip answers nullptr
+char* dd_process_json(lc_delimiter_processor_t* p, const char* groupJson, char* err, size_t errcap) {
+    int rc = LC_OK;
+    char* out = dd_process_json_rc(p, groupJson, &rc, err, errcap);
+    if (out && rc != LC_OK) {
         std::snprintf(err, errcap, "lc_delimiter_processor_process_native failed: %d", rc);
+        std::free(out);
         return nullptr;
     }
-    return strdup(group.ToJsonString().c_str());
+    return out;
 }
 void* lc_group_native(lc_event_group_t*) { return nullptr; }  // (the fixture wrapper of c_processor_slot.cpp is not part of this build)
 void dd_free(void* p) { std::free(p); }

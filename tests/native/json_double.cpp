@@ -17,7 +17,16 @@
 #include "../../loongcollector_amd/csrc/json_vm.hpp"
 
 static uint64_t gWalkCalls = 0, gWalkLines = 0;
-static int gFailNext = 0;
+// what the processor does behind a failed device trip: jd_fail_next_trips(n) fails the next n engine calls, jd_fail_after(k) lets
+// k calls through and fails the one behind them (the mop-up alone, for k = 1)
+static int gFailNext = 0, gFailAfter = -1;
+static bool tripFails() {
+    if (gFailNext) {
+        --gFailNext;
+        return true;
+    }
+    return gFailAfter >= 0 && gFailAfter-- == 0;
+}
 
 extern "C" {
 const char* lc_last_error(void) { return "the JSON double has no device"; }
@@ -35,10 +44,7 @@ int lc_json_walk_host(const uint8_t* const* lines, const uint32_t* len, uint32_t
                       uint32_t* errpos, lc_json_member_t* records, uint8_t* shadow, uint64_t* shadow_bytes_moved) {
     if (shadow_bytes_moved) *shadow_bytes_moved = 0;
     if (n && (!lines || !len || !status || !nmembers || !errpos || !shadow || (W && !records))) return LC_ERR_ARG;
-    if (gFailNext) {  // (jd_fail_next_trips: what the processor does behind a failed device trip)
-        --gFailNext;
-        return LC_ERR_HIP;
-    }
+    if (tripFails()) return LC_ERR_HIP;
     ++gWalkCalls;
     gWalkLines += n;
     size_t at = 0;
@@ -53,6 +59,7 @@ void jd_walk_stats(uint64_t out[2]) {
     out[1] = gWalkLines;
 }
 void jd_fail_next_trips(int n) { gFailNext = n; }
+void jd_fail_after(int k) { gFailAfter = k; }
 
 // fixture JSON in -> lc_json_processor_process_native -> fixture JSON out (malloc'ed; jd_free).  rc_out: the processor's return code
 char* jd_process_json(lc_json_processor_t* p, const char* groupJson, int* rc_out, char* err, size_t errcap) {

@@ -22,6 +22,16 @@ struct lc_strptime {
     StrptimeProgram prog;
 };
 static uint64_t gParseCalls = 0, gParseValues = 0;
+// what the processor does behind a failed device trip: td_fail_next_trips(n) fails the next n engine calls, td_fail_after(k) lets
+// k calls through and fails the one behind them (the mop-up alone, for k = 1)
+static int gFailNext = 0, gFailAfter = -1;
+static bool tripFails() {
+    if (gFailNext) {
+        --gFailNext;
+        return true;
+    }
+    return gFailAfter >= 0 && gFailAfter-- == 0;
+}
 
 extern "C" {
 const char* lc_last_error(void) { return "the timestamp double has no device"; }
@@ -60,6 +70,7 @@ void td_parse_one(const lc_strptime_t* t, const uint8_t* val, uint32_t len, uint
 }
 int lc_strptime_parse_host(lc_strptime_t* t, const uint8_t* const* vals, const uint32_t* len, uint32_t n, const lc_ts_out_t* out) {
     if (!t || (n && (!vals || !len || !out))) return LC_ERR_ARG;
+    if (tripFails()) return LC_ERR_HIP;
     ++gParseCalls;
     gParseValues += n;
     for (uint32_t i = 0; i < n; ++i) {
@@ -73,25 +84,34 @@ int lc_strptime_parse_host(lc_strptime_t* t, const uint8_t* const* vals, const u
     }
     return LC_OK;
 }
+void td_fail_next_trips(int n) { gFailNext = n; }
+void td_fail_after(int k) { gFailAfter = k; }
 void td_parse_stats(uint64_t out[2]) {
     out[0] = gParseCalls;
     out[1] = gParseValues;
 }
 
-// fixture JSON in -> lc_timestamp_processor_process_native -> fixture JSON out (malloc'ed; td_free)
-char* td_process_json(lc_timestamp_processor_t* p, const char* groupJson, char* err, size_t errcap) {
+// fixture JSON in -> lc_timestamp_processor_process_native -> fixture JSON out (malloc'ed; td_free).  rc_out: the processor's return code
+char* td_process_json_rc(lc_timestamp_processor_t* p, const char* groupJson, int* rc_out, char* err, size_t errcap) {
     logtail::PipelineEventGroup group(std::make_shared<logtail::SourceBuffer>());
     std::string error;
     if (!group.FromJsonString(groupJson, &error)) {
         std::snprintf(err, errcap, "%s", error.c_str());
         return nullptr;
     }
-    const int rc = lc_timestamp_processor_process_native(p, &group);
-    if (rc != LC_OK) {
+    *rc_out = lc_timestamp_processor_process_native(p, &group);
+    return strdup(group.ToJsonString().c_str());
+}
+// the same; a failed trip answers nullptr
+char* td_process_json(lc_timestamp_processor_t* p, const char* groupJson, char* err, size_t errcap) {
+    int rc = LC_OK;
+    char* out = td_process_json_rc(p, groupJson, &rc, err, errcap);
+    if (out && rc != LC_OK) {
         std::snprintf(err, errcap, "lc_timestamp_processor_process_native failed: %d", rc);
+        std::free(out);
         return nullptr;
     }
-    return strdup(group.ToJsonString().c_str());
+    return out;
 }
 void* lc_group_native(lc_event_group_t*) { return nullptr; }  // (the fixture wrapper of c_processor_slot.cpp is not part of this build)
 void td_free(void* p) { std::free(p); }

@@ -28,7 +28,7 @@ def _double():
     csrc = os.path.join(ROOT, "loongcollector_amd", "csrc")
     srcs = [os.path.join(ROOT, "tests", "native", "delimiter_double.cpp")] + [os.path.join(csrc, f) for f in (
         "processor_parse_delimiter_gpu.cpp", "processor_parse_regex_gpu.cpp", "event_model.cpp")]
-    deps = srcs + [os.path.join(csrc, h) for h in ("delim_vm.hpp", "processor_parse_delimiter_gpu.hpp", "processor_parse_regex_gpu.hpp",
+    deps = srcs + [os.path.join(csrc, h) for h in ("delim_vm.hpp", "processor_parse_delimiter_gpu.hpp", "processor_parse_regex_gpu.hpp", "parse_processor_shell.hpp",
                                                    "event_model.hpp", "json_min.hpp")] + [os.path.join(ROOT, "include", "lc_delimiter.h")]
     if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
         subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-w", "-I", os.path.join(ROOT, "include"), "-I", csrc,
@@ -46,6 +46,10 @@ def _double():
     L.lc_delimiter_processor_set_first_trip_columns.argtypes = [vp, u32]
     L.dd_process_json.restype = vp
     L.dd_process_json.argtypes = [vp, cp, cp, sz]
+    L.dd_process_json_rc.restype = vp
+    L.dd_process_json_rc.argtypes = [vp, cp, ctypes.POINTER(ctypes.c_int), cp, sz]
+    L.dd_fail_next_trips.argtypes = [ctypes.c_int]
+    L.dd_fail_after.argtypes = [ctypes.c_int]
     L.dd_free.argtypes = [vp]
     L.lc_delim_create.argtypes = [cp, u32, ctypes.c_uint8, ctypes.c_int, u32, ctypes.POINTER(vp)]
     L.lc_delim_destroy.argtypes = [vp]
@@ -99,6 +103,17 @@ class Product:
             out.append(ev)
         return out
 
+    def process_group_rc(self, group):
+        """fixture group in -> (the processor's return code, the group's events as ToJsonString prints them)"""
+        err = ctypes.create_string_buffer(512)
+        rc = ctypes.c_int(0)
+        p = self.L.dd_process_json_rc(self.h, json.dumps(group, ensure_ascii=False).encode("latin-1"), ctypes.byref(rc), err, 512)
+        assert p, err.value
+        try:
+            return rc.value, (json.loads(ctypes.string_at(p).decode("latin-1")) or {}).get("events", [])
+        finally:
+            self.L.dd_free(p)
+
     def process_lines(self, lines):
         events = [{"contents": [["content", ln]], "timestamp": 1, "type": 1} for ln in lines]
         events.append({"contents": [["other", "x"]], "timestamp": 1, "type": 1})
@@ -145,6 +160,55 @@ def test_the_mop_up_rule_a_small_first_trip_gives_the_same_events_as_a_huge_one(
             assert stats[0] - calls0 <= 2                      # one trip, and at most one mop-up
             assert got == huge.process_lines(case["lines"]) == case["out"], (k, w, case["config"])
             assert small.counters()[:4] == case["counters"] and [m for _, m in small.alarms] == case["alarms"]
+
+
+RAW = {"content": "no log event", "timestamp": 1, "type": 4}      # (the fixture's one event type besides the log event)
+
+
+def _log(contents):
+    return {"contents": contents, "timestamp": 1, "type": 1}
+
+
+def test_a_failed_first_trip_is_reported_counted_and_a_healthy_call_behind_it_parses(capfd):
+    """one parsable event, one without the key, one that is no log event; counters as [discarded, out_failed, out_key_not_found,
+    out_successful, in_events, out_events]: the gather's out_failed (the raw event) and key_not_found are added behind a failed trip"""
+    L = _double()
+    events = [_log({"content": "x,y"}), _log({"other": "y"}), RAW]
+    text = "GPU split failed (rc=4: the delimiter double has no device); 1 events left unparsed"
+    p = Product({"SourceKey": "content", "Separator": ",", "Keys": ["a", "b"]})
+    L.dd_fail_next_trips(1)
+    assert p.process_group_rc({"events": events}) == (4, events)
+    assert p.alarms == [(3, text)]
+    c = p.counters()
+    assert c[:6] == [0, 1, 1, 0, 3, 3] and c[11] == 1
+    # no sink: exactly one line on stderr
+    L.lc_delimiter_processor_set_alarm_sink(p.h, None, None)
+    capfd.readouterr()
+    L.dd_fail_next_trips(1)
+    assert p.process_group_rc({"events": events}) == (4, events)
+    assert capfd.readouterr().err == "[processor_parse_delimiter_gpu] " + text + "\n"
+    assert len(p.alarms) == 1 and p.counters()[11] == 2
+    assert p.process_group_rc({"events": events}) == (0, [_log({"a": "x", "b": "y"}), _log({"other": "y"}), RAW])
+    c = p.counters()
+    assert c[:6] == [0, 3, 3, 1, 9, 9] and c[11] == 2
+
+
+def test_a_failed_second_trip_leaves_the_group_untouched_and_counts_the_first_trip_s_lines():
+    L = _double()
+    stats = (ctypes.c_uint64 * 2)()
+    events = [_log({"content": "x,y,z"}), _log({"content": "x"}), _log({"other": "y"})]
+    p = Product({"SourceKey": "content", "Separator": ",", "Keys": ["a", "b"], "AllowingShortenedFields": True}, first_trip_columns=1)
+    L.dd_split_stats(stats)
+    calls0 = stats[0]
+    L.dd_fail_after(1)
+    assert p.process_group_rc({"events": events}) == (4, events)
+    L.dd_split_stats(stats)
+    assert stats[0] - calls0 == 1          # the first trip went through; the mop-up is the call that failed
+    assert p.alarms == [(3, "GPU split failed (rc=4: the delimiter double has no device); 2 events left unparsed")]
+    c = p.counters()
+    assert c[:6] == [0, 0, 1, 0, 3, 3] and c[11] == 2
+    assert p.process_group_rc({"events": events}) == (0, [_log({"a": "x", "b": "y", "__column2__": "z"}), _log({"a": "x"}), _log({"other": "y"})])
+    assert p.counters()[:4] == [0, 0, 2, 2] and p.counters()[11] == 2
 
 
 def _unit(golden_dir):

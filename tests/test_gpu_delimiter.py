@@ -312,3 +312,27 @@ def test_split_host_after_thread_release_gives_the_same_answer():
     first, second, error = fresh_thread.run(body)
     assert all(np.array_equal(a, b) for a, b in zip(first, second)) and list(first[1]) == [2, 2, 0, 1]
     assert not error
+
+
+def test_four_threads_share_one_processor_and_every_group_takes_the_mop_up():
+    """three groups of 64 events per thread at a first trip of ONE column: 62 one-column lines, one line of six columns (the mop-up's)
+    and one event without the key"""
+    from loongcollector_amd import delimiter
+    from helpers.shared_processor import four_threads_equal_one_thread
+
+    def log(contents):
+        return {"contents": contents, "timestamp": 1, "type": 1}
+
+    def group(t, g):
+        tag = "t%dg%d" % (t, g)
+        events = [log({"content": "%s-%d" % (tag, i)}) for i in range(62)]
+        events.insert(g * 20 + t, log({"content": '%s,"q,""1""",c,d,e,f' % tag}))
+        return {"events": events + [log({"other": tag})]}
+
+    groups = [[group(t, g) for g in range(3)] for t in range(4)]
+    config = {"SourceKey": "content", "Separator": ",", "Keys": ["a", "b"], "AllowingShortenedFields": True}
+    want, c = four_threads_equal_one_thread(lambda: delimiter.DelimiterProcessor(config, first_trip_columns=1), groups)
+    assert want[2][1][22]["contents"] == {"a": "t2g1", "b": 'q,"1"', "__column2__": "c", "__column3__": "d", "__column4__": "e", "__column5__": "f"}
+    assert want[2][1][0]["contents"] == {"a": "t2g1-0"}
+    assert [c[k] for k in ("discarded_events_total", "out_failed_events_total", "out_key_not_found_events_total", "out_successful_events_total",
+                           "in_events_total", "out_events_total")] == [0, 0, 12, 12 * 63, 12 * 64, 12 * 64]

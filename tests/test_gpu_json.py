@@ -358,3 +358,27 @@ def test_walk_host_after_thread_release_gives_the_same_answer():
     first, second, error = fresh_thread.run(body)
     assert all(np.array_equal(a, b) for a, b in zip(first, second)) and list(first[0]) == [jm.OK, jm.OK, jm.EMPTY, jm.OK, jm.FAIL]
     assert not error
+
+
+def test_four_threads_share_one_processor_and_every_group_takes_the_mop_up():
+    """three groups of 64 events per thread at a first trip of ONE member: 61 one-member lines, one line of five members (the mop-up's),
+    one that fails and one event without the key"""
+    from loongcollector_amd import json_parse
+    from helpers.shared_processor import four_threads_equal_one_thread
+
+    def log(contents):
+        return {"contents": contents, "timestamp": 1, "type": 1}
+
+    def group(t, g):
+        tag = "t%dg%d" % (t, g)
+        events = [log({"content": '{"k%d":"%s\\n%d"}' % (i, tag, i)}) for i in range(61)]
+        events.insert(g * 20 + t, log({"content": '{"a":"%s","b":1.5,"c":null,"d":[1, 2],"e":"\\t"}' % tag}))
+        return {"events": events + [log({"content": '{"a":tru}'}), log({"other": tag})]}
+
+    groups = [[group(t, g) for g in range(3)] for t in range(4)]
+    config = {"SourceKey": "content", "KeepingSourceWhenParseFail": True}
+    want, c = four_threads_equal_one_thread(lambda: json_parse.JsonProcessor(config, first_trip_members=1), groups)
+    assert want[2][1][22]["contents"] == {"a": "t2g1", "b": "1.500000", "c": "", "d": "[1, 2]", "e": "\t"}      # all five: the second trip
+    assert want[2][1][0]["contents"] == {"k0": "t2g1\n0"}
+    assert [c[k] for k in ("discarded_events_total", "out_failed_events_total", "out_key_not_found_events_total", "out_successful_events_total",
+                           "in_events_total", "out_events_total")] == [0, 12, 12, 12 * 63, 12 * 64, 12 * 64]

@@ -30,7 +30,7 @@ def _double():
     csrc = os.path.join(ROOT, "loongcollector_amd", "csrc")
     srcs = [os.path.join(ROOT, "tests", "native", f) for f in ("json_double.cpp", "json_host_check.cpp")] + [os.path.join(csrc, f) for f in (
         "processor_parse_json_gpu.cpp", "processor_parse_regex_gpu.cpp", "event_model.cpp")]
-    deps = srcs + [os.path.join(csrc, h) for h in ("json_vm.hpp", "processor_parse_json_gpu.hpp", "processor_parse_regex_gpu.hpp",
+    deps = srcs + [os.path.join(csrc, h) for h in ("json_vm.hpp", "processor_parse_json_gpu.hpp", "processor_parse_regex_gpu.hpp", "parse_processor_shell.hpp",
                                                    "event_model.hpp", "json_min.hpp")] + [os.path.join(ROOT, "include", "lc_json.h")]
     if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
         subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-w", "-I", os.path.join(ROOT, "include"), "-I", csrc,
@@ -51,6 +51,7 @@ def _double():
     L.jd_free.argtypes = [vp]
     L.jd_walk_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     L.jd_fail_next_trips.argtypes = [ctypes.c_int]
+    L.jd_fail_after.argtypes = [ctypes.c_int]
     L.jh_walk_line.restype = None
     L.jh_walk_line.argtypes = [cp, u32, u32, u32, vp, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int)]
     L.jh_walk_line_first.restype = None
@@ -281,6 +282,55 @@ def test_a_failed_device_trip_leaves_the_group_untouched_and_is_counted():
     assert c[11] == 2 and c[2] == 1 and c[3] == 0 and c[0] == 0
     assert [k for k, _ in p.alarms] == [3]
     assert p.process_contents(events) == [{b"a": b"1"}, {b"other": b"y"}] and p.rc == 0
+
+
+RAW = {"content": "no log event", "timestamp": 1, "type": 4}      # (the fixture's one event type besides the log event)
+
+
+def _log(contents):
+    return {"contents": contents, "timestamp": 1, "type": 1}
+
+
+def test_a_failed_first_trip_is_reported_counted_and_a_healthy_call_behind_it_parses(capfd):
+    """one parsable event, one without the key, one that is no log event; counters as [discarded, out_failed, out_key_not_found,
+    out_successful, in_events, out_events]: the gather's out_failed (the raw event) and key_not_found are added behind a failed trip"""
+    L = _double()
+    events = [_log({"content": '{"a":1}'}), _log({"other": "y"}), RAW]
+    text = "GPU JSON walk failed (rc=4: the JSON double has no device); 1 events left unparsed"
+    p = Product({"SourceKey": "content"})
+    L.jd_fail_next_trips(1)
+    assert p.process_group({"events": events}) == events and p.rc == 4
+    assert p.alarms == [(3, text.encode())]
+    c = p.counters()
+    assert c[:6] == [0, 1, 1, 0, 3, 3] and c[11] == 1
+    # no sink: exactly one line on stderr
+    L.lc_json_processor_set_alarm_sink(p.h, None, None)
+    capfd.readouterr()
+    L.jd_fail_next_trips(1)
+    assert p.process_group({"events": events}) == events and p.rc == 4
+    assert capfd.readouterr().err == "[processor_parse_json_gpu] " + text + "\n"
+    assert len(p.alarms) == 1 and p.counters()[11] == 2
+    assert p.process_group({"events": events}) == [_log({"a": "1"}), _log({"other": "y"}), RAW] and p.rc == 0
+    c = p.counters()
+    assert c[:6] == [0, 3, 3, 1, 9, 9] and c[11] == 2
+
+
+def test_a_failed_second_trip_leaves_the_group_untouched_and_counts_the_first_trip_s_lines():
+    L = _double()
+    stats = (ctypes.c_uint64 * 2)()
+    events = [_log({"content": '{"a":1,"b":"\\n"}'}), _log({"content": '{"a":1}'}), _log({"other": "y"})]
+    p = Product({"SourceKey": "content"}, first_trip_members=1)
+    L.jd_walk_stats(stats)
+    calls0 = stats[0]
+    L.jd_fail_after(1)
+    assert p.process_group({"events": events}) == events and p.rc == 4
+    L.jd_walk_stats(stats)
+    assert stats[0] - calls0 == 1          # the first trip went through; the mop-up is the call that failed
+    assert p.alarms == [(3, b"GPU JSON walk failed (rc=4: the JSON double has no device); 2 events left unparsed")]
+    c = p.counters()
+    assert c[:6] == [0, 0, 1, 0, 3, 3] and c[11] == 2
+    assert p.process_group({"events": events}) == [_log({"a": "1", "b": "\n"}), _log({"a": "1"}), _log({"other": "y"})] and p.rc == 0
+    assert p.counters()[:4] == [0, 0, 2, 2] and p.counters()[11] == 2
 
 
 def test_init_answers_false_with_the_reference_s_messages():

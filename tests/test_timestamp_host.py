@@ -211,6 +211,37 @@ def test_event_outcomes_and_counters(tz):
     assert p.alarms == [(0, "garbage %Y-%m-%d %H:%M:%S"), (1, "logTime: 1703379723"), (1, "logTime: -1")]
 
 
+def test_a_failed_trip_is_reported_counted_and_a_healthy_call_behind_it_parses(tz, capfd):
+    """one parsable event, one without the key, one that is no log event: this processor counts those two in the walk, so a failed trip
+    adds nothing but device_failed_events_total"""
+    tz("UTC")
+    L = double()
+    events = [{"contents": {"time": "2023-12-25 01:02:03"}, "timestamp": 1, "type": 1}, {"contents": {"other": "x"}, "timestamp": 1, "type": 1},
+              {"content": "no log event", "timestamp": 1, "type": 4}]
+    text = "GPU timestamp parse failed (rc=4: the timestamp double has no device); 1 events left without a parsed time"
+    zero = {"discarded": 0, "out_failed": 0, "key_not_found": 0, "out_successful": 0, "history_failure": 0}
+
+    def all_counters(p):
+        c = (ctypes.c_uint64 * 12)()
+        L.lc_timestamp_processor_counters(p.h, c)
+        return [int(x) for x in c]
+    p = Product({"SourceKey": "time", "SourceFormat": "%Y-%m-%d %H:%M:%S"}, now=1703466123 + 100)
+    L.td_fail_next_trips(1)
+    assert p.process_group_rc({"events": events}) == (4, events)
+    assert p.alarms == [(3, text)]
+    assert p.counters() == zero and all_counters(p)[4:6] == [3, 3] and all_counters(p)[11] == 1
+    # no sink: exactly one line on stderr
+    L.lc_timestamp_processor_set_alarm_sink(p.h, None, None)
+    capfd.readouterr()
+    L.td_fail_next_trips(1)
+    assert p.process_group_rc({"events": events}) == (4, events)
+    assert capfd.readouterr().err == "[processor_parse_timestamp_gpu] " + text + "\n"
+    assert len(p.alarms) == 1 and p.counters() == zero and all_counters(p)[11] == 2
+    rc, left = p.process_group_rc({"events": events})
+    assert rc == 0 and left == [dict(events[0], timestamp=1703466123, timestampNanosecond=0)] + events[1:]
+    assert p.counters() == dict(zero, out_failed=1, key_not_found=1, out_successful=1) and all_counters(p)[11] == 2
+
+
 def _random_group(rng, fmt_kind):
     """values of one format with planted collisions: repeats, values that extend a predecessor, failures in between"""
     vals = []
