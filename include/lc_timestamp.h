@@ -14,7 +14,7 @@
  *   time(NULL)                                                                   lc_timestamp_processor_set_clock
  *
  * There is no CPU path for the parse: without a HIP device every entry point that would parse a value returns LC_ERR_NO_DEVICE.
- * Out of scope: processor_parse_apsara_native, the reference's commented-out precise-timestamp key, locales other than C, and the
+ * processor_parse_apsara_native is lc_apsara.h.  Out of scope: the reference's commented-out precise-timestamp key, locales other than C, and the
  * fused lc_pipeline_* path (it does not call this processor).
  */
 #ifndef LC_TIMESTAMP_H

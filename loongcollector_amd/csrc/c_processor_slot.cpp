@@ -26,6 +26,9 @@ __attribute__((weak)) void lcDelimiterSlotFinalize(void* state);
 __attribute__((weak)) int lcTimestampSlotInit(const char* config_text, void** state);  // processor_parse_timestamp_gpu.cpp
 __attribute__((weak)) void lcTimestampSlotProcess(void* state, void* native_group);
 __attribute__((weak)) void lcTimestampSlotFinalize(void* state);
+__attribute__((weak)) int lcApsaraSlotInit(const char* config_text, void** state);  // processor_parse_apsara_gpu.cpp
+__attribute__((weak)) void lcApsaraSlotProcess(void* state, void* native_group);
+__attribute__((weak)) void lcApsaraSlotFinalize(void* state);
 }
 namespace {
 struct SlotEntry {
@@ -38,6 +41,7 @@ struct SlotEntry {
 const SlotEntry kSlotTable[] = {
     {"processor_parse_delimiter_gpu", "delimiter parser", lcDelimiterSlotInit, lcDelimiterSlotProcess, lcDelimiterSlotFinalize},
     {"processor_parse_timestamp_gpu", "timestamp processor", lcTimestampSlotInit, lcTimestampSlotProcess, lcTimestampSlotFinalize},
+    {"processor_parse_apsara_gpu", "Apsara parser", lcApsaraSlotInit, lcApsaraSlotProcess, lcApsaraSlotFinalize},
 };
 }  // namespace
 

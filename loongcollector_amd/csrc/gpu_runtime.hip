@@ -2084,6 +2084,7 @@ extern "C" void lc_thread_release(void) {
     lcFilterThreadRelease();
     lcDelimThreadRelease();
     lcTimestampThreadRelease();
+    lcApsaraThreadRelease();
     lcJsonThreadRelease();
 }
 

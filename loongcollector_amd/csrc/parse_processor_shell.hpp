@@ -1,4 +1,4 @@
-// parse_processor_shell.hpp -- what processor_parse_delimiter_gpu, processor_parse_timestamp_gpu and processor_parse_json_gpu share around
+// parse_processor_shell.hpp -- what processor_parse_delimiter_gpu, processor_parse_timestamp_gpu, processor_parse_json_gpu and processor_parse_apsara_gpu share around
 // their own Init, engine call and stitch: the config readers, the counters / alarm sink / tally every parse processor holds, the gather,
 // the ONE second trip for lines wider than the first trip kept, the report of a failed trip, the source-key tail, the in-place
 // compaction, and the C ABI bodies as templates over the handle type.  Header-only; it uses only the event API the stand-in and the
@@ -86,6 +86,29 @@ inline bool mandatoryStringList(const lcjson::Value& cfg, const std::string& key
         err = "mandatory list param " + key + " is empty";
         return false;
     }
+    return true;
+}
+
+// std::from_chars<int> over exactly two bytes (StringTo of core/common/StringTools.h)
+inline bool twoCharInt(const char* s, int& out) {
+    const bool neg = s[0] == '-';
+    if (neg) {
+        if (s[1] < '0' || s[1] > '9') return false;
+        out = -(s[1] - '0');
+        return true;
+    }
+    if (s[0] < '0' || s[0] > '9' || s[1] < '0' || s[1] > '9') return false;
+    out = (s[0] - '0') * 10 + (s[1] - '0');
+    return true;
+}
+// ParseTimeZoneOffsetSecond (TimeUtil.cpp:407-426)
+inline bool parseTimeZoneOffsetSecond(const std::string& tz, int& out) {
+    if (tz.size() != 9 || tz[6] != ':' || (tz[3] != '+' && tz[3] != '-')) return false;
+    if (tz.compare(0, 3, "GMT") != 0) return false;
+    int hour = 0, minute = 0;
+    if (!twoCharInt(tz.data() + 4, hour) || !twoCharInt(tz.data() + 7, minute)) return false;
+    out = hour * 3600 + minute * 60;
+    if (tz[3] == '-') out = -out;
     return true;
 }
 

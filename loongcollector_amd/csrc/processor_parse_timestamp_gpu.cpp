@@ -88,29 +88,6 @@ namespace logtail {
 const std::string ProcessorParseTimestampGpu::sName = "processor_parse_timestamp_gpu";
 
 namespace {
-// std::from_chars<int> over exactly two bytes (StringTo of core/common/StringTools.h)
-bool twoCharInt(const char* s, int& out) {
-    const bool neg = s[0] == '-';
-    if (neg) {
-        if (s[1] < '0' || s[1] > '9') return false;
-        out = -(s[1] - '0');
-        return true;
-    }
-    if (s[0] < '0' || s[0] > '9' || s[1] < '0' || s[1] > '9') return false;
-    out = (s[0] - '0') * 10 + (s[1] - '0');
-    return true;
-}
-// ParseTimeZoneOffsetSecond (TimeUtil.cpp:407-426)
-bool parseTimeZoneOffsetSecond(const std::string& tz, int& out) {
-    if (tz.size() != 9 || tz[6] != ':' || (tz[3] != '+' && tz[3] != '-')) return false;
-    if (tz.compare(0, 3, "GMT") != 0) return false;
-    int hour = 0, minute = 0;
-    if (!twoCharInt(tz.data() + 4, hour) || !twoCharInt(tz.data() + 7, minute)) return false;
-    out = hour * 3600 + minute * 60;
-    if (tz[3] == '-') out = -out;
-    return true;
-}
-
 struct ProcessScratch {
     std::vector<uint8_t> kind, status, same;
     std::vector<const uint8_t*> ptr;

@@ -10,7 +10,7 @@
 //     a prefix takes the cached second -- by walking only run heads and values whose same_as_prev bit is clear.  Inside a run of set
 //     bits the cache holds exactly the run's matched prefix, so every value of the run hits it and takes the second the run's head
 //     left behind.
-// Out of scope: processor_parse_apsara_native; the precise-timestamp key the reference has commented out (:172-176, :233-239).
+// processor_parse_apsara_native is processor_parse_apsara_gpu.hpp.  Out of scope: the precise-timestamp key the reference has commented out (:172-176, :233-239).
 #pragma once
 
 #include <atomic>

@@ -19,6 +19,7 @@ void lcMultilineThreadRelease();                       // multiline_device.hip: 
 void lcFilterThreadRelease();                          // processor_filter_gpu.cpp: the same for the filter
 void lcDelimThreadRelease();                           // delim_device.hip: the same for the delimiter parser's host entry
 void lcTimestampThreadRelease();                       // timestamp_device.hip: the same for the timestamp parser's host entry
+void lcApsaraThreadRelease();                          // apsara_device.hip: the same for the Apsara parser's host entry
 void lcJsonThreadRelease();                            // json_device.hip: the same for the JSON parser's host entry
 // The device a DEVICE-pointer entry point runs on: the caller's current HIP device; LC_ERR_ARG when d_ptr lives on another device.
 int lcDeviceEntryDevice(const void* d_ptr, int* dev);

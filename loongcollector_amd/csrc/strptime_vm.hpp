@@ -133,6 +133,69 @@ LC_TS_HD bool tsConvNanos(const Source& src, uint32_t len, uint32_t& pos, uint32
     return true;
 }
 
+// conv_num(llim, ulim) at `pos`: false when no digit stands there (pos stays) or the number is out of range (pos is behind the digits
+// it took); v is written on success only
+template <class Source>
+LC_TS_HD bool tsConvNum(const Source& src, uint32_t len, uint32_t& pos, uint32_t llim, uint32_t ulim, int32_t& v) {
+    uint32_t ch = pos < len ? src.at(pos) : 0u;
+    if (!tsIsDigit(ch)) return false;
+    uint32_t result = 0, rulim = ulim;
+    do {
+        result = result * 10u + (ch - '0');
+        rulim /= 10u;
+        ++pos;
+        ch = pos < len ? src.at(pos) : 0u;
+    } while (result * 10u <= ulim && rulim && tsIsDigit(ch));
+    if (result < llim || result > ulim) return false;
+    v = int32_t(result);
+    return true;
+}
+
+// the "%s" format over the whole span.  strtoll: white space, one sign, digits (saturating); then the reference keeps the first ten
+// characters of the decimal rendering as the second and reads what follows the tenth byte OF THE BUFFER as the fraction.  false: no
+// digit, or a second of 0.  pos: behind the digits strtoll took
+template <class Source>
+LC_TS_HD bool tsConvEpoch(const Source& src, uint32_t len, int64_t& epochSecs, uint32_t& nanos, int32_t& fracLen, uint32_t& pos) {
+    uint32_t p = 0;
+    while (p < len && tsIsSpace(src.at(p))) ++p;
+    bool neg = false;
+    if (p < len && (src.at(p) == '+' || src.at(p) == '-')) {
+        neg = src.at(p) == '-';
+        ++p;
+    }
+    uint64_t mag = 0;
+    const uint64_t lim = neg ? 9223372036854775808ull : 9223372036854775807ull;
+    uint32_t nd = 0;
+    bool sat = false;
+    while (p < len && tsIsDigit(src.at(p))) {
+        const uint32_t d = src.at(p) - '0';
+        if (sat || mag > (lim - d) / 10) {
+            sat = true;
+            mag = lim;
+        } else {
+            mag = mag * 10 + d;
+        }
+        ++p;
+        ++nd;
+    }
+    uint32_t rendered = neg && mag ? 1u : 0u;  // std::to_string(n).length()
+    {
+        uint64_t t = mag;
+        do {
+            ++rendered;
+            t /= 10;
+        } while (t);
+    }
+    const uint32_t keep = rendered >= 10 ? 10u : rendered;
+    for (uint32_t i = keep; i < rendered; ++i) mag /= 10;  // (truncation toward zero, the sign aside)
+    if (nd == 0 || mag == 0) return false;
+    epochSecs = neg ? -int64_t(mag) : int64_t(mag);
+    uint32_t q = keep;
+    (void)tsConvNanos(src, len, q, nanos, fracLen);
+    pos = p;
+    return true;
+}
+
 // Source: uint32_t at(uint32_t i) const for i < len.  prog / names: pointers (of any address space: LDS on the device) to the program
 // words and to the name block.  The routine never calls at() with i >= len.
 template <class Source, class ProgPtr, class NamePtr>
@@ -176,20 +239,7 @@ LC_TS_HD StrptimeResult strptimeRun(const Source& src, uint32_t len, ProgPtr pro
                     case TS_F_CENT_FIRST: case TS_F_CENT_SPLIT: v = 20; break;
                     default: v = 0; break;
                 }
-                uint32_t ch = TS_AT(pos);
-                if (!tsIsDigit(ch)) {
-                    fail = true;
-                } else {
-                    uint32_t result = 0, rulim = ulim;
-                    do {
-                        result = result * 10u + (ch - '0');
-                        rulim /= 10u;
-                        ++pos;
-                        ch = TS_AT(pos);
-                    } while (result * 10u <= ulim && rulim && tsIsDigit(ch));
-                    if (result < llim || result > ulim) fail = true;
-                    else v = int32_t(result);
-                }
+                if (!tsConvNum(src, len, pos, llim, ulim, v)) fail = true;
                 // the statements behind conv_num run whether or not it succeeded
                 switch (field) {
                     case TS_F_SEC: sec = v; break;
@@ -314,52 +364,10 @@ LC_TS_HD StrptimeResult strptimeRun(const Source& src, uint32_t len, ProgPtr pro
                 }
                 break;
             }
-            case TS_OP_EPOCH: {
-                // strtoll: white space, one sign, digits (saturating); then the reference keeps the first ten characters of the decimal
-                // rendering as the second and reads what follows the tenth byte OF THE BUFFER as the fraction
-                uint32_t p = 0;
-                while (p < len && tsIsSpace(src.at(p))) ++p;
-                bool neg = false;
-                if (p < len && (src.at(p) == '+' || src.at(p) == '-')) {
-                    neg = src.at(p) == '-';
-                    ++p;
-                }
-                uint64_t mag = 0;
-                const uint64_t lim = neg ? 9223372036854775808ull : 9223372036854775807ull;
-                uint32_t nd = 0;
-                bool sat = false;
-                while (p < len && tsIsDigit(src.at(p))) {
-                    const uint32_t d = src.at(p) - '0';
-                    if (sat || mag > (lim - d) / 10) {
-                        sat = true;
-                        mag = lim;
-                    } else {
-                        mag = mag * 10 + d;
-                    }
-                    ++p;
-                    ++nd;
-                }
-                uint32_t rendered = neg && mag ? 1u : 0u;  // std::to_string(n).length()
-                {
-                    uint64_t t = mag;
-                    do {
-                        ++rendered;
-                        t /= 10;
-                    } while (t);
-                }
-                const uint32_t keep = rendered >= 10 ? 10u : rendered;
-                for (uint32_t i = keep; i < rendered; ++i) mag /= 10;  // (truncation toward zero, the sign aside)
-                if (nd == 0 || mag == 0) {
-                    fail = true;
-                } else {
-                    epoch = 1;
-                    epochSecs = neg ? -int64_t(mag) : int64_t(mag);
-                    uint32_t q = keep;
-                    (void)tsConvNanos(src, len, q, nanos, fracLen);
-                    pos = p;
-                }
+            case TS_OP_EPOCH:
+                if (tsConvEpoch(src, len, epochSecs, nanos, fracLen, pos)) epoch = 1;
+                else fail = true;
                 break;
-            }
             case TS_OP_RESET_NS:
                 nanos = 0;
                 break;
