@@ -315,6 +315,9 @@ static int lcAllowLds(const void* kern, size_t lds) {
     return LC_OK;
 }
 
+#ifndef LC_TDFA_DEFER_STAMPS_DEFAULT
+#define LC_TDFA_DEFER_STAMPS_DEFAULT 0  // (what LC_TDFA_DEFER_STAMPS is when the environment does not say)
+#endif
 // The kernel behind a (workgroup size, table format) pair: the interleaved-issue kernel (tdfa_stream_kernel.hpp) for the
 // class-indexed tables with or without the byte-pair extension.
 template <int BLOCK, bool PAIR, bool COMPACT = false>
@@ -343,6 +346,18 @@ static int launchTdfaBlock(const void* dBlob, uint32_t blobBytes, uint32_t regBy
             kern = mopUp ? reinterpret_cast<const void*>(tdfa_stream_kernel<BLOCK, COMPACT, true, kOne | kMopUp>)
                          : reinterpret_cast<const void*>(tdfa_stream_kernel<BLOCK, COMPACT, true, kOne>);
             name = COMPACT ? "tdfa_stream_kernel<compact,nogeneral,pair1,dma>" : "tdfa_stream_kernel<nogeneral,pair1>";
+            // COMPACT, LC_TDFA_DEFER_STAMPS=1: the capture stamps wait in VGPRs until some lane of the wave holds two (tdfa_stream_kernel.hpp
+            // kLabDeferStamps; rows that start at the line's first byte only).  Exact, and measured SLOWER on the headline batch -- 0.2019-0.2034
+            // ms per step against 0.1672-0.1688 with a stamp per pair (profiles/tdfa_deferred_stamps_and_epilogue.md) --, so the default is
+            // off; =0 / =1 pick either whatever it is (read per launch: the A/B knob of one process, and of the parity tests)
+            if constexpr (COMPACT && LC_TDFA_ROW_ALIGN == 1) {
+                const char* e = getenv("LC_TDFA_DEFER_STAMPS");
+                const bool defer = e ? e[0] != '0' : bool(LC_TDFA_DEFER_STAMPS_DEFAULT);
+                if (defer) {
+                    kern = reinterpret_cast<const void*>(tdfa_stream_kernel<BLOCK, COMPACT, true, kOne | kLabDeferStamps>);
+                    name = "tdfa_stream_kernel<compact,nogeneral,pair1,dma,defer>";
+                }
+            }
         } else {
             kern = mopUp ? reinterpret_cast<const void*>(tdfa_stream_kernel<BLOCK, COMPACT, true, kMopUp>)
                          : reinterpret_cast<const void*>(tdfa_stream_kernel<BLOCK, COMPACT, true>);

@@ -75,7 +75,7 @@ __device__ __forceinline__ void tdfaWaveLdsSync() {
 // Measurement variants (tools/tdfa_lab.hip instantiates them; the product instantiates LAB = 0 and, for tables that carry no
 // general register program at all -- device_tables.h TD_NREGS_NO_GENERAL --, kTdfaNoGeneralPrograms).  They answer "what
 // does each of the three LDS instructions per byte cost" on the real kernel instead of a model of it:
-//   kLabNoStamp    phase 2 is skipped (capture offsets come out wrong: timing only)
+//   kLabNoStamp    phase 2 is skipped (capture offsets come out wrong: timing only); with kLabPairOne: no stamp and no settled doubles
 //   kLabPreClass   the input bytes ARE column offsets already (host pre-classified copy of the corpus): no class lookup
 //   kLabGlobalClass the class lookup goes to the 256-byte map in global memory (vector L1) instead of LDS
 //   kLabReplicated the transition table is stored 16 times, entry e of replica r at ((e * 16) + r) * 4: lane l reads replica
@@ -90,7 +90,8 @@ enum { kLabNoStamp = 1, kLabPreClass = 2, kLabGlobalClass = 4, kLabReplicated = 
        kLabWaves5 = 512 /* tdfa_stream_kernel: register budget of 5 waves per SIMD (96 VGPRs) */,
        kLabNoDmaWait = 1024 /* DMA staging without the wait for the stage (wrong bytes: timing only -- what the wave loses there) */,
        kLabPairOne = 4096 /* byte-pair chunks on a ONE-STAMP pair table (device_tables.h TP1_*, LC_TDFA_PAIR=2): exact */,
-       kLabMopUp = 8192 /* tdfa_stream_kernel: the launch behind a COMPACT one -- a small grid whose workgroups take the line blocks in turn */ };
+       kLabMopUp = 8192 /* tdfa_stream_kernel: the launch behind a COMPACT one -- a small grid whose workgroups take the line blocks in turn */,
+       kLabDeferStamps = 16384 /* one-stamp pair kernel, COMPACT: stamps wait in two VGPRs per lane until some lane holds two (exact) */ };
 constexpr int kTdfaNoGeneralPrograms = kLabNoGeneral;  // the product's second instantiation (gpu_runtime.hip launchTdfaBlock)
 
 // general register program (a list of moves); rare for log regexes
@@ -229,19 +230,35 @@ __device__ __forceinline__ void tdfaWriteResults(uint8_t* smem, uint32_t tileAdd
             }
         }
     }
+    constexpr uint32_t kTileWords = 1024;  // 64 rows x 64 bytes: the smaller of the two tile layouts
+    const bool viaTile = !permuted && nOut != 0 && nOut <= kTileWords && __all(live);
+    // Lines of one format end in the same accepting state: then the slot -> register map is the same for the whole wave
+    // and the row is built without a per-slot, per-lane map lookup and its branches.
+    const uint32_t fid0 = __builtin_amdgcn_readfirstlane(fid);
+    const bool sameMap = __all(fid == fid0) && fid0 != 0xFFFFu;
+    // The usual wave (one format, at most kRowRegs slots, at most 64 derive words): every lane reads the registers behind its nOut
+    // slots ONCE, into VGPRs -- the walk's are dead by now --, and the derive words are applied to the slot map (a derived slot
+    // reads as its source register + the sum of the deltas: wave-uniform) instead of to every lane's registers in LDS.  It used
+    // to be 24 register reads for 20 slots in each of the two passes, behind a read-add-write chain per derive word.
+    constexpr uint32_t kRowRegs = 24;
+    // one-stamp pair tables: a register that is only ever stamped one byte behind another one lost its own stamps and reads as that
+    // one + delta (device_tables.h TP_OFF_DERIVE; in table order: every source is settled before it is used)
+    uint32_t nDerive = 0;
+    const uint32_t* deriveWords = nullptr;
     if constexpr ((LAB & kLabPairOne) != 0) {
-        // one-stamp pair tables: a register that is only ever stamped one byte behind another one lost its own stamps and reads
-        // as that one + delta (device_tables.h TP_OFF_DERIVE; in table order: every source is settled before it is used)
         const uint32_t* ph = reinterpret_cast<const uint32_t*>(smem + hdr[TD_OFF_PAIR]);
         const uint32_t dOff = ph[TP_OFF_DERIVE];
         if (dOff) {
-            const uint32_t* dw = reinterpret_cast<const uint32_t*>(smem + dOff);
-            TdfaReg* rw = reinterpret_cast<TdfaReg*>(smem + regsBase) + tdfaRegLane<TdfaReg>(tid);
-            const uint32_t nWords = __builtin_amdgcn_readfirstlane(dw[0]);
-            for (uint32_t i = 0; i < nWords; ++i) {
-                const uint32_t w = __builtin_amdgcn_readfirstlane(dw[1 + i]);
-                rw[(w & 0xFFu) * BLOCK] = TdfaReg(rw[((w >> 8) & 0xFFu) * BLOCK] + TdfaReg(w >> 16));
-            }
+            deriveWords = reinterpret_cast<const uint32_t*>(smem + dOff) + 1;
+            nDerive = __builtin_amdgcn_readfirstlane(deriveWords[-1]);
+        }
+    }
+    const bool rowInRegs = viaTile && sameMap && nOut <= kRowRegs && nDerive <= 64;
+    if (!rowInRegs && nDerive != 0) {  // every other path reads the registers from LDS: the words are applied there, in table order
+        TdfaReg* rw = reinterpret_cast<TdfaReg*>(smem + regsBase) + tdfaRegLane<TdfaReg>(tid);
+        for (uint32_t i = 0; i < nDerive; ++i) {
+            const uint32_t w = __builtin_amdgcn_readfirstlane(deriveWords[i]);
+            rw[(w & 0xFFu) * BLOCK] = TdfaReg(rw[((w >> 8) & 0xFFu) * BLOCK] + TdfaReg(w >> 16));
         }
     }
     auto slotValue = [&](uint32_t s) -> int32_t {
@@ -253,23 +270,58 @@ __device__ __forceinline__ void tdfaWriteResults(uint8_t* smem, uint32_t tileAdd
         }
         return val;
     };
-    constexpr uint32_t kTileWords = 1024;  // 64 rows x 64 bytes: the smaller of the two tile layouts
-    if (!permuted && nOut != 0 && nOut <= kTileWords && __all(live)) {
+    if (viaTile) {
         int32_t* tile = reinterpret_cast<int32_t*>(smem + tileAddr);
         uint32_t rowsPerPass = kTileWords / nOut;
         if (rowsPerPass > 64) rowsPerPass = 64;
         if (rowsPerPass > 1) rowsPerPass &= ~1u;  // even: every pass starts on a 16-byte boundary of the capture table (nOut is even)
         int32_t* gout = caps + size_t(line - lane) * nOut;  // (lines of the wave are consecutive: line - lane = lane 0's)
-        // Lines of one format end in the same accepting state: then the slot -> register map is the same for the whole wave
-        // and the row is built without a per-slot, per-lane map lookup and its branches.
-        const uint32_t fid0 = __builtin_amdgcn_readfirstlane(fid);
-        const bool sameMap = __all(fid == fid0) && fid0 != 0xFFFFu;
         const int32_t end = int32_t(L + from);
+        int32_t rowv[kRowRegs];
+        if (rowInRegs) {
+            // lane i resolves slot i: its register, followed back through the derive words (last word first: a word's source is
+            // settled by the words before it), and the deltas met on the way
+            const uint8_t* map = finalMap + fid0 * nSlots;
+            const uint32_t mapv = (lane < nSlots && lane < nOut) ? uint32_t(map[lane]) : uint32_t(TD_REG_NONE);
+            const uint32_t dwv = lane < nDerive ? deriveWords[lane] : 0u;  // (lane i holds derive word i)
+            uint32_t root = mapv, dsum = 0;
+            for (uint32_t i = nDerive; i-- > 0;) {
+                const uint32_t w = uint32_t(__builtin_amdgcn_readlane(int(dwv), int(i)));
+                const bool hit = root == (w & 0xFFu);  // (TD_REG_POS / TD_REG_NONE are no register: never a word's target)
+                root = hit ? (w >> 8) & 0xFFu : root;
+                dsum += hit ? w >> 16 : 0u;
+            }
+#pragma unroll
+            for (int k = 0; k < int(kRowRegs); k += 2) {  // (nOut is even; wave-uniform: no read past the row's slots)
+                if (uint32_t(k) < nOut) {
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const uint32_t m = uint32_t(__builtin_amdgcn_readlane(int(root), k + h));
+                        const uint32_t d = uint32_t(__builtin_amdgcn_readlane(int(dsum), k + h));
+                        const uint32_t r = m < TD_REG_NONE ? m : 0u;
+                        const int32_t reg = int32_t(TdfaReg(regs[r * BLOCK + rl] + TdfaReg(d)) + from);
+                        int32_t val = m == TD_REG_POS ? end : reg;
+                        val = m == TD_REG_NONE ? -1 : val;
+                        rowv[k + h] = state != 0 ? val : -1;
+                    }
+                }
+            }
+        }
         for (uint32_t p0 = 0; p0 < 64; p0 += rowsPerPass) {
             tdfaWaveLdsSync();
             const bool inPass = lane >= p0 && lane - p0 < rowsPerPass;
             int32_t* row = tile + (inPass ? lane - p0 : 0u) * nOut;
-            if (sameMap) {
+            if (rowInRegs) {
+                if (inPass) {
+#pragma unroll
+                    for (int k = 0; k < int(kRowRegs); k += 2) {
+                        if (uint32_t(k) < nOut) {
+                            row[k] = rowv[k];
+                            row[k + 1] = rowv[k + 1];
+                        }
+                    }
+                }
+            } else if (sameMap) {
                 const uint8_t* map = finalMap + fid0 * nSlots;
                 for (uint32_t s0 = 0; s0 < nOut; s0 += 64) {  // (one trip unless the pattern has more than 32 groups)
                     const uint32_t sl = s0 + lane;

@@ -141,12 +141,61 @@ __device__ __forceinline__ uint32_t tdfaStreamPairChunk(uint32_t t, const uint32
 // max(register, pos + 1) -- only in chunks in which some lane of the wavefront met a DOUBLE.  Positions only grow along a line
 // and registers start at 0, so "latest" is "largest" and the order of the two kinds of store among themselves does not matter:
 // tests/helpers/table_interp.py TdfaPair1Interp is this function, store for store.
-template <int BLOCK, int NB, bool CHECKED, typename TdfaReg>
+//
+// DEFERRED stamps (kLabDeferStamps; 16-bit registers and rows that start at the line's first byte only).  On the headline corpus 6 %
+// of the pairs stamp a real register, the others the dummy row that nobody reads (profiles/round6_tdfa_why_not.md section 4) -- one
+// ds_write_b16 per pair, the dearest LDS instruction of the walk, for nothing.  Here a pair's stamp is an EVENT word (tdfaDeferEvent)
+// that a lane pushes onto a queue of two VGPRs (e1 = e0; e0 = event) if its register is a real one; the WAVE flushes -- e1, then e0,
+// every lane, empty slots into the dummy row as before -- as soon as some lane holds two.  After a pair every lane so holds at most
+// one event or the queue has just been emptied: two slots never overflow, however many real stamps a lane meets in a chunk.
+// Order: a lane's events leave first in, first out, and a wave's LDS stores land in issue order, so the latest stamp of a register
+// still lands last.  The settled DOUBLEs are max(register, pos + 1) and commute with plain stamps only as long as no plain stamp of
+// the same register with a SMALLER value lands behind them: the queue is flushed in front of the doubles of a chunk in which some
+// lane met one (tdfaSettleDoubles), and at the end of the line.  tests/helpers/deferred_stamps.py is this walk, store for store.
+// MEASURED (profiles/tdfa_deferred_stamps_and_epilogue.md): the walk without any stamp is 6 % faster than with one per pair
+// (0.1543 against 0.1645 ms per Mi lines of 512 bytes) -- and this one is 20 % SLOWER (0.1985): the push is six more VALU
+// instructions and a wave-uniform branch per pair in front of the next chain link, and the flush is taken every three or four
+// pairs.  It stays as a variant (gpu_runtime.hip LC_TDFA_DEFER_STAMPS=1, tools/tdfa_lab.hip); the default is a stamp per pair.
+__device__ __forceinline__ uint32_t tdfaDeferEvent(uint32_t entry, uint32_t posU) {
+    return (entry & 0x00FF0000u) | posU;  // bits 16..22 register index, bit 23 the +1 flag, low half the pair's position
+}
+template <int BLOCK, typename TdfaReg>
+__device__ __forceinline__ void tdfaDeferStore(uint32_t ev, uint32_t regAddr0) {
+    typedef LdsRegPtrT<TdfaReg> LdsRegPtr;
+    constexpr uint32_t kRegShift = (BLOCK == 1024 ? 12 : BLOCK == 512 ? 11 : BLOCK == 256 ? 10 : BLOCK == 128 ? 9 : 8) -
+                                   (sizeof(TdfaReg) == 2 ? 1 : 0);
+    uint32_t ra, delta, addr;
+    asm("v_bfe_u32 %0, %1, 16, 7" : "=v"(ra) : "v"(ev));
+    asm("v_lshl_add_u32 %0, %1, %2, %3" : "=v"(addr) : "v"(ra), "n"(kRegShift), "v"(regAddr0));
+    asm("v_bfe_u32 %0, %1, 23, 1" : "=v"(delta) : "v"(ev));
+    *reinterpret_cast<LdsRegPtr>(addr) = TdfaReg(ev + delta);  // (the store takes the low half: position + flag)
+}
+// every lane writes its two slots, oldest first, and empties them
+template <int BLOCK, typename TdfaReg>
+__device__ __forceinline__ void tdfaDeferFlush(uint32_t& e0, uint32_t& e1, uint32_t dummyEv, uint32_t regAddr0) {
+    tdfaDeferStore<BLOCK, TdfaReg>(e1, regAddr0);
+    tdfaDeferStore<BLOCK, TdfaReg>(e0, regAddr0);
+    e0 = dummyEv;
+    e1 = dummyEv;
+}
+// the stamp of one pair: pushed if it names a real register; the wave flushes when some lane holds two
+template <int BLOCK, typename TdfaReg>
+__device__ __forceinline__ void tdfaDeferPush(uint32_t entry, uint32_t posU, uint32_t& e0, uint32_t& e1, uint32_t dummyEv,
+                                              uint32_t regAddr0) {
+    const uint32_t ev = tdfaDeferEvent(entry, posU);
+    const bool real = (entry & 0x007F0000u) != dummyEv;  // (dummyEv: the dummy register's index in bits 16..22, nothing else)
+    e1 = real ? e0 : e1;
+    e0 = real ? ev : e0;
+    if (__any(e1 != dummyEv)) tdfaDeferFlush<BLOCK, TdfaReg>(e0, e1, dummyEv, regAddr0);
+}
+
+template <int BLOCK, int NB, bool CHECKED, typename TdfaReg, int LAB = 0>
 __device__ __forceinline__ uint32_t tdfaStreamPair1Chunk(uint32_t t, const uint32_t (&colp)[NB / 2], uint32_t (&na)[NB / 2],
                                                          uint32_t (&nc)[NB / 2], const uint32_t (&nwords)[NB / 4], uint32_t nbase,
                                                          uint32_t L, uint32_t cmapA, uint32_t idAAddr,
                                                          const uint32_t (&ptt)[NB / 2], uint32_t (&tt)[NB / 2], uint32_t pbase,
-                                                         uint32_t regAddr0, const uint8_t* __restrict__ gcmap8 = nullptr) {
+                                                         uint32_t regAddr0, uint32_t& e0, uint32_t& e1, uint32_t dummyEv,
+                                                         const uint8_t* __restrict__ gcmap8 = nullptr) {
     typedef LdsRegPtrT<TdfaReg> LdsRegPtr;
     constexpr uint32_t kRegShift = (BLOCK == 1024 ? 12 : BLOCK == 512 ? 11 : BLOCK == 256 ? 10 : BLOCK == 128 ? 9 : 8) -
                                    (sizeof(TdfaReg) == 2 ? 1 : 0);  // log2(BLOCK * sizeof(TdfaReg))
@@ -172,6 +221,11 @@ __device__ __forceinline__ uint32_t tdfaStreamPair1Chunk(uint32_t t, const uint3
 #endif
         }
         // the previous chunk's pair p: ONE stamp
+        if constexpr ((LAB & kLabNoStamp) != 0) {
+            // (timing only: what the walk costs without any stamp -- the ceiling of what deferring them can buy)
+        } else if constexpr ((LAB & kLabDeferStamps) != 0) {
+            tdfaDeferPush<BLOCK, TdfaReg>(ptt[p], __builtin_amdgcn_readfirstlane(pbase) + uint32_t(2 * p), e0, e1, dummyEv, regAddr0);
+        } else
 #if LC_TDFA_STAMP_ISA
         // Round 6: the stamp's address and value in FOUR instructions instead of the six the compiler picks (v_lshrrev 6, v_and
         // 0x1fc00, v_add | v_lshrrev 23, v_and_or, v_or: profiles/round5_tdfa_isa_budget.md, 3.25 of the kernel's 7.47 VALU per line
@@ -198,8 +252,9 @@ __device__ __forceinline__ uint32_t tdfaStreamPair1Chunk(uint32_t t, const uint3
     return t;
 }
 // the second registers of the DOUBLE entries among ptt[] (the pairs at line offset pbase, pbase + 2, ...): behind their chunk's stamps
-template <int BLOCK, int NP, typename TdfaReg>
-__device__ __forceinline__ void tdfaSettleDoubles(const uint32_t (&ptt)[NP], uint32_t pbase, uint32_t regAddr0) {
+template <int BLOCK, int NP, typename TdfaReg, int LAB = 0>
+__device__ __forceinline__ void tdfaSettleDoubles(const uint32_t (&ptt)[NP], uint32_t pbase, uint32_t regAddr0, uint32_t& e0,
+                                                  uint32_t& e1, uint32_t dummyEv) {
     typedef LdsRegPtrT<TdfaReg> LdsRegPtr;
     constexpr uint32_t kRegShift = (BLOCK == 1024 ? 12 : BLOCK == 512 ? 11 : BLOCK == 256 ? 10 : BLOCK == 128 ? 9 : 8) -
                                    (sizeof(TdfaReg) == 2 ? 1 : 0);
@@ -207,6 +262,9 @@ __device__ __forceinline__ void tdfaSettleDoubles(const uint32_t (&ptt)[NP], uin
 #pragma unroll
     for (int p = 0; p < NP; ++p) any |= ptt[p];
     if (!__any(int32_t(any) < 0)) return;  // (the usual case: no lane of the wavefront met a DOUBLE in this chunk)
+    // deferred stamps: max(register, pos + 1) is only "the latest stamp" if every plain stamp that comes before it in the line HAS
+    // landed -- a pending one of the same register (smaller value) would overwrite the settled one later.  The queue goes first.
+    if constexpr ((LAB & kLabDeferStamps) != 0) tdfaDeferFlush<BLOCK, TdfaReg>(e0, e1, dummyEv, regAddr0);
 #pragma unroll
     for (int p = 0; p < NP; ++p) {
         if (int32_t(ptt[p]) < 0) {
@@ -255,6 +313,10 @@ __device__ __forceinline__ void tdfaStreamBody(
     constexpr bool DMA = COMPACT && (LAB & kLabDmaStage) != 0 && kTdfaStageBytes == 64;
     constexpr bool PAIR1 = PAIR && (LAB & kLabPairOne) != 0;  // the pair table is a ONE-STAMP table (the launcher checks TP_FORMAT)
     static_assert(!PAIR1 || (LAB & kLabNoGeneral) != 0, "one-stamp pair tables have no general register programs");
+    constexpr bool DEFER = PAIR1 && (LAB & kLabDeferStamps) != 0;
+    static_assert(!DEFER || (COMPACT && LC_TDFA_ROW_ALIGN == 1), "deferred stamps: 16-bit positions, wave-uniform pair positions");
+    // the chunk function's LAB bits (the stamp variants)
+    constexpr int kStampLab = LAB & (kLabDeferStamps | kLabNoStamp);
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t tid = threadIdx.x;
     if (nLinesPtr) {
@@ -460,6 +522,9 @@ __device__ __forceinline__ void tdfaStreamBody(
         for (int j = 0; j < NC; ++j) ptt[j] = dummyT;
     }
     uint32_t pbase = 0;
+    // the deferred-stamp queue (two events per lane; empty = the dummy register's event)
+    const uint32_t dummyEv = PAIR1 ? __builtin_amdgcn_readfirstlane(dummyT) : 0u;
+    uint32_t e0 = dummyEv, e1 = dummyEv;
 
     if constexpr ((LAB & kLabNoLoop) != 0) maxStages = 0;
     for (uint32_t s = 0; s < maxStages; ++s) {
@@ -521,9 +586,9 @@ __device__ __forceinline__ void tdfaStreamBody(
             bool general;
             if constexpr (PAIR1) {
                 uint32_t na[NC], nc[NC];
-                if (ALLFULL || waveFull || __all(fullNext)) t = tdfaStreamPair1Chunk<BLOCK, NB, false, TdfaReg>(t, col, na, nc, nwords, nbase, L, pi.cmapA, idAAddr, ptt, tt, pbase, regAddr0, reinterpret_cast<const uint8_t*>(blob) + TD_CMAP_OFFSET);
-                else t = tdfaStreamPair1Chunk<BLOCK, NB, true, TdfaReg>(t, col, na, nc, nwords, nbase, L, pi.cmapA, idAAddr, ptt, tt, pbase, regAddr0);
-                tdfaSettleDoubles<BLOCK, NC, TdfaReg>(ptt, pbase, regAddr0);
+                if (ALLFULL || waveFull || __all(fullNext)) t = tdfaStreamPair1Chunk<BLOCK, NB, false, TdfaReg, kStampLab>(t, col, na, nc, nwords, nbase, L, pi.cmapA, idAAddr, ptt, tt, pbase, regAddr0, e0, e1, dummyEv, reinterpret_cast<const uint8_t*>(blob) + TD_CMAP_OFFSET);
+                else t = tdfaStreamPair1Chunk<BLOCK, NB, true, TdfaReg, kStampLab>(t, col, na, nc, nwords, nbase, L, pi.cmapA, idAAddr, ptt, tt, pbase, regAddr0, e0, e1, dummyEv);
+                if constexpr ((LAB & kLabNoStamp) == 0) tdfaSettleDoubles<BLOCK, NC, TdfaReg, kStampLab>(ptt, pbase, regAddr0, e0, e1, dummyEv);
 #pragma unroll
                 for (int j = 0; j < NC; ++j) ncol[j] = na[j] + nc[j];
                 seen = 0;
@@ -599,13 +664,23 @@ __device__ __forceinline__ void tdfaStreamBody(
         if (__all((t & 0xFFFFu) == deadRow || s + 1 >= myStages)) break;
     }
     if constexpr (DMA) tdfaDmaWait();  // (a stage in flight when the loop was left would land in the result tile)
-    if constexpr (PAIR1) {  // the last chunk's stamps
+    if constexpr (PAIR1 && (LAB & kLabNoStamp) != 0) {
+        // (timing only: no stamps at all)
+    } else if constexpr (DEFER) {
+        // the last chunk's stamps go through the queue like every other, then the queue is emptied whatever it holds: no event
+        // is left behind (the doubles of the last chunk are settled behind it, as everywhere)
+#pragma unroll
+        for (int j = 0; j < NC; ++j)
+            tdfaDeferPush<BLOCK, TdfaReg>(ptt[j], __builtin_amdgcn_readfirstlane(pbase) + uint32_t(2 * j), e0, e1, dummyEv, regAddr0);
+        tdfaDeferFlush<BLOCK, TdfaReg>(e0, e1, dummyEv, regAddr0);
+        tdfaSettleDoubles<BLOCK, NC, TdfaReg>(ptt, pbase, regAddr0, e0, e1, dummyEv);
+    } else if constexpr (PAIR1) {  // the last chunk's stamps
         constexpr uint32_t kRegShift = (BLOCK == 1024 ? 12 : BLOCK == 512 ? 11 : BLOCK == 256 ? 10 : BLOCK == 128 ? 9 : 8) -
                                        (sizeof(TdfaReg) == 2 ? 1 : 0);
 #pragma unroll
         for (int j = 0; j < NC; ++j)
             *reinterpret_cast<LdsRegPtr>(regAddr0 + (((ptt[j] >> 16) & 0x7Fu) << kRegShift)) = TdfaReg(pbase + 2 * j + ((ptt[j] >> 23) & 1u));
-        tdfaSettleDoubles<BLOCK, NC, TdfaReg>(ptt, pbase, regAddr0);
+        tdfaSettleDoubles<BLOCK, NC, TdfaReg>(ptt, pbase, regAddr0, e0, e1, dummyEv);
     } else if constexpr ((LAB & kLabNoStamp) == 0) {  // the last chunk's stamps
         if constexpr (PAIR) {
             constexpr uint32_t kRegShift = (BLOCK == 1024 ? 12 : BLOCK == 512 ? 11 : BLOCK == 256 ? 10 : BLOCK == 128 ? 9 : 8) -

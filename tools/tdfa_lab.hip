@@ -249,6 +249,16 @@ int main(int argc, char** argv) {
         runVariant<512, kLabNoGeneral | kLabPairOne | kLabDmaStage, false, true>("stream 512 PAIR1, DMA (again)", in, d, &refCaps, &refStatus, iters);
         runVariant<512, kLabNoGeneral | kLabPairOne | kLabDmaStage | kLabNoOutput, false, true>("stream 512 PAIR1, DMA, no output", in, d, &refCaps, &refStatus, iters);
         runVariant<512, kLabNoGeneral | kLabPairOne | kLabDmaStage, true, true>("stream 512 PAIR1, DMA, pool", in, d, &refCaps, &refStatus, iters);
+        // the stamps of the one-stamp pair walk: none at all (timing only: the ceiling of deferring them), deferred (exact), and the
+        // kernel with a stamp per pair between them, twice over (drift of the box within one process)
+        runVariant<512, kLabNoGeneral | kLabPairOne | kLabDmaStage | kLabNoStamp, false, true>("stream 512 PAIR1, DMA, NO stamps", in, d, &refCaps, &refStatus, iters);
+        if constexpr (LC_TDFA_ROW_ALIGN == 1)  // (deferred stamps need rows that start at the line's first byte)
+            runVariant<512, kLabNoGeneral | kLabPairOne | kLabDmaStage | kLabDeferStamps, false, true>("stream 512 PAIR1, DMA, deferred", in, d, &refCaps, &refStatus, iters);
+        runVariant<512, kLabNoGeneral | kLabPairOne | kLabDmaStage, false, true>("stream 512 PAIR1, DMA (3rd)", in, d, &refCaps, &refStatus, iters);
+        runVariant<512, kLabNoGeneral | kLabPairOne | kLabDmaStage | kLabNoStamp, false, true>("PAIR1, DMA, NO stamps (again)", in, d, &refCaps, &refStatus, iters);
+        if constexpr (LC_TDFA_ROW_ALIGN == 1)
+            runVariant<512, kLabNoGeneral | kLabPairOne | kLabDmaStage | kLabDeferStamps, false, true>("PAIR1, DMA, deferred (again)", in, d, &refCaps, &refStatus, iters);
+        runVariant<512, kLabNoGeneral | kLabPairOne | kLabDmaStage, false, true>("stream 512 PAIR1, DMA (4th)", in, d, &refCaps, &refStatus, iters);
         return 0;
     }
     if (in.blob[TD_OFF_PAIR] && getenv("LAB_DMA")) {
