@@ -59,11 +59,27 @@ def _pack(subs):
     return data, off, length
 
 
+# One wave of every corpus from 128 lines on (lines 64..127) is ALL LONG: 200..260 bytes, no short line in it, so that its shortest span
+# lets whole stages run the copy of the chunk loop that does not ask (ALLFULL) and the deferred-stamp queue is walked by that copy too.
+LONG_WAVE = range(64, 128)
+
+
+def _long_a_lines():
+    out = []
+    for w in (200, 213, 231, 248, 260):
+        data, off, length = corpus.apache_batch(13, "A", line_bytes=w, pool_lines=64)
+        out += [bytes(data[off[i]:off[i] + length[i]]) for i in range(13)]
+    return out
+
+
 def _regex_a_lines(n, rng):
     data, off, length = corpus.apache_batch(n, "A", empty_every=5)
     subs = [bytes(data[off[i]:off[i] + length[i]]) for i in range(n)]
+    long_lines = _long_a_lines() if n > LONG_WAVE[0] else []
     for i in range(n):
-        if i % 64 == 7:
+        if i in LONG_WAVE:
+            subs[i] = long_lines[i - LONG_WAVE[0]]
+        elif i % 64 == 7:
             subs[i] = b"no match " + subs[i][:40]                  # a line that fails in every wave
         elif i % 3 == 1:                                          # ragged: the free last field cut or stretched, 0..600 bytes
             want = int(rng.integers(0, 601))
@@ -77,7 +93,9 @@ def _field_lines(n, rng):
     alphabet = list(b"ab1 ,;_9")
     subs = []
     for i in range(n):
-        if i % 64 == 9:
+        if i in LONG_WAVE:
+            subs.append(b"ab" + b"c" * (i % 3) + b"," + b"7" * (i % 4) + b";xy" + bytes(rng.choice(alphabet, size=194 + (i * 7) % 50).astype(np.uint8)))
+        elif i % 64 == 9:
             subs.append(b";;no comma")
         elif i % 4 == 0:
             subs.append(b"ab" + b"c" * (i % 3) + b"," + b"7" * (i % 4) + b";xy" + bytes(rng.choice(alphabet, size=int(rng.integers(0, 600))).astype(np.uint8)))
@@ -93,7 +111,9 @@ def _field_lines(n, rng):
 def _chain_lines(n, rng):
     subs = []
     for i in range(n):
-        if i % 64 == 11:
+        if i in LONG_WAVE:
+            subs.append(b"abcdefghi " + b"7" * (i % 5) + b" " + b"r" * (189 + (i * 11) % 46))
+        elif i % 64 == 11:
             subs.append(b"abcdefgh 1")
         else:
             subs.append(b"abcdefghi " + b"7" * (i % 5) + (b" " + b"r" * int(rng.integers(0, 590)) if i % 2 else b""))
