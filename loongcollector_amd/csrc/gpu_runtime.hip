@@ -301,11 +301,14 @@ struct DoneRequest {
 static thread_local DoneRequest tlsDone;
 static thread_local bool tlsJobTableInPlace = false;  // lcSetJobTableInPlace (zero-copy trips of the processors, below)
 
-// hipFuncSetAttribute for a launch that asks for more than the default 64 KiB of LDS: once per (kernel, device) and size
-static int lcAllowLds(const void* kern, size_t lds) {
-    if (lds <= 64 * 1024) return LC_OK;
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
+static hipStream_t streamOf(const MatchBatch& b) { return static_cast<hipStream_t>(b.stream); }
+// an argument slot of hipLaunchKernel's array (the runtime only reads through it)
+template <class T>
+static void* kernelArg(const T& v) { return const_cast<T*>(&v); }
+
+// hipFuncSetAttribute for a launch that asks for more than 48 KiB of LDS (runtime_internal.hpp): once per (kernel, device) and size
+int lcAllowLds(const void* kern, int dev, size_t lds) {
+    if (lds <= 48 * 1024) return LC_OK;
     static thread_local std::map<std::pair<const void*, int>, size_t> set;  // the attribute belongs to (function, device)
     size_t& have = set[{kern, dev}];
     if (lds > have) {
@@ -315,16 +318,29 @@ static int lcAllowLds(const void* kern, size_t lds) {
     return LC_OK;
 }
 
+// What a launch of the LDS kernels takes beside the batch: the tables' device copy with their LDS budget, and what ties a COMPACT launch
+// to the mop-up launch behind it (minLen != 0: only lines at least that long; the long-line flag and this launch's number in it).
+// nregsWord: the blob's TD_NREGS; pairOne: its byte-pair extension is a one-stamp table.
+struct TdfaTablesArg {
+    const void* dBlob;
+    uint32_t blobBytes, regBytes;
+    size_t lds;
+    uint32_t minLen;
+    uint32_t* longFlag;
+    uint32_t seq;
+    uint32_t nregsWord;
+    bool pairOne;
+};
+
 #ifndef LC_TDFA_DEFER_STAMPS_DEFAULT
 #define LC_TDFA_DEFER_STAMPS_DEFAULT 0  // (what LC_TDFA_DEFER_STAMPS is when the environment does not say)
 #endif
 // The kernel behind a (workgroup size, table format) pair: the interleaved-issue kernel (tdfa_stream_kernel.hpp) for the
 // class-indexed tables with or without the byte-pair extension.
 template <int BLOCK, bool PAIR, bool COMPACT = false>
-static int launchTdfaBlock(const void* dBlob, uint32_t blobBytes, uint32_t regBytes, size_t lds, const uint8_t* d_data,
-                           const uint32_t* d_off, const uint32_t* d_len, uint32_t sep, uint32_t minLen, uint32_t n, const uint32_t* d_n, const uint32_t* d_order, const uint32_t* d_resume, uint32_t ngroups,
-                           int32_t* d_caps, uint8_t* d_status, hipStream_t stream, uint32_t* longFlag = nullptr, uint32_t seq = 0,
-                           uint32_t nregsWord = 0, bool pairOne = false) {
+static int launchTdfaBlock(const TdfaTablesArg& t, const MatchBatch& b) {
+    const uint32_t minLen = t.minLen, nregsWord = t.nregsWord;
+    const bool pairOne = t.pairOne;
     // tables without any general register program (TD_NREGS_NO_GENERAL: the usual case once multi-stamp programs are folded,
     // regex_handle.cpp) run the instantiation that neither tracks nor replays them; LC_TDFA_NOGEN=0 keeps the checking one
     static const bool noGenOff = [] {
@@ -382,19 +398,19 @@ static int launchTdfaBlock(const void* dBlob, uint32_t blobBytes, uint32_t regBy
         const char* e = getenv("LC_TDFA_EXTRA_LDS");
         return e ? size_t(atol(e)) : size_t(0);
     }();
-    lds += extraLds;
-    if (const int rc = lcAllowLds(kern, lds); rc != LC_OK) return rc;
-    uint32_t grid = (n + BLOCK - 1) / BLOCK;
+    const size_t lds = t.lds + extraLds;
+    if (const int rc = lcAllowLds(kern, b.dev, lds); rc != LC_OK) return rc;
+    uint32_t grid = (b.n + BLOCK - 1) / BLOCK;
     if (mopUp) grid = std::min(grid, 256u);
     noteKernel(name);
     // (hipLaunchKernel reports the launch's own status: no second runtime call to fetch it)
-    const uint32_t* blobArg = static_cast<const uint32_t*>(dBlob);
+    const uint32_t* blobArg = static_cast<const uint32_t*>(t.dBlob);
     // completion signal requested by the zero-copy host path (tlsDone, below): this launch carries it when it is the match's
     // only launch (no mop-up launch follows, nothing runs behind it)
     uint32_t* doneCounter = nullptr;
     uint32_t* doneFlag = nullptr;
     uint32_t doneSeq = 0;
-    if (tlsDone.armed && minLen == 0 && longFlag == nullptr) {
+    if (tlsDone.armed && minLen == 0 && t.longFlag == nullptr) {
         doneCounter = tlsDone.counter;
         doneFlag = tlsDone.flag;
         doneSeq = tlsDone.seq;
@@ -405,9 +421,11 @@ static int launchTdfaBlock(const void* dBlob, uint32_t blobBytes, uint32_t regBy
     // batch: 0.243 ms against 0.227 -- the dispatcher already starts a new workgroup the moment one retires, in the middle of
     // the other resident workgroups' loops, which hides the prologue better than a wave serialising its own epilogue and
     // prologue does.)
-    void* args[] = {&d_data, &d_off, &d_len, &sep, &minLen, &n, &d_n, &d_order, &d_resume, &blobArg, &blobBytes, &regBytes, &ngroups,
-                    &d_caps, &d_status, &longFlag, &seq, &doneCounter, &doneFlag, &doneSeq};
-    HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(BLOCK), args, lds, stream));
+    void* args[] = {kernelArg(b.d_data), kernelArg(b.d_off), kernelArg(b.d_len), kernelArg(b.sep), kernelArg(minLen), kernelArg(b.n),
+                    kernelArg(b.d_n), kernelArg(b.d_order), kernelArg(b.d_resume), &blobArg, kernelArg(t.blobBytes), kernelArg(t.regBytes),
+                    kernelArg(b.ngroups), kernelArg(b.d_caps), kernelArg(b.d_status), kernelArg(t.longFlag), kernelArg(t.seq), &doneCounter,
+                    &doneFlag, &doneSeq};
+    HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(BLOCK), args, lds, streamOf(b)));
     return LC_OK;
 }
 
@@ -421,14 +439,12 @@ static bool lcPairOneFormat(const std::vector<uint32_t>& blob) {
 // words on the host (header fields); `dBlob`: its device copy.  pendingFlag / seq: lazy automata only (TL_MISS) -- where a line that
 // stepped on an uncomputed transition raises the launch's pending flag.  launchTdfa (the LDS kernels) serves a handle that asked for the
 // wave walk (`waveByChoice`) when LC_TDFA_WAVE_MAX=0 takes the wave walk away.
-static int launchTdfa(lc_regex* re, int dev, const uint8_t* d_data, const uint32_t* d_off, const uint32_t* d_len,
-                      uint32_t sep, uint32_t n, const uint32_t* d_n, const uint32_t* d_order, const uint32_t* d_resume, uint32_t ngroups, int32_t* d_caps,
-                      uint8_t* d_status, hipStream_t stream);
-static int launchTdfaL2Family(lc_regex* re, const uint32_t* hostBlob, const void* dBlob, bool waveByChoice, int dev, const uint8_t* d_data,
-                              const uint32_t* d_off, const uint32_t* d_len, uint32_t sep, uint32_t n, const uint32_t* d_n,
-                              const uint32_t* d_order, const uint32_t* d_resume, uint32_t ngroups, int32_t* d_caps, uint8_t* d_status,
-                              hipStream_t stream, uint32_t* pendingFlag, uint32_t seq) {
+static int launchTdfa(lc_regex* re, const MatchBatch& b);
+static int launchTdfaL2Family(lc_regex* re, const uint32_t* hostBlob, const void* dBlob, bool waveByChoice, const MatchBatch& b,
+                              uint32_t* pendingFlag, uint32_t seq) {
     const uint32_t nRegs = hostBlob[TL_NREGS];
+    const uint32_t n = b.n;
+    hipStream_t stream = streamOf(b);
     // Small and medium batches wait for their longest value: ONE VALUE PER WAVEFRONT (tdfa_wave_kernel: wave-uniform state, quiet
     // runs crossed 256 bytes at a time).  Large batches are about values in flight: one value per lane.  LC_TDFA_WAVE_MAX: the
     // largest batch that takes the wave kernel (0 = never; A/B measurements).
@@ -437,7 +453,7 @@ static int launchTdfaL2Family(lc_regex* re, const uint32_t* hostBlob, const void
     const uint32_t waveMax = uint32_t(waveEnv ? atol(waveEnv) : 65536);
     const bool perWave = n <= waveMax && (waveMax != 0 || !waveByChoice);
     if (waveByChoice && !perWave)  // (LC_TDFA_WAVE_MAX=0: the LDS kernels, as if the handle had not asked)
-        return launchTdfa(re, dev, d_data, d_off, d_len, sep, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, stream);
+        return launchTdfa(re, b);
     size_t lds = perWave ? size_t(nRegs) * kTdfaWaveValues * 4 : size_t(nRegs) * kTdfaL2Block * 4;
     // the register programs (opsStart + ops, contiguous in the blob) ride in LDS when the batch is small (tdfa_l2_kernel.hpp)
     uint32_t stageBytes = 0;
@@ -446,38 +462,37 @@ static int launchTdfaL2Family(lc_regex* re, const uint32_t* hostBlob, const void
         const uint32_t progBytes = (hostBlob[TL_OFF_FINALID] - hostBlob[TL_OFF_OPSSTART] + 3u) & ~3u;
         if (!stageOffAll && n <= 32768 && progBytes <= 40 * 1024 && lds + progBytes <= 60 * 1024) stageBytes = progBytes;
     }
+    lds += stageBytes;
     if (perWave) {
-        lds += stageBytes;
-        static thread_local size_t waveLdsAttrSet[kLcMaxDevices] = {};
-        if (lds > 48 * 1024 && dev < kLcMaxDevices && lds > waveLdsAttrSet[dev]) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(tdfa_wave_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-            waveLdsAttrSet[dev] = lds;
-        }
+        if (const int rc = lcAllowLds(reinterpret_cast<const void*>(tdfa_wave_kernel), b.dev, lds); rc != LC_OK) return rc;
         noteKernel(pendingFlag ? "tdfa_l2_kernel:wave:lazy" : "tdfa_l2_kernel:wave");
         hipLaunchKernelGGL(tdfa_wave_kernel, dim3((n + kTdfaWaveValues - 1) / kTdfaWaveValues), dim3(kTdfaWaveBlock), lds, stream,
-                           d_data, d_off, d_len, sep, n, d_n, d_order, d_resume, static_cast<const uint32_t*>(dBlob), ngroups, d_caps,
-                           d_status, stageBytes, pendingFlag, seq);
+                           b.d_data, b.d_off, b.d_len, b.sep, n, b.d_n, b.d_order, b.d_resume, static_cast<const uint32_t*>(dBlob), b.ngroups,
+                           b.d_caps, b.d_status, stageBytes, pendingFlag, seq);
         HIP_TRY(hipGetLastError());
         return LC_OK;
     }
-    lds += stageBytes;
-    static thread_local size_t ldsAttrSet[kLcMaxDevices] = {};
-    if (lds > 48 * 1024 && dev < kLcMaxDevices && lds > ldsAttrSet[dev]) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(tdfa_l2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-        ldsAttrSet[dev] = lds;
-    }
+    if (const int rc = lcAllowLds(reinterpret_cast<const void*>(tdfa_l2_kernel), b.dev, lds); rc != LC_OK) return rc;
     noteKernel(pendingFlag ? "tdfa_l2_kernel:lazy" : "tdfa_l2_kernel");
     // (no completion signal of its own: a caller that polls queues lc_signal_kernel behind it, see tlsDone)
-    hipLaunchKernelGGL(tdfa_l2_kernel, dim3((n + kTdfaL2Block - 1) / kTdfaL2Block), dim3(kTdfaL2Block), lds, stream, d_data, d_off,
-                       d_len, sep, n, d_n, d_order, d_resume, static_cast<const uint32_t*>(dBlob), ngroups, d_caps, d_status, stageBytes,
-                       pendingFlag, seq);
+    hipLaunchKernelGGL(tdfa_l2_kernel, dim3((n + kTdfaL2Block - 1) / kTdfaL2Block), dim3(kTdfaL2Block), lds, stream, b.d_data, b.d_off,
+                       b.d_len, b.sep, n, b.d_n, b.d_order, b.d_resume, static_cast<const uint32_t*>(dBlob), b.ngroups, b.d_caps, b.d_status,
+                       stageBytes, pendingFlag, seq);
     HIP_TRY(hipGetLastError());
     return LC_OK;
 }
 
-static int launchTdfa(lc_regex* re, int dev, const uint8_t* d_data, const uint32_t* d_off, const uint32_t* d_len,
-                      uint32_t sep, uint32_t n, const uint32_t* d_n, const uint32_t* d_order, const uint32_t* d_resume, uint32_t ngroups, int32_t* d_caps,
-                      uint8_t* d_status, hipStream_t stream) {
+// launchTdfaBlock's instantiations, [workgroup size, largest first][0: with the byte-pair table, 1: without]: the COMPACT launch and
+// the main one
+typedef int (*TdfaBlockFn)(const TdfaTablesArg&, const MatchBatch&);
+static const TdfaBlockFn kTdfaCompactLaunch[2][2] = {{launchTdfaBlock<512, true, true>, launchTdfaBlock<512, false, true>},
+                                                     {launchTdfaBlock<256, true, true>, launchTdfaBlock<256, false, true>}};
+static const TdfaBlockFn kTdfaLaunch[3][2] = {{launchTdfaBlock<256, true>, launchTdfaBlock<256, false>},
+                                              {launchTdfaBlock<128, true>, launchTdfaBlock<128, false>},
+                                              {launchTdfaBlock<64, true>, launchTdfaBlock<64, false>}};
+
+static int launchTdfa(lc_regex* re, const MatchBatch& b) {
+    const int dev = b.dev;
     void* dBlob = nullptr;
     int rc = ensureUploaded(re, dev, kBlobTdfa, &dBlob);
     if (rc != LC_OK) return rc;
@@ -488,7 +503,7 @@ static int launchTdfa(lc_regex* re, int dev, const uint8_t* d_data, const uint32
     uint32_t minLen = 0;
     uint32_t* longFlag = nullptr;
     uint32_t seq = 0;
-    if (!re->tdfaWideBlob.empty() && (re->tdfaWideForced || n >= kCompactMinLines)) {
+    if (!re->tdfaWideBlob.empty() && (re->tdfaWideForced || b.n >= kCompactMinLines)) {
         void* dWide = nullptr;
         rc = ensureUploaded(re, dev, kBlobTdfaWide, &dWide);
         if (rc != LC_OK) return rc;
@@ -496,20 +511,20 @@ static int launchTdfa(lc_regex* re, int dev, const uint8_t* d_data, const uint32
         longFlag = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(dWide) + wideBytes);
         seq = ++re->tdfaWideSeq[dev];
         if (seq == 0) {  // the 32-bit sequence wrapped: start over below every flag value seen so far
-            HIP_TRY(hipMemsetAsync(longFlag, 0, 4, stream));
+            HIP_TRY(hipMemsetAsync(longFlag, 0, 4, streamOf(b)));
             seq = ++re->tdfaWideSeq[dev];
         }
         const int wb = re->tdfaWideBlock;
-        const uint32_t wRegBytes = uint32_t(size_t(re->tdfaWidePackedRegs + 1) * size_t(wb) * 2);
-        const size_t wLds = lcTdfaCompactLdsBytes(wideBytes, re->tdfaWidePackedRegs, wb);
-        if (wb == 512 && re->tdfaWideBlob[TD_OFF_PAIR])
-            rc = launchTdfaBlock<512, true, true>(dWide, wideBytes, wRegBytes, wLds, d_data, d_off, d_len, sep, 0, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, stream, longFlag, seq, re->tdfaWideBlob[TD_NREGS], lcPairOneFormat(re->tdfaWideBlob));
-        else if (wb == 512)
-            rc = launchTdfaBlock<512, false, true>(dWide, wideBytes, wRegBytes, wLds, d_data, d_off, d_len, sep, 0, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, stream, longFlag, seq, re->tdfaWideBlob[TD_NREGS]);
-        else if (re->tdfaWideBlob[TD_OFF_PAIR])
-            rc = launchTdfaBlock<256, true, true>(dWide, wideBytes, wRegBytes, wLds, d_data, d_off, d_len, sep, 0, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, stream, longFlag, seq, re->tdfaWideBlob[TD_NREGS], lcPairOneFormat(re->tdfaWideBlob));
-        else
-            rc = launchTdfaBlock<256, false, true>(dWide, wideBytes, wRegBytes, wLds, d_data, d_off, d_len, sep, 0, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, stream, longFlag, seq, re->tdfaWideBlob[TD_NREGS]);
+        const TdfaTablesArg compact{.dBlob = dWide,
+                                    .blobBytes = wideBytes,
+                                    .regBytes = uint32_t(size_t(re->tdfaWidePackedRegs + 1) * size_t(wb) * 2),
+                                    .lds = lcTdfaCompactLdsBytes(wideBytes, re->tdfaWidePackedRegs, wb),
+                                    .minLen = 0,
+                                    .longFlag = longFlag,
+                                    .seq = seq,
+                                    .nregsWord = re->tdfaWideBlob[TD_NREGS],
+                                    .pairOne = re->tdfaWideBlob[TD_OFF_PAIR] && lcPairOneFormat(re->tdfaWideBlob)};
+        rc = kTdfaCompactLaunch[wb == 512 ? 0 : 1][re->tdfaWideBlob[TD_OFF_PAIR] ? 0 : 1](compact, b);
         if (rc != LC_OK) return rc;
         minLen = kTdfaWideMaxLine + 1;
     }
@@ -519,16 +534,19 @@ static int launchTdfa(lc_regex* re, int dev, const uint8_t* d_data, const uint32
         tlsError = "tdfa tables + registers exceed LDS";
         return LC_ERR_UNSUPPORTED;
     }
-    const size_t lds = lcTdfaLdsBytes(blobBytes, re->tdfaPackedRegs, block);
-    const uint32_t regBytes = uint32_t(lcTdfaRegBytes(re->tdfaPackedRegs, block));
     // small automata carry a byte-pair transition table: half as many dependent LDS lookups per byte
     static const bool pairOff = getenv("LC_TDFA_NO_PAIR") != nullptr;
     const bool pair = re->tdfaBlob[TD_OFF_PAIR] != 0 && !pairOff;
-    switch (block) {
-        case 256: return pair ? launchTdfaBlock<256, true>(dBlob, blobBytes, regBytes, lds, d_data, d_off, d_len, sep, minLen, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, stream, longFlag, seq, re->tdfaBlob[TD_NREGS], lcPairOneFormat(re->tdfaBlob)) : launchTdfaBlock<256, false>(dBlob, blobBytes, regBytes, lds, d_data, d_off, d_len, sep, minLen, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, stream, longFlag, seq, re->tdfaBlob[TD_NREGS]);
-        case 128: return pair ? launchTdfaBlock<128, true>(dBlob, blobBytes, regBytes, lds, d_data, d_off, d_len, sep, minLen, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, stream, longFlag, seq, re->tdfaBlob[TD_NREGS], lcPairOneFormat(re->tdfaBlob)) : launchTdfaBlock<128, false>(dBlob, blobBytes, regBytes, lds, d_data, d_off, d_len, sep, minLen, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, stream, longFlag, seq, re->tdfaBlob[TD_NREGS]);
-        default: return pair ? launchTdfaBlock<64, true>(dBlob, blobBytes, regBytes, lds, d_data, d_off, d_len, sep, minLen, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, stream, longFlag, seq, re->tdfaBlob[TD_NREGS], lcPairOneFormat(re->tdfaBlob)) : launchTdfaBlock<64, false>(dBlob, blobBytes, regBytes, lds, d_data, d_off, d_len, sep, minLen, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, stream, longFlag, seq, re->tdfaBlob[TD_NREGS]);
-    }
+    const TdfaTablesArg full{.dBlob = dBlob,
+                             .blobBytes = blobBytes,
+                             .regBytes = uint32_t(lcTdfaRegBytes(re->tdfaPackedRegs, block)),
+                             .lds = lcTdfaLdsBytes(blobBytes, re->tdfaPackedRegs, block),
+                             .minLen = minLen,
+                             .longFlag = longFlag,
+                             .seq = seq,
+                             .nregsWord = re->tdfaBlob[TD_NREGS],
+                             .pairOne = pair && lcPairOneFormat(re->tdfaBlob)};
+    return kTdfaLaunch[block == 256 ? 0 : block == 128 ? 1 : 2][pair ? 0 : 1](full, b);
 }
 
 
@@ -609,12 +627,11 @@ void lcSetDecideSlot(int slot) { tlsDecideSlot = slot >= 0 && slot < kDecideSlot
 
 // The thread-list kernels of this launch may have left lines LC_OVERFLOW: settle them (plan + walk, both no-ops unless the
 // overflow flag carries this launch's sequence number).
-static int launchDecide(lc_regex* re, int dev, const void* dBlob, const uint8_t* d_data, const uint32_t* d_off, const uint32_t* d_len,
-                        uint32_t sep, uint32_t n, const uint32_t* d_n, const uint32_t* d_order, const uint32_t* d_resume,
-                        uint32_t ngroups, int32_t* d_caps, uint8_t* d_status, hipStream_t stream, uint32_t* overflowFlag,
-                        uint32_t seq, bool forced = false) {
+static int launchDecide(lc_regex* re, const void* dBlob, const MatchBatch& b, uint32_t* overflowFlag, uint32_t seq, bool forced = false) {
     static const bool off = getenv("LC_NFA_NO_DECIDE") != nullptr;
     if (off && !forced) return LC_OK;
+    const int dev = b.dev;
+    hipStream_t stream = streamOf(b);
     DecidePool& pool = tlsDecidePools[tlsDecideSlot];
     lcRegisterExitHook();
     if (pool.device != dev || !pool.p) {
@@ -629,10 +646,10 @@ static int launchDecide(lc_regex* re, int dev, const void* dBlob, const uint8_t*
     const DecideShape shape{re->decideClosedCap, re->decideMaxEnter};
     const uint32_t nPos = uint32_t(re->nfa.positions.size());
     noteKernel("nfa_decide_kernel");
-    hipLaunchKernelGGL(nfa_decide_plan_kernel, dim3(1), dim3(256), 0, stream, d_off, d_len, sep, n, d_n, d_order, d_resume, nPos, shape,
-                       d_status, overflowFlag, seq, pool.p, uint64_t(pool.bytes));
-    hipLaunchKernelGGL(nfa_decide_kernel, dim3(kDecideWorkers), dim3(64), 0, stream, d_data, d_off, d_len, sep, d_resume,
-                       static_cast<const uint32_t*>(dBlob), shape, ngroups, d_caps, d_status, overflowFlag, seq, pool.p);
+    hipLaunchKernelGGL(nfa_decide_plan_kernel, dim3(1), dim3(256), 0, stream, b.d_off, b.d_len, b.sep, b.n, b.d_n, b.d_order, b.d_resume, nPos,
+                       shape, b.d_status, overflowFlag, seq, pool.p, uint64_t(pool.bytes));
+    hipLaunchKernelGGL(nfa_decide_kernel, dim3(kDecideWorkers), dim3(64), 0, stream, b.d_data, b.d_off, b.d_len, b.sep, b.d_resume,
+                       static_cast<const uint32_t*>(dBlob), shape, b.ngroups, b.d_caps, b.d_status, overflowFlag, seq, pool.p);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(pool.lastUse, stream));
     pool.lastStream = stream;
@@ -649,20 +666,21 @@ enum { kNfaWholeChain = 0, kNfaFirstChance = 1, kNfaSecondChance = 2, kNfaWideFi
 static thread_local uint32_t* tlsWideNote = nullptr;  // lcSetWideNote: where the next wide launch reports "more than 64 threads were needed"
 void lcSetWideNote(uint32_t* note) { tlsWideNote = note; }
 
+// nfa_wide_kernel's LDS for a program of nPos positions (the kernel runs programs whose share fits 64 KiB), and LC_NFA_NO_WIDE
+static size_t nfaWideLdsBytes(uint32_t nPos) { return (size_t((nPos + 3) & ~3u) + 3 * kNfaWideThreads + 64) * 4; }
+static bool nfaWideFits(uint32_t nPos) { return nfaWideLdsBytes(nPos) <= 64 * 1024; }
+static bool nfaWideOff() {
+    static const bool off = getenv("LC_NFA_NO_WIDE") != nullptr;
+    return off;
+}
+
 template <int NS, bool ATOMIC, bool GLOBAL>
-static int launchNfaSlots(const void* dBlob, uint32_t blobBytes, uint32_t nPos, size_t lds, const uint8_t* d_data,
-                          const uint32_t* d_off, const uint32_t* d_len, uint32_t sep, uint32_t n, const uint32_t* d_n, const uint32_t* d_order, const uint32_t* d_resume, uint32_t ngroups,
-                          int32_t* d_caps, uint8_t* d_status, hipStream_t stream, uint32_t* overflowFlag, uint32_t seq,
-                          const uint32_t* pendingFlag, int chance = 0) {
+static int launchNfaSlots(const void* dBlob, uint32_t blobBytes, uint32_t nPos, size_t lds, const MatchBatch& b, uint32_t* overflowFlag,
+                          uint32_t seq, const uint32_t* pendingFlag, int chance = 0) {
     constexpr int BLOCK = kNfaBlock;
-    static thread_local size_t ldsAttrSet[kLcMaxDevices] = {};  // the attribute belongs to (function, device)
-    int devNow = 0;
-    if (lds > 64 * 1024) HIP_TRY(hipGetDevice(&devNow));
-    if (lds > 64 * 1024 && devNow < kLcMaxDevices && lds > ldsAttrSet[devNow]) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&nfa_match_kernel<NS, ATOMIC, GLOBAL>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-        ldsAttrSet[devNow] = lds;
-    }
+    if (const int rc = lcAllowLds(reinterpret_cast<const void*>(&nfa_match_kernel<NS, ATOMIC, GLOBAL>), b.dev, lds); rc != LC_OK) return rc;
+    const uint32_t n = b.n;
+    hipStream_t stream = streamOf(b);
     constexpr uint32_t kWaves = BLOCK / 64;
     const uint32_t grid = (n + kWaves - 1) / kWaves;
     uint32_t* const wideNote = tlsWideNote;
@@ -674,16 +692,13 @@ static int launchNfaSlots(const void* dBlob, uint32_t blobBytes, uint32_t nPos, 
     // lines and the wide kernel is its second chance, as in the whole chain -- "wide first" walks every line whatever its status says
     const bool behindFirstEngine = pendingFlag != nullptr && wideFirst;
     if (behindFirstEngine) wideFirst = false;
-    {
-        static const bool wideOff = getenv("LC_NFA_NO_WIDE") != nullptr;
-        const size_t wideLds0 = (size_t((nPos + 3) & ~3u) + 3 * kNfaWideThreads + 64) * 4;
-        if (wideOff || !overflowFlag || wideLds0 > 64 * 1024) wideFirst = false;
-    }
+    const bool wideRuns = !nfaWideOff() && overflowFlag && nfaWideFits(nPos);
+    if (!wideRuns) wideFirst = false;
     if (chance != kNfaSecondChance && !wideFirst) {
         noteKernel(ATOMIC ? "nfa_match_kernel<atomic>" : "nfa_match_kernel");
-        hipLaunchKernelGGL((nfa_match_kernel<NS, ATOMIC, GLOBAL>), dim3(grid), dim3(BLOCK), lds, stream, d_data, d_off, d_len, sep, n,
-                           d_n, d_order, d_resume, static_cast<const uint32_t*>(dBlob), blobBytes, ngroups, d_caps, d_status, overflowFlag,
-                           seq, pendingFlag);
+        hipLaunchKernelGGL((nfa_match_kernel<NS, ATOMIC, GLOBAL>), dim3(grid), dim3(BLOCK), lds, stream, b.d_data, b.d_off, b.d_len, b.sep, n,
+                           b.d_n, b.d_order, b.d_resume, static_cast<const uint32_t*>(dBlob), blobBytes, b.ngroups, b.d_caps, b.d_status,
+                           overflowFlag, seq, pendingFlag);
         HIP_TRY(hipGetLastError());
     }
     if (chance == kNfaFirstChance || (chance == kNfaWideFirst && !wideFirst && !behindFirstEngine)) return LC_OK;
@@ -691,22 +706,21 @@ static int launchNfaSlots(const void* dBlob, uint32_t blobBytes, uint32_t nPos, 
     // patterns without atomic groups whose capture offsets fit twice into a lane's registers.  Its workgroups return at
     // once unless the launch above raised the overflow flag.
     if constexpr (!ATOMIC && NS <= 64) {
-        static const bool wideOff = getenv("LC_NFA_NO_WIDE") != nullptr;
-        const size_t wideLds = (size_t((nPos + 3) & ~3u) + 3 * kNfaWideThreads + 64) * 4;
-        if (!wideOff && overflowFlag && wideLds <= 64 * 1024) {
+        if (wideRuns) {
             noteKernel(wideFirst ? "nfa_wide_kernel:first" : "nfa_wide_kernel");
-            hipLaunchKernelGGL((nfa_wide_kernel<NS>), dim3(n), dim3(64), wideLds, stream, d_data, d_off, d_len, sep, n, d_n, d_order,
-                               d_resume, static_cast<const uint32_t*>(dBlob), ngroups, d_caps, d_status, overflowFlag, seq,
-                               wideFirst ? 1u : 0u, wideNote);
+            hipLaunchKernelGGL((nfa_wide_kernel<NS>), dim3(n), dim3(64), nfaWideLdsBytes(nPos), stream, b.d_data, b.d_off, b.d_len, b.sep, n,
+                               b.d_n, b.d_order, b.d_resume, static_cast<const uint32_t*>(dBlob), b.ngroups, b.d_caps, b.d_status, overflowFlag,
+                               seq, wideFirst ? 1u : 0u, wideNote);
             HIP_TRY(hipGetLastError());
         }
     }
     return LC_OK;
 }
 
-static int launchNfa(lc_regex* re, int dev, const uint8_t* d_data, const uint32_t* d_off, const uint32_t* d_len,
-                     uint32_t sep, uint32_t n, const uint32_t* d_n, const uint32_t* d_order, const uint32_t* d_resume, uint32_t ngroups, int32_t* d_caps,
-                     uint8_t* d_status, hipStream_t stream, bool decideOnly = false, int chance = kNfaWholeChain, uint32_t* seqInOut = nullptr) {
+static int launchNfa(lc_regex* re, const MatchBatch& b, bool decideOnly = false, int chance = kNfaWholeChain, uint32_t* seqInOut = nullptr) {
+    const int dev = b.dev;
+    const uint32_t n = b.n;
+    hipStream_t stream = streamOf(b);
     if (re->nfaBlob.empty()) {
         tlsError = "pattern has no NFA program";
         return LC_ERR_UNSUPPORTED;
@@ -773,8 +787,7 @@ static int launchNfa(lc_regex* re, int dev, const uint8_t* d_data, const uint32_
             if (rc != LC_OK) return rc;
             if (dLazy) {
                 uint32_t* pf = overflowFlag + 1;
-                rc = launchTdfaL2Family(re, lazyHeader.data(), dLazy, false, dev, d_data, d_off, d_len, sep, n, d_n, d_order, d_resume, ngroups,
-                                        d_caps, d_status, stream, pf, seq);
+                rc = launchTdfaL2Family(re, lazyHeader.data(), dLazy, false, b, pf, seq);
                 if (rc != LC_OK) return rc;
                 pendingFlag = pf;
                 lazyFront = true;
@@ -816,9 +829,9 @@ static int launchNfa(lc_regex* re, int dev, const uint8_t* d_data, const uint32_
         HIP_TRY(hipMemsetAsync(pool.p, 0, sizeof(DfsPoolHeader), stream));
         uint32_t* pf = overflowFlag + 1;
         noteKernel("nfa_dfs_kernel");
-        hipLaunchKernelGGL(nfa_dfs_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, d_data, d_off, d_len, sep, n, d_n, d_order, d_resume,
-                           static_cast<const uint32_t*>(dBlob), shape, ngroups, d_caps, d_status, pf, seq, pool.p, uint64_t(pool.bytes),
-                           stepsPerByte);
+        hipLaunchKernelGGL(nfa_dfs_kernel, dim3((n + 63) / 64), dim3(64), 0, stream, b.d_data, b.d_off, b.d_len, b.sep, n, b.d_n, b.d_order,
+                           b.d_resume, static_cast<const uint32_t*>(dBlob), shape, b.ngroups, b.d_caps, b.d_status, pf, seq, pool.p,
+                           uint64_t(pool.bytes), stepsPerByte);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipEventRecord(pool.lastUse, stream));
         pool.lastStream = stream;
@@ -826,19 +839,17 @@ static int launchNfa(lc_regex* re, int dev, const uint8_t* d_data, const uint32_
         pendingFlag = pf;
     }
     if (decideOnly) {  // LC_ENGINE_DECIDE: every line goes to the depth-first walk
-        hipLaunchKernelGGL(nfa_decide_mark_all_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, d_n, d_order, d_status,
+        hipLaunchKernelGGL(nfa_decide_mark_all_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, n, b.d_n, b.d_order, b.d_status,
                            overflowFlag, seq);
         HIP_TRY(hipGetLastError());
-        return launchDecide(re, dev, dBlob, d_data, d_off, d_len, sep, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, stream,
-                            overflowFlag, seq, true);
+        return launchDecide(re, dBlob, b, overflowFlag, seq, true);
     }
     // kernel instance by capture slots carried per thread (VGPRs), atomic groups, tables in LDS or read from HBM
     auto launch = [&](auto ns) {
         constexpr int NS = decltype(ns)::value;
         auto go = [&](auto a, auto g) {
             constexpr bool A = decltype(a)::value, G = decltype(g)::value;
-            return launchNfaSlots<NS, A, G>(dBlob, stageBytes, nPos, lds, d_data, d_off, d_len, sep, n, d_n, d_order, d_resume, ngroups, d_caps,
-                                            d_status, stream, overflowFlag, seq, pendingFlag, chance);
+            return launchNfaSlots<NS, A, G>(dBlob, stageBytes, nPos, lds, b, overflowFlag, seq, pendingFlag, chance);
         };
         if (atomic && global) return go(std::true_type{}, std::true_type{});
         if (atomic) return go(std::true_type{}, std::false_type{});
@@ -855,11 +866,10 @@ static int launchNfa(lc_regex* re, int dev, const uint8_t* d_data, const uint32_
     else rc = launch(std::integral_constant<int, 320>{});
     if (rc != LC_OK) return rc;
     // Can a thread list overflow at all?  Without atomic groups a list holds at most one thread per position.
-    const bool wideApplies = !atomic && slots <= 64 && (size_t((nPos + 3) & ~3u) + 3 * kNfaWideThreads + 64) * 4 <= 64 * 1024;
+    const bool wideApplies = !atomic && slots <= 64 && nfaWideFits(nPos);
     const bool canOverflow = atomic || nPos > (wideApplies ? uint32_t(kNfaWideThreads) : 64u);
     if (!canOverflow || chance == kNfaFirstChance || chance == kNfaWideFirst) return LC_OK;
-    return launchDecide(re, dev, dBlob, d_data, d_off, d_len, sep, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, stream,
-                        overflowFlag, seq);
+    return launchDecide(re, dBlob, b, overflowFlag, seq);
 }
 
 // Groups written "(?=(S*))" (regex_ast.hpp Node::runCapture, Grok's "(?=%{GREEDYDATA:message})"): the automata stamp only
@@ -923,42 +933,44 @@ int lcEnsureScreenUploaded(lc_regex* re, int dev, const uint32_t** out) {
     return rc;
 }
 
-int lcScreenOnStream(lc_regex* re, int dev, const uint8_t* d_data, const uint32_t* d_off, const uint32_t* d_len, uint32_t n,
-                     const uint32_t* d_in, uint32_t* d_out, uint32_t* d_counters, void* streamPtr) {
+int lcScreenOnStream(lc_regex* re, const MatchBatch& b, uint32_t* d_out, uint32_t* d_counters) {
     if (re->screenBlob.empty()) {
         tlsError = "handle carries no screen table";
         return LC_ERR_UNSUPPORTED;
     }
-    if (n == 0) return LC_OK;
+    if (b.n == 0) return LC_OK;
     void* dBlob = nullptr;
-    int rc = ensureUploaded(re, dev, kBlobScreen, &dBlob);
+    int rc = ensureUploaded(re, b.dev, kBlobScreen, &dBlob);
     if (rc != LC_OK) return rc;
     noteKernel("dfa_screen_kernel");
-    hipLaunchKernelGGL(dfa_screen_kernel, dim3((n + kScreenBlock - 1) / kScreenBlock), dim3(kScreenBlock), 0,
-                       static_cast<hipStream_t>(streamPtr), d_data, d_off, d_len, d_in, n, static_cast<const uint32_t*>(dBlob), d_out,
-                       d_counters);
+    hipLaunchKernelGGL(dfa_screen_kernel, dim3((b.n + kScreenBlock - 1) / kScreenBlock), dim3(kScreenBlock), 0, streamOf(b), b.d_data,
+                       b.d_off, b.d_len, b.d_order, b.n, static_cast<const uint32_t*>(dBlob), d_out, d_counters);
     HIP_TRY(hipGetLastError());
     return LC_OK;
+}
+
+// What every entry that takes DEVICE pointers asks once its arguments are checked: is there a device at all (requireDevice: the host
+// entries ask that too), and is it the one d_ptr lives on (lcDeviceEntryDevice)
+static int requireDevice() {
+    if (lc_device_count() > 0) return LC_OK;
+    tlsError = "no HIP device";
+    return LC_ERR_NO_DEVICE;
+}
+static int deviceEntry(const void* d_ptr, int* dev) {
+    const int rc = requireDevice();
+    return rc != LC_OK ? rc : lcDeviceEntryDevice(d_ptr, dev);
 }
 
 extern "C" int lc_regex_screen_device(lc_regex_t* re, const uint8_t* d_data, const uint32_t* d_off, const uint32_t* d_len,
                                       uint32_t n, const uint32_t* d_lines, uint32_t* d_out, uint32_t* d_count, void* stream) {
     if (!re || !d_data || !d_off || !d_len || !d_out || !d_count) return LC_ERR_ARG;
-    if (lc_device_count() <= 0) {
-        tlsError = "no HIP device";
-        return LC_ERR_NO_DEVICE;
-    }
     int dev = 0;
-    {
-        const int rcDev = lcDeviceEntryDevice(d_data, &dev);
-        if (rcDev != LC_OK) return rcDev;
-    }
-    return lcScreenOnStream(re, dev, d_data, d_off, d_len, n, d_lines, d_out, d_count, stream);
+    if (const int rc = deviceEntry(d_data, &dev); rc != LC_OK) return rc;
+    return lcScreenOnStream(re, {.d_data = d_data, .d_off = d_off, .d_len = d_len, .n = n, .d_order = d_lines, .dev = dev, .stream = stream},
+                            d_out, d_count);
 }
 
-static int lcMatchChainOnStream(lc_regex* re, int engine, int dev, const uint8_t* d_data, const uint32_t* d_off,
-                         const uint32_t* d_len, uint32_t sep, uint32_t n, const uint32_t* d_n, const uint32_t* d_order, const uint32_t* d_resume, uint32_t ngroups,
-                         int32_t* d_caps, uint8_t* d_status, void* streamPtr, int chance, uint32_t* seqInOut);
+static int lcMatchChainOnStream(lc_regex* re, int engine, const MatchBatch& b, int chance, uint32_t* seqInOut);
 
 // ---- several automata over their own values in ONE launch (runtime_internal.hpp; the Grok plan's round 0)
 bool lcNfaWideApplies(const lc_regex* re);
@@ -1031,61 +1043,40 @@ int lcLaunchWaveJobs(const uint8_t* d_data, const TdfaWaveJob* jobs, uint32_t nJ
     // (LC_GROK_FUSED_LDS=<bytes>: at least that much LDS per workgroup -- fewer workgroups, so fewer wavefronts, per CU: the walk is scalar
     // code, and a SIMD issues one scalar instruction every four cycles for ALL its wavefronts; A/B measurements)
     if (const char* padEnv = getenv("LC_GROK_FUSED_LDS")) ldsBytes = std::max<uint32_t>(ldsBytes, uint32_t(atol(padEnv)));
-    static thread_local size_t ldsAttrSet[kLcMaxDevices] = {};
-    if (ldsBytes > 48 * 1024 && dev < kLcMaxDevices && ldsBytes > ldsAttrSet[dev]) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(tdfa_wave_multi_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(ldsBytes)));
-        ldsAttrSet[dev] = ldsBytes;
-    }
+    if (const int rc = lcAllowLds(reinterpret_cast<const void*>(tdfa_wave_multi_kernel), dev, ldsBytes); rc != LC_OK) return rc;
     noteKernel("tdfa_wave_multi_kernel");
     hipLaunchKernelGGL(tdfa_wave_multi_kernel, dim3(totalBlocks), dim3(kTdfaWaveBlock), ldsBytes, st, d_data, static_cast<const uint32_t*>(dTable), nJobs);
     HIP_TRY(hipGetLastError());
     return LC_OK;
 }
 
-int lcMatchOnStream(lc_regex* re, int engine, int dev, const uint8_t* d_data, const uint32_t* d_off,
-                         const uint32_t* d_len, uint32_t sep, uint32_t n, const uint32_t* d_n, const uint32_t* d_order, const uint32_t* d_resume, uint32_t ngroups,
-                         int32_t* d_caps, uint8_t* d_status, void* streamPtr) {
-    return lcMatchChainOnStream(re, engine, dev, d_data, d_off, d_len, sep, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, streamPtr,
-                                kNfaWholeChain, nullptr);
-}
+int lcMatchOnStream(lc_regex* re, int engine, const MatchBatch& b) { return lcMatchChainOnStream(re, engine, b, kNfaWholeChain, nullptr); }
 // The engine's main kernel only; *seq = what lcMatchSecondChanceOnStream needs to finish the lines that came back LC_OVERFLOW
 // (0: this engine has no second chance -- a DFA decides every line).  The Grok matcher queues the second chance only for the
 // entries whose first chance reported overflows (grok_device.hip).
-int lcMatchFirstOnStream(lc_regex* re, int engine, int dev, const uint8_t* d_data, const uint32_t* d_off, const uint32_t* d_len,
-                         uint32_t sep, uint32_t n, const uint32_t* d_n, const uint32_t* d_order, const uint32_t* d_resume, uint32_t ngroups,
-                         int32_t* d_caps, uint8_t* d_status, uint32_t* seq, void* streamPtr) {
+int lcMatchFirstOnStream(lc_regex* re, int engine, const MatchBatch& b, uint32_t* seq) {
     *seq = 0;
-    return lcMatchChainOnStream(re, engine, dev, d_data, d_off, d_len, sep, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, streamPtr,
-                                kNfaFirstChance, seq);
+    return lcMatchChainOnStream(re, engine, b, kNfaFirstChance, seq);
 }
-int lcMatchSecondChanceOnStream(lc_regex* re, int engine, int dev, const uint8_t* d_data, const uint32_t* d_off, const uint32_t* d_len,
-                                uint32_t sep, uint32_t n, const uint32_t* d_n, const uint32_t* d_order, const uint32_t* d_resume,
-                                uint32_t ngroups, int32_t* d_caps, uint8_t* d_status, uint32_t seq, void* streamPtr) {
+int lcMatchSecondChanceOnStream(lc_regex* re, int engine, const MatchBatch& b, uint32_t seq) {
     if (!seq || engine != LC_ENGINE_NFA) return LC_OK;
-    return lcMatchChainOnStream(re, engine, dev, d_data, d_off, d_len, sep, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, streamPtr,
-                                kNfaSecondChance, &seq);
+    return lcMatchChainOnStream(re, engine, b, kNfaSecondChance, &seq);
 }
 
-int lcMatchWideFirstOnStream(int part, lc_regex* re, int engine, int dev, const uint8_t* d_data, const uint32_t* d_off, const uint32_t* d_len,
-                             uint32_t sep, uint32_t n, const uint32_t* d_n, const uint32_t* d_order, const uint32_t* d_resume,
-                             uint32_t ngroups, int32_t* d_caps, uint8_t* d_status, uint32_t* seq, uint32_t* wideNote, void* streamPtr) {
+int lcMatchWideFirstOnStream(int part, lc_regex* re, int engine, const MatchBatch& b, uint32_t* seq, uint32_t* wideNote) {
     if (part == 1) {
         if (!seq || !*seq || engine != LC_ENGINE_NFA) return LC_OK;
-        return lcMatchChainOnStream(re, engine, dev, d_data, d_off, d_len, sep, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, streamPtr,
-                                    kNfaDecideOnly, seq);
+        return lcMatchChainOnStream(re, engine, b, kNfaDecideOnly, seq);
     }
     if (seq) *seq = 0;
     if (engine == LC_ENGINE_NFA) lcSetWideNote(wideNote);
-    const int rc = lcMatchChainOnStream(re, engine, dev, d_data, d_off, d_len, sep, n, d_n, d_order, d_resume, ngroups, d_caps, d_status,
-                                        streamPtr, part == 0 ? kNfaWideFirst : kNfaWideChain, seq);
+    const int rc = lcMatchChainOnStream(re, engine, b, part == 0 ? kNfaWideFirst : kNfaWideChain, seq);
     lcSetWideNote(nullptr);
     return rc;
 }
 bool lcNfaWideApplies(const lc_regex* re) {
-    static const bool wideOff = getenv("LC_NFA_NO_WIDE") != nullptr;
-    if (!re || wideOff || re->nfaBlob.empty() || re->nfa.atomicCount > 0 || re->nfa.slotCount() > 64) return false;
-    const uint32_t nPos = uint32_t(re->nfa.positions.size());
-    return (size_t((nPos + 3) & ~3u) + 3 * kNfaWideThreads + 64) * 4 <= 64 * 1024;
+    if (!re || nfaWideOff() || re->nfaBlob.empty() || re->nfa.atomicCount > 0 || re->nfa.slotCount() > 64) return false;
+    return nfaWideFits(uint32_t(re->nfa.positions.size()));
 }
 
 // The backtracking engine (bt_kernel.hpp): patterns with back-references.  The scratch pool of the launch -- 64 KB per lane in flight
@@ -1133,9 +1124,10 @@ thread_local BtScratchCache tlsBtScratch;
 constexpr size_t kBtCachedWordsMax = size_t(64) << 18;  // 64 MB: above it the pool
 }  // namespace
 
-static int launchBt(lc_regex* re, int dev, const uint8_t* d_data, const uint32_t* d_off, const uint32_t* d_len, uint32_t sep, uint32_t n,
-                    const uint32_t* d_n, const uint32_t* d_order, const uint32_t* d_resume, uint32_t ngroups, int32_t* d_caps, uint8_t* d_status,
-                    hipStream_t stream) {
+static int launchBt(lc_regex* re, const MatchBatch& b) {
+    const int dev = b.dev;
+    const uint32_t n = b.n;
+    hipStream_t stream = streamOf(b);
     if (re->btBlob.empty()) {
         tlsError = "pattern has no backtracking program";
         return LC_ERR_UNSUPPORTED;
@@ -1197,14 +1189,15 @@ static int launchBt(lc_regex* re, int dev, const uint8_t* d_data, const uint32_t
     hipError_t launched = hipMemsetAsync(scratch, 0, kBtPoolHeaderWords * 4, stream);
     lcNoteKernel("bt_match_kernel");
     if (launched == hipSuccess) {
-        hipLaunchKernelGGL(bt_match_kernel, dim3(firstBlocks), dim3(kBtBlock), stageWords * 4, stream, d_data, d_off, d_len, sep, n, d_n, d_order, d_resume,
-                           static_cast<const uint32_t*>(dBlob), blobWords, stageWords, ngroups, d_caps, d_status, scratch, sliceWords, budget, 0u);
+        hipLaunchKernelGGL(bt_match_kernel, dim3(firstBlocks), dim3(kBtBlock), stageWords * 4, stream, b.d_data, b.d_off, b.d_len, b.sep, n, b.d_n,
+                           b.d_order, b.d_resume, static_cast<const uint32_t*>(dBlob), blobWords, stageWords, b.ngroups, b.d_caps, b.d_status,
+                           scratch, sliceWords, budget, 0u);
         launched = hipGetLastError();
     }
     if (launched == hipSuccess && sliceWords != kBtRetrySliceWords) {  // pass 2: the values that filled their slice (none: the kernel returns at once)
-        hipLaunchKernelGGL(bt_match_kernel, dim3(retryBlocks), dim3(kBtBlock), stageWords * 4, stream, d_data, d_off, d_len, sep, n, d_n, d_order,
-                           d_resume, static_cast<const uint32_t*>(dBlob), blobWords, stageWords, ngroups, d_caps, d_status, scratch,
-                           kBtRetrySliceWords, budget, 1u);
+        hipLaunchKernelGGL(bt_match_kernel, dim3(retryBlocks), dim3(kBtBlock), stageWords * 4, stream, b.d_data, b.d_off, b.d_len, b.sep, n, b.d_n,
+                           b.d_order, b.d_resume, static_cast<const uint32_t*>(dBlob), blobWords, stageWords, b.ngroups, b.d_caps, b.d_status,
+                           scratch, kBtRetrySliceWords, budget, 1u);
         launched = hipGetLastError();
     }
     if (!cached) (void)hipFreeAsync(scratch, stream);
@@ -1212,47 +1205,42 @@ static int launchBt(lc_regex* re, int dev, const uint8_t* d_data, const uint32_t
     return LC_OK;
 }
 
-static int lcMatchChainOnStream(lc_regex* re, int engine, int dev, const uint8_t* d_data, const uint32_t* d_off,
-                         const uint32_t* d_len, uint32_t sep, uint32_t n, const uint32_t* d_n, const uint32_t* d_order, const uint32_t* d_resume, uint32_t ngroups,
-                         int32_t* d_caps, uint8_t* d_status, void* streamPtr, int chance, uint32_t* seqInOut) {
-    hipStream_t stream = static_cast<hipStream_t>(streamPtr);
+static int lcMatchChainOnStream(lc_regex* re, int engine, const MatchBatch& b, int chance, uint32_t* seqInOut) {
     int rc;
     if (engine == LC_ENGINE_BT || re->engine == LC_ENGINE_BT) {
         if (engine != LC_ENGINE_BT) {
             tlsError = "pattern runs on the backtracking engine only (back-references)";
             return LC_ERR_UNSUPPORTED;
         }
-        return launchBt(re, dev, d_data, d_off, d_len, sep, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, stream);
+        return launchBt(re, b);
     }
     if (!re->nfa.runGroups.empty()) tlsDone.armed = false;  // run_capture_kernel runs behind the match: it cannot signal
     // (a handle that asked for it -- lcPreferWaveTdfa: the Grok matcher's entries -- takes the wave-per-value kernel on small batches
     // even though its automaton fits the LDS kernels: those walk one value per lane, and a batch of a few hundred 4 KiB values waits
     // 0.3-1.4 ms for the longest of them)
-    const bool waveByChoice = engine == LC_ENGINE_TDFA && re->hasTdfa && re->preferWave && !re->tdfaL2Blob.empty() && n <= 16384;
+    const bool waveByChoice = engine == LC_ENGINE_TDFA && re->hasTdfa && re->preferWave && !re->tdfaL2Blob.empty() && b.n <= 16384;
     if (engine == LC_ENGINE_TDFA && (waveByChoice || !re->hasTdfa) && !re->tdfaL2Blob.empty()) {
         // the automaton is too large for the LDS kernels: tables in global memory, one line per lane (tdfa_l2_kernel.hpp)
         void* dBlob = nullptr;
-        rc = ensureUploaded(re, dev, kBlobTdfaL2, &dBlob);
+        rc = ensureUploaded(re, b.dev, kBlobTdfaL2, &dBlob);
         if (rc != LC_OK) return rc;
-        rc = launchTdfaL2Family(re, re->tdfaL2Blob.data(), dBlob, waveByChoice, dev, d_data, d_off, d_len, sep, n, d_n, d_order, d_resume, ngroups,
-                                d_caps, d_status, stream, nullptr, 0u);
+        rc = launchTdfaL2Family(re, re->tdfaL2Blob.data(), dBlob, waveByChoice, b, nullptr, 0u);
     } else if (engine == LC_ENGINE_TDFA) {
         if (!re->hasTdfa) {
             tlsError = "pattern has no TDFA: " + re->tdfaError;
             return LC_ERR_UNSUPPORTED;
         }
-        rc = launchTdfa(re, dev, d_data, d_off, d_len, sep, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, stream);
+        rc = launchTdfa(re, b);
     } else {
-        rc = launchNfa(re, dev, d_data, d_off, d_len, sep, n, d_n, d_order, d_resume, ngroups, d_caps, d_status, stream,
-                       engine == LC_ENGINE_DECIDE, engine == LC_ENGINE_DECIDE ? kNfaWholeChain : chance, seqInOut);
+        rc = launchNfa(re, b, engine == LC_ENGINE_DECIDE, engine == LC_ENGINE_DECIDE ? kNfaWholeChain : chance, seqInOut);
     }
     if (rc != LC_OK) return rc;
     for (const auto& rg : re->nfa.runGroups) {
-        if (uint32_t(rg.first) >= ngroups) continue;  // the caller did not ask for this group
+        if (uint32_t(rg.first) >= b.ngroups) continue;  // the caller did not ask for this group
         RunSet set;
         for (int k = 0; k < 8; ++k) set.w[k] = uint32_t(rg.second.w[size_t(k) / 2] >> (32 * (k & 1)));
-        hipLaunchKernelGGL(run_capture_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_data, d_off, d_len, sep, n, d_n,
-                           d_order, uint32_t(rg.first), set, ngroups, d_caps, d_status);
+        hipLaunchKernelGGL(run_capture_kernel, dim3((b.n + 255) / 256), dim3(256), 0, streamOf(b), b.d_data, b.d_off, b.d_len, b.sep, b.n, b.d_n,
+                           b.d_order, uint32_t(rg.first), set, b.ngroups, b.d_caps, b.d_status);
         HIP_TRY(hipGetLastError());
     }
     return LC_OK;
@@ -1264,18 +1252,12 @@ extern "C" int lc_regex_match_device_engine(lc_regex_t* re, int engine, const ui
     if (!re) return LC_ERR_ARG;
     if (n == 0) return LC_OK;
     if (!d_data || !d_off || !d_caps || !d_status) return LC_ERR_ARG;
-    if (lc_device_count() <= 0) {
-        tlsError = "no HIP device";
-        return LC_ERR_NO_DEVICE;
-    }
     int dev = 0;
-    {
-        const int rcDev = lcDeviceEntryDevice(d_data, &dev);
-        if (rcDev != LC_OK) return rcDev;
-    }
+    if (const int rc = deviceEntry(d_data, &dev); rc != LC_OK) return rc;
     if (engine == LC_ENGINE_AUTO) engine = re->engine;
-    return lcMatchOnStream(re, engine, dev, d_data, d_off, d_len, sep_bytes, n, nullptr, nullptr, nullptr, ngroups, d_caps, d_status,
-                         static_cast<hipStream_t>(stream));
+    return lcMatchOnStream(re, engine,
+                           {.d_data = d_data, .d_off = d_off, .d_len = d_len, .sep = sep_bytes, .n = n,
+                            .ngroups = ngroups, .d_caps = d_caps, .d_status = d_status, .dev = dev, .stream = stream});
 }
 
 // ---- lc_regex_match_device_multi: a job table (TdfaJob[] + u16 blockToJob[]) is packed in pinned host memory and copied to its
@@ -1314,15 +1296,9 @@ struct JobTableRing {
 thread_local JobTableRing tlsJobTables;
 
 template <int BLOCK, bool PAIR1>
-int launchTdfaMulti(const TdfaJob* table, const uint16_t* blockToJob, uint32_t totalBlocks, size_t lds, hipStream_t stream) {
+int launchTdfaMulti(const TdfaJob* table, const uint16_t* blockToJob, uint32_t totalBlocks, size_t lds, int dev, hipStream_t stream) {
     auto kern = tdfa_stream_multi_kernel<BLOCK, false, PAIR1>;
-    static thread_local size_t ldsAttrSet[kLcMaxDevices] = {};
-    int devNow = 0;
-    if (lds > 64 * 1024) HIP_TRY(hipGetDevice(&devNow));
-    if (lds > 64 * 1024 && devNow < kLcMaxDevices && lds > ldsAttrSet[devNow]) {
-        HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-        ldsAttrSet[devNow] = lds;
-    }
+    if (const int rc = lcAllowLds(reinterpret_cast<const void*>(kern), dev, lds); rc != LC_OK) return rc;
     noteKernel(PAIR1 ? "tdfa_stream_multi_kernel<pair1>" : "tdfa_stream_multi_kernel");
     uint32_t* nullCounter = nullptr;
     uint32_t* nullFlag = nullptr;
@@ -1336,15 +1312,8 @@ int launchTdfaMulti(const TdfaJob* table, const uint16_t* blockToJob, uint32_t t
 extern "C" int lc_regex_match_device_multi(const lc_match_job* jobs, uint32_t njobs, void* streamPtr) {
     if (!jobs && njobs) return LC_ERR_ARG;
     if (njobs == 0) return LC_OK;
-    if (lc_device_count() <= 0) {
-        tlsError = "no HIP device";
-        return LC_ERR_NO_DEVICE;
-    }
     int dev = 0;
-    {
-        const int rcDev = lcDeviceEntryDevice(jobs[0].d_data, &dev);
-        if (rcDev != LC_OK) return rcDev;
-    }
+    if (const int rc = deviceEntry(jobs[0].d_data, &dev); rc != LC_OK) return rc;
     hipStream_t stream = static_cast<hipStream_t>(streamPtr);
     for (uint32_t i = 0; i < njobs; ++i) {
         const lc_match_job& j = jobs[i];
@@ -1463,12 +1432,12 @@ extern "C" int lc_regex_match_device_multi(const lc_match_job* jobs, uint32_t nj
         const uint16_t* dMap = reinterpret_cast<const uint16_t*>(tableAt + mapAt);
         int rc = LC_OK;
         switch (variant) {
-            case 0: rc = launchTdfaMulti<256, false>(dJobs, dMap, blocks, lds, stream); break;
-            case 1: rc = launchTdfaMulti<256, true>(dJobs, dMap, blocks, lds, stream); break;
-            case 2: rc = launchTdfaMulti<128, false>(dJobs, dMap, blocks, lds, stream); break;
-            case 3: rc = launchTdfaMulti<128, true>(dJobs, dMap, blocks, lds, stream); break;
-            case 4: rc = launchTdfaMulti<64, false>(dJobs, dMap, blocks, lds, stream); break;
-            default: rc = launchTdfaMulti<64, true>(dJobs, dMap, blocks, lds, stream); break;
+            case 0: rc = launchTdfaMulti<256, false>(dJobs, dMap, blocks, lds, dev, stream); break;
+            case 1: rc = launchTdfaMulti<256, true>(dJobs, dMap, blocks, lds, dev, stream); break;
+            case 2: rc = launchTdfaMulti<128, false>(dJobs, dMap, blocks, lds, dev, stream); break;
+            case 3: rc = launchTdfaMulti<128, true>(dJobs, dMap, blocks, lds, dev, stream); break;
+            case 4: rc = launchTdfaMulti<64, false>(dJobs, dMap, blocks, lds, dev, stream); break;
+            default: rc = launchTdfaMulti<64, true>(dJobs, dMap, blocks, lds, dev, stream); break;
         }
         if (rc != LC_OK) return rc;
         HIP_TRY(hipEventRecord(tab.done, stream));
@@ -1482,8 +1451,9 @@ extern "C" int lc_regex_match_device_multi(const lc_match_job* jobs, uint32_t nj
         if (re->engine == LC_ENGINE_TDFA && re->hasTdfa && re->nfa.runGroups.empty() &&
             (re->tdfaBlock == 256 || re->tdfaBlock == 128 || re->tdfaBlock == 64))
             continue;  // went with a packed launch
-        const int rc = lcMatchOnStream(re, re->engine, dev, j.d_data, j.d_off, j.d_len, j.sep_bytes, j.n, nullptr, nullptr, nullptr,
-                                       j.ngroups, j.d_caps, j.d_status, stream);
+        const int rc = lcMatchOnStream(re, re->engine,
+                                       {.d_data = j.d_data, .d_off = j.d_off, .d_len = j.d_len, .sep = j.sep_bytes, .n = j.n,
+                                        .ngroups = j.ngroups, .d_caps = j.d_caps, .d_status = j.d_status, .dev = dev, .stream = stream});
         if (rc != LC_OK) return rc;
     }
     return LC_OK;
@@ -1500,18 +1470,15 @@ extern "C" int lc_regex_match_device_from(lc_regex_t* re, int engine, const uint
         tlsError = "resume offsets need a pattern compiled with LC_SYNTAX_SEARCH";
         return LC_ERR_ARG;
     }
-    if (lc_device_count() <= 0) {
-        tlsError = "no HIP device";
-        return LC_ERR_NO_DEVICE;
-    }
     int dev = 0;
-    {
-        const int rcDev = lcDeviceEntryDevice(d_data, &dev);
-        if (rcDev != LC_OK) return rcDev;
-    }
+    if (const int rc = deviceEntry(d_data, &dev); rc != LC_OK) return rc;
     if (engine == LC_ENGINE_AUTO) engine = re->engine;
-    return lcMatchOnStream(re, engine, dev, d_data, d_off, d_len, sep_bytes, n, d_nlines, d_lines, d_from, ngroups, d_caps,
-                           d_status, static_cast<hipStream_t>(stream));
+    return lcMatchOnStream(re, engine,
+                           {.d_data = d_data, .d_off = d_off, .d_len = d_len, .sep = sep_bytes, .n = n,
+                            .d_n = d_nlines,
+                            .d_order = d_lines,
+                            .d_resume = d_from,
+                            .ngroups = ngroups, .d_caps = d_caps, .d_status = d_status, .dev = dev, .stream = stream});
 }
 
 extern "C" int lc_regex_match_device_dyn(lc_regex_t* re, int engine, const uint8_t* d_data, const uint32_t* d_off,
@@ -1520,18 +1487,13 @@ extern "C" int lc_regex_match_device_dyn(lc_regex_t* re, int engine, const uint8
     if (!re || !d_nlines) return LC_ERR_ARG;
     if (max_lines == 0) return LC_OK;
     if (!d_data || !d_off || !d_caps || !d_status) return LC_ERR_ARG;
-    if (lc_device_count() <= 0) {
-        tlsError = "no HIP device";
-        return LC_ERR_NO_DEVICE;
-    }
     int dev = 0;
-    {
-        const int rcDev = lcDeviceEntryDevice(d_data, &dev);
-        if (rcDev != LC_OK) return rcDev;
-    }
+    if (const int rc = deviceEntry(d_data, &dev); rc != LC_OK) return rc;
     if (engine == LC_ENGINE_AUTO) engine = re->engine;
-    return lcMatchOnStream(re, engine, dev, d_data, d_off, nullptr, sep_bytes, max_lines, d_nlines, nullptr, nullptr, ngroups, d_caps,
-                         d_status, static_cast<hipStream_t>(stream));
+    return lcMatchOnStream(re, engine,
+                           {.d_data = d_data, .d_off = d_off, .sep = sep_bytes, .n = max_lines,
+                            .d_n = d_nlines,
+                            .ngroups = ngroups, .d_caps = d_caps, .d_status = d_status, .dev = dev, .stream = stream});
 }
 
 extern "C" size_t lc_sched_scratch_bytes(uint32_t max_lines) { return (size_t(max_lines) + 2 * kSchedBuckets) * 4; }
@@ -1558,15 +1520,8 @@ extern "C" int lc_regex_match_device_ragged(lc_regex_t* re, int engine, const ui
     if (n == 0) return LC_OK;
     if (!d_data || !d_off || !d_caps || !d_status || !d_scratch || scratch_bytes < lc_sched_scratch_bytes(n))
         return LC_ERR_ARG;
-    if (lc_device_count() <= 0) {
-        tlsError = "no HIP device";
-        return LC_ERR_NO_DEVICE;
-    }
     int dev = 0;
-    {
-        const int rcDev = lcDeviceEntryDevice(d_data, &dev);
-        if (rcDev != LC_OK) return rcDev;
-    }
+    if (const int rc = deviceEntry(d_data, &dev); rc != LC_OK) return rc;
     if (engine == LC_ENGINE_AUTO) engine = re->engine;
     hipStream_t st = static_cast<hipStream_t>(stream);
     uint32_t* hist = static_cast<uint32_t*>(d_scratch);
@@ -1579,8 +1534,11 @@ extern "C" int lc_regex_match_device_ragged(lc_regex_t* re, int engine, const ui
     hipLaunchKernelGGL(sched_scatter_kernel, dim3(grid), dim3(kSchedBlock), 0, st, d_off, d_len, sep_bytes, n, d_nlines,
                        cursor, order);
     HIP_TRY(hipGetLastError());
-    return lcMatchOnStream(re, engine, dev, d_data, d_off, d_len, sep_bytes, n, d_nlines, order, nullptr, ngroups, d_caps, d_status,
-                         st);
+    return lcMatchOnStream(re, engine,
+                           {.d_data = d_data, .d_off = d_off, .d_len = d_len, .sep = sep_bytes, .n = n,
+                            .d_n = d_nlines,
+                            .d_order = order,
+                            .ngroups = ngroups, .d_caps = d_caps, .d_status = d_status, .dev = dev, .stream = stream});
 }
 
 // ------------------------------------------------------------------------------------------------ line split
@@ -1594,10 +1552,7 @@ extern "C" int lc_split_lines_device(const uint8_t* d_data, uint64_t nbytes, uin
                                      void* stream) {
     if (!d_off || !d_nlines || off_capacity < 2) return LC_ERR_ARG;
     if (nbytes >= (uint64_t(1) << 32) - 1) return LC_ERR_ARG;  // offsets are 32-bit, like the match kernels'
-    if (lc_device_count() <= 0) {
-        tlsError = "no HIP device";
-        return LC_ERR_NO_DEVICE;
-    }
+    if (const int rc = requireDevice(); rc != LC_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (nbytes == 0) {
         HIP_TRY(hipMemsetAsync(d_nlines, 0, 4, st));
@@ -1635,15 +1590,8 @@ extern "C" int lc_span_filter_device(const lc_span_filter_t* filters, uint32_t n
     if (nfilters > kSpanFilterMax || (nfilters && !filters) || !d_nlines || !d_counts || ngroups == 0) return LC_ERR_ARG;
     if (max_lines == 0) return LC_OK;
     if (!d_data || !d_off || !d_caps || !d_status || (packed_cap_rows && !d_packed)) return LC_ERR_ARG;
-    if (lc_device_count() <= 0) {
-        tlsError = "no HIP device";
-        return LC_ERR_NO_DEVICE;
-    }
     int dev = 0;
-    {
-        const int rcDev = lcDeviceEntryDevice(d_data, &dev);
-        if (rcDev != LC_OK) return rcDev;
-    }
+    if (const int rc = deviceEntry(d_data, &dev); rc != LC_OK) return rc;
     SpanFilterArgs args{};
     args.n = nfilters;
     for (uint32_t f = 0; f < nfilters; ++f) {
@@ -1692,21 +1640,32 @@ std::atomic<int> gZeroCopyWaiters{0};
 // left of a trip is to learn that the last kernel is done.  lcQueueTripSignal puts a one-lane kernel behind everything queued on the
 // stream that stores `seq` into the pinned word; lcAwaitTripSignal spins on the word while few threads wait and blocks in the runtime
 // when many do (a spinning thread burns a core the others stitch on) -- the policy runHostPipeline measured in round 2.
-int lcQueueTripSignal(uint32_t* hFlag, uint32_t seq, hipStream_t stream) {
+static hipError_t launchTripSignal(uint32_t* hFlag, uint32_t seq, hipStream_t stream) {
     void* fargs[] = {&hFlag, &seq};
-    HIP_TRY(hipLaunchKernel(reinterpret_cast<const void*>(lc_signal_kernel), dim3(1), dim3(1), fargs, 0, stream));
+    return hipLaunchKernel(reinterpret_cast<const void*>(lc_signal_kernel), dim3(1), dim3(1), fargs, 0, stream);
+}
+int lcQueueTripSignal(uint32_t* hFlag, uint32_t seq, hipStream_t stream) {
+    const hipError_t e = launchTripSignal(hFlag, seq, stream);
+    if (e != hipSuccess)  // (the text the launch has always failed with)
+        return hipFail(e, "hipLaunchKernel(reinterpret_cast<const void*>(lc_signal_kernel), dim3(1), dim3(1), fargs, 0, stream)");
     return LC_OK;
 }
-int lcAwaitTripSignal(const uint32_t* hFlag, uint32_t seq, hipStream_t stream) {
-    static const bool pollOff = getenv("LC_HOST_NO_POLL") != nullptr;
+static bool hostNoPoll() {
+    static const bool off = getenv("LC_HOST_NO_POLL") != nullptr;
+    return off;
+}
+// The wait itself.  queueSignal: nothing queued so far stores the word (runHostPipeline, when the match launch did not carry the signal
+// itself) -- the one-lane kernel is queued here, and only by a thread that is going to spin.
+static int awaitTripSignal(uint32_t* hFlag, uint32_t seq, hipStream_t stream, bool queueSignal) {
     const int ahead = gZeroCopyWaiters.fetch_add(1, std::memory_order_relaxed);
     hipError_t waitErr = hipSuccess;
-    if (pollOff || ahead >= 4) {
+    if (hostNoPoll() || ahead >= 4) {
         waitErr = hipStreamSynchronize(stream);
     } else {
+        if (queueSignal) waitErr = launchTripSignal(hFlag, seq, stream);
         const volatile uint32_t* flag = hFlag;
         unsigned spins = 0;
-        while (*flag != seq) {
+        while (waitErr == hipSuccess && *flag != seq) {
             __builtin_ia32_pause();
             if (++spins > 40000u) {  // ~1 ms: a long kernel, or something is wrong -- the runtime's wait reports errors
                 waitErr = hipStreamSynchronize(stream);
@@ -1718,6 +1677,9 @@ int lcAwaitTripSignal(const uint32_t* hFlag, uint32_t seq, hipStream_t stream) {
     gZeroCopyWaiters.fetch_sub(1, std::memory_order_relaxed);
     HIP_TRY(waitErr);
     return LC_OK;
+}
+int lcAwaitTripSignal(const uint32_t* hFlag, uint32_t seq, hipStream_t stream) {
+    return awaitTripSignal(const_cast<uint32_t*>(hFlag), seq, stream, false);
 }
 // lc_regex_match_device_multi on behalf of a zero-copy trip: the (small) job table is read by the kernel where the host wrote it, in
 // pinned memory -- no copy command per group on the SDMA queue, where the groups of all runner threads would meet.  A dozen workgroups
@@ -1846,10 +1808,7 @@ struct LineSource {
 int runHostPipeline(lc_regex_t* re, const LineSource& src, uint32_t n, uint32_t ngroups, int32_t* caps,
                     uint8_t* status) {
     if (n == 0) return LC_OK;
-    if (lc_device_count() <= 0) {
-        tlsError = "no HIP device";
-        return LC_ERR_NO_DEVICE;
-    }
+    if (const int rcAny = requireDevice(); rcAny != LC_OK) return rcAny;
     // the thread's device: its binding (lc_runtime_bind_thread; by default the thread's ordinal modulo the visible devices)
     int dev = 0;
     {
@@ -1933,7 +1892,6 @@ int runHostPipeline(lc_regex_t* re, const LineSource& src, uint32_t n, uint32_t 
                 }
             }
             std::memset(s.hData + stageBytes, 0, 16);
-            static const bool pollOff = getenv("LC_HOST_NO_POLL") != nullptr;
             const uint32_t doneSeqNo = ++s.flagSeq;
             // Whatever way this block is left: the completion request is disarmed (a later, unrelated launch of this thread must
             // not signal a stale flag), and after an error nothing queued here may still be reading the staging block or writing
@@ -1949,19 +1907,19 @@ int runHostPipeline(lc_regex_t* re, const LineSource& src, uint32_t n, uint32_t 
                     }
                 }
             } zc{s.stream};
-            tlsDone = DoneRequest{s.dDone, s.hFlag, doneSeqNo, !pollOff, false};
+            tlsDone = DoneRequest{s.dDone, s.hFlag, doneSeqNo, !hostNoPoll(), false};
             zc.queued = true;
             // (the backtracking engine reads a value in small steps, some of them more than once: through the pinned mapping every
             // step would be a PCIe read of its own -- its group is copied up first, in one piece)
+            MatchBatch in{.d_data = s.hData, .d_off = hOff, .d_len = hLen, .n = n,
+                          .ngroups = ngroups, .d_caps = s.hCaps, .d_status = s.hStatus, .dev = dev, .stream = s.stream};
             if (zeroCopyEnv == 2 || re->engine == LC_ENGINE_BT) {
                 HIP_TRY(hipMemcpyAsync(s.dData, s.hData, blockBytes, hipMemcpyHostToDevice, s.stream));
-                rc = lcMatchOnStream(re, re->engine, dev, s.dData, reinterpret_cast<uint32_t*>(s.dData + tableAt),
-                                     reinterpret_cast<uint32_t*>(s.dData + tableAt) + n, 0, n, nullptr, nullptr, nullptr, ngroups,
-                                     s.hCaps, s.hStatus, s.stream);
-            } else {
-                rc = lcMatchOnStream(re, re->engine, dev, s.hData, hOff, hLen, 0, n, nullptr, nullptr, nullptr, ngroups, s.hCaps,
-                                     s.hStatus, s.stream);
+                in.d_data = s.dData;
+                in.d_off = reinterpret_cast<uint32_t*>(s.dData + tableAt);
+                in.d_len = in.d_off + n;
             }
+            rc = lcMatchOnStream(re, re->engine, in);
             const bool signalled = tlsDone.consumed;
             tlsDone = DoneRequest{};
             if (rc != LC_OK) return rc;
@@ -1969,30 +1927,8 @@ int runHostPipeline(lc_regex_t* re, const LineSource& src, uint32_t n, uint32_t 
             // a 1000-line group last ~60 us; the runtime's wait costs ~40 us more per group than a spin: 2.5 vs 2.1 GB/s with one
             // thread).  Many: spinning threads burn the cores the others stitch on, and the runtime's blocking wait scales better
             // (20.0 vs 16.6 GB/s with 16 threads on a 16-core quota) -- tools/inagent_bench.cpp, profiles/round2_inagent.txt.
-            std::atomic<int>& waiters = gZeroCopyWaiters;
-            const int ahead = waiters.fetch_add(1, std::memory_order_relaxed);
-            hipError_t waitErr = hipSuccess;
-            if (pollOff || ahead >= 4) {
-                waitErr = hipStreamSynchronize(s.stream);
-            } else {
-                uint32_t seq = doneSeqNo;
-                if (!signalled) {  // the match was more than one launch (or not a TDFA launch): a one-lane kernel behind it signals
-                    void* fargs[] = {&s.hFlag, &seq};
-                    waitErr = hipLaunchKernel(reinterpret_cast<const void*>(lc_signal_kernel), dim3(1), dim3(1), fargs, 0, s.stream);
-                }
-                volatile uint32_t* flag = s.hFlag;
-                unsigned spins = 0;
-                while (waitErr == hipSuccess && *flag != seq) {
-                    __builtin_ia32_pause();
-                    if (++spins > 40000u) {  // ~1 ms: long kernel, or something is wrong -- the runtime's wait reports errors
-                        waitErr = hipStreamSynchronize(s.stream);
-                        break;
-                    }
-                }
-                __atomic_thread_fence(__ATOMIC_ACQUIRE);
-            }
-            waiters.fetch_sub(1, std::memory_order_relaxed);
-            HIP_TRY(waitErr);
+            // (the match was more than one launch, or not a TDFA launch: a one-lane kernel behind it signals)
+            if ((rc = awaitTripSignal(s.hFlag, doneSeqNo, s.stream, !signalled)) != LC_OK) return rc;
             if (ngroups) std::memcpy(caps, s.hCaps, size_t(n) * 2 * ngroups * 4);
             std::memcpy(status, s.hStatus, n);
             zc.ok = true;

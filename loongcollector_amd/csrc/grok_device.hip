@@ -230,11 +230,14 @@ static int grokMatchSequential(const std::vector<GrokDevicePattern>& patterns, G
             if (scr == gp.screen && gp.relaxed && nIn <= prefixAbove) continue;
             uint32_t* out = in == outs[0] ? outs[1] : outs[0];
             if (!scr->hasTdfa && !scr->screenBlob.empty()) {  // a plain DFA with its table in L2: screens and filters in one kernel
-                int rc = lcScreenOnStream(scr, dev, d_data, d_off, d_len, nIn, in, out, counters, st);
+                int rc = lcScreenOnStream(scr, {.d_data = d_data, .d_off = d_off, .d_len = d_len, .n = nIn, .d_order = in, .dev = dev, .stream = st},
+                                          out, counters);
                 if (rc != LC_OK) return rc;
             } else {
-                int rc = lcMatchOnStream(scr, LC_ENGINE_TDFA, dev, d_data, d_off, d_len, 0, nIn, nullptr, in, nullptr, 0, caps,
-                                         status, st);
+                int rc = lcMatchOnStream(scr, LC_ENGINE_TDFA,
+                                         {.d_data = d_data, .d_off = d_off, .d_len = d_len, .n = nIn,
+                                          .d_order = in,
+                                          .d_caps = caps, .d_status = status, .dev = dev, .stream = st});
                 if (rc != LC_OK) return rc;
                 hipLaunchKernelGGL(grok_status_filter_kernel, dim3((nIn + kGrokBlock - 1) / kGrokBlock), dim3(kGrokBlock), 0, st,
                                    in, nIn, status, out, counters);
@@ -254,8 +257,11 @@ static int grokMatchSequential(const std::vector<GrokDevicePattern>& patterns, G
         // one search round over the values listed in `list`: the pattern's kernel, then grok_advance_kernel (matches recorded,
         // values that stay in play appended to `out`, their number added to counters[0])
         auto searchRound = [&](lc_regex* re, const uint32_t* list, uint32_t nList, const uint32_t* resume, uint32_t* out) -> int {
-            int rc = lcMatchOnStream(re, re->engine, dev, d_data, d_off, d_len, 0, nList, nullptr, list, resume, capsRow / 2, caps,
-                                     status, st);
+            int rc = lcMatchOnStream(re, re->engine,
+                                     {.d_data = d_data, .d_off = d_off, .d_len = d_len, .n = nList,
+                                      .d_order = list,
+                                      .d_resume = resume,
+                                      .ngroups = capsRow / 2, .d_caps = caps, .d_status = status, .dev = dev, .stream = st});
             if (rc != LC_OK) return rc;
             hipLaunchKernelGGL(grok_advance_kernel, dim3((nList + kGrokBlock - 1) / kGrokBlock), dim3(kGrokBlock), 0, st, list, nList,
                                status, caps, capsRow, row, gp.columns, d_len, from, nmatch, d_pattern, d_first, d_extra, extraCap, out,
@@ -269,8 +275,10 @@ static int grokMatchSequential(const std::vector<GrokDevicePattern>& patterns, G
             // later).  Both append to the same next-round list.
             auto tRound = now();
             uint32_t* out = outs[flip];
-            int rc = lcMatchOnStream(gp.anchored, gp.anchored->engine, dev, d_data, d_off, d_len, 0, nIn, nullptr, in, nullptr, capsRow / 2,
-                                     caps, status, st);
+            int rc = lcMatchOnStream(gp.anchored, gp.anchored->engine,
+                                     {.d_data = d_data, .d_off = d_off, .d_len = d_len, .n = nIn,
+                                      .d_order = in,
+                                      .ngroups = capsRow / 2, .d_caps = caps, .d_status = status, .dev = dev, .stream = st});
             if (rc != LC_OK) return rc;
             hipLaunchKernelGGL(grok_unmatched_kernel, dim3((nIn + kGrokBlock - 1) / kGrokBlock), dim3(kGrokBlock), 0, st, in, nIn, status,
                                unanchored, counters + 3);
@@ -590,11 +598,7 @@ int grokPlanPhase1(const std::vector<GrokDevicePattern>& patterns, GrokDeviceSta
         return ((state->literalBlob[GL_OFF_MASKS] & 7u) == 0 && bytes <= 78 * 1024) ? bytes : 0u;
     }();
     if (litStageBytes) {
-        static thread_local size_t litAttr[kLcMaxDevices] = {};
-        if (litStageBytes > 48 * 1024 && dev < kLcMaxDevices && litStageBytes > litAttr[dev]) {
-            HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(grok_literal_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, int(litStageBytes)));
-            litAttr[dev] = litStageBytes;
-        }
+        if (const int rc = lcAllowLds(reinterpret_cast<const void*>(grok_literal_lds_kernel), dev, litStageBytes); rc != LC_OK) return rc;
         static thread_local uint32_t cus[kLcMaxDevices] = {};
         if (dev < kLcMaxDevices && !cus[dev]) {
             hipDeviceProp_t prop;
@@ -877,6 +881,15 @@ int grokMatchSpeculative(const std::vector<GrokDevicePattern>& patterns, GrokDev
     uint32_t* gate = tail + TW_GATE;
     uint32_t* xcount = tail + TW_XCOUNT;
     const uint32_t nAct = uint32_t(act.size());
+    // entry e's candidates as a launch sees them: `bound` of them at most, the count on the device, the list and the resume offsets
+    auto entryBatch = [&](const PlanEntry& e, uint32_t bound, const uint32_t* count, const uint32_t* list, const uint32_t* resume,
+                          hipStream_t ws) {
+        return MatchBatch{.d_data = d_data, .d_off = e.dev.off, .d_len = e.dev.len, .n = bound,
+                          .d_n = count,
+                          .d_order = list,
+                          .d_resume = resume,
+                          .ngroups = e.capsRow / 2, .d_caps = e.caps, .d_status = e.status, .dev = dev, .stream = ws};
+    };
     // ---- phase 3: the first contributing entry per value; its rows go out.  All of it returns at once when values are still in
     // play somewhere (gate != 0): the host then finishes those entries and queues it again
     const uint32_t gridCand = (maxCand + kGrokPlanBlock - 1) / kGrokPlanBlock;
@@ -1033,23 +1046,17 @@ int grokMatchSpeculative(const std::vector<GrokDevicePattern>& patterns, GrokDev
         // one engine call of entry e on stream ws: the first-chance kernel ...
         auto runFirst = [&](PlanEntry& e, lc_regex* h, bool wide, const uint32_t* count, const uint32_t* list, bool withFrom, uint32_t* seq,
                             hipStream_t ws) -> int {
-            const uint32_t* resume = withFrom ? e.dev.from : nullptr;
-            if (wide)
-                return lcMatchWideFirstOnStream(0, h, h->engine, dev, d_data, e.dev.off, e.dev.len, 0, e.cand, count, list, resume, e.capsRow / 2,
-                                                e.caps, e.status, seq, e.dev.cnt + GC_WIDE, ws);
-            return lcMatchFirstOnStream(h, h->engine, dev, d_data, e.dev.off, e.dev.len, 0, e.cand, count, list, resume, e.capsRow / 2, e.caps,
-                                        e.status, seq, ws);
+            const MatchBatch b = entryBatch(e, e.cand, count, list, withFrom ? e.dev.from : nullptr, ws);
+            if (wide) return lcMatchWideFirstOnStream(0, h, h->engine, b, seq, e.dev.cnt + GC_WIDE);
+            return lcMatchFirstOnStream(h, h->engine, b, seq);
         };
         // ... and what is left behind it (note: the entry's GC_WIDE word, set when the wide kernel had anything to do)
         auto runSecond = [&](PlanEntry& e, lc_regex* h, bool wide, const uint32_t* count, const uint32_t* list, bool withFrom, uint32_t seq,
                              uint32_t* note, hipStream_t ws) -> int {
-            const uint32_t* resume = withFrom ? e.dev.from : nullptr;
-            if (wide)
-                return lcMatchWideFirstOnStream(1, h, h->engine, dev, d_data, e.dev.off, e.dev.len, 0, e.cand, count, list, resume, e.capsRow / 2,
-                                                e.caps, e.status, &seq, nullptr, ws);
+            const MatchBatch b = entryBatch(e, e.cand, count, list, withFrom ? e.dev.from : nullptr, ws);
+            if (wide) return lcMatchWideFirstOnStream(1, h, h->engine, b, &seq, nullptr);
             lcSetWideNote(note);
-            const int r = lcMatchSecondChanceOnStream(h, h->engine, dev, d_data, e.dev.off, e.dev.len, 0, e.cand, count, list, resume,
-                                                      e.capsRow / 2, e.caps, e.status, seq, ws);
+            const int r = lcMatchSecondChanceOnStream(h, h->engine, b, seq);
             lcSetWideNote(nullptr);
             return r;
         };
@@ -1280,8 +1287,7 @@ int grokMatchSpeculative(const std::vector<GrokDevicePattern>& patterns, GrokDev
                     const uint32_t* list = r == 1 ? (screened ? e.unanchored : e.listA) : (r & 1) ? e.listA : e.listB;
                     uint32_t* out2 = (r & 1) ? e.listB : e.listA;
                     const uint32_t* countPtr = r == 1 ? e.dev.cnt + (screened ? GC_REMAINDER : GC_ROUND0) : e.dev.cnt + GC_ROUND0 + r - 1;
-                    rc = lcMatchOnStream(gp.re, gp.re->engine, dev, d_data, e.dev.off, e.dev.len, 0, e.cand, countPtr, list, e.dev.from,
-                                         e.capsRow / 2, e.caps, e.status, ws);
+                    rc = lcMatchOnStream(gp.re, gp.re->engine, entryBatch(e, e.cand, countPtr, list, e.dev.from, ws));
                     if (rc != LC_OK) return;
                     hipLaunchKernelGGL(grok_advance2_kernel, dim3(grid), dim3(kGrokPlanBlock), 0, ws, list, e.cand, countPtr, e.status, e.caps,
                                        e.capsRow, e.columns, e.dev, xtmp, xcap, xstride, xcount, out2, e.dev.cnt + GC_ROUND0 + r,
@@ -1600,8 +1606,7 @@ int grokMatchSpeculative(const std::vector<GrokDevicePattern>& patterns, GrokDev
                     uint32_t* out = (r & 1) ? e.listB : e.listA;
                     const uint32_t bound = k == 0 ? inPlay : e.cand;
                     const uint32_t* countPtr = k == 0 ? nullptr : e.dev.cnt + GC_ROUND0 + k - 1;
-                    int rc = lcMatchOnStream(gp.re, gp.re->engine, dev, d_data, e.dev.off, e.dev.len, 0, bound, countPtr, list, e.dev.from,
-                                             e.capsRow / 2, e.caps, e.status, st);
+                    int rc = lcMatchOnStream(gp.re, gp.re->engine, entryBatch(e, bound, countPtr, list, e.dev.from, st));
                     if (rc != LC_OK) return rc;
                     hipLaunchKernelGGL(grok_advance2_kernel, dim3((bound + kGrokPlanBlock - 1) / kGrokPlanBlock), dim3(kGrokPlanBlock), 0, st,
                                        list, bound, countPtr, e.status, e.caps, e.capsRow, e.columns, e.dev, xtmp, xcap, xstride, xcount, out,

@@ -147,7 +147,10 @@ int lcMultilineSplitTrip(lc_multiline* m, const uint8_t* data, uint32_t nbytes, 
         if (!res[k]) continue;
         uint8_t* st = static_cast<uint8_t*>(T.dStatus.p) + size_t(k) * statusStride;
         status[k] = st;
-        rc = lcMatchOnStream(res[k], res[k]->engine, dev, dData, dOff, nullptr, 1, maxLines, dN, nullptr, nullptr, 0, dCapsDummy, st, T.stream);
+        rc = lcMatchOnStream(res[k], res[k]->engine,
+                             {.d_data = dData, .d_off = dOff, .sep = 1, .n = maxLines,
+                              .d_n = dN,
+                              .d_caps = dCapsDummy, .d_status = st, .dev = dev, .stream = T.stream});
     }
     if (rc != LC_OK) return rc;
     rc = boundsAndFetch(T, modeOf(*m, true), status, dN, maxLines, dOff, nbytes, out, counts);

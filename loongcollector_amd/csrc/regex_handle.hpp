@@ -165,27 +165,36 @@ lc_regex* lcCompilePrefixScreen(const char* pattern, size_t len, uint32_t syntax
 lc_regex* lcCompileRelaxedScreen(const char* pattern, size_t len, uint32_t syntax_flags, uint32_t maxStates, size_t maxBlobBytes);
 lc_regex* lcCompileRelaxedScreenPreferring(const char* pattern, size_t len, uint32_t syntax_flags, uint32_t maxStates, size_t maxBlobBytes,
                                            size_t preferStageBytes);
+// What one launch matches and where its answers go: every launcher of gpu_runtime.hip and its callers (grok_device.hip,
+// multiline_device.hip) hand this on by reference.  Callers name the fields they set; the rest keep these defaults.
+struct MatchBatch {
+    const uint8_t* d_data = nullptr;
+    const uint32_t* d_off = nullptr;
+    const uint32_t* d_len = nullptr;     // nullptr: a line ends `sep` bytes before the next one's offset
+    uint32_t sep = 0;
+    uint32_t n = 0;
+    const uint32_t* d_n = nullptr;       // optional: line count on the device (n bounds it)
+    const uint32_t* d_order = nullptr;   // optional: the lines to process
+    const uint32_t* d_resume = nullptr;  // optional, indexed by line: resume offsets of a search pattern
+    uint32_t ngroups = 0;
+    int32_t* d_caps = nullptr;
+    uint8_t* d_status = nullptr;
+    int dev = 0;
+    void* stream = nullptr;              // hipStream_t
+};
 // implemented in gpu_runtime.hip: one pass of a screen handle that carries a screenBlob (dfa_screen_kernel) over the values
-// listed in d_in (nullptr: all n); accepted values are appended to d_out, their number added to d_counters[0]
-int lcScreenOnStream(lc_regex* re, int dev, const uint8_t* d_data, const uint32_t* d_off, const uint32_t* d_len, uint32_t n,
-                     const uint32_t* d_in, uint32_t* d_out, uint32_t* d_counters, void* stream);
+// listed in b.d_order (nullptr: all b.n); accepted values are appended to d_out, their number added to d_counters[0]
+int lcScreenOnStream(lc_regex* re, const MatchBatch& b, uint32_t* d_out, uint32_t* d_counters);
 // implemented in gpu_runtime.hip; frees device copies
 void lcReleaseDeviceTables(lc_regex* re);
 // regex_handle.cpp: ask for the wave-per-value kernel on small batches of this handle (packs the global-memory form of its tagged
 // DFA beside the LDS form; no effect on handles without a tagged DFA).  Call before the handle's first launch.
 void lcPreferWaveTdfa(lc_regex* re);
-// implemented in gpu_runtime.hip: one launch of the engine's kernel.  d_n (optional): line count on the device;
-// d_order (optional): the lines to process; d_resume (optional, indexed by line): resume offsets of a search pattern.
-int lcMatchOnStream(lc_regex* re, int engine, int dev, const uint8_t* d_data, const uint32_t* d_off, const uint32_t* d_len,
-                    uint32_t sep, uint32_t n, const uint32_t* d_n, const uint32_t* d_order, const uint32_t* d_resume,
-                    uint32_t ngroups, int32_t* d_caps, uint8_t* d_status, void* stream);
+// implemented in gpu_runtime.hip: one launch of the engine's kernel.
+int lcMatchOnStream(lc_regex* re, int engine, const MatchBatch& b);
 // the engine's main kernel only (*seq: see below), and the second chance for the lines it left LC_OVERFLOW (gpu_runtime.hip)
-int lcMatchFirstOnStream(lc_regex* re, int engine, int dev, const uint8_t* d_data, const uint32_t* d_off, const uint32_t* d_len,
-                         uint32_t sep, uint32_t n, const uint32_t* d_n, const uint32_t* d_order, const uint32_t* d_resume, uint32_t ngroups,
-                         int32_t* d_caps, uint8_t* d_status, uint32_t* seq, void* streamPtr);
-int lcMatchSecondChanceOnStream(lc_regex* re, int engine, int dev, const uint8_t* d_data, const uint32_t* d_off, const uint32_t* d_len,
-                                uint32_t sep, uint32_t n, const uint32_t* d_n, const uint32_t* d_order, const uint32_t* d_resume,
-                                uint32_t ngroups, int32_t* d_caps, uint8_t* d_status, uint32_t seq, void* streamPtr);
+int lcMatchFirstOnStream(lc_regex* re, int engine, const MatchBatch& b, uint32_t* seq);
+int lcMatchSecondChanceOnStream(lc_regex* re, int engine, const MatchBatch& b, uint32_t seq);
 // Round 5, "wide first" (nfa_wide_kernel.hpp): for a caller that knows the pattern needs more than 64 threads on its data.
 //   part 0: the wide kernel over every line as the first chance (*seq as above; lines beyond 128 threads keep LC_OVERFLOW);
 //   part 1: what is left behind part 0 -- the decide kernels alone (seq: what part 0 returned);
@@ -193,8 +202,6 @@ int lcMatchSecondChanceOnStream(lc_regex* re, int engine, int dev, const uint8_t
 // Engines and programs the wide kernel does not run (tagged DFAs, atomic groups, more than 64 capture slots) take their usual
 // kernels: part 0 = lcMatchFirstOnStream, part 2 = lcMatchOnStream.  wideNote (optional, device word): set to 1 by the launch when
 // some line did need more than 64 threads.
-int lcMatchWideFirstOnStream(int part, lc_regex* re, int engine, int dev, const uint8_t* d_data, const uint32_t* d_off, const uint32_t* d_len,
-                             uint32_t sep, uint32_t n, const uint32_t* d_n, const uint32_t* d_order, const uint32_t* d_resume,
-                             uint32_t ngroups, int32_t* d_caps, uint8_t* d_status, uint32_t* seq, uint32_t* wideNote, void* streamPtr);
+int lcMatchWideFirstOnStream(int part, lc_regex* re, int engine, const MatchBatch& b, uint32_t* seq, uint32_t* wideNote);
 // does the wide kernel run this handle's thread-list program at all?
 bool lcNfaWideApplies(const lc_regex* re);

@@ -21,6 +21,9 @@ void lcDelimThreadRelease();                           // delim_device.hip: the 
 void lcTimestampThreadRelease();                       // timestamp_device.hip: the same for the timestamp parser's host entry
 void lcApsaraThreadRelease();                          // apsara_device.hip: the same for the Apsara parser's host entry
 void lcJsonThreadRelease();                            // json_device.hip: the same for the JSON parser's host entry
+// hipFuncSetAttribute for a launch of `kern` on `dev` that asks for more than 48 KiB of dynamic LDS: once per (thread, kernel, device)
+// and size, grow-only.  The only place the attribute is set.
+int lcAllowLds(const void* kern, int dev, size_t lds);
 // The device a DEVICE-pointer entry point runs on: the caller's current HIP device; LC_ERR_ARG when d_ptr lives on another device.
 int lcDeviceEntryDevice(const void* d_ptr, int* dev);
 // the decide pool the calling thread's next NFA launches use (0 = default; 1.. = worker streams of the Grok matcher)

@@ -1068,3 +1068,44 @@ def test_atomic_lazy_loop_commits_on_the_thread_list_engine(torch_dev):
                         assert status[i] == B.LC_NOMATCH and (caps[i] == -1).all(), (p, eng, search, s)
                     else:
                         assert status[i] == B.LC_MATCH and list(caps[i]) == exp, (p, eng, search, s, list(caps[i]), exp)
+
+
+# One host-fed chunk of 65 lines (a full wave and one lane), one of them empty, through lc_regex_match_host: the zero-copy trip of
+# runHostPipeline.  On the thread-list engine the match is several launches, so a polling thread queues the signal kernel behind them;
+# regex A's tagged DFA is one launch that carries the signal itself.  What is asserted: captures and status equal the oracle's on three
+# trips in a row, and the engine's kernel ran.  (A signal that never arrived would not show here: the spin ends in the runtime's wait
+# after 40 000 turns and the results are the same.)
+_HOST_TRIP_CODE = r"""
+import numpy as np
+from loongcollector_amd import binding as B, corpus
+from oracle.oracle import OracleRegex
+data, off, length = corpus.apache_batch(65, "A", poison_every=9)
+length = length.copy()
+length[20] = 0
+exp_caps, exp_status = OracleRegex(corpus.REGEX_A).fullmatch_batch(data, off[:-1], length)
+assert exp_status[20] == B.LC_NOMATCH and 0 < exp_status.sum() < 65
+for engine, kernel in ((B.LC_ENGINE_NFA, "nfa_match_kernel"), (B.LC_ENGINE_TDFA, "tdfa_stream_kernel")):
+    rx = B.GpuRegex(corpus.REGEX_A, engine=engine)
+    assert rx.info()["engine"] == engine
+    B.launched_kernels()
+    for turn in range(3):   # (the slot's sequence number goes on from trip to trip)
+        caps, status = rx.match_host(data, off[:-1], length)
+        assert np.array_equal(status, exp_status), (engine, turn, status.tolist())
+        assert np.array_equal(caps, exp_caps), (engine, turn)
+    assert kernel in B.launched_kernels()
+print("ok")
+"""
+
+
+def test_host_fed_chunk_of_65_lines_equals_the_oracle_on_both_engines(torch_dev):
+    exec(compile(_HOST_TRIP_CODE, "<host trip>", "exec"), {})
+
+
+def test_host_fed_chunk_of_65_lines_equals_the_oracle_with_polling_switched_off():
+    """The same with LC_HOST_NO_POLL=1 (read once per process: a fresh interpreter), where the trip ends in the runtime's wait."""
+    import subprocess
+    import sys
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+    env = dict(os.environ, LC_HOST_NO_POLL="1")
+    out = subprocess.run([sys.executable, "-c", _HOST_TRIP_CODE], cwd=root, env=env, capture_output=True, text=True, timeout=240)
+    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), (out.stdout[-500:], out.stderr[-1500:])
