@@ -1,0 +1,412 @@
+"""Test-only corpus for the engines that walk ONE VALUE PER WAVEFRONT (csrc/nfa_kernel.hpp nfa_match_kernel, csrc/nfa_wide_kernel.hpp,
+csrc/tdfa_l2_kernel.hpp tdfaWaveBody) and for their lane-per-value neighbours (tdfa_l2_kernel, nfa_decide_kernel, nfa_dfs_kernel,
+bt_match_kernel): values in which ONE decision of the walk falls on a chosen byte, for every alignment of the value's first byte.
+
+The wave walks hold a 256-byte chunk of the value as one dword per lane.  The view is word-aligned (head = address & 3), so a chunk
+border falls at line offset 256k - head.  tdfa_l2_kernel reads 16-byte pieces (head = address & 15).  Every shortcut inside a chunk --
+the steady / quiet run scan, the search skip, the doomed-spawn look-ahead, the chunk reload, the resume chunk, the suffix-thread exit,
+the stop on the absorbing state -- is a comparison against a chunk border, the end of the value or the start offset.
+
+A case is (family, kind, variant, p, head, line, after, frm): `p` is the line offset of the event the kind names, `head` the residue
+the line's first byte must have in device memory, `after` the byte right behind the line in the packed data (never part of the line),
+`frm` the offset a search resumes at (resume cases only).  Kinds:
+  run_stop      a quiet / steady run ends at p: byte p is the first that is not quiet (the run starts at 0, p-1, p-2, p-5, p-40)
+  run_to_end    the value ends at L = p inside a run; NEEDY variants have the byte behind them in memory that would change the result
+  stamp         a capture begins or ends at p; a one-byte field [p, p+1); an empty field at p
+  dead          the value fails in byte p; the bytes behind it would match if walked
+  absorb        the automaton reaches its final (.*) at p, with 300+ bytes behind
+  search_start  (search patterns) the first byte a match can start with is at p: (a) a match follows, (b) a doomed start -- the second
+                byte refuses it --, (c) a start byte that is the last byte of the value, (d) a start the look-behind refuses
+  resume        (search patterns) the search resumes at frm = p-1, p, p+1; the next match begins at frm, frm+1 or in the next chunk
+  threads       (NFA only) 8, exactly 6 (kNfaSteadyScanThreads) or 1 live steady threads in a run that ends at p
+What a pattern cannot do is said by its family (Family.kinds: kind -> the smallest p it exists for).  tests/test_chunk_edges.py
+asserts all of this against the oracle and against the compiled tables, so that the GPU test cannot pass on a degenerate corpus.
+
+pack(form, modulus): "len" = (off, len) with filler bytes between the lines that give every line its head (the filler would change
+the answer if it were read); "sep" = off[n + 1] and one separator byte, where alignment follows from the lengths (the residues that
+came out are returned, the tests assert that all occur).  Not part of the product, never imported by loongcollector_amd/."""
+import functools
+from collections import namedtuple
+
+import numpy as np
+
+from loongcollector_amd import binding as B
+
+W256_P = tuple(range(0, 6)) + tuple(range(246, 263)) + tuple(range(502, 519))   # 6 below .. 6 behind the first two borders, any head
+W16_P = tuple(range(0, 34))
+WALKS = {"w256": (W256_P, 4), "w16": (W16_P, 16)}                               # walk -> (offsets, modulus of head)
+RUN_BACK = (1, 2, 5, 40)                                                        # a run that ends at p starts at p - k (or at 0)
+GUARD_BYTES = 64                                                                # zero bytes behind the packed data
+
+Case = namedtuple("Case", "family kind variant p head line after frm")
+
+
+def _cyc(alphabet, n, phase=0):
+    return bytes(alphabet[(phase + i) % len(alphabet)] for i in range(n)) if n > 0 else b""
+
+
+class Family:
+    """A pattern and the lines that put each of its kinds on offset p.  cases(kind, p) -> [(variant, line, after, frm)];
+    kinds: kind -> smallest p;  needy_min: smallest p at which run_to_end has a variant whose result the byte behind changes."""
+    name = pattern = None
+    flags = 0
+    search = False
+    kinds = {}
+    needy_min = None
+    filler = b"\n"            # between the lines of the (off, len) form: bytes that would change the answer if read
+    after = b"\n"             # behind a line that names no byte of its own
+
+    def cases(self, kind, p):
+        return getattr(self, "k_" + kind)(p)
+
+
+class LogFamily(Family):
+    """a full-match log format that ends in (.*): [^x]* fields give quiet runs, the last separator the absorbing state"""
+    name, pattern = "log", rb"([^,]*),(\d*);([^ ]*) (.*)"
+    kinds = {"run_stop": 0, "run_to_end": 0, "stamp": 0, "dead": 1, "absorb": 3}
+    needy_min = 2
+    filler, after = b",7; ", b"7"
+    TAIL = b" ok,1;z "
+
+    def _line(self, c, s, t, L):
+        """[^,]* bytes [0, c), a comma at c, digits, a semicolon at s, [^ ]* bytes, a space at t, anything up to L"""
+        assert 0 <= c < s < t < L, (c, s, t, L)
+        return _cyc(b"xyz-", c, c) + b"," + _cyc(b"0123456789", s - c - 1, s) + b";" + _cyc(b"uvw;", t - s - 1, t) + b" " + _cyc(self.TAIL, L - t - 1)
+
+    def k_run_stop(self, p):
+        out = [("f1_from0", self._line(p, p + 2, p + 4, p + 8), None, None)]
+        for k in RUN_BACK:
+            if p - k - 1 >= 0:
+                out.append(("digits_%d" % k, self._line(p - k - 1, p, p + 3, p + 8), None, None))     # comma at p-k-1, digits [p-k, p), ';' at p
+            if p - k - 2 >= 0:
+                out.append(("f3_%d" % k, self._line(0, p - k - 1, p, p + 8), None, None))             # ';' at p-k-1, [^ ]* [p-k, p), ' ' at p
+        return out
+
+    def k_run_to_end(self, p):
+        out = [("f1", _cyc(b"xyz-", p), b";", None)]                                                  # fails: no comma
+        if p >= 1:
+            out.append(("digits", b"," + _cyc(b"0123456789", p - 1), b";", None))
+            out.append(("digits_f1", _cyc(b"xy", (p - 1) // 2) + b"," + _cyc(b"0123456789", p - 1 - (p - 1) // 2), b";", None))
+        if p >= 2:
+            out.append(("f3_needy", b",;" + _cyc(b"uvw", p - 2), b" ", None))                          # fails for want of the space behind it
+        if p >= 4:
+            out.append(("f3_needy_f1", _cyc(b"xy", (p - 2) // 2) + b",;" + _cyc(b"uvw;", p - 2 - (p - 2) // 2), b" ", None))
+        return out
+
+    def k_stamp(self, p):
+        out = []
+        if p >= 1:
+            out += [("digits_begin", self._line(p - 1, p + 3, p + 5, p + 9), None, None),
+                    ("digits_end", self._line(max(0, p - 3), p, p + 2, p + 6), None, None),
+                    ("one_byte", self._line(p - 1, p + 1, p + 3, p + 7), None, None),
+                    ("empty", self._line(p - 1, p, p + 2, p + 6), None, None)]
+        else:
+            out += [("one_byte", b"x,1;u t", None, None), ("empty", b",1;u t", None, None)]
+        if p >= 2:
+            out.append(("f3_end", self._line(0, max(1, p - 3), p, p + 5), None, None))
+        if p >= 3:
+            out.append(("rest_begin", self._line(0, 1, p - 1, p + 5), None, None))
+            out.append(("rest_empty", self._line(0, 1, p - 1, p), None, None))                         # (.*) empty at p = L
+        return out
+
+    def k_dead(self, p):
+        c = p - 1 if p < 4 else p - 3
+        return [("digits", _cyc(b"xyz-", c, c) + b"," + _cyc(b"0123456789", p - c - 1) + b"Z" + b"7;u " + _cyc(self.TAIL, 5), None, None)]
+
+    def k_absorb(self, p):
+        c = max(0, p - 6)
+        return [("space", self._line(c, c + 1 if p < 5 else p - 3, p - 1, p + 300 + p % 7), None, None)]
+
+
+class BigFamily(LogFamily):
+    """a tagged DFA of 8 000+ states: its tables stay in global memory, so tdfa_l2_kernel / tdfa_wave_kernel run by necessity"""
+    name, pattern = "big", rb"([^,]*),(\d*);(?:a|b)*a(?:a|b){12}(c+)(d*) (.*)"
+    kinds = {"run_stop": 0, "run_to_end": 0, "stamp": 0, "dead": 1, "absorb": 17}
+    needy_min = 16
+    filler, after = b",7;c ", b"c"
+    AB = 13                                                                        # bytes of "a" + 12 of [ab]
+
+    def _big(self, c, s, m, k, j, L):
+        """as _line up to the semicolon at s, then m bytes of [ab], "a" and 12 of [ab], c's [u, u + k), d's, a space, anything up to L"""
+        u = s + 1 + m + self.AB
+        assert 0 <= c < s and k >= 1 and u + k + j < L, (c, s, m, k, j, L)
+        return (_cyc(b"xyz-", c, c) + b"," + _cyc(b"0123456789", s - c - 1, s) + b";" + _cyc(b"ab", m, m) + b"a" + _cyc(b"bab", 12, s) +
+                b"c" * k + b"d" * j + b" " + _cyc(self.TAIL, L - u - k - j - 1))
+
+    def k_run_stop(self, p):
+        out = [("f1_from0", self._big(p, p + 2, 1, 2, 1, p + 30), None, None)]
+        for k in RUN_BACK:
+            if p - k - 1 >= 0:
+                out.append(("digits_%d" % k, self._big(p - k - 1, p, 2, 1, 0, p + 26), None, None))
+            if p - k - 15 >= 0:
+                out.append(("c_%d" % k, self._big(0, 1, p - k - 15, k, 2, p + 9), None, None))         # c's [p-k, p), a 'd' at p
+        return out
+
+    def k_run_to_end(self, p):
+        out = [("f1", _cyc(b"xyz-", p), b";", None)]
+        if p >= 1:
+            out.append(("digits", b"," + _cyc(b"0123456789", p - 1), b";", None))
+        if p >= 16:
+            out.append(("c_needy", self._big(0, 1, 0, p - 15, 0, p + 1)[:p], b" ", None))             # fails for want of the space behind it
+        if p >= 17:
+            out.append(("d_needy", self._big(0, 1, 0, 1, p - 16, p + 1)[:p], b" ", None))
+        return out
+
+    def k_stamp(self, p):
+        out = []
+        if p >= 1:
+            out += [("digits_begin", self._big(p - 1, p + 3, 0, 1, 1, p + 24), None, None),
+                    ("digits_end", self._big(max(0, p - 3), p, 1, 2, 0, p + 24), None, None),
+                    ("one_byte", self._big(p - 1, p + 1, 0, 1, 0, p + 22), None, None),
+                    ("empty", self._big(p - 1, p, 0, 1, 0, p + 22), None, None)]
+        else:
+            out += [("one_byte", self._big(1, 3, 0, 1, 0, 24), None, None), ("empty", self._big(0, 2, 0, 1, 0, 24), None, None)]
+        if p >= 15:
+            out.append(("c_begin", self._big(0, 1, p - 15, 3, 2, p + 9), None, None))
+        if p >= 16:
+            out.append(("c_one_byte_d_empty", self._big(0, 1, p - 16, 1, 0, p + 5), None, None))      # c+ = [p-1, p), d* empty at p
+        if p >= 18:
+            out.append(("rest_empty", self._big(0, 1, p - 18, 2, 0, p), None, None))                  # the space is the value's last byte, behind a run
+        return out
+
+    def k_dead(self, p):
+        c = p - 1 if p < 4 else p - 3
+        out = [("digits", _cyc(b"xyz-", c, c) + b"," + _cyc(b"0123456789", p - c - 1) + b"Z7" + self._big(0, 1, 0, 1, 0, 22)[1:], None, None)]
+        if p >= 3:
+            out.append(("ab", b",;" + _cyc(b"ab", p - 2) + b"Z" + self._big(0, 1, 0, 1, 0, 22)[2:], None, None))
+        return out
+
+    def k_absorb(self, p):
+        return [("space", self._big(0, 1, p - 17, 1, 0, p + 300 + p % 7), None, None)]              # c at p-2, the space at p-1
+
+
+class SearchFamily(Family):
+    """search patterns: junk the pattern cannot start in, then what the kind asks for at p"""
+    search, flags = True, B.LC_SYNTAX_SEARCH
+    kinds = {"search_start": 0, "resume": 0}
+    JUNK = b"xyz -"
+    HIT = DOOMED = START = None      # a match; a start byte and a byte that refuses it; the start byte alone
+    BEHIND = None                    # (look-behind patterns) a byte in front of HIT that refuses the start
+    filler = after = None            # set per family: the beginning of HIT / what completes a match
+
+    def k_search_start(self, p):
+        j = _cyc(self.JUNK, p, p)
+        out = [("a_match", j + self.HIT + b" t", None, None), ("a_match_at_end", j + self.HIT, None, None),
+               ("b_doomed", j + self.DOOMED + _cyc(self.JUNK, 2) + self.HIT + b" t", None, None),
+               ("b_doomed_far", j + self.DOOMED + _cyc(self.JUNK, 300, p) + self.HIT, None, None),
+               ("b_doomed_alone", j + self.DOOMED + _cyc(self.JUNK, 3), None, None),
+               ("c_last_byte", j + self.START, None, None)]
+        if self.BEHIND is not None and p >= 1:
+            out.append(("d_behind", j[:-1] + self.BEHIND + self.HIT + b" " + self.HIT + b" t", None, None))
+        return out
+
+    def k_resume(self, p):
+        out = []
+        for frm in (p - 1, p, p + 1):
+            if frm < 0:
+                continue
+            for name, gap in (("at_from", 0), ("at_from1", 1), ("next_chunk", 300)):
+                line = self.HIT + b" " + _cyc(self.JUNK, max(0, frm + gap - len(self.HIT) - 1), frm)
+                line = line[:frm + gap] + self.HIT + b" t" if len(line) >= frm + gap else None
+                if line is not None:
+                    out.append(("from%+d_%s" % (frm - p, name), line, None, frm))
+        return out
+
+
+class QuasiFamily(SearchFamily):
+    """QUASI_PATTERNS[2] of tests/test_host_compilers.py: a doomed-spawn shape (a start byte most occurrences of which lead nowhere)"""
+    name, pattern = "quasi", rb"Group = (.*), IP = (\d+), NAT"
+    HIT, DOOMED, START = b"Group = ab, IP = 9, NAT", b"Gx", b"G"
+    JUNK = b"xyz -,"
+    filler, after = b"Group = ", b"T"
+
+    def k_search_start(self, p):
+        out = super().k_search_start(p)
+        out.append(("needy", _cyc(self.JUNK, p, p) + self.HIT[:-1], b"T", None))                       # fails for want of the 'T' behind it
+        return out
+
+
+class LookFamily(SearchFamily):
+    """a look-behind in front of the first byte: the class of byte p - 1 decides whether a match may begin at p"""
+    name, pattern = "look", rb"(?<![0-9.])(\d+)\.(\d+)\.(\d+)\.(\d+)(?![0-9])"
+    HIT, DOOMED, START, BEHIND = b"10.2.3.4", b"1x", b"1", b"."
+    filler, after = b"9.", b"5"                                                                        # (a digit behind a line: the look-ahead would refuse)
+
+
+class AtomicFamily(SearchFamily):
+    """an atomic group: nfa_match_kernel<atomic>"""
+    name, pattern = "atomic", rb"(?>[a-z]+)(\d\d)"
+    JUNK = b"-_ ."
+    HIT, DOOMED, START = b"ab12", b"a-", b"a"
+    filler, after = b"q", b"3"
+
+    def k_search_start(self, p):
+        out = super().k_search_start(p)
+        out.append(("needy", _cyc(self.JUNK, p, p) + b"ab1", b"2", None))                              # fails for want of the digit behind it
+        return out
+
+
+class ThreadsFamily(Family):
+    """eight alternatives, each a self loop on the run's bytes: a digit k in front of the run kills alternative k, what is left are
+    that many live threads, all steady, until the comma at p (NFA only: a DFA has one state whatever the count)"""
+    name = "threads"
+    pattern = b"(?:" + b"|".join(b"([^,%d]*)" % k for k in range(1, 9)) + b"),(.*)"
+    kinds = {"threads": 0}
+    filler, after = b",", b","
+    LIVE = {8: b"", 7: b"1", 6: b"12", 5: b"123", 1: b"1234567"}
+
+    def k_threads(self, p):
+        out = []
+        for live, kill in self.LIVE.items():
+            if len(kill) <= p:
+                out.append(("live%d" % live, kill + _cyc(b"xyz-", p - len(kill), p) + b"," + b"tail, 1", None, None))
+                out.append(("live%d_to_end" % live, kill + _cyc(b"xyz-", p - len(kill), p), b",", None))   # L = p: fails, the comma is behind it
+        return out
+
+
+class BackrefFamily(Family):
+    """a back-reference: only the backtracking engine runs it (bt_match_kernel reads bytes directly: no chunk, the same offsets)"""
+    name, pattern = "backref", rb"(\w+),(\d*);\1 ?(.*)"
+    kinds = {"stamp": 1, "dead": 2, "run_to_end": 3}
+    needy_min = 3
+    filler, after = b"a,;a", b"a"
+
+    @staticmethod
+    def _line(c, s, L):
+        """a word of c bytes, a comma, digits, a semicolon at s, the word again, a space, anything up to L"""
+        w = _cyc(b"abc_9", c, c)
+        assert 1 <= c < s and s + 1 + c < L, (c, s, L)
+        return w + b"," + _cyc(b"0123456789", s - c - 1) + b";" + w + b" " + _cyc(b"t ,;a", L - s - c - 2)
+
+    def k_stamp(self, p):
+        out = [("word_end", self._line(p, p + 2, 2 * p + 7), None, None)]
+        if p >= 2:
+            out += [("digits_end", self._line(max(1, p - 3), p, p + max(1, p - 3) + 6), None, None),
+                    ("empty", self._line(p - 1, p, 2 * p + 4), None, None)]
+        if p >= 5:
+            c = (p - 3) // 2
+            out.append(("rest_begin", self._line(c, p - c - 2, p + 4), None, None))                   # the space at p - 1
+        return out
+
+    def k_dead(self, p):
+        c = max(1, p - 3)
+        if c >= p:
+            return []
+        return [("digits", _cyc(b"abc_9", c, c) + b"," + _cyc(b"0123456789", p - c - 1) + b"Z" + b"7;" + _cyc(b"abc_9", c, c) + b" t", None, None)]
+
+    def k_run_to_end(self, p):
+        """the value ends one byte short of the word's second copy: that byte is behind it"""
+        c = (p - 1) // 2
+        d = p - 2 * c - 1                                   # digits: 0 or 1
+        w = _cyc(b"abc_9", c, c)
+        if c < 1:
+            return []
+        return [("needy", w + b"," + b"7" * d + b";" + w[:-1], w[-1:], None)]
+
+
+FAMILIES = {f.name: f for f in (LogFamily(), BigFamily(), QuasiFamily(), LookFamily(), AtomicFamily(), ThreadsFamily(), BackrefFamily())}
+
+
+class Corpus:
+    def __init__(self, family, walk, cases):
+        self.family, self.walk, self.cases = family, walk, cases
+        self.lines = [c.line for c in cases]
+        self.offsets, self.modulus = WALKS[walk]
+
+    def label(self, i):
+        c = self.cases[i]
+        return "(%s, %s/%s, p=%d, head=%d%s), line %d of %d bytes" % (c.family, c.kind, c.variant, c.p, c.head,
+                                                                      "" if c.frm is None else ", from=%d" % c.frm, i, len(c.line))
+
+    def kinds_of(self, bad):
+        """{kind: count} of the listed case indices: for failure messages"""
+        out = {}
+        for i in bad:
+            out[self.cases[int(i)].kind] = out.get(self.cases[int(i)].kind, 0) + 1
+        return out
+
+    def frm(self):
+        return np.array([c.frm or 0 for c in self.cases], np.uint32)
+
+    def pack(self, form):
+        """-> (data, off, len, residues).  "len": off[n], every line at an address = its head (mod the walk's modulus) when `data`
+        itself is aligned, the line's `after` byte and filler between the lines; "sep": off[n + 1], one byte (`after`) behind each line.
+        GUARD_BYTES zero bytes end the data, so that a walk that runs a piece too far still reads inside the allocation."""
+        fam, M = self.family, self.modulus
+        buf, off = bytearray(), []
+        for k, c in enumerate(self.cases):
+            if form == "len":
+                buf += _cyc(fam.filler, (c.head - len(buf)) % M, k)
+            off.append(len(buf))
+            buf += c.line + (c.after or fam.after)
+        length = np.array([len(c.line) for c in self.cases], np.uint32)
+        off = np.array(off + ([len(buf)] if form == "sep" else []), np.uint32)
+        data = np.frombuffer(bytes(buf) + b"\0" * GUARD_BYTES, np.uint8)
+        return data, off, length, (off[:len(self.cases)] % M).astype(np.int64)
+
+
+@functools.lru_cache(maxsize=None)
+def generate(family, walk="w256"):
+    """-> Corpus of FAMILIES[family] for the offsets and residues of `walk` (computed once per process: callers leave it unchanged).
+    The order is shuffled (seeded), so that in the separator form the residues follow no pattern of the generator's loops."""
+    fam = FAMILIES[family]
+    offsets, M = WALKS[walk]
+    cases = []
+    for kind, min_p in fam.kinds.items():
+        for p in offsets:
+            if p < min_p:
+                continue
+            made = [m for m in fam.cases(kind, p) if m is not None]
+            assert made, (family, kind, p)
+            for head in range(M):
+                for variant, line, after, frm in made:
+                    cases.append(Case(family, kind, variant, p, head, line, after, frm))
+    order = np.random.default_rng(20261018).permutation(len(cases))
+    return Corpus(fam, walk, [cases[int(i)] for i in order])
+
+
+# ---- the instantiations the GPU test runs the corpus through: how the handle is compiled and launched, the families (with the walk
+# whose offsets they take), and the kernel name lc_launched_kernels must report.  compile_engine / launch_engine: the engine= arguments;
+# env: set before the pattern is compiled, kept for the launch; wave: the handle asks for the wave walk (prefer_wave_tdfa); dfs:
+# lc_nfa_set_dfs(1) around the launch (restored to -1); min_n: the corpus is repeated until the batch has at least that many values.
+# A (row, kind) pair outside this table is not run: every row runs every kind its families declare.
+Row = namedtuple("Row", "id kernel families walk compile_engine launch_engine env wave dfs min_n")
+_NFA, _TDFA = B.LC_ENGINE_NFA, B.LC_ENGINE_TDFA
+_NOLAZY = {"LC_LAZY_TDFA": "0"}
+ENV_KEYS = ("LC_LAZY_TDFA", "LC_NFA_WIDE_FIRST", "LC_TDFA_WAVE_MAX", "LC_BT_LANES")
+UNSTAGED_ABOVE = 32768                     # gpu_runtime.hip launchTdfaL2Family: the register programs ride in LDS up to this many values
+ROWS = [
+    Row("nfa", "nfa_match_kernel", ("log", "quasi", "look", "threads"), "w256", _NFA, _NFA, _NOLAZY, False, False, 0),
+    Row("nfa-atomic", "nfa_match_kernel<atomic>", ("atomic",), "w256", _NFA, _NFA, _NOLAZY, False, False, 0),
+    Row("nfa-wide-first", "nfa_wide_kernel:first", ("log", "quasi", "look", "threads"), "w256", _NFA, _NFA,
+        dict(_NOLAZY, LC_NFA_WIDE_FIRST="1"), False, False, 0),
+    Row("wave-small-staged", "tdfa_l2_kernel:wave", ("log", "quasi", "look", "atomic"), "w256", B.LC_ENGINE_AUTO, _TDFA, {}, True, False, 0),
+    Row("wave-large-staged", "tdfa_l2_kernel:wave", ("big",), "w256", B.LC_ENGINE_AUTO, _TDFA, {}, False, False, 0),
+    # (a handle that ASKED for the wave walk gets it up to 16 384 values only: the unstaged launch needs the large automaton)
+    Row("wave-unstaged", "tdfa_l2_kernel:wave", ("big",), "w256", B.LC_ENGINE_AUTO, _TDFA, {}, False, False, UNSTAGED_ABOVE + 1),
+    Row("l2-lane", "tdfa_l2_kernel", ("big",), "w16", B.LC_ENGINE_AUTO, _TDFA, {"LC_TDFA_WAVE_MAX": "0"}, False, False, 0),
+    Row("decide", "nfa_decide_kernel", ("log", "look"), "w256", _NFA, B.LC_ENGINE_DECIDE, _NOLAZY, False, False, 0),
+    Row("dfs", "nfa_dfs_kernel", ("log", "quasi"), "w256", _NFA, _NFA, _NOLAZY, False, True, 0),
+    Row("bt", "bt_match_kernel", ("backref",), "w256", B.LC_ENGINE_BT, B.LC_ENGINE_BT, {"LC_BT_LANES": "64"}, False, False, 0),
+]
+SEARCH_ROWS = [r for r in ROWS if any(FAMILIES[f].search for f in r.families)]
+# test_result_edges: one family per kernel
+EDGE_FAMILY = {"nfa": "log", "nfa-atomic": "atomic", "nfa-wide-first": "log", "wave-small-staged": "log", "wave-large-staged": "big",
+               "wave-unstaged": "big", "l2-lane": "big", "decide": "log", "dfs": "log", "bt": "backref"}
+
+
+def set_env(monkeypatch, row):
+    """the environment of a row: set before the pattern is compiled, kept for the launch"""
+    for k in ENV_KEYS:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in row.env.items():
+        monkeypatch.setenv(k, v)
+
+
+def compile_row(row, family):
+    """the handle of a (row, family) as the row says, under the environment set_env has set"""
+    fam = FAMILIES[family]
+    rx = B.GpuRegex(fam.pattern, syntax_flags=fam.flags, engine=row.compile_engine)
+    if row.wave:
+        assert rx.prefer_wave_tdfa(), (row.id, family)
+    return rx

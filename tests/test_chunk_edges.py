@@ -1,0 +1,308 @@
+"""The chunk-edge corpus of tests/helpers/chunk_edges.py, without a GPU: that every case does what its label says (conditions on the
+INPUTS of tests/test_gpu_chunk_edges.py, so that test cannot pass on a degenerate corpus), that every (offset, residue) pair is there
+for every kind, that the instantiation table runs what the families declare, and that the product's own compiled tables -- walked by
+the host interpreters (tests/helpers/table_interp.py, tests/helpers/nfa_atomic_interp.py, the backtracking program's host walk of
+tests/native/bt_host_check.cpp) -- give the oracle's answer on every line.  A mismatch on the GPU is then a kernel's, not the tables'.
+For run_stop the tables' own quiet / steady masks say that the run bytes are quiet and byte p is not: the kernels' run scans are on
+the path."""
+import collections
+
+import numpy as np
+import pytest
+
+from loongcollector_amd import binding as B
+from oracle.oracle import OracleRegex
+from tests.helpers import chunk_edges as ce
+from tests.helpers.nfa_atomic_interp import AtomicNfaInterp
+from tests.helpers.table_interp import NfaInterp, TdfaL2BlobInterp
+from tests.test_backref import host_vm  # noqa: F401  (fixture: builds tests/_build/libbt_host_check.so)
+
+CORPORA = sorted({(f, r.walk) for r in ce.ROWS for f in r.families})
+_cache = {}
+
+
+def _flat(fam, res):
+    """an oracle result as the row a kernel writes: groups 1..G of a full match, groups 0..G of a search"""
+    return None if res is None else [v for be in (res if fam.search else res[1:]) for v in be]
+
+
+def _oracle(name, walk="w256"):
+    """(corpus, oracle handle, expected row per case) -- computed once"""
+    if (name, walk) not in _cache:
+        c = ce.generate(name, walk)
+        o = OracleRegex(c.family.pattern)
+        run = o.search if c.family.search else o.fullmatch
+        _cache[name, walk] = (c, o, [_flat(c.family, run(k.line)) for k in c.cases])
+    return _cache[name, walk]
+
+
+@pytest.mark.parametrize("name,walk", CORPORA)
+def test_every_offset_and_residue_is_there_for_every_kind(name, walk):
+    c, o, exp = _oracle(name, walk)
+    fam = c.family
+    offsets, M = ce.WALKS[walk]
+    assert (offsets, M) == ((ce.W256_P, 4) if walk == "w256" else (ce.W16_P, 16))
+    # 6 below .. 6 behind the first two chunk borders of the aligned view (line offset 256k - head), and the start of the value
+    assert set(ce.W256_P) >= {b - h + d for b in (256, 512) for h in range(4) for d in range(-6, 7)} | set(range(6))
+    seen = collections.defaultdict(set)
+    needy = set()
+    for k in c.cases:
+        seen[k.kind].add((k.p, k.head))
+        if k.kind == "run_to_end" and "needy" in k.variant:
+            needy.add((k.p, k.head))
+    assert set(seen) == set(fam.kinds)
+    for kind, min_p in fam.kinds.items():
+        assert seen[kind] == {(p, h) for p in offsets if p >= min_p for h in range(M)}, (name, kind)
+    if fam.needy_min is not None:
+        assert needy == {(p, h) for p in offsets if p >= fam.needy_min for h in range(M)}
+    # both input forms give every kind every residue: by filler in the (off, len) form, from the lengths in the separator form
+    for form in ("len", "sep"):
+        data, off, length, residue = c.pack(form)
+        assert len(off) == len(c.cases) + (form == "sep") and len(data) == int(off[-1]) + (int(length[-1]) + 1 if form == "len" else 0) + ce.GUARD_BYTES
+        by_kind = collections.defaultdict(set)
+        for i, k in enumerate(c.cases):
+            assert bytes(data[int(off[i]):int(off[i]) + int(length[i])]) == k.line
+            assert bytes(data[int(off[i]) + int(length[i]):][:1]) == (k.after or fam.after)               # the byte behind the line
+            assert form == "sep" or int(residue[i]) == k.head
+            by_kind[k.kind].add(int(residue[i]))
+        assert all(v == set(range(M)) for v in by_kind.values()), (name, form, {k: sorted(v) for k, v in by_kind.items()})
+    assert len(c.cases) <= 9000 and max(len(s) for s in c.lines) <= 1100
+
+
+@pytest.mark.parametrize("name,walk", CORPORA)
+def test_cases_do_what_their_label_says(name, walk):
+    c, o, exp = _oracle(name, walk)
+    fam = c.family
+    run = o.search if fam.search else o.fullmatch
+    counts = collections.Counter()
+    for k, e in zip(c.cases, exp):
+        what = (name, k.kind, k.variant, k.p)
+        counts[k.kind, k.variant] += 1
+        if k.kind in ("run_stop", "stamp"):
+            assert e is not None and k.p in e, what                                                  # a capture begins or ends at p
+            if k.variant.startswith("one_byte"):
+                assert any(e[2 * g] == k.p and e[2 * g + 1] == k.p + 1 for g in range(len(e) // 2)), what
+            if k.variant.startswith("empty"):
+                assert any(e[2 * g] == k.p == e[2 * g + 1] for g in range(len(e) // 2)), what
+        elif k.kind == "run_to_end":
+            assert len(k.line) == k.p, what
+            if "needy" in k.variant:                                                                  # the byte behind it changes the result
+                assert _flat(fam, run(k.line + k.after)) != e, what
+        elif k.kind == "dead":
+            assert e is None and run(k.line[:k.p] + k.line[k.p + 1:]) is not None, what              # ... and matches without byte p
+            assert run(k.line[:k.p] + k.line[k.p + 1:k.p + 2] + k.line[k.p + 1:]) is not None, what   # (byte p is what kills it: another one there matches)
+        elif k.kind == "absorb":
+            assert e is not None and e[-2] == k.p and e[-1] == len(k.line) >= k.p + 300, what
+        elif k.kind == "threads":
+            if k.variant.endswith("to_end"):
+                assert e is None and len(k.line) == k.p and run(k.line + k.after) is not None, what
+            else:
+                live = int(k.variant[4:])
+                g = 8 - live                                                                          # the first alternative still alive
+                assert e is not None and e[2 * g:2 * g + 2] == [0, k.p] and e[-2] == k.p + 1, what
+        elif k.kind == "search_start":
+            v = k.variant
+            if v != "d_behind":
+                assert fam.START not in k.line[:k.p] and k.line[k.p:k.p + 1] == fam.START, what       # the first start byte is at p
+            if v.startswith("a_match"):
+                assert e is not None and e[0] == k.p, what
+                assert v != "a_match_at_end" or e[1] == len(k.line), what
+            elif v == "b_doomed":
+                assert k.line[k.p:k.p + 2] == fam.DOOMED and e is not None and e[0] == k.p + 4, what
+            elif v == "b_doomed_far":
+                assert e is not None and e[0] == k.p + 302, what                                      # the match begins in a later chunk
+            elif v in ("b_doomed_alone", "c_last_byte"):
+                assert e is None and (v != "c_last_byte" or len(k.line) == k.p + 1), what
+            elif v == "d_behind":
+                assert k.line[k.p - 1:k.p] == fam.BEHIND and k.line[k.p:].startswith(fam.HIT) and e is not None and e[0] > k.p, what
+            elif v == "needy":
+                assert e is None and _flat(fam, run(k.line + k.after))[0] == k.p, what
+            else:
+                raise AssertionError(what)
+        elif k.kind == "resume":
+            assert k.frm in (k.p - 1, k.p, k.p + 1), what
+            r = _flat(fam, o.search(k.line, k.frm))
+            gap = {"at_from": 0, "at_from1": 1, "next_chunk": 300}[k.variant.split("_", 1)[1]]
+            assert r is None or r[0] >= k.frm, what
+            if k.frm > len(fam.HIT):                                             # (the line's first hit lies in front)
+                assert r is not None and r[0] == k.frm + gap and e[0] == 0, what
+        else:
+            raise AssertionError(what)
+    assert all(n >= len(ce.WALKS[walk][0]) for n in counts.values()) or name in ("threads",), counts  # no variant is a rarity
+    for kind in fam.kinds:
+        assert sum(n for (kd, _), n in counts.items() if kd == kind) >= 100, (name, kind)
+
+
+def test_the_instantiation_table_runs_what_the_families_declare():
+    """every family is run by some row, every row runs every kind of its families (>= 90 % is the cap the table must meet; a case
+    set a row leaves out would be an entry of the table), search rows have search families, the edge families belong to their rows"""
+    assert {f for r in ce.ROWS for f in r.families} == set(ce.FAMILIES)
+    assert len({r.id for r in ce.ROWS}) == len(ce.ROWS) == 10
+    assert {r.kernel for r in ce.ROWS} == {"nfa_match_kernel", "nfa_match_kernel<atomic>", "nfa_wide_kernel:first", "tdfa_l2_kernel:wave",
+                                           "tdfa_l2_kernel", "nfa_decide_kernel", "nfa_dfs_kernel", "bt_match_kernel"}
+    for r in ce.ROWS:
+        for f in r.families:
+            c = ce.generate(f, r.walk)
+            ran = {k.kind for k in c.cases}                                                           # a row runs the whole corpus
+            assert len(ran) >= 0.9 * len(ce.FAMILIES[f].kinds) and ran == set(ce.FAMILIES[f].kinds), (r.id, f)
+        assert ce.EDGE_FAMILY[r.id] in r.families
+        assert set(r.env) <= set(ce.ENV_KEYS)
+    unstaged = [r for r in ce.ROWS if r.min_n]
+    assert [r.id for r in unstaged] == ["wave-unstaged"] and unstaged[0].min_n == ce.UNSTAGED_ABOVE + 1 and unstaged[0].families == ("big",)
+    n = len(ce.generate("big").cases)
+    copies = -(-unstaged[0].min_n // n)
+    assert ce.UNSTAGED_ABOVE < copies * n <= 65536                                                    # still a wave launch (LC_TDFA_WAVE_MAX)
+    assert {r.id for r in ce.SEARCH_ROWS} == {"nfa", "nfa-atomic", "nfa-wide-first", "wave-small-staged", "decide", "dfs"}
+
+
+# ---- the product's tables on the host
+
+def _check(c, exp, walkers, label):
+    """every case through every walker (name, fn(line) -> row or None) against the oracle's row"""
+    for name, fn in walkers:
+        bad = [i for i, (k, e) in enumerate(zip(c.cases, exp)) if fn(k.line) != e]
+        assert not bad, "%s, %s: %d cases differ %s; first: %s" % (label, name, len(bad), c.kinds_of(bad), c.label(bad[0]))
+
+
+def _l2_trace(it, s):
+    """[(state before byte i, quiet in that state: stays without a program and its class is in the state's QUIET mask)] of the L2 blob"""
+    out, state = [], it.start
+    for b in s:
+        if state == 0 or state == it.absorb:
+            break
+        cls = int(it.cmap[b])
+        t = int(it.trans[state * it.ncls + cls])
+        masked = cls < 64 and bool((int(it.quiet[state]) >> cls) & 1)
+        assert masked == ((t >> 16) == 0 and (t & 0xFFFF) == state), (state, cls)                     # the mask says what the table says
+        out.append((state, masked))
+        state = t & 0xFFFF
+    return out
+
+
+def _run_of(k):
+    """the bytes [first, p) of a run_stop case that the run scan must find quiet: behind the run's first byte, which may enter the state"""
+    tail = k.variant.rsplit("_", 1)[1]
+    return (k.p - int(tail) if tail.isdigit() else 0) + 1
+
+
+@pytest.mark.parametrize("name,walk", [(f, w) for f, w in CORPORA if any(r.launch_engine == B.LC_ENGINE_TDFA and f in r.families for r in ce.ROWS)])
+def test_global_memory_tdfa_tables_give_the_oracles_rows(name, walk):
+    c, o, exp = _oracle(name, walk)
+    fam = c.family
+    rx = B.GpuRegex(fam.pattern, syntax_flags=fam.flags)
+    assert rx.info()["engine"] == B.LC_ENGINE_TDFA
+    if name == "big":
+        assert rx.info()["states"] > 1000 and rx.table(B.LC_TABLE_TDFA_BLOB, np.uint32) is None       # no LDS kernel can run it
+    else:
+        assert rx.prefer_wave_tdfa()
+    it = TdfaL2BlobInterp(rx)
+    assert it.miss == 0 and (fam.search or it.absorb != 0)
+    # the register programs fit the share of LDS a launch of up to 32 768 values stages them in (gpu_runtime.hip launchTdfaL2Family):
+    # the rows named "staged" are, and the row above that count is the same walk with the programs in global memory
+    blob = rx.table(B.LC_TABLE_TDFA_L2_BLOB, np.uint32)
+    prog_bytes = (int(blob[9]) - int(blob[7]) + 3) & ~3                                               # TL_OFF_FINALID - TL_OFF_OPSSTART
+    assert 0 < prog_bytes <= 40 * 1024 and it.nregs * 4 * 4 + prog_bytes <= 60 * 1024, (name, prog_bytes)
+    _check(c, exp, (("tdfa_wave_kernel's walk", it.fullmatch_wave), ("tdfa_l2_kernel's walk", it.fullmatch)), name)
+    ends_quiet = 0
+    for k in c.cases:
+        if k.kind == "run_stop":
+            tr = _l2_trace(it, k.line)
+            first = _run_of(k)
+            assert all(q for _, q in tr[first:k.p]) and not tr[k.p][1], (name, k.variant, k.p)        # quiet up to p, not at p
+            assert k.p - first < 1 or len({s for s, _ in tr[first:k.p + 1]}) == 1
+        elif k.kind == "run_to_end" and k.p >= 2:
+            tr = _l2_trace(it, k.line)
+            # the value ends inside a quiet run (or on the byte that enters it)
+            assert len(tr) == k.p and (tr[-1][1] or it.cmap[k.line[-1]] != it.cmap[k.line[-2]]), (name, k.variant, k.p)
+            ends_quiet += tr[-1][1]
+        elif k.kind == "absorb":
+            tr = _l2_trace(it, k.line)
+            # (byte p carries the program that stamps the begin of (.*); the absorbing state is what it leads to)
+            assert len(tr) == k.p + 1 and tr[k.p][0] != it.absorb, (name, k.p)
+        elif k.kind == "dead":
+            assert len(_l2_trace(it, k.line)) == k.p + 1, (name, k.p)                                 # the dead state behind byte p
+        elif k.kind == "resume":
+            want = _flat(fam, o.search(k.line, k.frm))
+            assert it.fullmatch_wave(k.line, start=k.frm) == want and it.fullmatch(k.line, start=k.frm) == want, c.label(c.cases.index(k))
+    assert fam.search or ends_quiet >= 0.8 * sum(k.kind == "run_to_end" and k.p >= 2 for k in c.cases)
+
+
+def _nfa_trace(it, s, start=0):
+    """NfaInterp's walk once more, step by step: [(live threads, every one of them steady on this byte)] per byte"""
+    threads, prev = ([it.npos], it.ncls) if not start else ([0], int(it.cmap[s[start - 1]]))
+    out = []
+    for pos in range(start, len(s)):
+        if it.search_suffix >= 0 and threads == [it.search_suffix]:
+            break
+        cls = int(it.cmap[s[pos]])
+        nxt = int(it.cmap[s[pos + 1]]) if pos + 1 < len(s) else -1
+
+        def quiet(p):
+            if (it.stable[p] >> cls) & 1:
+                return True
+            if nxt < 0 or it.quasi_idx is None or p >= len(it.quasi_idx) or not int(it.quasi_idx[p]):
+                return False
+            return bool((it.quasi_rows[int(it.quasi_idx[p]) - 1][cls] >> nxt) & 1)
+        steady = all(quiet(p) for p in threads)
+        out.append((len(threads), steady))
+        if not steady:
+            holds = it.behind[prev] | it.ahead[cls]
+            new = []
+            for p in threads:
+                for tgt, cond, _ in it.follow[p]:
+                    if tgt >= 0 and tgt not in new and (it.posmask[tgt] >> cls) & 1 and not (cond & ~holds):
+                        new.append(tgt)
+            if it.search_suffix in new:
+                new = new[:new.index(it.search_suffix) + 1]
+            threads = new
+        prev = cls
+        if not threads:
+            break
+    return out
+
+
+@pytest.mark.parametrize("name", sorted({f for r in ce.ROWS if r.compile_engine == B.LC_ENGINE_NFA for f in r.families}))
+def test_nfa_program_gives_the_oracles_rows(name):
+    c, o, exp = _oracle(name)
+    fam = c.family
+    rx = B.GpuRegex(fam.pattern, syntax_flags=fam.flags, engine=B.LC_ENGINE_NFA)
+    assert (rx.atomic_groups()[0] > 0) == (name == "atomic")
+    it = (AtomicNfaInterp if name == "atomic" else NfaInterp)(rx)
+    assert (it.search_suffix >= 0) == fam.search
+    if name == "quasi":
+        assert it.quasi_rows                                                                          # doomed-spawn rows exist for this shape
+    _check(c, exp, (("the thread-list walk", it.fullmatch),), name)
+    for k in c.cases:
+        if k.kind == "run_stop":
+            tr = _nfa_trace(it, k.line)
+            first = _run_of(k)
+            assert all(q and n <= 6 for n, q in tr[first:k.p]) and not tr[k.p][1], (name, k.variant, k.p)   # steady up to p, not at p
+        elif k.kind == "threads":
+            tr = _nfa_trace(it, k.line)
+            live = int(k.variant.split("_")[0][4:])
+            first = 8 - live + 1
+            assert all(t == (live, True) for t in tr[first:k.p]), (k.variant, k.p, tr[first:first + 3])
+            assert k.p >= len(k.line) or not tr[k.p][1]
+        elif k.kind == "search_start" and k.variant in ("a_match", "b_doomed", "c_last_byte"):
+            tr = _nfa_trace(it, k.line)
+            assert all(t == (1, True) for t in tr[1:k.p]), (name, k.variant, k.p)                      # the prefix thread alone, steady up to p
+            if k.variant == "b_doomed" and name in ("quasi", "look") and k.p >= 1:
+                assert tr[k.p] == (1, True)                                                           # ... and on the doomed start: its rows say so
+            if k.variant == "a_match":
+                assert not tr[k.p][1]
+        elif k.kind == "resume" and name != "atomic":
+            assert it.fullmatch(k.line, start=k.frm) == _flat(fam, o.search(k.line, k.frm)), c.label(c.cases.index(k))
+    kinds = {k.kind for k in c.cases}
+    assert name != "threads" or {int(k.variant.split("_")[0][4:]) for k in c.cases} >= {8, 7, 6, 1}    # beyond, at and below kNfaSteadyScanThreads
+
+
+def test_backtracking_program_gives_the_oracles_rows(host_vm):  # noqa: F811
+    c, o, exp = _oracle("backref")
+    rx = B.GpuRegex(c.family.pattern)
+    assert rx.info()["engine"] == B.LC_ENGINE_BT                                                      # only the backtracking engine runs it
+
+    def walk(line):
+        r, caps = host_vm(rx, line)
+        assert r >= 0
+        return caps[2:] if r else None
+    _check(c, exp, (("btRun on the host", walk),), "backref")

@@ -13,11 +13,9 @@ import pytest
 from loongcollector_amd import binding as B
 from oracle.oracle import OracleRegex
 from tests.helpers import wave_shapes as ws
+from tests.helpers.guarded_launch import GuardedResults      # (the sentinel rows around the results: shared with tests/test_gpu_chunk_edges.py)
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 4                      # sentinel rows in front of and behind the results
-CAPS_SENTINEL, STATUS_SENTINEL = -7, 9
 
 
 @pytest.fixture(scope="module")
@@ -53,20 +51,12 @@ def _launch(torch, rx, batch, n, ngroups, form, caps_shift=0):
     """One launch over the first n lines -> (caps[n, 2 * ngroups], status[n], kernel names).  form: "len" = (off, len), "sep" = off[n + 1]
     and a separator byte, "ragged" = the length-scheduled entry (a permuted order).  caps_shift: the capture table starts that many
     dwords into a 16-byte aligned allocation.  Asserts that the sentinel rows around the results are untouched."""
-    dev = torch.device("cuda:0")
-    n_out = 2 * ngroups
-    words = (n + 2 * GUARD) * n_out
-    buf = torch.full((words + 8,), CAPS_SENTINEL, dtype=torch.int32, device=dev)
-    assert buf.data_ptr() % 16 == 0
-    first = caps_shift + GUARD * n_out
-    d_caps = buf[first:first + max(n * n_out, 1)]
-    assert (d_caps.data_ptr() - buf.data_ptr()) == 4 * first and (4 * GUARD * n_out) % 16 == 0   # (shift 0: 16-byte aligned rows)
-    sbuf = torch.full((n + 2 * 4 * GUARD,), STATUS_SENTINEL, dtype=torch.uint8, device=dev)
-    d_status = sbuf[4 * GUARD:4 * GUARD + n]
+    res = GuardedResults(torch, n, ngroups, caps_shift)
+    d_caps, d_status = res.d_caps, res.d_status
     stream = torch.cuda.current_stream().cuda_stream
     B.launched_kernels()
     if form == "ragged":
-        d_scratch = torch.empty((B.sched_scratch_bytes(n) // 4 + 1,), dtype=torch.int32, device=dev)
+        d_scratch = torch.empty((B.sched_scratch_bytes(n) // 4 + 1,), dtype=torch.int32, device=torch.device("cuda:0"))
         rx.match_device_ragged(batch["d_data"], batch["d_off"], batch["d_len"], n, d_caps, d_status, d_scratch, ngroups=ngroups,
                                engine=B.LC_ENGINE_TDFA, stream=stream)
     elif form == "len":
@@ -77,12 +67,8 @@ def _launch(torch, rx, batch, n, ngroups, form, caps_shift=0):
                         engine=B.LC_ENGINE_TDFA)
     torch.cuda.synchronize()
     names = B.launched_kernels().split(", ")
-    out, sout = buf.cpu().numpy(), sbuf.cpu().numpy()
-    where = (form, n, ngroups, caps_shift)
-    assert (out[:first] == CAPS_SENTINEL).all(), ("rows in front of the capture table were written", where)
-    assert (out[first + n * n_out:] == CAPS_SENTINEL).all(), ("rows behind the capture table were written", where)
-    assert (sout[:4 * GUARD] == STATUS_SENTINEL).all() and (sout[4 * GUARD + n:] == STATUS_SENTINEL).all(), ("status guard bytes were written", where)
-    return out[first:first + n * n_out].reshape(n, n_out), sout[4 * GUARD:4 * GUARD + n], names
+    caps, status = res.read((form, n, ngroups, caps_shift))
+    return caps, status, names
 
 
 def _expected(batch, n, ngroups):
