@@ -19,6 +19,9 @@ the line's first byte must have in device memory, `after` the byte right behind 
                 byte refuses it --, (c) a start byte that is the last byte of the value, (d) a start the look-behind refuses
   resume        (search patterns) the search resumes at frm = p-1, p, p+1; the next match begins at frm, frm+1 or in the next chunk
   threads       (NFA only) 8, exactly 6 (kNfaSteadyScanThreads) or 1 live steady threads in a run that ends at p
+  miss          (lazy automata) byte p is the first on which the partial automaton has no transition: the kernel hands the value back
+                and the thread-list kernels take it from its first byte; it matches, matches with 300 bytes behind p, does not match, or
+                fails for want of the byte behind it
 What a pattern cannot do is said by its family (Family.kinds: kind -> the smallest p it exists for).  tests/test_chunk_edges.py
 asserts all of this against the oracle and against the compiled tables, so that the GPU test cannot pass on a degenerate corpus.
 
@@ -121,35 +124,41 @@ class LogFamily(Family):
 class BigFamily(LogFamily):
     """a tagged DFA of 8 000+ states: its tables stay in global memory, so tdfa_l2_kernel / tdfa_wave_kernel run by necessity"""
     name, pattern = "big", rb"([^,]*),(\d*);(?:a|b)*a(?:a|b){12}(c+)(d*) (.*)"
-    kinds = {"run_stop": 0, "run_to_end": 0, "stamp": 0, "dead": 1, "absorb": 17}
-    needy_min = 16
     filler, after = b",7;c ", b"c"
-    AB = 13                                                                        # bytes of "a" + 12 of [ab]
+    AB = 13                                                                        # bytes of "a" + 12 of [ab]: the first c is AB + 2 behind a stretch that starts at 2
+    kinds = {"run_stop": 0, "run_to_end": 0, "stamp": 0, "dead": 1, "absorb": AB + 4}
+    needy_min = AB + 3
 
     def _big(self, c, s, m, k, j, L):
-        """as _line up to the semicolon at s, then m bytes of [ab], "a" and 12 of [ab], c's [u, u + k), d's, a space, anything up to L"""
+        """as _line up to the semicolon at s, then m bytes of [ab], "a" and AB - 1 of [ab], c's [u, u + k), d's, a space, anything up to L"""
         u = s + 1 + m + self.AB
         assert 0 <= c < s and k >= 1 and u + k + j < L, (c, s, m, k, j, L)
-        return (_cyc(b"xyz-", c, c) + b"," + _cyc(b"0123456789", s - c - 1, s) + b";" + _cyc(b"ab", m, m) + b"a" + _cyc(b"bab", 12, s) +
+        return (_cyc(b"xyz-", c, c) + b"," + _cyc(b"0123456789", s - c - 1, s) + b";" + self._free(m) + self._tail(s) +
                 b"c" * k + b"d" * j + b" " + _cyc(self.TAIL, L - u - k - j - 1))
+
+    def _free(self, m):
+        return _cyc(b"ab", m, m)
+
+    def _tail(self, s):
+        return b"a" + _cyc(b"bab", self.AB - 1, s)
 
     def k_run_stop(self, p):
         out = [("f1_from0", self._big(p, p + 2, 1, 2, 1, p + 30), None, None)]
         for k in RUN_BACK:
             if p - k - 1 >= 0:
                 out.append(("digits_%d" % k, self._big(p - k - 1, p, 2, 1, 0, p + 26), None, None))
-            if p - k - 15 >= 0:
-                out.append(("c_%d" % k, self._big(0, 1, p - k - 15, k, 2, p + 9), None, None))         # c's [p-k, p), a 'd' at p
+            if p - k - self.AB - 2 >= 0:
+                out.append(("c_%d" % k, self._big(0, 1, p - k - self.AB - 2, k, 2, p + 9), None, None))   # c's [p-k, p), a 'd' at p
         return out
 
     def k_run_to_end(self, p):
         out = [("f1", _cyc(b"xyz-", p), b";", None)]
         if p >= 1:
             out.append(("digits", b"," + _cyc(b"0123456789", p - 1), b";", None))
-        if p >= 16:
-            out.append(("c_needy", self._big(0, 1, 0, p - 15, 0, p + 1)[:p], b" ", None))             # fails for want of the space behind it
-        if p >= 17:
-            out.append(("d_needy", self._big(0, 1, 0, 1, p - 16, p + 1)[:p], b" ", None))
+        if p >= self.AB + 3:
+            out.append(("c_needy", self._big(0, 1, 0, p - self.AB - 2, 0, p + 1)[:p], b" ", None))   # fails for want of the space behind it
+        if p >= self.AB + 4:
+            out.append(("d_needy", self._big(0, 1, 0, 1, p - self.AB - 3, p + 1)[:p], b" ", None))
         return out
 
     def k_stamp(self, p):
@@ -161,12 +170,12 @@ class BigFamily(LogFamily):
                     ("empty", self._big(p - 1, p, 0, 1, 0, p + 22), None, None)]
         else:
             out += [("one_byte", self._big(1, 3, 0, 1, 0, 24), None, None), ("empty", self._big(0, 2, 0, 1, 0, 24), None, None)]
-        if p >= 15:
-            out.append(("c_begin", self._big(0, 1, p - 15, 3, 2, p + 9), None, None))
-        if p >= 16:
-            out.append(("c_one_byte_d_empty", self._big(0, 1, p - 16, 1, 0, p + 5), None, None))      # c+ = [p-1, p), d* empty at p
-        if p >= 18:
-            out.append(("rest_empty", self._big(0, 1, p - 18, 2, 0, p), None, None))                  # the space is the value's last byte, behind a run
+        if p >= self.AB + 2:
+            out.append(("c_begin", self._big(0, 1, p - self.AB - 2, 3, 2, p + 9), None, None))
+        if p >= self.AB + 3:
+            out.append(("c_one_byte_d_empty", self._big(0, 1, p - self.AB - 3, 1, 0, p + 5), None, None))   # c+ = [p-1, p), d* empty at p
+        if p >= self.AB + 5:
+            out.append(("rest_empty", self._big(0, 1, p - self.AB - 5, 2, 0, p), None, None))   # the space is the value's last byte, behind a run
         return out
 
     def k_dead(self, p):
@@ -177,7 +186,56 @@ class BigFamily(LogFamily):
         return out
 
     def k_absorb(self, p):
-        return [("space", self._big(0, 1, p - 17, 1, 0, p + 300 + p % 7), None, None)]              # c at p-2, the space at p-1
+        return [("space", self._big(0, 1, p - self.AB - 4, 1, 0, p + 300 + p % 7), None, None)]   # c at p-2, the space at p-1
+
+
+class LazyFamily(BigFamily):
+    """the big family with 14 in the place of 12: it does not determinise, so the handle is a thread-list program, and lazy_train
+    builds a partial automaton along TRAINING lines (kept apart from the cases).  Behind an a/b stretch the automaton's state is the
+    stretch's last AB bytes.  Every decided line's stretch is one fixed shape -- "abab..." from its first byte, then "aa" and a fixed
+    rest --, so the windows the training lines walk are the alternating ones and those that hold the "aa".  A `miss` case alternates
+    up to p - 2, where a 'b' stands, and has a second 'b' at p - 1: a window no training line has, on a value that may match all the
+    same.  Byte p is the first the automaton has no transition for."""
+    name, pattern = "lazy", rb"([^,]*),(\d*);(?:a|b)*a(?:a|b){14}(c+)(d*) (.*)"
+    AB = 15
+    kinds = {"run_stop": 0, "run_to_end": 0, "stamp": 0, "dead": 1, "absorb": AB + 4, "miss": AB + 2}
+    needy_min = AB + 3
+    REST = b"bbabbabbabbab"
+    TRAIN_M = tuple(range(0, 2 * AB + 4)) + (600, 601)       # stretch lengths: every short one, and both parities of the long ones
+
+    def _free(self, m):
+        return _cyc(b"ab", m)
+
+    def _tail(self, s):
+        return b"aa" + self.REST
+
+    def _alt_bb(self, p):
+        """",;" and an alternating stretch [2, p - 1) whose last byte, at p - 2, is 'b'; then the second 'b' at p - 1.  The automaton
+        has the state behind it (every state a training line enters gets all its transitions) but none of the transitions out of it:
+        the walk leaves on byte p"""
+        return b",;" + _cyc(b"ab", p - 3, (p - 1) % 2) + b"b"
+
+    def k_miss(self, p):
+        head = self._alt_bb(p)
+        assert len(head) == p and head[p - 2:] == b"bb" and head[p - self.AB:p - self.AB + 1] == b"a"
+        return [("last", head + b"cd " + _cyc(self.TAIL, 6), None, None),                             # byte p - 1 is the last of the stretch
+                ("far", head + _cyc(b"ab", 300 + p % 5) + self._tail(0) + b"c " + _cyc(self.TAIL, 6), None, None),
+                ("no_match", head + b"Z" + self._tail(0) + b"c t", None, None),
+                ("needy", head + b"cc", b" ", None)]                                                  # fails for want of the space behind it
+
+    def training(self):
+        """the lines lazy_train gets: every shape a decided case has, at stretch lengths that span the offsets (a state behind AB or
+        more stretch bytes depends on their parity alone), none of them a case"""
+        out = []
+        for m in self.TRAIN_M:
+            for k, j in ((1, 0), (2, 1), (3, 2)):
+                full = self._big(1, 3 + j, m, k, j, 3 + j + m + self.AB + k + j + 2 + 5 * k)
+                out += [full, full[:full.index(b" ") + 1], full[:full.index(b" ")], full[:full.index(b" ") - j]]
+            out.append(b"t,4;" + self._free(m) + b"Z" + self._tail(0) + b"c t")
+            out.append(b",;" + self._free(m) + self._tail(0)[:m % self.AB] + b"Zc t")
+            out.append(b"t,4;b" + self._free(m) + self._tail(0) + b"cd t")                             # (a stretch may begin with the 'b')
+        out += [b"t,4Z;" + self._tail(0) + b"c t", b"xyz-xyz;", b"xy,0123;;"]
+        return list(dict.fromkeys(out))
 
 
 class SearchFamily(Family):
@@ -304,7 +362,7 @@ class BackrefFamily(Family):
         return [("needy", w + b"," + b"7" * d + b";" + w[:-1], w[-1:], None)]
 
 
-FAMILIES = {f.name: f for f in (LogFamily(), BigFamily(), QuasiFamily(), LookFamily(), AtomicFamily(), ThreadsFamily(), BackrefFamily())}
+FAMILIES = {f.name: f for f in (LogFamily(), BigFamily(), LazyFamily(), QuasiFamily(), LookFamily(), AtomicFamily(), ThreadsFamily(), BackrefFamily())}
 
 
 class Corpus:
@@ -365,12 +423,67 @@ def generate(family, walk="w256"):
     return Corpus(fam, walk, [cases[int(i)] for i in order])
 
 
+# ---- dfa_screen_kernel (csrc/screen_kernel.hpp): one value per lane, 16-byte pieces from `address & ~15`, a yes/no walk that leaves on the
+# sink ("a match is certain whatever follows"), and a list of the accepted values.  Every family but the back-reference gets a relaxed
+# screen; the corpus is the w16 one.  A screen is a search, so it has no dead state: its walk ends on the sink or with the value.
+SCREEN_FAMILIES = ("log", "big", "quasi", "look", "atomic", "threads")
+SCREEN_BORDERS = (16, 32)                  # the first two piece borders of the aligned view
+
+
+def compile_screen(family):
+    fam = FAMILIES[family]
+    scr = B.GpuRegex.compile_screen(fam.pattern, syntax_flags=fam.flags, relaxed=True, max_states=20000, max_table_bytes=2 << 20)
+    assert scr is not None, family
+    return scr
+
+
+@functools.lru_cache(maxsize=None)
+def screen_corpus(family):
+    """the w16 corpus, and for the search families -- whose corpus the pattern finds something in nearly everywhere -- each value
+    that ends with its match once more, cut one and two bytes short: kind `cut`, rejected, and the one-byte cut has the missing byte
+    right behind it in memory"""
+    base = generate(family, "w16")
+    cuts = []
+    for k in base.cases:
+        if k.variant == "a_match_at_end":
+            cuts.append(k._replace(kind="cut", variant="needy_1", line=k.line[:-1], after=k.line[-1:]))
+            cuts.append(k._replace(kind="cut", variant="short_2", line=k.line[:-2], after=None))
+    return Corpus(base.family, "w16", base.cases + cuts)
+
+
+class ScreenWalk:
+    """the screen's logical tables (tests/helpers/table_interp.py TdfaInterp reads the same) walked as dfa_screen_kernel walks its blob:
+    the sink is the first accepting state every byte class keeps (regex_handle.cpp packScreenBlob)"""
+
+    def __init__(self, it):
+        self.cmap, self.start = it.cmap, it.start
+        self.next = (it.trans & 0xFFFF).reshape(it.nstates, it.ncls)
+        self.accept = it.final_id != 0xFFFF
+        keeps = [st for st in range(1, it.nstates) if self.accept[st] and (self.next[st] == st).all()]
+        self.sink = keeps[0] if keeps else None
+        self.dead_transitions = int((self.next[1:] == 0).sum())
+
+    def walk(self, line):
+        """-> (accepted, "absorb" | "dead" | "end", the offset behind the last byte the walk looked at)"""
+        state = self.start
+        for i, b in enumerate(line):
+            state = int(self.next[state, self.cmap[b]])
+            if state == 0:
+                return False, "dead", i + 1
+            if state == self.sink:
+                return True, "absorb", i + 1
+        return bool(self.accept[state]), "end", len(line)
+
+
 # ---- the instantiations the GPU test runs the corpus through: how the handle is compiled and launched, the families (with the walk
 # whose offsets they take), and the kernel name lc_launched_kernels must report.  compile_engine / launch_engine: the engine= arguments;
 # env: set before the pattern is compiled, kept for the launch; wave: the handle asks for the wave walk (prefer_wave_tdfa); dfs:
 # lc_nfa_set_dfs(1) around the launch (restored to -1); min_n: the corpus is repeated until the batch has at least that many values.
+# train: the handle is a thread-list program that gets a lazy automaton right after it is compiled (training_lines): "family" = the
+# family's own training lines, so that its `miss` cases miss and are handed to the thread-list kernels; "corpus" = the first
+# TRAIN_CORPUS lines of the corpus itself, which decide everything else (the decided path alone).
 # A (row, kind) pair outside this table is not run: every row runs every kind its families declare.
-Row = namedtuple("Row", "id kernel families walk compile_engine launch_engine env wave dfs min_n")
+Row = namedtuple("Row", "id kernel families walk compile_engine launch_engine env wave dfs min_n train", defaults=(None,))
 _NFA, _TDFA = B.LC_ENGINE_NFA, B.LC_ENGINE_TDFA
 _NOLAZY = {"LC_LAZY_TDFA": "0"}
 ENV_KEYS = ("LC_LAZY_TDFA", "LC_NFA_WIDE_FIRST", "LC_TDFA_WAVE_MAX", "LC_BT_LANES")
@@ -388,11 +501,17 @@ ROWS = [
     Row("decide", "nfa_decide_kernel", ("log", "look"), "w256", _NFA, B.LC_ENGINE_DECIDE, _NOLAZY, False, False, 0),
     Row("dfs", "nfa_dfs_kernel", ("log", "quasi"), "w256", _NFA, _NFA, _NOLAZY, False, True, 0),
     Row("bt", "bt_match_kernel", ("backref",), "w256", B.LC_ENGINE_BT, B.LC_ENGINE_BT, {"LC_BT_LANES": "64"}, False, False, 0),
+    Row("lazy-wave", "tdfa_l2_kernel:wave:lazy", ("lazy",), "w256", _NFA, _NFA, {}, False, False, 0, "family"),
+    Row("lazy-lane", "tdfa_l2_kernel:lazy", ("lazy",), "w16", _NFA, _NFA, {"LC_TDFA_WAVE_MAX": "0"}, False, False, 0, "family"),
+    Row("lazy-wave-decided", "tdfa_l2_kernel:wave:lazy", ("log", "threads"), "w256", _NFA, _NFA, {}, False, False, 0, "corpus"),
+    Row("lazy-lane-decided", "tdfa_l2_kernel:lazy", ("log", "threads"), "w16", _NFA, _NFA, {"LC_TDFA_WAVE_MAX": "0"}, False, False, 0, "corpus"),
 ]
+TRAIN_CORPUS = 200
 SEARCH_ROWS = [r for r in ROWS if any(FAMILIES[f].search for f in r.families)]
 # test_result_edges: one family per kernel
 EDGE_FAMILY = {"nfa": "log", "nfa-atomic": "atomic", "nfa-wide-first": "log", "wave-small-staged": "log", "wave-large-staged": "big",
-               "wave-unstaged": "big", "l2-lane": "big", "decide": "log", "dfs": "log", "bt": "backref"}
+               "wave-unstaged": "big", "l2-lane": "big", "decide": "log", "dfs": "log", "bt": "backref",
+               "lazy-wave": "lazy", "lazy-lane": "lazy", "lazy-wave-decided": "log", "lazy-lane-decided": "threads"}
 
 
 def set_env(monkeypatch, row):
@@ -403,10 +522,17 @@ def set_env(monkeypatch, row):
         monkeypatch.setenv(k, v)
 
 
+def training_lines(row, family):
+    """what a row with a lazy automaton hands to lazy_train, once"""
+    return FAMILIES[family].training() if row.train == "family" else generate(family, row.walk).lines[:TRAIN_CORPUS]
+
+
 def compile_row(row, family):
     """the handle of a (row, family) as the row says, under the environment set_env has set"""
     fam = FAMILIES[family]
     rx = B.GpuRegex(fam.pattern, syntax_flags=fam.flags, engine=row.compile_engine)
     if row.wave:
         assert rx.prefer_wave_tdfa(), (row.id, family)
+    if row.train:
+        assert rx.lazy_train(training_lines(row, family))["in_use"] == 1, (row.id, family)
     return rx

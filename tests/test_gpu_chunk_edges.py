@@ -6,17 +6,24 @@ instantiation table, against the oracle, bit for bit.  Each of those decisions i
 the value or the start offset: a slip in one of them misparses only the values whose event sits on that byte for that alignment.
 tests/test_chunk_edges.py says on the CPU that the corpus holds those values and that the tables are right.
 
+The lazy rows put a partial automaton in front of a thread-list program (both walks): the `lazy` family's `miss` cases leave it on a
+chosen byte and must come back with the thread-list kernels' answer, `log` and `threads` run the decided path alone.  The GLOBAL
+instantiation of nfa_match_kernel runs in one child process (LC_NFA_GLOBAL_KB is read once per process).
+
 Every launch keeps four sentinel rows in front of and behind the capture table and the status bytes (tests/helpers/guarded_launch.py)
 and runs in both forms: (off, len), where filler gives each line its residue, and off[n + 1] with a separator byte."""
-import ctypes
+import json
+import os
+import subprocess
+import sys
+import time
 
 import numpy as np
 import pytest
 
 from loongcollector_amd import binding as B
-from oracle.oracle import OracleRegex
 from tests.helpers import chunk_edges as ce
-from tests.helpers.guarded_launch import CAPS_SENTINEL, STATUS_SENTINEL, GuardedResults
+from tests.helpers.chunk_edge_launch import cut as _cut, differing, launch as _launch, make_batches, rows as _rows
 
 pytestmark = pytest.mark.gpu
 
@@ -29,126 +36,21 @@ def torch_dev():
     return torch
 
 
-def _rows(fam, results, G):
-    """oracle results -> (caps[n, 2G], status[n]) as a kernel writes them: a value that does not match reads -1 everywhere"""
-    caps = np.full((len(results), 2 * G), -1, np.int32)
-    status = np.zeros(len(results), np.uint8)
-    for i, r in enumerate(results):
-        if r is not None:
-            caps[i] = [v for be in (r if fam.search else r[1:]) for v in be]
-            status[i] = 1
-    return caps, status
-
-
-def _tile(data, off, length, form, copies, M=16):
-    """the packed corpus `copies` times over: every copy of a line keeps its residue in the (off, len) form (copies start at multiples
-    of M); in the separator form the copies follow each other without a gap, as off[n + 1] demands"""
-    if copies == 1:
-        return data, off, length
-    n = len(length)
-    body = data[:len(data) - ce.GUARD_BYTES]
-    step = len(body) if form == "sep" else (len(body) + M - 1) // M * M
-    block = np.zeros(step, np.uint8)
-    block[:len(body)] = body
-    big = np.concatenate([np.tile(block, copies), np.zeros(ce.GUARD_BYTES, np.uint8)])
-    offs = np.concatenate([off[:n] + np.uint32(k * step) for k in range(copies)] + ([np.array([copies * step], np.uint32)] if form == "sep" else []))
-    return big, offs.astype(np.uint32), np.tile(length, copies)
-
-
 @pytest.fixture(scope="module")
 def batches(torch_dev):
-    """(family, walk, copies) -> the corpus on the device in both forms and the oracle's rows for it: computed once, shared by every
-    test, left unchanged"""
-    torch = torch_dev
-    dev = torch.device("cuda:0")
-    made = {}
-
-    def get(name, walk, copies=1):
-        key = (name, walk, copies)
-        if key not in made:
-            c = ce.generate(name, walk)
-            fam = c.family
-            o = OracleRegex(fam.pattern)
-            G = o.groups + (1 if fam.search else 0)
-            caps, status = _rows(fam, [(o.search if fam.search else o.fullmatch)(k.line) for k in c.cases], G)
-            batch = dict(corpus=c, oracle=o, G=G, n0=len(c.cases), n=copies * len(c.cases), caps=np.tile(caps, (copies, 1)), status=np.tile(status, copies))
-            for form in ("len", "sep"):
-                data, off, length, _ = c.pack(form)
-                data, off, length = _tile(data, off, length, form, copies)
-                d_data = torch.from_numpy(data.copy()).to(dev)
-                assert d_data.data_ptr() % 16 == 0                              # a line's residue is its offset's
-                batch[form] = dict(d_data=d_data, d_off=torch.from_numpy(off.view(np.int32).copy()).to(dev),
-                                   d_len=torch.from_numpy(length.view(np.int32).copy()).to(dev) if form == "len" else None)
-            made[key] = batch
-        return made[key]
-    return get
+    """(family, walk, copies) -> the corpus on the device in both forms and the oracle's rows for it (tests/helpers/chunk_edge_launch.py)"""
+    return make_batches(torch_dev)
 
 
 def _copies(row, n0):
     return -(-row.min_n // n0) if row.min_n else 1
 
 
-def _launch(torch, row, rx, batch, form, ngroups=None, caps_shift=0, n=None, lines=None, nlines=None, frm=None, ragged=False):
-    """One launch of `row` -> (caps[N, 2 * ngroups], status[N], kernel names): rows for ALL N values of the batch, of which the launch
-    takes the first n, or those `lines` lists, or as many as `nlines` says on the device.  Asserts the sentinels around the results."""
-    dev = torch.device("cuda:0")
-    N = batch["n"]
-    n = N if n is None else n
-    ngroups = batch["G"] if ngroups is None else ngroups
-    res = GuardedResults(torch, N, ngroups, caps_shift)
-    io = batch[form]
-    sep = 0 if form == "len" else 1
-    stream = torch.cuda.current_stream().cuda_stream
-    i32 = lambda a: None if a is None else torch.from_numpy(np.asarray(a, np.uint32).view(np.int32).copy()).to(dev)
-    L = B.load()
-    L.lc_nfa_set_dfs.argtypes = [ctypes.c_int]
-    B.launched_kernels()
-    try:
-        if row.dfs:
-            L.lc_nfa_set_dfs(1)
-        if ragged:
-            d_scratch = torch.empty((B.sched_scratch_bytes(n) // 4 + 1,), dtype=torch.int32, device=dev)
-            rx.match_device_ragged(io["d_data"], io["d_off"], io["d_len"], n, res.d_caps, res.d_status, d_scratch, ngroups=ngroups, sep_bytes=sep,
-                                   engine=row.launch_engine, stream=stream)
-        elif lines is not None or nlines is not None or frm is not None:
-            rx.match_device_from(io["d_data"], io["d_off"], io["d_len"], n, res.d_caps, res.d_status, d_lines=i32(lines),
-                                 d_nlines=i32(None if nlines is None else [nlines]), d_from=i32(frm), ngroups=ngroups, sep_bytes=sep, stream=stream,
-                                 engine=row.launch_engine)
-        else:
-            rx.match_device(io["d_data"], io["d_off"], io["d_len"], n, res.d_caps, res.d_status, ngroups=ngroups, sep_bytes=sep, stream=stream,
-                            engine=row.launch_engine)
-        torch.cuda.synchronize()
-    finally:
-        if row.dfs:
-            L.lc_nfa_set_dfs(-1)
-    names = B.launched_kernels().split(", ")
-    caps, status = res.read((row.id, form, n, ngroups, caps_shift))
-    return caps, status, names
-
-
-def _cut(caps, ngroups):
-    """the oracle's rows at ngroups output groups: fewer groups cut the row, further ones read -1"""
-    G = caps.shape[1] // 2
-    if ngroups <= G:
-        return caps[:, :2 * ngroups]
-    return np.concatenate([caps, np.full((len(caps), 2 * (ngroups - G)), -1, np.int32)], axis=1)
-
-
 def _compare(batch, got_caps, got_status, exp_caps, exp_status, where, listed=None):
     """the rows of the `listed` values (default: all) against the oracle's; every other row still holds its sentinels"""
-    N = batch["n"]
-    took = np.ones(N, bool) if listed is None else np.zeros(N, bool)
-    if listed is not None:
-        took[np.asarray(listed, np.int64)] = True
-    wrong = (got_status != exp_status) | (got_caps != exp_caps).any(axis=1)
-    untouched = (got_status == STATUS_SENTINEL) & (got_caps == CAPS_SENTINEL).all(axis=1)
-    bad = np.nonzero(np.where(took, wrong, ~untouched))[0]
-    if bad.size:
-        c, i = batch["corpus"], int(bad[0])
-        k = i % batch["n0"]
-        pytest.fail("%s: %d values differ, by kind %s; first: %s%s%s\n  expected status %d row %s\n  actual   status %d row %s" % (
-            where, bad.size, c.kinds_of(bad % batch["n0"]), c.label(k), "" if i == k else ", copy %d" % (i // batch["n0"]),
-            "" if took[i] else " (NOT LISTED: its row must keep the sentinels)", int(exp_status[i]), exp_caps[i].tolist(), int(got_status[i]), got_caps[i].tolist()))
+    n, first = differing(batch, got_caps, got_status, exp_caps, exp_status, where, listed)
+    if n:
+        pytest.fail(first)
 
 
 def _ran(row, names, where):
@@ -230,3 +132,31 @@ def test_result_edges(torch_dev, monkeypatch, batches, row):
     if row.launch_engine in (B.LC_ENGINE_TDFA, B.LC_ENGINE_NFA) and not row.dfs:
         for shift in (0, 2):
             check("length-scheduled, table %d bytes off" % (4 * shift), form="len", caps_shift=shift, n=full, listed=range(full), ragged=True)
+
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_global_memory_nfa_kernel_in_a_process_of_its_own(torch_dev):
+    """nfa_match_kernel<..., GLOBAL=true> runs where a program exceeds 52 KB, and LC_NFA_GLOBAL_KB, which moves that bound, is read
+    once per process: ONE child process with LC_NFA_GLOBAL_KB=0 (every non-empty batch takes the GLOBAL instantiation) runs rows `nfa`
+    and `nfa-atomic` in both forms, the resumed searches and the result edges on `log` (tests/helpers/global_nfa_child.py) and reports
+    per launch how many values differ from the oracle's rows.  A child that faults, aborts or runs out of time fails the test with
+    its stderr; nothing is started afterwards."""
+    env = dict(os.environ)
+    for k in ce.ENV_KEYS + ("LC_NFA_DFS", "LC_NFA_NO_WIDE"):
+        env.pop(k, None)
+    env.update(LC_NFA_GLOBAL_KB="0", LC_LAZY_TDFA="0")
+    t0 = time.perf_counter()
+    out = subprocess.run([sys.executable, "-c", "from tests.helpers.global_nfa_child import main; main()"], cwd=ROOT, env=env,
+                         capture_output=True, text=True, timeout=600)
+    wall = time.perf_counter() - t0
+    assert out.returncode == 0, "the child ended with status %d\n%s\n%s" % (out.returncode, out.stdout[-2000:], out.stderr[-4000:])
+    res = json.loads(out.stdout.strip().splitlines()[-1])
+    print("GLOBAL nfa_match_kernel child: %.1f s wall, of which imports %.1f s, launches and oracle %.1f s; %d launches" % (
+        wall, res["seconds"]["imports"], res["seconds"]["work"], len(res["launches"])))
+    bad = [x for x in res["launches"] if x["differ"] or not x["ran"]]
+    assert not bad, "%d of %d launches differ; first: %s" % (len(bad), len(res["launches"]), bad[0])
+    # 4 + 1 families in both forms, 3 search families resumed in both forms, 16 + 2 + 4 result-edge launches
+    assert len(res["launches"]) == 2 * 5 + 2 * 3 + 22, len(res["launches"])
+    assert "nfa_match_kernel" in res["kernels"] and "nfa_match_kernel<atomic>" in res["kernels"], res["kernels"]
