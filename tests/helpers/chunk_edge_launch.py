@@ -64,14 +64,16 @@ def make_batches(torch):
     return get
 
 
-def launch(torch, row, rx, batch, form, ngroups=None, caps_shift=0, n=None, lines=None, nlines=None, frm=None, ragged=False):
+def launch(torch, row, rx, batch, form, ngroups=None, caps_shift=0, n=None, lines=None, nlines=None, frm=None, ragged=False,
+           status_fill=STATUS_SENTINEL):
     """One launch of `row` -> (caps[N, 2 * ngroups], status[N], kernel names): rows for ALL N values of the batch, of which the launch
-    takes the first n, or those `lines` lists, or as many as `nlines` says on the device.  Asserts the sentinels around the results."""
+    takes the first n, or those `lines` lists, or as many as `nlines` says on the device.  Asserts the sentinels around the results.
+    status_fill: what every status byte holds before the launch instead of its sentinel."""
     dev = torch.device("cuda:0")
     N = batch["n"]
     n = N if n is None else n
     ngroups = batch["G"] if ngroups is None else ngroups
-    res = GuardedResults(torch, N, ngroups, caps_shift)
+    res = GuardedResults(torch, N, ngroups, caps_shift, status_fill)
     io = batch[form]
     sep = 0 if form == "len" else 1
     stream = torch.cuda.current_stream().cuda_stream
@@ -110,15 +112,24 @@ def cut(caps, ngroups):
     return np.concatenate([caps, np.full((len(caps), 2 * (ngroups - G)), -1, np.int32)], axis=1)
 
 
-def differing(batch, got_caps, got_status, exp_caps, exp_status, where, listed=None):
-    """the rows of the `listed` values (default: all) against the oracle's; every other row still holds its sentinels.
+def decide_stats():
+    """lc_decide_stats -> (values the calling thread's last decide launches settled, values they gave up)"""
+    L = B.load()
+    stats = (ctypes.c_uint64 * 2)()
+    assert L.lc_decide_stats(stats) == 0
+    return int(stats[0]), int(stats[1])
+
+
+def differing(batch, got_caps, got_status, exp_caps, exp_status, where, listed=None, status_fill=STATUS_SENTINEL):
+    """the rows of the `listed` values (default: all) against the oracle's; every other row still holds its sentinels (its status byte:
+    `status_fill`, what the launch found there).
     -> (number of values that differ, a description of the first or None)"""
     N = batch["n"]
     took = np.ones(N, bool) if listed is None else np.zeros(N, bool)
     if listed is not None:
         took[np.asarray(listed, np.int64)] = True
     wrong = (got_status != exp_status) | (got_caps != exp_caps).any(axis=1)
-    untouched = (got_status == STATUS_SENTINEL) & (got_caps == CAPS_SENTINEL).all(axis=1)
+    untouched = (got_status == status_fill) & (got_caps == CAPS_SENTINEL).all(axis=1)
     bad = np.nonzero(np.where(took, wrong, ~untouched))[0]
     if not bad.size:
         return 0, None

@@ -15,6 +15,8 @@ BODIES = {   # family -> its pattern with named groups; {k} = the entry's number
     "log": r"(?P<a{k}>[^,]*),(?P<b{k}>\d*);(?P<c{k}>[^ ]*) (?P<d{k}>.*)",
     "big": r"(?P<a{k}>[^,]*),(?P<b{k}>\d*);(?:a|b)*a(?:a|b){{12}}(?P<c{k}>c+)(?P<d{k}>d*) (?P<e{k}>.*)",
     "lazy": r"(?P<a{k}>[^,]*),(?P<b{k}>\d*);(?:a|b)*a(?:a|b){{14}}(?P<c{k}>c+)(?P<d{k}>d*) (?P<e{k}>.*)",
+    "over64": r"(?P<a{k}>[^;]*);(?P<b{k}>.*)a(?P<c{k}>.{{70}})",
+    "over128": r"(?P<a{k}>[^;]*);(?P<b{k}>.*)a(?P<c{k}>.{{140}})",
     "quasi": r"Group = (?P<g{k}>.*), IP = (?P<ip{k}>\d+), NAT",
     "look": r"(?<![0-9.])(?P<o{k}>\d+)\.(?P<p{k}>\d+)\.(?P<q{k}>\d+)\.(?P<r{k}>\d+)(?![0-9])",
 }
@@ -103,3 +105,16 @@ def border_list(n_entries):
             values.append(v._replace(entry=k, bytes=tag(k) + v.bytes[TAG_BYTES:]))
             at += 1
     return match, values
+
+
+def overflow_list():
+    """-> (Match list, values): the overflow families (the 65th / 129th live thread on an offset of W256_P of the tagged value, and the
+    `at_cap` controls), the log family, and an entry nobody is a candidate of.  Entries 0 and 1 are thread-list programs whose
+    values walk the plan's own chain: first chance, overflow list, nfa_wide_kernel, nfa_decide_kernel"""
+    match = [entry(0, "over64"), entry(1, "over128"), entry(2, "log"), entry(3, "over64")]
+    return match, family_values(0, "over64") + family_values(1, "over128") + family_values(2, "log")
+
+
+def needs_wide(v):
+    """the value's thread list outgrows nfa_match_kernel's 64 threads (every over128 value does: its controls peak at 128)"""
+    return v.family == "over128" or (v.family == "over64" and not v.variant.startswith("at_cap"))

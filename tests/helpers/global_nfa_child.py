@@ -1,7 +1,8 @@
 """Test-only: the body of the ONE child process of tests/test_gpu_chunk_edges.py test_global_memory_nfa_kernel_in_a_process_of_its_own.
 LC_NFA_GLOBAL_KB is read once per process; with LC_NFA_GLOBAL_KB=0 in the environment every non-empty batch takes
 nfa_match_kernel<..., GLOBAL=true> (the program stays in global memory, LDS holds the scratch alone).  main() runs rows `nfa` and
-`nfa-atomic` of the instantiation table in both input forms, the resumed searches, and the result edges on `log`, compares with the
+`nfa-atomic` of the instantiation table in both input forms, the resumed searches, and the result edges on `log`, then rows `nfa-ns64`,
+`nfa-ns128` and `nfa-ns320` (the slot-by-slot capture transfer with 4 and 10 tag words, the accumulation registers) in both forms, compares with the
 oracle's rows behind sentinels, and prints one JSON object: per launch the number of values that differ and the first, the kernel
 names, and where the time went.  Not part of the product."""
 import json
@@ -30,7 +31,7 @@ def main():
         out["launches"].append({"launch": where, "differ": n, "first": first, "ran": row.kernel in names})
         out["kernels"] = sorted(set(out["kernels"]) | set(names))
 
-    for row in (r for r in ce.ROWS if r.id in ("nfa", "nfa-atomic")):
+    for row in (r for r in ce.ROWS if r.id in ("nfa", "nfa-atomic") + tuple(ce.NS_ROWS)):
         assert row.env == {"LC_LAZY_TDFA": "0"} and not row.dfs and not row.min_n
         for family in row.families:
             rx = ce.compile_row(row, family)

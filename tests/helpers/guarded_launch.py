@@ -7,17 +7,18 @@ CAPS_SENTINEL, STATUS_SENTINEL = -7, 9
 
 
 class GuardedResults:
-    def __init__(self, torch, n, ngroups, caps_shift=0):
-        """room for n rows of 2 * ngroups capture offsets and n status bytes, everything filled with the sentinels"""
+    def __init__(self, torch, n, ngroups, caps_shift=0, status_fill=STATUS_SENTINEL):
+        """room for n rows of 2 * ngroups capture offsets and n status bytes, everything filled with the sentinels; status_fill: what
+        the status bytes, guards included, hold instead of their sentinel (a stale LC_OVERFLOW of an earlier launch, say)"""
         dev = torch.device("cuda:0")
-        self.n, self.n_out = n, 2 * ngroups
+        self.n, self.n_out, self.status_fill = n, 2 * ngroups, status_fill
         words = (n + 2 * GUARD) * self.n_out
         self.buf = torch.full((words + 8,), CAPS_SENTINEL, dtype=torch.int32, device=dev)
         assert self.buf.data_ptr() % 16 == 0
         self.first = caps_shift + GUARD * self.n_out
         self.d_caps = self.buf[self.first:self.first + max(n * self.n_out, 1)]
         assert (self.d_caps.data_ptr() - self.buf.data_ptr()) == 4 * self.first and (4 * GUARD * self.n_out) % 16 == 0   # (shift 0: 16-byte aligned rows)
-        self.sbuf = torch.full((n + 2 * 4 * GUARD,), STATUS_SENTINEL, dtype=torch.uint8, device=dev)
+        self.sbuf = torch.full((n + 2 * 4 * GUARD,), status_fill, dtype=torch.uint8, device=dev)
         self.d_status = self.sbuf[4 * GUARD:4 * GUARD + n]
 
     def read(self, where):
@@ -26,5 +27,5 @@ class GuardedResults:
         out, sout = self.buf.cpu().numpy(), self.sbuf.cpu().numpy()
         assert (out[:first] == CAPS_SENTINEL).all(), ("rows in front of the capture table were written", where)
         assert (out[first + n * n_out:] == CAPS_SENTINEL).all(), ("rows behind the capture table were written", where)
-        assert (sout[:4 * GUARD] == STATUS_SENTINEL).all() and (sout[4 * GUARD + n:] == STATUS_SENTINEL).all(), ("status guard bytes were written", where)
+        assert (sout[:4 * GUARD] == self.status_fill).all() and (sout[4 * GUARD + n:] == self.status_fill).all(), ("status guard bytes were written", where)
         return out[first:first + n * n_out].reshape(n, n_out), sout[4 * GUARD:4 * GUARD + n]

@@ -115,6 +115,13 @@ class NfaInterp:
                 tags = sum(int(aux[aw * a + 1 + k]) << (32 * k) for k in range(min(aw - 1, 10)))
                 lst.append((-1 if tgt == 0xFFFF else tgt, cond, tags))
             self.follow.append(lst)
+        self._tagged = {}
+
+    def _slots(self, tags):
+        """the slots a tag word stamps (kept per word: programs with hundreds of slots stamp a few of them per transition)"""
+        if tags not in self._tagged:
+            self._tagged[tags] = tuple(sl for sl in range(self.nslots) if (tags >> sl) & 1)
+        return self._tagged[tags]
 
     @_with_run_captures
     def fullmatch(self, s: bytes, max_threads=64, start=0, steady=True):
@@ -154,9 +161,8 @@ class NfaInterp:
                         continue
                     seen.add(tgt)
                     c2 = list(caps)
-                    for sl in range(self.nslots):
-                        if (tags >> sl) & 1:
-                            c2[sl] = pos
+                    for sl in self._slots(tags):
+                        c2[sl] = pos
                     new.append((tgt, c2))
             if steady and self.search_suffix >= 0:      # nothing ranked below a thread on the suffix position can win any more
                 for k, (p, _) in enumerate(new):
@@ -175,9 +181,8 @@ class NfaInterp:
                 if tgt >= 0 or (cond & ~holds):
                     continue
                 c2 = list(caps)
-                for sl in range(self.nslots):
-                    if (tags >> sl) & 1:
-                        c2[sl] = len(s)
+                for sl in self._slots(tags):
+                    c2[sl] = len(s)
                 return c2
         return None
 

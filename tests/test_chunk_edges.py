@@ -41,7 +41,9 @@ def test_every_offset_and_residue_is_there_for_every_kind(name, walk):
     c, o, exp = _oracle(name, walk)
     fam = c.family
     offsets, M = ce.WALKS[walk]
-    assert (offsets, M) == ((ce.W256_P, 4) if walk == "w256" else (ce.W16_P, 16))
+    assert (offsets, M) == {"w256": (ce.W256_P, 4), "w16": (ce.W16_P, 16), "w16r": (ce.W16R_P, 16)}[walk]
+    # (w16r: the 16-byte walk and 16 consecutive offsets with room for a run of 40 bytes in front -- two whole 16-byte loads and a tail)
+    assert set(ce.W16R_P) >= set(ce.W16_P) | set(range(42, 58)) and max(ce.RunCaptureFamily.BACK) + 2 == 42
     # 6 below .. 6 behind the first two chunk borders of the aligned view (line offset 256k - head), and the start of the value
     assert set(ce.W256_P) >= {b - h + d for b in (256, 512) for h in range(4) for d in range(-6, 7)} | set(range(6))
     seen = collections.defaultdict(set)
@@ -68,6 +70,10 @@ def test_every_offset_and_residue_is_there_for_every_kind(name, walk):
         assert all(v == set(range(M)) for v in by_kind.values()), (name, form, {k: sorted(v) for k, v in by_kind.items()})
     # (two corpora of the 16-byte walk hold more: log, whose size the screen test's figures fix, and lazy, the big family plus the misses)
     assert len(c.cases) <= (11000 if (name, walk) in (("log", "w16"), ("lazy", "w16")) else 9000) and max(len(s) for s in c.lines) <= 1100
+    if name.startswith("over"):
+        # the seeded shuffle mixes controls and overflowing values: some workgroup of four values holds both, and each alone
+        groups = [{fam.overflows(k) for k in c.cases[i:i + 4]} for i in range(0, len(c.cases), 4)]
+        assert {True, False} in groups and {True} in groups and {False} in groups, name
 
 
 @pytest.mark.parametrize("name,walk", CORPORA)
@@ -79,7 +85,23 @@ def test_cases_do_what_their_label_says(name, walk):
     for k, e in zip(c.cases, exp):
         what = (name, k.kind, k.variant, k.p)
         counts[k.kind, k.variant] += 1
-        if k.kind in ("run_stop", "stamp"):
+        if name == "runcap" and k.kind == "run_stop":
+            back = int(k.variant.rsplit("_", 1)[1])                                                   # the run [p - back, p) ends on the FIRST '|'
+            assert e is not None and e[2:4] == [k.p - back, k.p] and k.line.index(b"|") == k.p, what
+            assert k.line[k.p - back - 1:k.p - back] == b"!" and (back < 2 or e[5] < k.p), what        # (the next field ends inside the run)
+        elif k.kind == "absent":
+            assert e is not None and e[2:4] == [-1, -1] and e[1] == k.p - 1 and k.line[k.p:k.p + 1] != b"!" and b"|" in k.line, what
+        elif k.kind == "overflow":
+            m = fam.cap - (1 if k.variant.startswith("at_cap") else 0)
+            assert k.line[k.p - m + 1:k.p + 1] == b"a" * m and k.line[k.p - m - 3:k.p - m + 1] == b";bbb" and fam.overflows(k) == (m == fam.cap), what
+            v = k.variant[7:] if k.variant.startswith("at_cap") else k.variant
+            assert (e is not None) == (v in ("match", "far")), what
+            assert v != "match" or (e[-2] == k.p + 1 and e[-1] == len(k.line)), what                    # the run's last 'a' is the one
+            assert v != "far" or (e[-2] >= k.p + 300 and len(k.line) - k.p > 300), what                # ... or one a chunk further on
+            assert v != "ends" or len(k.line) == k.p + 1, what
+            assert v != "one_more" or run(k.line[:-1]) is not None, what
+            assert v != "match" or run(k.line + fam.after) is None, what                              # (the byte behind it, read, would refuse it)
+        elif k.kind in ("run_stop", "stamp"):
             assert e is not None and k.p in e, what                                                  # a capture begins or ends at p
             if k.variant.startswith("one_byte"):
                 assert any(e[2 * g] == k.p and e[2 * g + 1] == k.p + 1 for g in range(len(e) // 2)), what
@@ -87,6 +109,8 @@ def test_cases_do_what_their_label_says(name, walk):
                 assert any(e[2 * g] == k.p == e[2 * g + 1] for g in range(len(e) // 2)), what
         elif k.kind == "run_to_end":
             assert len(k.line) == k.p, what
+            if name == "runcap":                                                                      # the run reaches the end of the value; the byte behind belongs to its set
+                assert e is not None and e[2] >= 2 and e[3] == k.p and b"|" not in k.line[e[2]:] and k.after == b"u", what
             if "needy" in k.variant:                                                                  # the byte behind it changes the result
                 assert _flat(fam, run(k.line + k.after)) != e, what
         elif k.kind == "dead":
@@ -148,10 +172,10 @@ def test_the_instantiation_table_runs_what_the_families_declare():
     """every family is run by some row, every row runs every kind of its families (>= 90 % is the cap the table must meet; a case
     set a row leaves out would be an entry of the table), search rows have search families, the edge families belong to their rows"""
     assert {f for r in ce.ROWS for f in r.families} == set(ce.FAMILIES)
-    assert len({r.id for r in ce.ROWS}) == len(ce.ROWS) == 14
+    assert len({r.id for r in ce.ROWS}) == len(ce.ROWS) == 23
     assert {r.kernel for r in ce.ROWS} == {"nfa_match_kernel", "nfa_match_kernel<atomic>", "nfa_wide_kernel:first", "tdfa_l2_kernel:wave",
                                            "tdfa_l2_kernel", "nfa_decide_kernel", "nfa_dfs_kernel", "bt_match_kernel",
-                                           "tdfa_l2_kernel:wave:lazy", "tdfa_l2_kernel:lazy"}
+                                           "tdfa_l2_kernel:wave:lazy", "tdfa_l2_kernel:lazy", "nfa_wide_kernel", "tdfa_stream_kernel*"}
     for r in ce.ROWS:
         for f in r.families:
             c = ce.generate(f, r.walk)
@@ -171,6 +195,28 @@ def test_the_instantiation_table_runs_what_the_families_declare():
     copies = -(-unstaged[0].min_n // n)
     assert ce.UNSTAGED_ABOVE < copies * n <= 65536                                                    # still a wave launch (LC_TDFA_WAVE_MAX)
     assert {r.id for r in ce.SEARCH_ROWS} == {"nfa", "nfa-atomic", "nfa-wide-first", "wave-small-staged", "decide", "dfs"}
+    # the rows of the chain's hand-offs, of the slot widths and of the run capture: one family each, the plain NFA launch
+    by_id = {r.id: r for r in ce.ROWS}
+    new = {"chain64": ("nfa_wide_kernel", "over64"), "chain128": ("nfa_decide_kernel", "over128"), "chain-slots": ("nfa_decide_kernel", "over64s"),
+           "nfa-ns64": ("nfa_match_kernel", "log64"), "nfa-ns128": ("nfa_match_kernel", "log128"), "nfa-ns320": ("nfa_match_kernel", "log320"),
+           "runcap-nfa": ("nfa_match_kernel", "runcap")}
+    for rid, (kernel, family) in new.items():
+        r = by_id[rid]
+        assert (r.kernel, r.families, ce.EDGE_FAMILY[rid]) == (kernel, (family,), family), rid
+        assert (r.compile_engine, r.launch_engine, r.env, r.wave, r.dfs, r.min_n, r.train) == (B.LC_ENGINE_NFA, B.LC_ENGINE_NFA, {"LC_LAZY_TDFA": "0"},
+                                                                                           False, False, 0, None), rid
+        assert r.walk == ("w16r" if family == "runcap" else "w256")
+    assert [(r.id, r.kernel, r.families, r.walk, r.compile_engine, r.launch_engine, r.wave) for r in ce.ROWS if r.id in ("runcap-wave", "runcap-lds")] == [
+        ("runcap-wave", "tdfa_l2_kernel:wave", ("runcap",), "w16r", B.LC_ENGINE_AUTO, B.LC_ENGINE_TDFA, True),
+        ("runcap-lds", "tdfa_stream_kernel*", ("runcap",), "w16r", B.LC_ENGINE_AUTO, B.LC_ENGINE_TDFA, False)]
+    # nfa_wide_kernel<64> as the first chance: the 64-slot family, not the wider ones (NS > 64 never goes wide first)
+    assert by_id["nfa-wide-first"].families == ("log", "quasi", "look", "threads", "over64", "over128", "log64")
+    assert set(ce.CHAIN) == {("chain64", "over64"), ("chain128", "over128"), ("chain-slots", "over64s"), ("nfa-wide-first", "over64"),
+                             ("nfa-wide-first", "over128")} and set(ce.DECIDES) == {k for k, (has, _) in ce.CHAIN.items() if "nfa_decide_kernel" in has}
+    for (rid, family), (has, has_not) in ce.CHAIN.items():
+        assert family in by_id[rid].families and by_id[rid].kernel in has and not set(has) & set(has_not)
+        assert "nfa_wide_kernel:first" in (has if rid == "nfa-wide-first" else has_not)
+    assert set(ce.NS_ROWS) == {rid for rid in new if rid.startswith("nfa-ns")}
 
 
 # ---- the product's tables on the host
@@ -223,6 +269,8 @@ def test_global_memory_tdfa_tables_give_the_oracles_rows(name, walk):
     _check(c, exp, (("tdfa_wave_kernel's walk", it.fullmatch_wave), ("tdfa_l2_kernel's walk", it.fullmatch)), name)
     ends_quiet = 0
     for k in c.cases:
+        if name == "runcap":
+            continue                                                                                  # (its events are run_capture_kernel's, not the automaton's)
         if k.kind == "run_stop":
             tr = _l2_trace(it, k.line)
             first = _run_of(k)
@@ -242,11 +290,16 @@ def test_global_memory_tdfa_tables_give_the_oracles_rows(name, walk):
         elif k.kind == "resume":
             want = _flat(fam, o.search(k.line, k.frm))
             assert it.fullmatch_wave(k.line, start=k.frm) == want and it.fullmatch(k.line, start=k.frm) == want, c.label(c.cases.index(k))
-    assert fam.search or ends_quiet >= 0.8 * sum(k.kind == "run_to_end" and k.p >= 2 for k in c.cases)
+    assert fam.search or name == "runcap" or ends_quiet >= 0.8 * sum(k.kind == "run_to_end" and k.p >= 2 for k in c.cases)
+    if name == "runcap":
+        # the run group survives in the tagged DFA, inside the optional branch: the tables stamp its begin, the end is the run kernel's
+        assert [g for g, _ in rx.run_captures()] == [1] and rx.run_captures()[0][1] == frozenset(range(256)) - {ord("|")}
+        assert rx.table(B.LC_TABLE_TDFA_BLOB, np.uint32) is not None                                  # (the LDS kernels can run it: row runcap-lds)
 
 
-def _nfa_trace(it, s, start=0):
-    """NfaInterp's walk once more, step by step: [(live threads, every one of them steady on this byte)] per byte"""
+def _nfa_trace(it, s, start=0, end=False):
+    """NfaInterp's walk once more, step by step: [(live threads, every one of them steady on this byte)] per byte; end: and the
+    threads the step on the last byte leaves, as (count, None)"""
     threads, prev = ([it.npos], it.ncls) if not start else ([0], int(it.cmap[s[start - 1]]))
     out = []
     for pos in range(start, len(s)):
@@ -276,13 +329,20 @@ def _nfa_trace(it, s, start=0):
         prev = cls
         if not threads:
             break
+    if end:
+        out.append((len(threads), None))
     return out
 
 
 # (the lazy family's program: test_the_lazy_family_misses_where_it_says_and_nowhere_else walks it on the values the kernels hand it)
-@pytest.mark.parametrize("name", sorted({f for r in ce.ROWS if r.compile_engine == B.LC_ENGINE_NFA for f in r.families} - {"lazy"}))
+OVER = ("over64", "over128", "over64s")
+
+
+# (... and the overflow families': test_the_overflow_families_exceed_each_cap_by_the_step_on_byte_p, with the caps the kernels have)
+@pytest.mark.parametrize("name", sorted({f for r in ce.ROWS if r.compile_engine == B.LC_ENGINE_NFA for f in r.families} - {"lazy"} - set(OVER)))
 def test_nfa_program_gives_the_oracles_rows(name):
-    c, o, exp = _oracle(name)
+    walk = "w16r" if name == "runcap" else "w256"
+    c, o, exp = _oracle(name, walk)
     fam = c.family
     rx = B.GpuRegex(fam.pattern, syntax_flags=fam.flags, engine=B.LC_ENGINE_NFA)
     assert (rx.atomic_groups()[0] > 0) == (name == "atomic")
@@ -290,8 +350,17 @@ def test_nfa_program_gives_the_oracles_rows(name):
     assert (it.search_suffix >= 0) == fam.search
     if name == "quasi":
         assert it.quasi_rows                                                                          # doomed-spawn rows exist for this shape
+    if isinstance(fam, ce.NestedLogFamily):
+        # nesting d deep: 4 d groups and 8 d slots on the log family's 7 positions -- each instantiation at its exact fit
+        assert (o.groups, it.nslots, it.npos) == (4 * fam.depth, 8 * fam.depth, 7) and it.nslots == int(name[3:]) in (64, 128, 320)
+        assert B.GpuRegex(fam.pattern).info()["engine"] == (B.LC_ENGINE_NFA if fam.depth == 40 else B.LC_ENGINE_TDFA)
+        assert ce.NS_ROWS[ce.ROWS[[r.families for r in ce.ROWS].index((name,))].id] == it.nslots
+    if name == "runcap":
+        assert [g for g, _ in rx.run_captures()] == [1]                                               # the run group survives, inside the optional branch
     _check(c, exp, (("the thread-list walk", it.fullmatch),), name)
     for k in c.cases:
+        if name == "runcap":
+            continue                                                                                  # (its events are run_capture_kernel's, not the program's)
         if k.kind == "run_stop":
             tr = _nfa_trace(it, k.line)
             first = _run_of(k)
@@ -313,6 +382,51 @@ def test_nfa_program_gives_the_oracles_rows(name):
             assert it.fullmatch(k.line, start=k.frm) == _flat(fam, o.search(k.line, k.frm)), c.label(c.cases.index(k))
     kinds = {k.kind for k in c.cases}
     assert name != "threads" or {int(k.variant.split("_")[0][4:]) for k in c.cases} >= {8, 7, 6, 1}    # beyond, at and below kNfaSteadyScanThreads
+
+
+@pytest.mark.parametrize("depth,slots,engine", [(6, 48, B.LC_ENGINE_TDFA), (12, 96, B.LC_ENGINE_TDFA), (20, 160, B.LC_ENGINE_TDFA), (40, 320, B.LC_ENGINE_NFA)])
+def test_nesting_the_log_family_gives_eight_slots_a_level(depth, slots, engine):
+    """nesting d gives 4 d groups and 8 d slots on 7 positions; AUTO takes the tagged DFA up to depth 20 and the thread-list program at 40"""
+    fam = ce.NestedLogFamily(depth)
+    it = NfaInterp(B.GpuRegex(fam.pattern, engine=B.LC_ENGINE_NFA))
+    assert (OracleRegex(fam.pattern).groups, it.nslots, it.npos) == (4 * depth, slots, 7)
+    assert B.GpuRegex(fam.pattern).info()["engine"] == engine
+    line = b"xy,12;uv w z"
+    want = [v for be in OracleRegex(fam.pattern).fullmatch(line)[1:] for v in be]
+    assert it.fullmatch(line) == want == [v for be in ((0, 2), (3, 5), (6, 8), (9, 12)) for _ in range(depth) for v in be]
+
+
+@pytest.mark.parametrize("name", OVER)
+def test_the_overflow_families_exceed_each_cap_by_the_step_on_byte_p(name):
+    """What rows chain64 / chain128 / chain-slots rest on.  The programs have 74 / 144 / 74 positions and 6 / 6 / 66 slots.  On every
+    case the thread list first exceeds the family's cap BY THE STEP ON BYTE p (cap threads behind byte p - 1, cap + 1 behind byte p)
+    and the `at_cap` controls peak at exactly the cap, behind byte p, and exceed it nowhere.  The walk with nfa_match_kernel's 64
+    threads says "overflow" exactly on over64's overflow variants (and on every over128 case from its 65th thread on), with
+    nfa_wide_kernel's 128 it decides all of over64 and says "overflow" exactly on over128's overflow variants, and with room for
+    every thread it gives the oracle's row everywhere."""
+    c, o, exp = _oracle(name)
+    fam = c.family
+    rx = B.GpuRegex(fam.pattern, engine=B.LC_ENGINE_NFA)
+    assert rx.info()["engine"] == B.LC_ENGINE_NFA and rx.atomic_groups()[0] == 0
+    it = NfaInterp(rx)
+    assert (it.npos, it.nslots, fam.cap) == {"over64": (74, 6, 64), "over128": (144, 6, 128), "over64s": (74, 66, 64)}[name]
+    assert it.search_suffix < 0 and not it.quasi_rows
+    over = [fam.overflows(k) for k in c.cases]
+    assert collections.Counter((k.variant, v) for k, v in zip(c.cases, over)) == dict(
+        [((v, True), 136) for v in ("match", "far", "ends", "one_more")] + [((v, False), 136) for v in ("at_cap_match", "at_cap_far")])
+    walked = set()
+    for k, e, ov in zip(c.cases, exp, over):
+        what = (name, k.variant, k.p)
+        if k.line in walked:
+            continue                                                                                  # (the same bytes at another residue)
+        walked.add(k.line)
+        counts = [n for n, _ in _nfa_trace(it, k.line, end=True)]                                     # counts[i]: live threads in front of byte i
+        assert counts[k.p] == fam.cap - (0 if ov else 1) and counts[k.p + 1] == counts[k.p] + 1, what  # the step on byte p adds the last one
+        assert max(counts[:k.p + 1]) <= fam.cap and max(counts) == fam.cap + (1 if ov else 0), what
+        for cap in (64, 128, 4096):
+            got = it.fullmatch(k.line, max_threads=cap)
+            assert got == ("overflow" if ov and fam.cap >= cap or fam.cap > cap else e), what + (cap,)
+    assert len(walked) == len(c.cases) // 4
 
 
 def test_backtracking_program_gives_the_oracles_rows(host_vm):  # noqa: F811
@@ -370,6 +484,32 @@ def test_the_lazy_family_misses_where_it_says_and_nowhere_else(walk):
     nfa = NfaInterp(rx)
     missed = {k.line: e for k, e in zip(c.cases, exp) if k.kind == "miss"}
     assert all(nfa.fullmatch(line) == e for line, e in missed.items())
+
+
+@pytest.mark.parametrize("walk", ["w256", "w16"])
+def test_a_lazy_automaton_trained_again_on_its_misses_is_another_automaton(walk):
+    """tests/test_gpu_chunk_edges.py launches rows lazy-wave and lazy-lane, hands the family's `miss` lines to lazy_train and launches
+    the SAME handle again (gpu_runtime.hip ensureLazyUploaded: a new version, a new header, a new device copy).  Here: before the
+    second call exactly the `miss` cases miss (544 of the 256-byte walk's corpus), after it no case does, every case is decided as the
+    oracle decides it, and the blob has grown (1640 -> 1796 words for the 256-byte walk's lines): the second launch walks different
+    tables."""
+    c, o, exp = _oracle("lazy", walk)
+    row = next(r for r in LAZY_ROWS if r.walk == walk and r.train == "family")
+    rx = ce.compile_row(row, "lazy")
+    it, walks = _lazy_walks(rx)
+    words = len(rx.table(B.LC_TABLE_LAZY_TDFA_BLOB, np.uint32))
+    missed = [i for i, k in enumerate(c.cases) if it.fullmatch(k.line) == it.MISS]
+    assert missed == [i for i, k in enumerate(c.cases) if k.kind == "miss"] and len(missed) == {"w256": 544, "w16": 1088}[walk]
+    again = ce.miss_lines(walk)
+    assert len(again) == len(missed) // ce.WALKS[walk][1] and set(again) == {c.cases[i].line for i in missed}
+    r = rx.lazy_train(again)
+    assert r["in_use"] == 1 and r["sample_misses"] == 0, r
+    it, walks = _lazy_walks(rx)
+    grown = len(rx.table(B.LC_TABLE_LAZY_TDFA_BLOB, np.uint32))
+    assert grown > words and (walk != "w256" or (words, grown) == (1640, 1796)), (words, grown)
+    for name, fn in walks:
+        assert not [k for k in c.cases if fn(k.line) == it.MISS], name
+    _check(c, exp, walks, "lazy, trained again")
 
 
 @pytest.mark.parametrize("row", [r for r in LAZY_ROWS if r.train == "corpus"], ids=lambda r: r.id)

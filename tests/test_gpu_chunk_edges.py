@@ -10,6 +10,12 @@ The lazy rows put a partial automaton in front of a thread-list program (both wa
 chosen byte and must come back with the thread-list kernels' answer, `log` and `threads` run the decided path alone.  The GLOBAL
 instantiation of nfa_match_kernel runs in one child process (LC_NFA_GLOBAL_KB is read once per process).
 
+The chain rows put the 65th / 129th live thread on a chosen byte (families over64 / over128 / over64s): nfa_match_kernel hands the
+value to nfa_wide_kernel, that one to nfa_decide_kernel, the `at_cap` controls in the same workgroups stay where they are, and
+lc_decide_stats counts exactly the values that had to be sent on.  Rows nfa-ns64 / 128 / 320 run the log family with 64, 128 and 320
+capture slots, rows runcap-* put the end of a run capture (run_capture_kernel) on a chosen byte for all 16 residues.  The handles of
+lazy-wave and lazy-lane are launched, trained again on their misses and launched once more: a rebuilt automaton behind one handle.
+
 Every launch keeps four sentinel rows in front of and behind the capture table and the status bytes (tests/helpers/guarded_launch.py)
 and runs in both forms: (off, len), where filler gives each line its residue, and off[n + 1] with a separator byte."""
 import json
@@ -23,7 +29,8 @@ import pytest
 
 from loongcollector_amd import binding as B
 from tests.helpers import chunk_edges as ce
-from tests.helpers.chunk_edge_launch import cut as _cut, differing, launch as _launch, make_batches, rows as _rows
+from tests.helpers.chunk_edge_launch import cut as _cut, decide_stats, differing, launch as _launch, make_batches, rows as _rows
+from tests.helpers.guarded_launch import STATUS_SENTINEL
 
 pytestmark = pytest.mark.gpu
 
@@ -46,19 +53,36 @@ def _copies(row, n0):
     return -(-row.min_n // n0) if row.min_n else 1
 
 
-def _compare(batch, got_caps, got_status, exp_caps, exp_status, where, listed=None):
+def _compare(batch, got_caps, got_status, exp_caps, exp_status, where, listed=None, status_fill=STATUS_SENTINEL):
     """the rows of the `listed` values (default: all) against the oracle's; every other row still holds its sentinels"""
-    n, first = differing(batch, got_caps, got_status, exp_caps, exp_status, where, listed)
+    n, first = differing(batch, got_caps, got_status, exp_caps, exp_status, where, listed, status_fill)
     if n:
         pytest.fail(first)
 
 
-def _ran(row, names, where):
-    assert row.kernel in names, (where, names)                                 # (the instantiation the row names is what ran)
+def _ran(row, names, where, family=None):
+    assert ce.ran(row, names), (where, names)                                  # (the instantiation the row names is what ran)
     if row.id == "nfa-wide-first":
         assert "nfa_match_kernel" not in names, (where, names)
     if row.id == "l2-lane":
         assert "tdfa_l2_kernel:wave" not in names, (where, names)
+    has, has_not = ce.CHAIN.get((row.id, family), ((), ()))                    # the chain's hand-offs: who took part, who did not
+    assert set(has) <= set(names) and not set(has_not) & set(names), (where, names)
+
+
+def _sent_on(row, family, batch, names, where, listed=None):
+    """lc_decide_stats right behind a launch of a chain row: nfa_decide_kernel settled exactly the values of the launch in which a
+    thread list outgrows the last thread-list kernel -- an `at_cap` value sent on would be counted -- and gave none up.  A row whose
+    program cannot outgrow it queues no decide launch at all (asserted by _ran): nothing was sent on."""
+    if (row.id, family) not in ce.CHAIN:
+        return
+    c, fam = batch["corpus"], batch["corpus"].family
+    over = [fam.overflows(c.cases[int(i) % batch["n0"]]) for i in (range(batch["n"]) if listed is None else listed)]
+    assert 0 < sum(over) < len(over), where                                    # (overflowing values and controls in every launch)
+    if (row.id, family) in ce.DECIDES:
+        assert decide_stats() == (sum(over), 0), (where, decide_stats(), sum(over))
+    else:
+        assert "nfa_decide_kernel" not in names, (where, names)
 
 
 @pytest.mark.parametrize("row", ce.ROWS, ids=[r.id for r in ce.ROWS])
@@ -71,8 +95,9 @@ def test_corpus_through_each_engine(torch_dev, monkeypatch, batches, row):
         for form in ("len", "sep"):
             where = "%s, %s, %s form" % (row.id, family, form)
             caps, status, names = _launch(torch_dev, row, rx, batch, form)
-            _ran(row, names, where)
+            _ran(row, names, where, family)
             _compare(batch, caps, status, batch["caps"], batch["status"], where)
+            _sent_on(row, family, batch, names, where)
 
 
 @pytest.mark.parametrize("row", ce.SEARCH_ROWS, ids=[r.id for r in ce.SEARCH_ROWS])
@@ -107,14 +132,19 @@ def test_result_edges(torch_dev, monkeypatch, batches, row):
     batch = batches(family, row.walk, _copies(row, len(ce.generate(family, row.walk).cases)))
     N, G = batch["n"], batch["G"]
     base = ce.UNSTAGED_ABOVE if row.min_n else 0                               # (the unstaged launch stays unstaged)
-    cuts = (base + 513, base + 515, base + 577)
+    # (the chain rows that leave values to nfa_decide_kernel -- one lane walks a value of 800 bytes for milliseconds --: the same
+    # shapes of n at a quarter of the size, the shuffled corpus's first values)
+    small = (row.id, family) in ce.DECIDES
+    cuts = (129, 131, 193) if small else (base + 513, base + 515, base + 577)
     assert [x % 4 for x in cuts] == [1, 3, 1] and cuts[2] % 64 == 1 and cuts[2] < N
-    full = base + 1025 if row.id in ("decide", "dfs") else N                    # (the depth-first kernels: a part of the corpus per launch)
+    # (the depth-first kernels: a part of the corpus per launch)
+    full = 257 if small else base + 1025 if row.id in ("decide", "dfs") else N
+    assert row.id not in ce.NS_ROWS or 2 * G == ce.NS_ROWS[row.id]              # (G + 3 groups below: past the instantiation's NS slots)
 
     def check(where, ngroups=G, listed=None, **kw):
         caps, status, names = _launch(torch_dev, row, rx, batch, ngroups=ngroups, **kw)
         if not kw.get("ragged"):
-            _ran(row, names, where)
+            _ran(row, names, where, family)
         _compare(batch, caps, status, _cut(batch["caps"], ngroups), batch["status"], "%s, %s, %s" % (row.id, family, where), listed=listed)
 
     for shift in (0, 1, 2, 3):
@@ -134,13 +164,67 @@ def test_result_edges(torch_dev, monkeypatch, batches, row):
             check("length-scheduled, table %d bytes off" % (4 * shift), form="len", caps_shift=shift, n=full, listed=range(full), ragged=True)
 
 
+STALE = [(r, f) for r in ce.ROWS for f in r.families if (r.id, f) in ce.CHAIN]
+
+
+@pytest.mark.parametrize("row,family", STALE, ids=["%s-%s" % (r.id, f) for r, f in STALE])
+def test_stale_overflow_bytes_of_unlisted_rows_are_left_alone(torch_dev, monkeypatch, batches, row, family):
+    """The second chance and the decide kernels take the values whose status byte says LC_OVERFLOW -- of the values the launch
+    LISTS.  The permuted-subset and device-count launches of test_result_edges once more, every status byte pre-filled with
+    LC_OVERFLOW instead of the sentinel (what an earlier launch into the same buffer may have left): the launch raises its own
+    overflow flag, and the rows it does not list come back untouched, capture rows and status bytes."""
+    assert B.LC_OVERFLOW == 2
+    ce.set_env(monkeypatch, row)
+    rx = ce.compile_row(row, family)
+    batch = batches(family, row.walk)
+    N, G = batch["n"], batch["G"]
+    cuts = (513, 515, 577)
+    subset = np.random.default_rng(7).permutation(N)[:cuts[1]]
+    assert cuts[2] < N and len(subset) < N
+
+    def check(what, listed, **kw):
+        where = "%s, %s, stale LC_OVERFLOW, %s" % (row.id, family, what)
+        caps, status, names = _launch(torch_dev, row, rx, batch, status_fill=B.LC_OVERFLOW, **kw)
+        _ran(row, names, where, family)
+        _compare(batch, caps, status, batch["caps"], batch["status"], where, listed=listed, status_fill=B.LC_OVERFLOW)
+        _sent_on(row, family, batch, names, where, listed=listed)
+
+    check("a permuted subset of %d" % len(subset), subset, form="len", n=len(subset), lines=subset)
+    check("a permuted subset of %d, separator form" % len(subset), subset, form="sep", caps_shift=1, n=len(subset), lines=subset)
+    check("%d of %d values by the count on the device" % (cuts[0], N), range(cuts[0]), form="sep", n=N, nlines=cuts[0])
+    check("257 of the subset by the count on the device", subset[:257], form="len", n=len(subset), lines=subset, nlines=257)
+
+
+@pytest.mark.parametrize("row", [r for r in ce.ROWS if r.train == "family"], ids=lambda r: r.id)
+def test_a_lazy_automaton_rebuilt_between_two_launches(torch_dev, monkeypatch, batches, row):
+    """gpu_runtime.hip ensureLazyUploaded: a handle whose automaton was rebuilt since its last launch gets a new header and a new device
+    copy.  The row's handle, trained as the row says, is launched; lazy_train gets the family's `miss` lines (tests/test_chunk_edges.py:
+    all of them missed, now none does, the blob has grown); the SAME handle is launched again, in both forms.  Both launches give the
+    oracle's rows.  Known limit: a device copy that stayed stale TOGETHER WITH its old header would still give right rows, because
+    the misses fall back to the thread-list kernels; what this catches is a new header over old tables and a torn upload."""
+    ce.set_env(monkeypatch, row)
+    rx = ce.compile_row(row, "lazy")
+    batch = batches("lazy", row.walk)
+    words = len(rx.table(B.LC_TABLE_LAZY_TDFA_BLOB, np.uint32))
+    for when in ("trained once", "trained again on its misses"):
+        for form in ("len", "sep"):
+            where = "%s, lazy, %s, %s form" % (row.id, when, form)
+            caps, status, names = _launch(torch_dev, row, rx, batch, form)
+            _ran(row, names, where)
+            _compare(batch, caps, status, batch["caps"], batch["status"], where)
+        if when == "trained once":
+            r = rx.lazy_train(ce.miss_lines(row.walk))
+            assert r["in_use"] == 1 and len(rx.table(B.LC_TABLE_LAZY_TDFA_BLOB, np.uint32)) > words, r
+
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_global_memory_nfa_kernel_in_a_process_of_its_own(torch_dev):
     """nfa_match_kernel<..., GLOBAL=true> runs where a program exceeds 52 KB, and LC_NFA_GLOBAL_KB, which moves that bound, is read
     once per process: ONE child process with LC_NFA_GLOBAL_KB=0 (every non-empty batch takes the GLOBAL instantiation) runs rows `nfa`
-    and `nfa-atomic` in both forms, the resumed searches and the result edges on `log` (tests/helpers/global_nfa_child.py) and reports
+    and `nfa-atomic` in both forms, the resumed searches and the result edges on `log`, and rows `nfa-ns64`, `nfa-ns128` and `nfa-ns320`
+    (64, 128 and 320 capture slots) in both forms (tests/helpers/global_nfa_child.py) and reports
     per launch how many values differ from the oracle's rows.  A child that faults, aborts or runs out of time fails the test with
     its stderr; nothing is started afterwards."""
     env = dict(os.environ)
@@ -157,6 +241,8 @@ def test_global_memory_nfa_kernel_in_a_process_of_its_own(torch_dev):
         wall, res["seconds"]["imports"], res["seconds"]["work"], len(res["launches"])))
     bad = [x for x in res["launches"] if x["differ"] or not x["ran"]]
     assert not bad, "%d of %d launches differ; first: %s" % (len(bad), len(res["launches"]), bad[0])
-    # 4 + 1 families in both forms, 3 search families resumed in both forms, 16 + 2 + 4 result-edge launches
-    assert len(res["launches"]) == 2 * 5 + 2 * 3 + 22, len(res["launches"])
+    # 4 + 1 families in both forms, 3 search families resumed in both forms, 16 + 2 + 4 result-edge launches, 3 slot widths in both forms
+    assert len(res["launches"]) == 2 * 5 + 2 * 3 + 22 + 2 * 3, len(res["launches"])
+    assert [x["launch"] for x in res["launches"][-6:]] == ["%s, %s, %s form" % (r, f, form) for r, f in (
+        ("nfa-ns64", "log64"), ("nfa-ns128", "log128"), ("nfa-ns320", "log320")) for form in ("len", "sep")]
     assert "nfa_match_kernel" in res["kernels"] and "nfa_match_kernel<atomic>" in res["kernels"], res["kernels"]

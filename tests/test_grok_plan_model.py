@@ -97,3 +97,36 @@ def test_counts_model_against_a_direct_count():
                 want[128 + p * 64 + bits[0]] += 1
     assert np.array_equal(got, want) and got[63] >= 4 and got[128 + 63 * 64 + 0] >= 2
     assert M.plan_counts(np.array([7], dtype=np.uint64), 2).tolist()[:3] == [1, 1, 0]     # (bits at or above the list's length are not counted per entry)
+
+
+def test_the_overflow_chain_list_puts_thread_65_and_129_where_it_says():
+    """What tests/test_gpu_grok_overflow_chain.py rests on (tests/helpers/fused_round0.py overflow_list).  Both overflow entries are
+    thread-list programs with AnchoredFirst on and off, beside a log entry that stays a tagged DFA.  On the ANCHORED form the plan
+    runs first (79 / 149 positions) the walk with nfa_match_kernel's 64 threads overflows exactly on the values needs_wide() names --
+    over64's overflow variants and every over128 value; over64's controls peak at 64 and are decided -- and with nfa_wide_kernel's 128
+    exactly on over128's overflow variants.  GrokOracle matches the overflow values (a Grok entry is a search: all but `ends`)."""
+    import collections
+
+    from loongcollector_amd import binding as B
+    from tests.helpers import fused_round0 as F
+    from tests.helpers.table_interp import NfaInterp
+    match, values = F.overflow_list()
+    for anchored_first in (True, False):
+        g = Grok(Match=match, AnchoredFirst=anchored_first)
+        assert [g.engine(k) for k in range(g.n_match)] == [B.LC_ENGINE_NFA, B.LC_ENGINE_NFA, B.LC_ENGINE_TDFA, B.LC_ENGINE_NFA]
+    per = collections.Counter((v.family, v.variant) for v in values if v.family != "log")
+    assert len(per) == 12 and set(per.values()) == {34} and sum(v.family == "log" for v in values) >= 500
+    assert {(v.family, v.head) for v in values} == {(f, h) for f in ("over64", "over128", "log") for h in range(4)}
+    o = GrokOracle(match)
+    for k, family, npos in ((0, "over64", 79), (1, "over128", 149)):
+        it = NfaInterp(B.GpuRegex(g.expanded(k).encode(), syntax_flags=C.GROK_SYNTAX | B.LC_SYNTAX_PREFIX, engine=B.LC_ENGINE_NFA))
+        assert it.npos == npos and it.nslots <= 8
+        for v in values:
+            if v.entry != k:
+                continue
+            assert v.family == family and v.p in F.ce.W256_P and v.bytes[v.p:v.p + 1] == b"a" and v.bytes[v.p + 1:v.p + 2] != b"a", v
+            over = not v.variant.startswith("at_cap")
+            assert (it.fullmatch(v.bytes, max_threads=64) == "overflow") == F.needs_wide(v) == (over or family == "over128"), v
+            assert (it.fullmatch(v.bytes, max_threads=128) == "overflow") == (over and family == "over128"), v
+            res, fields = o.process_value(v.bytes)
+            assert (res == 0) == (v.variant != "ends") and it.fullmatch(v.bytes, max_threads=4096) != "overflow", v
