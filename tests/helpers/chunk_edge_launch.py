@@ -37,29 +37,33 @@ def tile(data, off, length, form, copies, M=16):
     return big, offs.astype(np.uint32), np.tile(length, copies)
 
 
+def batch_of(torch, c, copies=1):
+    """a Corpus on the device in both forms and the oracle's rows for it"""
+    dev = torch.device("cuda:0")
+    fam = c.family
+    o = OracleRegex(fam.pattern)
+    G = o.groups + (1 if fam.search else 0)
+    caps, status = rows(fam, [(o.search if fam.search else o.fullmatch)(k.line) for k in c.cases], G)
+    batch = dict(corpus=c, oracle=o, G=G, n0=len(c.cases), n=copies * len(c.cases), caps=np.tile(caps, (copies, 1)), status=np.tile(status, copies))
+    for form in ("len", "sep"):
+        data, off, length, _ = c.pack(form)
+        data, off, length = tile(data, off, length, form, copies)
+        d_data = torch.from_numpy(data.copy()).to(dev)
+        assert d_data.data_ptr() % 16 == 0                                      # a line's residue is its offset's
+        batch[form] = dict(d_data=d_data, d_off=torch.from_numpy(off.view(np.int32).copy()).to(dev),
+                           d_len=torch.from_numpy(length.view(np.int32).copy()).to(dev) if form == "len" else None)
+    return batch
+
+
 def make_batches(torch):
     """-> get(family, walk, copies): the corpus on the device in both forms and the oracle's rows for it: computed once, shared by
     every caller, left unchanged"""
-    dev = torch.device("cuda:0")
     made = {}
 
     def get(name, walk, copies=1):
         key = (name, walk, copies)
         if key not in made:
-            c = ce.generate(name, walk)
-            fam = c.family
-            o = OracleRegex(fam.pattern)
-            G = o.groups + (1 if fam.search else 0)
-            caps, status = rows(fam, [(o.search if fam.search else o.fullmatch)(k.line) for k in c.cases], G)
-            batch = dict(corpus=c, oracle=o, G=G, n0=len(c.cases), n=copies * len(c.cases), caps=np.tile(caps, (copies, 1)), status=np.tile(status, copies))
-            for form in ("len", "sep"):
-                data, off, length, _ = c.pack(form)
-                data, off, length = tile(data, off, length, form, copies)
-                d_data = torch.from_numpy(data.copy()).to(dev)
-                assert d_data.data_ptr() % 16 == 0                              # a line's residue is its offset's
-                batch[form] = dict(d_data=d_data, d_off=torch.from_numpy(off.view(np.int32).copy()).to(dev),
-                                   d_len=torch.from_numpy(length.view(np.int32).copy()).to(dev) if form == "len" else None)
-            made[key] = batch
+            made[key] = batch_of(torch, ce.generate(name, walk), copies)
         return made[key]
     return get
 

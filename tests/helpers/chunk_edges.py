@@ -27,10 +27,26 @@ the line's first byte must have in device memory, `after` the byte right behind 
                 matches, matches 300+ bytes behind p, ends with byte p, has one byte too many -- and `at_cap`, the control: one
                 'a' fewer, the peak is EXACTLY the cap at p and nothing overflows
   absent        (run captures) the optional branch that holds the run group is not taken at p: the group reads (-1, -1)
+Kinds of the atomic instantiation, nfa_match_kernel<ATOMIC> (its ordered commit pass nfaAtomicStep, lane 0; tests/test_chunk_edges.py
+proves each event on byte p from the trace of tests/helpers/nfa_atomic_interp.py's faithful walk, for every head):
+  alog          the log family's kinds under (?>([^,]*)),(?>([0-9]*));(?>([^ ]*)) (.*): the commit pass on every byte of fields 1 to 3,
+                memberships alive across both chunk borders, the vector step and the skip from the last separator on
+  commit        (acommit) an atomic group is left on byte p behind a run of 1, 2, 5, 40, 300 bytes: the value matches; fails only
+                because the group gives no byte back; ends at p inside the group (the commit at the end of input decides, and the byte
+                behind the value would change the result)
+  enter         (acommit) the first byte that needs the commit pass is at p, behind a steady run from 0, p-1, p-2, p-5, p-40
+  alt           (acommit) (?>(ab|a)) is left on byte p through its first branch; the second, closed by then, would have matched
+  doomed        (aquasi: a kept atomic group AND doomed-spawn rows) a doomed spawn on byte p: skipped by its row, or -- p the last byte
+                of a chunk or of the value -- stepped in full
+  overflow      (akept64, avector64, alineage6, aclosed64, awork10) the step on byte p leaves through one named exit of the commit
+                pass, or through the vector step's 65th thread inside the ATOMIC instantiation, and nfa_decide_kernel takes the value;
+                the controls sit exactly at the cap on byte p: `at_cap` variants, or -- where the cap is the pattern's -- a sibling
+                family (alineage6c, aclosed64c, awork10c) launched beside it
 The `runcap` family gives run_stop and run_to_end to run_capture_kernel (gpu_runtime.hip): the run of a group written (?=(S*)) ends
 on byte p / with the value at p, for every residue mod 16 of the value's first byte and runs of 0 to 40 bytes in front of p.
 What a pattern cannot do is said by its family (Family.kinds: kind -> the smallest p it exists for).  tests/test_chunk_edges.py
 asserts all of this against the oracle and against the compiled tables, so that the GPU test cannot pass on a degenerate corpus.
+The atomic families rest on tests/helpers/nfa_atomic_interp.py: its faithful walk's trace says which step of the kernel falls on byte p.
 
 pack(form, modulus): "len" = (off, len) with filler bytes between the lines that give every line its head (the filler would change
 the answer if it were read); "sep" = off[n + 1] and one separator byte, where alignment follows from the lengths (the residues that
@@ -392,10 +408,10 @@ class OverflowFamily(Family):
     filler, after = b";ab", b"b"                                                  # (a 'b' behind a matching value: read, it would not match)
     HEAD = b";bbb"
 
-    def __init__(self, name, tail, cap, depth=1):
+    def __init__(self, name, tail, cap, depth=1, pattern=None):
         assert tail > cap
         self.name, self.tail, self.cap = name, tail, cap
-        self.pattern = nested(rb"[^;]*", depth) + b";" + nested(rb".*", depth) + b"a" + nested(b".{%d}" % tail, depth)
+        self.pattern = pattern or nested(rb"[^;]*", depth) + b";" + nested(rb".*", depth) + b"a" + nested(b".{%d}" % tail, depth)
         self.kinds = {"overflow": len(self.HEAD) + cap - 1}                       # the smallest p that leaves room for the run
 
     def _run(self, p, m):
@@ -458,10 +474,207 @@ class RunCaptureFamily(Family):
         return out
 
 
+# ---- nfa_match_kernel<ATOMIC>: the ordered commit pass (nfaAtomicStep) on chosen bytes, and each of its overflow exits
+
+class AtomicLogFamily(LogFamily):
+    """the log family's lines and kinds with its first three fields in atomic groups: 3 kept groups on the same 7 positions and
+    8 slots, the same rows -- and the commit pass on every byte of fields 1 to 3, memberships alive across the chunk borders"""
+    name, pattern = "alog", rb"(?>([^,]*)),(?>(\d*));(?>([^ ]*)) (.*)"
+
+
+def _pre(n):
+    """n >= 1 bytes of the two prefix fields of the acommit family: one comma, no semicolon"""
+    assert n >= 1
+    c = (n - 1) // 2
+    return _cyc(b"xyz_", c, n) + b"," + _cyc(b"uvw ", n - 1 - c, n)
+
+
+class AtomicCommitFamily(Family):
+    """two prefix fields, one atomic group whose run [a-z]* crosses the borders, a byte of the group's own set (or '-'), an atomic
+    alternation, a tail; everything behind the group is optional, so a value that ends inside the group matches by the commit at the
+    end of input.  commit: the group is LEFT on byte p ('-', the first byte outside its set) behind a run of 1, 2, 5, 40, 300 bytes;
+    `noback`: the run ends in "zad" / "zabd", which the plain form of the pattern would give back to match; `ends`: the value ends
+    at p inside the group (the byte behind it, read, would refuse it).  enter: the group is ENTERED on byte p, behind a steady run
+    of the second prefix field.  alt: (?>(ab|a)) is left on byte p through its first branch; `second_would`: only the second branch,
+    which the commit closed, would have matched."""
+    name, pattern = "acommit", rb"([^,]*),([^;]*);(?>([a-z]*))(?:(?:z|-)(?>(ab|a))(bc|d)(.*))?"
+    PLAIN = rb"([^,]*),([^;]*);(?:([a-z]*))(?:(?:z|-)(?:(ab|a))(bc|d)(.*))?"
+    kinds = {"commit": 3, "enter": 2, "alt": 6}
+    filler, after = b",;a", b"-"
+    RUNS = (1, 2, 5, 40, 300)
+
+    def k_commit(self, p):
+        out = []
+        for k in self.RUNS:
+            n = p - k - 1                                                       # prefix bytes in front of the semicolon
+            if n < 1:
+                continue
+            head = _pre(n) + b";"
+            out.append(("match_%d" % k, head + _cyc(b"abcdy", k, p) + b"-abd t", None, None))
+            out.append(("ends_%d" % k, head + _cyc(b"abcdy", k, p), b"-", None))
+            if k >= 5:          # (what the plain form gives back is "zabd" or "zad": no run of 1 or 2 bytes holds it)
+                out.append(("noback_%d" % k, head + _cyc(b"abcdy", k - 4, p) + b"zabd" + b"- t", None, None))
+        return out
+
+    def k_enter(self, p):
+        out = []
+        for k in (0, 1, 4, 39):                                                 # the steady run of field 2: [p - 1 - k, p - 1)
+            c = p - 2 - k
+            if c >= 0:
+                out.append(("from_%d" % (k + 1), _cyc(b"xyz_", c, p) + b"," + _cyc(b"uvw ", k, p) + b";" + b"abc-ad t", None, None))
+        if p >= 3:
+            out.append(("from0", b"," + _cyc(b"uvw ", p - 2, p) + b";" + b"abc-abd", None, None))
+        return out
+
+    def k_alt(self, p):
+        head = _pre(p - 5) + b";" + b"q-"                                       # "ab" at [p - 2, p)
+        return [("first", head + b"abd t", None, None), ("second_would", head + b"abc t", None, None),
+                ("second", _pre(p - 4) + b";" + b"q-" + b"ad t", None, None), ("ends", head + b"ab", b"d", None)]
+
+
+class AtomicQuasiFamily(Family):
+    """a full-match pattern with a kept atomic group AND doomed-spawn rows: the lazy field's thread spawns on a space and the spawn
+    is gone again unless an 'S' follows.  doomed: a space at p with no 'S' behind it -- skipped by the row, except where byte p + 1
+    lies in the next chunk or behind the value, where the step is taken in full"""
+    name, pattern = "aquasi", rb"(.*?) SA (?>([a-z]+)=)(\d+)"
+    kinds = {"doomed": 0}
+    filler, after = b" SA a=", b"7"
+    JUNK, HIT = b"xyz-_,", b" SA ab=12"
+
+    def k_doomed(self, p):
+        j = _cyc(self.JUNK, p, p)
+        return [("hit", j + self.HIT, None, None),                                                    # (not doomed: the 'S' follows)
+                ("doomed", j + b" x" + _cyc(self.JUNK, 2) + self.HIT, None, None),
+                ("doomed_S", j + b" Sx" + self.HIT, None, None),                                      # (the spawn lives one byte longer)
+                ("doomed_far", j + b" x" + _cyc(self.JUNK, 300, p) + self.HIT, None, None),
+                ("doomed_alone", j + b" x" + _cyc(self.JUNK, 3), None, None),
+                ("last_byte", j + b" ", b"S", None)]
+
+
+class LineageFamily(Family):
+    """([^;]*); and (a+) inside d atomic groups, then (z+): the step on the first 'a', byte p, enters all d groups.  d = 7: one
+    membership more than a thread carries (kNfaLineage); d = 6, the sibling: exactly 6 through the whole run of 'a's"""
+    kinds = {"overflow": 1}
+    filler, after = b";a", b"z"
+
+    def __init__(self, name, depth, over):
+        self.name, self.depth, self.over = name, depth, over
+        self.pattern = rb"([^;]*);" + b"(?>" * depth + b"(a+)" + b")" * depth + b"(z+)"
+
+    def _variants(self, head, p):
+        tag = "" if self.over else "at_cap_"
+        return [(tag + "match", head + b"az", None, None), (tag + "far", head + b"a" * (300 + p % 7) + b"z", None, None),
+                (tag + "ends", head, None, None), (tag + "one_more", head + b"azq", None, None)]
+
+    def k_overflow(self, p):
+        return self._variants(_cyc(b"xyz-", p - 1, p) + b";a", p)
+
+    def overflows(self, case):
+        return self.over
+
+
+class WorkFamily(LineageFamily):
+    """five atomic groups around a+ and n nested optional ones behind it: the step on 'h', byte p, carries 5 memberships and enters
+    and leaves n empty groups -- n = 6: the 11th work entry (kNfaLineageWork); n = 5, the sibling: exactly 10"""
+    kinds = {"overflow": 2}
+    filler, after = b";ah", b"z"
+
+    def __init__(self, name, n, over):
+        self.name, self.n, self.over = name, n, over
+        opt = b"(?>" * n + b")".join(b"%c?" % c for c in b"bcdefg"[:n]) + b")"
+        self.pattern = rb"([^;]*);(?>(?>(?>(?>(?>(a+" + opt + b"h))))))(z+)"
+
+    def k_overflow(self, p):
+        head = _cyc(b"xyz-", p - 2, p) + b";ah"
+        tag = "" if self.over else "at_cap_"
+        return [(tag + "match", head + b"z", None, None), (tag + "far", head + b"z" * (300 + p % 7), None, None),
+                (tag + "ends", head, None, None), (tag + "one_more", head + b"zq", None, None)]
+
+
+class ClosedFamily(LineageFamily):
+    """n alternatives, each ([^,K]*) inside d atomic groups, then a comma: the step on the comma, byte p, closes n * d segments --
+    22 x 3 = 66: the 65th closed segment of a step; 16 x 4, the sibling: exactly 64"""
+    kinds = {"overflow": 1}
+    filler, after = b";x,", b"t"
+
+    def __init__(self, name, n, depth, over):
+        self.name, self.n, self.depth, self.over = name, n, depth, over
+        alts = b"|".join(b"(?>" * depth + b"([^,\\x%02x]*)" % (k + 1) + b")" * depth for k in range(n))
+        self.pattern = rb"([^;]*);(?:" + alts + b"),(.*)"
+
+    def k_overflow(self, p):
+        """the semicolon at p - 1: byte p is the first behind it, and its step walks every alternative's way out, viable or not"""
+        return self._variants(_cyc(b"uvw ", p - 1, p) + b";", p)
+
+    def _variants(self, head, p):
+        tag = "" if self.over else "at_cap_"
+        return [(tag + "match", head + b",tail", None, None), (tag + "far", head + b"," + _cyc(b"tail ,;", 300 + p % 7), None, None),
+                (tag + "ends", head + b",", None, None), (tag + "one_more", head + b"xy,t", None, None)]
+
+
+_AKEPT = rb"([^;]*);(.*)a(?>(.{70}))"          # tail threads hold one membership each: every step a commit pass, the 65th survivor appended
+_AVECTOR = rb"(?>([^;]*));(.*)a(.{70})"        # no membership left behind the semicolon: the vector step's 65th thread, in the ATOMIC instantiation
+ATOMIC_EXITS = {"akept64": "kept64", "avector64": "vector64", "alineage6": "lineage6", "aclosed64": "closed64", "awork10": "work10"}
+# the families whose cap belongs to the pattern, not the value: family -> its control, a sibling family launched beside it
+SIBLING = {"alineage6": "alineage6c", "aclosed64": "aclosed64c", "awork10": "awork10c"}
+AT_CAP = {"akept64": ("kept", 64), "avector64": ("kept", 64), "alineage6c": ("lineage", 6), "aclosed64c": ("closed", 64), "awork10c": ("work", 10)}
+
+
+class BoundFamily(Family):
+    """a pattern and a handful of explicit values (the two bound tests of the atomic instantiation): no kinds, no offsets"""
+    kinds = {}
+
+    def __init__(self, name, pattern, filler, after):
+        self.name, self.pattern, self.filler, self.after = name, pattern, filler, after
+
+
+def explicit_corpus(fam, lines):
+    """the given lines as a Corpus of the 256-byte walk: line k at head k % 4"""
+    return Corpus(fam, "w256", [Case(fam.name, "bound", "line%d" % k, 0, k % 4, line, None, None) for k, line in enumerate(lines)])
+
+
+# nfa_match_kernel<ATOMIC> gives a value of L >= 2^17 - 2 bytes up before it looks at it (segment ids are (offset << 6 | thread) in 23 bits)
+LENGTH_BOUND = (1 << 17) - 2
+LENGTH_FAMILY = BoundFamily("alength", rb"([^;]*);(?>(\d+))(.*)", b";1", b"7")
+LENGTH_TAIL = b";12 x"
+
+
+def length_lines():
+    """values of 2^17 - 3, 2^17 - 2 and 2^17 bytes -- a [^;] run and a short tail -- among short ones"""
+    long = [_cyc(b"xyz-", L - len(LENGTH_TAIL), L) + LENGTH_TAIL for L in (LENGTH_BOUND - 1, LENGTH_BOUND, LENGTH_BOUND + 2)]
+    short = [b"ab;7 t", b"nothing here", b";42", b"x;12", b"uvw;x1", b"", b"q;007 rest;1", b"x" * 300 + b";5 y"]
+    return short[:3] + long[:1] + short[3:5] + long[1:2] + short[5:6] + long[2:] + short[6:]
+
+
+# a lineage key has 8 bits for the group instance: 255 instances compile, the last one (index 254) is the top of them
+INSTANCE_UNIT, INSTANCE_LAST = rb"(?>a+)a?,", rb"(?>(ab|a))(bc|;)"
+
+
+def instance_pattern(n, plain=False):
+    """n atomic group instances none of which the elision pass can drop, the last one an alternation that commits; plain: the same
+    pattern with ordinary groups"""
+    p = INSTANCE_UNIT * (n - 1) + INSTANCE_LAST
+    return p.replace(b"(?>", b"(?:") if plain else p
+
+
+INSTANCE_FAMILY = BoundFamily("ainstances", instance_pattern(255), b"a,", b"c")
+
+
+def instance_lines():
+    """(line, what): `commits` fails only because instance 254 gives nothing back"""
+    head = b"aa," * 200 + b"a," * 54
+    return [(head + b"ab;", "first"), (head + b"abc", "commits"), (head + b"abbc", "first_bc"), (head + b"a;", "second"),
+            (head + b"ab", "short"), (head[3:] + b"ab;", "a unit short"), (b"a,ab;", "tiny")]
+
+
 FAMILIES = {f.name: f for f in (LogFamily(), BigFamily(), LazyFamily(), QuasiFamily(), LookFamily(), AtomicFamily(), ThreadsFamily(), BackrefFamily(),
                                 NestedLogFamily(8), NestedLogFamily(16), NestedLogFamily(40),
                                 OverflowFamily("over64", 70, 64), OverflowFamily("over128", 140, 128), OverflowFamily("over64s", 70, 64, depth=11),
-                                RunCaptureFamily())}
+                                RunCaptureFamily(), AtomicLogFamily(), AtomicCommitFamily(), AtomicQuasiFamily(),
+                                OverflowFamily("akept64", 70, 64, pattern=_AKEPT), OverflowFamily("avector64", 70, 64, pattern=_AVECTOR),
+                                LineageFamily("alineage6", 7, True), LineageFamily("alineage6c", 6, False),
+                                ClosedFamily("aclosed64", 22, 3, True), ClosedFamily("aclosed64c", 16, 4, False),
+                                WorkFamily("awork10", 6, True), WorkFamily("awork10c", 5, False))}
 
 
 class Corpus:
@@ -590,6 +803,7 @@ UNSTAGED_ABOVE = 32768                     # gpu_runtime.hip launchTdfaL2Family:
 ROWS = [
     Row("nfa", "nfa_match_kernel", ("log", "quasi", "look", "threads"), "w256", _NFA, _NFA, _NOLAZY, False, False, 0),
     Row("nfa-atomic", "nfa_match_kernel<atomic>", ("atomic",), "w256", _NFA, _NFA, _NOLAZY, False, False, 0),
+    Row("nfa-atomic-edges", "nfa_match_kernel<atomic>", ("alog", "acommit", "aquasi"), "w256", _NFA, _NFA, _NOLAZY, False, False, 0),
     Row("nfa-wide-first", "nfa_wide_kernel:first", ("log", "quasi", "look", "threads", "over64", "over128", "log64"), "w256", _NFA, _NFA,
         dict(_NOLAZY, LC_NFA_WIDE_FIRST="1"), False, False, 0),
     Row("wave-small-staged", "tdfa_l2_kernel:wave", ("log", "quasi", "look", "atomic"), "w256", B.LC_ENGINE_AUTO, _TDFA, {}, True, False, 0),
@@ -608,6 +822,13 @@ ROWS = [
     Row("chain64", "nfa_wide_kernel", ("over64",), "w256", _NFA, _NFA, _NOLAZY, False, False, 0),
     Row("chain128", "nfa_decide_kernel", ("over128",), "w256", _NFA, _NFA, _NOLAZY, False, False, 0),
     Row("chain-slots", "nfa_decide_kernel", ("over64s",), "w256", _NFA, _NFA, _NOLAZY, False, False, 0),
+    # the overflow exits of the atomic instantiation, one row each: nfa_decide_kernel takes what it gives up (no wide kernel runs
+    # atomic programs); a family and its sibling control (SIBLING) share a row
+    Row("achain-kept64", "nfa_match_kernel<atomic>", ("akept64",), "w256", _NFA, _NFA, _NOLAZY, False, False, 0),
+    Row("achain-vector64", "nfa_match_kernel<atomic>", ("avector64",), "w256", _NFA, _NFA, _NOLAZY, False, False, 0),
+    Row("achain-lineage6", "nfa_match_kernel<atomic>", ("alineage6", "alineage6c"), "w256", _NFA, _NFA, _NOLAZY, False, False, 0),
+    Row("achain-closed64", "nfa_match_kernel<atomic>", ("aclosed64", "aclosed64c"), "w256", _NFA, _NFA, _NOLAZY, False, False, 0),
+    Row("achain-work10", "nfa_match_kernel<atomic>", ("awork10", "awork10c"), "w256", _NFA, _NFA, _NOLAZY, False, False, 0),
     # nfa_match_kernel<NS = 64 / 128 / 320> at their exact fit
     Row("nfa-ns64", "nfa_match_kernel", ("log64",), "w256", _NFA, _NFA, _NOLAZY, False, False, 0),
     Row("nfa-ns128", "nfa_match_kernel", ("log128",), "w256", _NFA, _NFA, _NOLAZY, False, False, 0),
@@ -628,13 +849,16 @@ CHAIN = {
     ("nfa-wide-first", "over64"): (("nfa_wide_kernel:first",), ("nfa_match_kernel", "nfa_wide_kernel", "nfa_decide_kernel")),
     ("nfa-wide-first", "over128"): (("nfa_wide_kernel:first", "nfa_decide_kernel"), ("nfa_match_kernel", "nfa_wide_kernel")),
 }
+ACHAIN = [(r.id, f) for r in ROWS if r.id.startswith("achain-") for f in r.families]
+CHAIN.update({k: (("nfa_match_kernel<atomic>", "nfa_decide_kernel"), ("nfa_wide_kernel", "nfa_wide_kernel:first", "nfa_match_kernel")) for k in ACHAIN})
 # (row, family) whose launches leave values to nfa_decide_kernel: lc_decide_stats must count exactly the overflow variants of the launch
-DECIDES = (("chain128", "over128"), ("chain-slots", "over64s"), ("nfa-wide-first", "over128"))
+DECIDES = (("chain128", "over128"), ("chain-slots", "over64s"), ("nfa-wide-first", "over128")) + tuple(ACHAIN)
 NS_ROWS = {"nfa-ns64": 64, "nfa-ns128": 128, "nfa-ns320": 320}                     # row -> the program's capture slots
 TRAIN_CORPUS = 200
 SEARCH_ROWS = [r for r in ROWS if any(FAMILIES[f].search for f in r.families)]
 # test_result_edges: one family per kernel
-EDGE_FAMILY = {"nfa": "log", "nfa-atomic": "atomic", "nfa-wide-first": "log", "wave-small-staged": "log", "wave-large-staged": "big",
+EDGE_FAMILY = {"nfa": "log", "nfa-atomic": "atomic", "nfa-atomic-edges": "alog", "achain-kept64": "akept64", "achain-vector64": "avector64",
+               "achain-lineage6": "alineage6", "achain-closed64": "aclosed64", "achain-work10": "awork10", "nfa-wide-first": "log", "wave-small-staged": "log", "wave-large-staged": "big",
                "wave-unstaged": "big", "l2-lane": "big", "decide": "log", "dfs": "log", "bt": "backref",
                "lazy-wave": "lazy", "lazy-lane": "lazy", "lazy-wave-decided": "log", "lazy-lane-decided": "threads",
                "chain64": "over64", "chain128": "over128", "chain-slots": "over64s", "nfa-ns64": "log64", "nfa-ns128": "log128",

@@ -2,7 +2,9 @@
 LC_NFA_GLOBAL_KB is read once per process; with LC_NFA_GLOBAL_KB=0 in the environment every non-empty batch takes
 nfa_match_kernel<..., GLOBAL=true> (the program stays in global memory, LDS holds the scratch alone).  main() runs rows `nfa` and
 `nfa-atomic` of the instantiation table in both input forms, the resumed searches, and the result edges on `log`, then rows `nfa-ns64`,
-`nfa-ns128` and `nfa-ns320` (the slot-by-slot capture transfer with 4 and 10 tag words, the accumulation registers) in both forms, compares with the
+`nfa-ns128` and `nfa-ns320` (the slot-by-slot capture transfer with 4 and 10 tag words, the accumulation registers) in both forms, family
+`alog` of row `nfa-atomic-edges` and row `achain-kept64` (the atomic instantiation's commit pass and its hand-off to nfa_decide_kernel,
+with lc_decide_stats exact) in both forms, compares with the
 oracle's rows behind sentinels, and prints one JSON object: per launch the number of values that differ and the first, the kernel
 names, and where the time went.  Not part of the product."""
 import json
@@ -18,7 +20,7 @@ def main():
     import numpy as np
     import torch
     from tests.helpers import chunk_edges as ce
-    from tests.helpers.chunk_edge_launch import cut, differing, launch, make_batches, rows
+    from tests.helpers.chunk_edge_launch import cut, decide_stats, differing, launch, make_batches, rows
     assert torch.cuda.is_available()
     torch.cuda.set_device(0)
     torch.zeros(1, device="cuda:0")
@@ -31,15 +33,19 @@ def main():
         out["launches"].append({"launch": where, "differ": n, "first": first, "ran": row.kernel in names})
         out["kernels"] = sorted(set(out["kernels"]) | set(names))
 
-    for row in (r for r in ce.ROWS if r.id in ("nfa", "nfa-atomic") + tuple(ce.NS_ROWS)):
+    for row in (r for r in ce.ROWS if r.id in ("nfa", "nfa-atomic", "nfa-atomic-edges", "achain-kept64") + tuple(ce.NS_ROWS)):
         assert row.env == {"LC_LAZY_TDFA": "0"} and not row.dfs and not row.min_n
-        for family in row.families:
+        for family in (("alog",) if row.id == "nfa-atomic-edges" else row.families):
             rx = ce.compile_row(row, family)
             batch = batches(family, row.walk)
             c, o = batch["corpus"], batch["oracle"]
             for form in ("len", "sep"):
                 caps, status, names = launch(torch, row, rx, batch, form)
                 note(row, "%s, %s, %s form" % (row.id, family, form), names, batch, caps, status, batch["caps"], batch["status"])
+                if (row.id, family) in ce.DECIDES:      # the values sent on: exactly the overflow variants, none given up, no wide kernel
+                    sent = (sum(c.family.overflows(k) for k in c.cases), 0)
+                    out["launches"][-1]["ran"] = (row.kernel in names and "nfa_decide_kernel" in names and decide_stats() == sent
+                                                  and not [x for x in names if x.startswith("nfa_wide")])
             if c.family.search:
                 frm = c.frm()
                 exp_caps, exp_status = rows(c.family, [o.search(k.line, int(f)) for k, f in zip(c.cases, frm)], batch["G"])

@@ -6,6 +6,8 @@ tests/native/bt_host_check.cpp) -- give the oracle's answer on every line.  A mi
 For run_stop the tables' own quiet / steady masks say that the run bytes are quiet and byte p is not: the kernels' run scans are on
 the path."""
 import collections
+import json
+import os
 
 import numpy as np
 import pytest
@@ -13,7 +15,8 @@ import pytest
 from loongcollector_amd import binding as B
 from oracle.oracle import OracleRegex
 from tests.helpers import chunk_edges as ce
-from tests.helpers.nfa_atomic_interp import AtomicNfaInterp
+from tests.helpers import nfa_atomic_interp as nai
+from tests.helpers.nfa_atomic_interp import AtomicNfaInterp, exit_of
 from tests.helpers.table_interp import NfaInterp, TdfaInterp, TdfaL2BlobInterp
 from tests.test_backref import host_vm  # noqa: F401  (fixture: builds tests/_build/libbt_host_check.so)
 
@@ -70,7 +73,7 @@ def test_every_offset_and_residue_is_there_for_every_kind(name, walk):
         assert all(v == set(range(M)) for v in by_kind.values()), (name, form, {k: sorted(v) for k, v in by_kind.items()})
     # (two corpora of the 16-byte walk hold more: log, whose size the screen test's figures fix, and lazy, the big family plus the misses)
     assert len(c.cases) <= (11000 if (name, walk) in (("log", "w16"), ("lazy", "w16")) else 9000) and max(len(s) for s in c.lines) <= 1100
-    if name.startswith("over"):
+    if name.startswith("over") or name in ("akept64", "avector64"):
         # the seeded shuffle mixes controls and overflowing values: some workgroup of four values holds both, and each alone
         groups = [{fam.overflows(k) for k in c.cases[i:i + 4]} for i in range(0, len(c.cases), 4)]
         assert {True, False} in groups and {True} in groups and {False} in groups, name
@@ -91,6 +94,49 @@ def test_cases_do_what_their_label_says(name, walk):
             assert k.line[k.p - back - 1:k.p - back] == b"!" and (back < 2 or e[5] < k.p), what        # (the next field ends inside the run)
         elif k.kind == "absent":
             assert e is not None and e[2:4] == [-1, -1] and e[1] == k.p - 1 and k.line[k.p:k.p + 1] != b"!" and b"|" in k.line, what
+        elif k.kind == "overflow" and isinstance(fam, ce.LineageFamily):
+            # (the exit families whose cap is the pattern's; that the step on byte p is the one: test_each_exit_is_taken_on_byte_p)
+            v = k.variant[7:] if k.variant.startswith("at_cap_") else k.variant
+            assert fam.overflows(k) == fam.over == (not k.variant.startswith("at_cap_")) == (name in ce.SIBLING), what
+            assert k.line[k.p - (2 if isinstance(fam, ce.WorkFamily) else 1):k.p].endswith(b";a" if isinstance(fam, ce.WorkFamily) else b";"), what
+            if isinstance(fam, ce.ClosedFamily):
+                assert e is not None and (k.line[k.p:k.p + 1] == b",") == (v != "one_more"), what     # (a comma follows at once, or a run first)
+            else:
+                assert (e is not None) == (v in ("match", "far")) and k.line[k.p:k.p + 1] == (b"h" if isinstance(fam, ce.WorkFamily) else b"a"), what
+            assert v != "far" or (len(k.line) - k.p > 300 and (isinstance(fam, ce.ClosedFamily) or e[-1] - e[-2] >= 300 or e[3] - e[2] >= 300)), what
+            assert v != "ends" or len(k.line) == k.p + 1, what
+        elif k.kind == "commit":
+            n = int(k.variant.rsplit("_", 1)[1])
+            assert k.line[k.p - n - 1:k.p - n] == b";" and all(97 <= b <= 122 for b in k.line[k.p - n:k.p]), what   # the run [p - n, p)
+            if k.variant.startswith("match"):
+                assert e is not None and e[4:6] == [k.p - n, k.p] and k.line[k.p:k.p + 1] == b"-", what
+            elif k.variant.startswith("ends"):
+                assert len(k.line) == k.p and e is not None and e[4:] == [k.p - n, k.p] + [-1] * 6 and run(k.line + k.after) is None, what
+            else:                                                                                     # noback: the plain form gives "zabd" back
+                pl = OracleRegex(fam.PLAIN).fullmatch(k.line)
+                assert e is None and k.line[k.p - 4:k.p + 1] == b"zabd-" and pl is not None and pl[3] == (k.p - n, k.p - 4), what
+        elif k.kind == "enter":
+            assert e is not None and e[4] == k.p and k.line[k.p - 1:k.p] == b";", what                 # the group begins at p
+            back = k.variant.split("_")[1] if "_" in k.variant else None
+            assert back is None or k.line[k.p - 1 - int(back):k.p - int(back)] == b",", what           # field 2 is the steady run in front
+        elif k.kind == "alt":
+            pl = OracleRegex(fam.PLAIN).fullmatch(k.line)
+            if k.variant == "first":
+                assert e is not None and e[6:10] == [k.p - 2, k.p, k.p, k.p + 1], what
+            elif k.variant == "second":
+                assert e is not None and e[6:10] == [k.p - 1, k.p, k.p, k.p + 1], what
+            elif k.variant == "second_would":
+                assert e is None and pl is not None and pl[4] == (k.p - 2, k.p - 1) and pl[5] == (k.p - 1, k.p + 1), what
+            else:
+                assert k.variant == "ends" and e is None and len(k.line) == k.p and run(k.line + k.after) is not None, what
+        elif k.kind == "doomed":
+            assert b" " not in k.line[:k.p] and k.line[k.p:k.p + 1] == b" ", what                       # the first space is at p
+            if k.variant == "hit":
+                assert e is not None and e[:2] == [0, k.p], what
+            elif k.variant in ("doomed", "doomed_S", "doomed_far"):
+                assert k.line[k.p + 1:k.p + 3] != b"SA" and e is not None and e[1] >= k.p + {"doomed": 4, "doomed_S": 3, "doomed_far": 300}[k.variant], what
+            else:
+                assert e is None and (k.variant != "last_byte" or len(k.line) == k.p + 1), what
         elif k.kind == "overflow":
             m = fam.cap - (1 if k.variant.startswith("at_cap") else 0)
             assert k.line[k.p - m + 1:k.p + 1] == b"a" * m and k.line[k.p - m - 3:k.p - m + 1] == b";bbb" and fam.overflows(k) == (m == fam.cap), what
@@ -172,7 +218,7 @@ def test_the_instantiation_table_runs_what_the_families_declare():
     """every family is run by some row, every row runs every kind of its families (>= 90 % is the cap the table must meet; a case
     set a row leaves out would be an entry of the table), search rows have search families, the edge families belong to their rows"""
     assert {f for r in ce.ROWS for f in r.families} == set(ce.FAMILIES)
-    assert len({r.id for r in ce.ROWS}) == len(ce.ROWS) == 23
+    assert len({r.id for r in ce.ROWS}) == len(ce.ROWS) == 29
     assert {r.kernel for r in ce.ROWS} == {"nfa_match_kernel", "nfa_match_kernel<atomic>", "nfa_wide_kernel:first", "tdfa_l2_kernel:wave",
                                            "tdfa_l2_kernel", "nfa_decide_kernel", "nfa_dfs_kernel", "bt_match_kernel",
                                            "tdfa_l2_kernel:wave:lazy", "tdfa_l2_kernel:lazy", "nfa_wide_kernel", "tdfa_stream_kernel*"}
@@ -211,8 +257,22 @@ def test_the_instantiation_table_runs_what_the_families_declare():
         ("runcap-lds", "tdfa_stream_kernel*", ("runcap",), "w16r", B.LC_ENGINE_AUTO, B.LC_ENGINE_TDFA, False)]
     # nfa_wide_kernel<64> as the first chance: the 64-slot family, not the wider ones (NS > 64 never goes wide first)
     assert by_id["nfa-wide-first"].families == ("log", "quasi", "look", "threads", "over64", "over128", "log64")
+    # the atomic instantiation: one row of ordinary families, one row per overflow exit (a family and its sibling control share it)
+    atomic = {"nfa-atomic-edges": ("alog", "acommit", "aquasi"), "achain-kept64": ("akept64",), "achain-vector64": ("avector64",),
+              "achain-lineage6": ("alineage6", "alineage6c"), "achain-closed64": ("aclosed64", "aclosed64c"), "achain-work10": ("awork10", "awork10c")}
+    for rid, families in atomic.items():
+        r = by_id[rid]
+        assert (r.kernel, r.families, r.walk, ce.EDGE_FAMILY[rid]) == ("nfa_match_kernel<atomic>", families, "w256", families[0]), rid
+        assert (r.compile_engine, r.launch_engine, r.env, r.wave, r.dfs, r.min_n, r.train) == (B.LC_ENGINE_NFA, B.LC_ENGINE_NFA, {"LC_LAZY_TDFA": "0"},
+                                                                                           False, False, 0, None), rid
+    assert [r.id for r in ce.ROWS if r.kernel == "nfa_match_kernel<atomic>"] == ["nfa-atomic"] + list(atomic)
+    achain = {(rid, f) for rid, fs in atomic.items() if rid.startswith("achain-") for f in fs}
+    assert set(ce.ACHAIN) == achain and all(ce.CHAIN[k] == (("nfa_match_kernel<atomic>", "nfa_decide_kernel"),
+                                                            ("nfa_wide_kernel", "nfa_wide_kernel:first", "nfa_match_kernel")) for k in achain)
+    assert {f for _, f in achain} == set(ce.ATOMIC_EXITS) | set(ce.SIBLING.values()) and set(ce.SIBLING) < set(ce.ATOMIC_EXITS)
+    assert set(ce.AT_CAP) == (set(ce.ATOMIC_EXITS) - set(ce.SIBLING)) | set(ce.SIBLING.values())
     assert set(ce.CHAIN) == {("chain64", "over64"), ("chain128", "over128"), ("chain-slots", "over64s"), ("nfa-wide-first", "over64"),
-                             ("nfa-wide-first", "over128")} and set(ce.DECIDES) == {k for k, (has, _) in ce.CHAIN.items() if "nfa_decide_kernel" in has}
+                             ("nfa-wide-first", "over128")} | achain and set(ce.DECIDES) == {k for k, (has, _) in ce.CHAIN.items() if "nfa_decide_kernel" in has}
     for (rid, family), (has, has_not) in ce.CHAIN.items():
         assert family in by_id[rid].families and by_id[rid].kernel in has and not set(has) & set(has_not)
         assert "nfa_wide_kernel:first" in (has if rid == "nfa-wide-first" else has_not)
@@ -336,10 +396,12 @@ def _nfa_trace(it, s, start=0, end=False):
 
 # (the lazy family's program: test_the_lazy_family_misses_where_it_says_and_nowhere_else walks it on the values the kernels hand it)
 OVER = ("over64", "over128", "over64s")
+# (... and the atomic instantiation's: test_atomic_walks_give_the_oracles_rows_and_the_gates_are_sound and the tests behind it)
+ATOMIC_NEW = ("alog", "acommit", "aquasi") + tuple(ce.ATOMIC_EXITS) + tuple(ce.SIBLING.values())
 
 
 # (... and the overflow families': test_the_overflow_families_exceed_each_cap_by_the_step_on_byte_p, with the caps the kernels have)
-@pytest.mark.parametrize("name", sorted({f for r in ce.ROWS if r.compile_engine == B.LC_ENGINE_NFA for f in r.families} - {"lazy"} - set(OVER)))
+@pytest.mark.parametrize("name", sorted({f for r in ce.ROWS if r.compile_engine == B.LC_ENGINE_NFA for f in r.families} - {"lazy"} - set(OVER) - set(ATOMIC_NEW)))
 def test_nfa_program_gives_the_oracles_rows(name):
     walk = "w16r" if name == "runcap" else "w256"
     c, o, exp = _oracle(name, walk)
@@ -592,3 +654,268 @@ def test_screen_events_fall_on_both_sides_of_the_first_two_piece_borders():
     assert absorbed["threads"][0] >= every and set().union(*(a for a, _ in absorbed.values())) >= every
     for name in ("log", "look", "atomic", "threads"):
         assert all(absorbed[name][1]["absorb", b] == {-1, 0, 1} for b in ce.SCREEN_BORDERS), name
+
+
+# ---- nfa_match_kernel<ATOMIC>: the faithful host walk (tests/helpers/nfa_atomic_interp.py walk), its gates, and the events of the
+# atomic families on byte p
+
+ATOMIC_FAMILIES = ("atomic",) + ATOMIC_NEW
+
+
+def _atomic(name):
+    """(corpus, expected rows, interpreter, walks) -- computed once.  walks[case index] = (result, trace, gate faults) of the
+    faithful walk at the case's own head.  The head reaches the walk through the doomed-spawn look-ahead alone (walk(): `nxt`), so
+    a program without such rows is walked once per line."""
+    if ("atomic", name) not in _cache:
+        c, o, exp = _oracle(name)
+        rx = B.GpuRegex(c.family.pattern, syntax_flags=c.family.flags, engine=B.LC_ENGINE_NFA)
+        it = AtomicNfaInterp(rx)
+        assert rx.atomic_groups()[0] > 0 and it.atomic
+        done, walks = {}, []
+        for k in c.cases:
+            key = (k.line, k.head if it.quasi_rows is not None else 0)
+            if key not in done:
+                faults = []
+                got, trace = it.walk(k.line, key[1], faults=faults)
+                done[key] = (got, trace, faults)
+            walks.append(done[key])
+        _cache["atomic", name] = (c, exp, it, walks, rx)
+    return _cache["atomic", name]
+
+
+def _at(trace, i):
+    """the trace's entry for byte i (None: the walk did not look at it)"""
+    return next((t for t in trace if t.i == i), None)
+
+
+def test_the_helper_quotes_the_kernels_constants():
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "loongcollector_amd", "csrc", "nfa_kernel.hpp")).read()
+    assert "constexpr int kNfaLineage = %d;" % nai.MAX_LINEAGE in src and "constexpr int kNfaLineageWork = %d;" % nai.LINEAGE_WORK in src
+    assert "if (nClosed == %d) return" % nai.MAX_CLOSED in src and "if (nKept == %d) {" % nai.MAX_THREADS in src
+    assert "totalWins + nWins > %d" % nai.MAX_THREADS in src and "L >= (1u << 17) - 2" in src and nai.MAX_LENGTH == ce.LENGTH_BOUND == (1 << 17) - 2
+    packer = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "loongcollector_amd", "csrc", "regex_handle.cpp")).read()
+    assert "if (nfa.atomicCount > %d) throw" % nai.MAX_INSTANCES in packer and "return (e >> 23) & 0xFFu;" in src     # 8 bits of a key
+    assert nai.EXITS == ("long", "vector64", "kept64", "closed64", "work10", "lineage6") and set(ce.ATOMIC_EXITS.values()) == set(nai.EXITS) - {"long"}
+
+
+def test_atomic_walks_give_the_golden_rows_and_the_gates_are_sound(golden_dir):
+    """tests/golden/regex_atomic_golden.json: faithful walk == uncapped plain walk == the golden row, for head 0..3; and wherever the
+    faithful walk skipped a byte or took the vector step, the plain commit pass on the same thread list leaves the same threads
+    (a skipped thread keeps the memberships it holds; the vector step is only taken where nobody holds one)."""
+    with open(os.path.join(golden_dir, "regex_atomic_golden.json")) as f:
+        d = json.load(f)
+    walked = skipped = vector = with_rows = 0
+    for kind, flags in (("full", 0), ("search", B.LC_SYNTAX_SEARCH)):
+        for c in d[kind]:
+            try:
+                rx = B.GpuRegex(c["p"].encode("latin-1"), syntax_flags=flags, engine=B.LC_ENGINE_NFA)
+            except B.RegexUnsupportedError:
+                continue
+            if not rx.has_nfa_program() or not rx.atomic_groups()[0]:
+                continue
+            it = AtomicNfaInterp(rx)
+            with_rows += it.quasi_rows is not None
+            for subj, flat in c["subs"]:
+                s = subj.encode("latin-1")
+                exp = flat if kind == "search" or flat is None else flat[2:]
+                assert it.fullmatch(s, capped=False) == exp, (c["p"], subj)
+                for head in range(4):
+                    faults = []
+                    got, trace = it.walk(s, head, faults=faults)
+                    assert got == exp and not faults and exit_of(trace) is None, (c["p"], subj, head, got, exp, faults[:2])
+                    walked += 1
+                    skipped += sum(t.what == "skip" for t in trace)
+                    vector += sum(t.what == "vector" for t in trace)
+    # (the set is not degenerate for this check: thousands of walks, skips and vector steps among them, programs with doomed-spawn rows)
+    assert walked > 6000 and skipped > 300 and vector > 2000 and with_rows >= 10, (walked, skipped, vector, with_rows)
+
+
+@pytest.mark.parametrize("name", ATOMIC_FAMILIES)
+def test_atomic_families_walks_give_the_oracles_rows(name):
+    """every case of the atomic families: the faithful walk at the case's head gives the oracle's row or leaves through an exit, the
+    uncapped plain walk gives the oracle's row on EVERY line (the overflowing ones too), no gate is unsound; the resumed searches of
+    `atomic` included"""
+    c, exp, it, walks, rx = _atomic(name)
+    fam = c.family
+    plain = {}
+    for i, (k, e, (got, trace, faults)) in enumerate(zip(c.cases, exp, walks)):
+        assert not faults, (c.label(i), faults[:2])
+        assert got == ("overflow" if exit_of(trace) else e), (c.label(i), got, e)
+        if k.line not in plain:
+            plain[k.line] = it.fullmatch(k.line, capped=False)
+        assert plain[k.line] == e, c.label(i)
+        if k.kind == "resume":
+            want = _flat(fam, OracleRegex(fam.pattern).search(k.line, k.frm))
+            faults = []
+            assert it.walk(k.line, k.head, start=k.frm, faults=faults)[0] == want and not faults, c.label(i)
+            assert it.fullmatch(k.line, start=k.frm, capped=False) == want, c.label(i)
+    over = [bool(exit_of(w[1])) for w in walks]
+    assert any(over) == (name in ce.ATOMIC_EXITS), name
+    assert (it.quasi_rows is not None) == (name == "aquasi")
+
+
+def test_alog_keeps_three_groups_and_commits_on_every_byte_of_its_fields():
+    c, exp, it, walks, rx = _atomic("alog")
+    log = _oracle("log")
+    assert [k.line for k in c.cases] == [k.line for k in log[0].cases] and exp == log[2]               # the log family's lines and rows
+    assert rx.atomic_groups() == (3, 0) and (it.npos, it.nslots) == (7, 8)
+    borders = collections.Counter()
+    for k, e, (got, trace, _) in zip(c.cases, exp, walks):
+        last = k.line.find(b" ", k.line.find(b";") + 1) if b";" in k.line and b"," in k.line[:k.line.find(b";")] else -1
+        for t in trace:
+            if t.what in ("end", "end_plain"):
+                continue
+            if e is not None:                                                                        # a matching line: fields 1 to 3 in front of `last`
+                assert (t.what == "commit") == (t.i <= last), (k.variant, k.p, t)
+                assert t.i >= last or t.lineage >= 1 or k.line[t.i:t.i + 1] in (b",", b";"), (k.variant, k.p, t)
+            for b in (256, 512):
+                if t.what == "commit" and t.lineage >= 1 and k.head + t.i + 1 == b and _at(trace, t.i + 1) is not None and _at(trace, t.i + 1).what == "commit":
+                    borders[b, k.head] += 1                                                          # a membership carried over the reload
+    assert all(borders[b, h] >= 20 for b in (256, 512) for h in range(4)), borders
+
+
+def test_acommit_and_aquasi_put_their_events_on_byte_p():
+    c, exp, it, walks, rx = _atomic("acommit")
+    assert rx.atomic_groups() == (2, 0)
+    for k, (got, trace, _) in zip(c.cases, walks):
+        what = (k.kind, k.variant, k.p, k.head)
+        t = _at(trace, k.p)
+        if k.kind == "commit" and k.variant.startswith("ends"):
+            assert t.what == "end" and t.closed == 1 and _at(trace, k.p - 1).lineage == 1, what        # the commit at the end of input
+        elif k.kind in ("commit", "alt") and k.variant != "ends":
+            assert t.what == "commit" and t.closed == 1 and t.lineage == 0 and _at(trace, k.p - 1).lineage == 1, what   # left on byte p
+            if k.kind == "commit":
+                n = int(k.variant.rsplit("_", 1)[1])
+                assert all(_at(trace, i).what == "commit" and _at(trace, i).lineage == 1 for i in range(k.p - n, k.p)), what
+        elif k.kind == "alt":
+            assert t.what == "end" and t.closed == 1, what
+        else:                                                                                         # enter: nothing in front of p is a commit pass
+            assert t.what == "commit" and t.lineage == 1 and [x.what for x in trace if x.i < k.p and x.what == "commit"] == [], what
+            back = int(k.variant.split("_")[1]) if "_" in k.variant else k.p - 1
+            # (field 2 begins at p - back: its first byte enters it, the others are steady, the semicolon at p - 1 is a vector step)
+            assert all(_at(trace, i).what == "skip" for i in range(k.p - back + 1, k.p - 1)) and _at(trace, k.p - 1).what == "vector", what
+    c, exp, it, walks, rx = _atomic("aquasi")
+    assert rx.atomic_groups() == (1, 0) and it.quasi_rows
+    blind = collections.Counter()
+    for k, (got, trace, _) in zip(c.cases, walks):
+        what = (k.variant, k.p, k.head)
+        t = _at(trace, k.p)
+        unknown = (k.head + k.p + 1) % 256 == 0 or k.p + 1 == len(k.line)                              # byte p + 1: next chunk, or none
+        if k.variant in ("doomed", "doomed_far", "doomed_alone") and k.p >= 1:
+            assert (t.what, t.quasi) == (("vector", False) if unknown else ("skip", True)), what       # skipped exactly where the row can be read
+            blind[k.variant, (k.head + k.p) % 256 == 255] += 1
+            assert all(x.what == "skip" and not x.quasi for x in trace if 1 <= x.i < k.p), what
+        else:
+            # a spawn that lives, or the last byte; or p == 0: the first byte is stepped from the start pseudo-position, which has
+            # neither a steady bit nor a doomed-spawn row -- the lazy field's own position is only reached behind it
+            assert t.what == "vector" and (k.p >= 1 or (it.stable[it.npos] == 0 and not int(it.quasi_idx[it.npos]))), what
+        first = (k.head + k.p) % 256 == 0
+        blind["first", first] += 1
+    assert all(blind[v, True] == 8 and blind[v, False] > 100 for v in ("doomed", "doomed_far", "doomed_alone")) and blind["first", True] >= 40, blind
+
+
+@pytest.mark.parametrize("name", sorted(ce.ATOMIC_EXITS) + sorted(ce.SIBLING.values()))
+def test_each_exit_is_taken_on_byte_p(name):
+    """the overflow variants leave through the family's exit ON byte p (a walk stops at its first exit: none is earlier), for every
+    head; the controls leave through none and sit exactly at the cap by the step on byte p: 64 survivors appended, 64 winners of
+    the vector step, 6 memberships, 64 closed segments, 10 work entries"""
+    c, exp, it, walks, rx = _atomic(name)
+    fam = c.family
+    seen = collections.Counter()
+    for k, (got, trace, _) in zip(c.cases, walks):
+        what = (name, k.variant, k.p, k.head)
+        t = _at(trace, k.p)
+        if fam.overflows(k):
+            assert got == "overflow" and exit_of(trace) == (ce.ATOMIC_EXITS[name], k.p) and t is trace[-1], (what, exit_of(trace))
+            assert t.what == ("vector" if name == "avector64" else "commit"), what
+        else:
+            control = name if name in ce.AT_CAP else None
+            assert exit_of(trace) is None and control, what
+            field, cap = ce.AT_CAP[name]
+            assert getattr(t, field) == cap and t.what == ("vector" if name == "avector64" else "commit"), (what, t)
+            assert max(getattr(x, field) for x in trace) == cap, what                                 # ... and nowhere beyond it
+        seen[fam.overflows(k), k.head] += 1
+    assert all(n >= 2 * 30 for n in seen.values()) and {h for _, h in seen} == set(range(4))      # (two variants or more at 30 offsets or more, per head)
+    assert {o for o, _ in seen} == ({True} if name in ce.SIBLING else {False} if name in ce.SIBLING.values() else {True, False})
+    shape = {"akept64": (1, 74), "avector64": (1, 74), "alineage6": (7, 4), "alineage6c": (6, 4), "aclosed64": (66, 26), "aclosed64c": (64, 20),
+             "awork10": (11, 11), "awork10c": (10, 10)}[name]
+    assert (it.ninstances, it.npos) == shape and rx.atomic_groups() == (shape[0], 0)
+
+
+def _mutable(it):
+    """the interpreter's own copies of the steady tables, as lists the test may change"""
+    it.quasi_idx = list(it.quasi_idx) if it.quasi_idx is not None else [0] * (it.npos + 1)
+    it.quasi_rows = [list(r) for r in it.quasi_rows or []]
+    return it
+
+
+def test_the_faithful_walk_reads_the_doomed_spawn_rows_and_the_touchy_bits():
+    """Mutations of the interpreter's own copy of the tables.  (?>a+?.): the row round 6's bug had -- the loop position, class of
+    'a', next class of '1' -- makes the faithful walk match "aa1", which is wrong; unmutated it does not.  A cleared touchy bit on
+    (?>(ab|a))(bc|d): the vector step enters the group without a membership, the first branch's exit closes nothing, the second
+    branch lives and "abc" matches, which is wrong."""
+    rx = B.GpuRegex(b"(?>a+?.)", engine=B.LC_ENGINE_NFA)
+    it = _mutable(AtomicNfaInterp(rx))
+    assert not it.quasi_rows and OracleRegex(b"(?>a+?.)").fullmatch(b"aa1") is None
+    assert it.walk(b"aa1")[0] is None and not it.gate_faults(b"aa1")
+    loop = [p for p in range(it.npos) if any(t == p for t, _, _ in it.follow[p])]
+    assert len(loop) == 1
+    ca, c1 = int(it.cmap[ord("a")]), int(it.cmap[ord("1")])
+    it.quasi_rows.append([(1 << c1) if c == ca else 0 for c in range(it.ncls)])
+    it.quasi_idx[loop[0]] = len(it.quasi_rows)
+    got, trace = it.walk(b"aa1")
+    assert got is not None and [t.what for t in trace if t.quasi] == ["skip"]                          # the row was read, and believed
+    assert it.gate_faults(b"aa1")                                                                     # ... and the gate check sees it
+
+    pat = b"(?>(ab|a))(bc|d)"
+    it = AtomicNfaInterp(B.GpuRegex(pat, engine=B.LC_ENGINE_NFA))
+    assert OracleRegex(pat).fullmatch(b"abc") is None and it.walk(b"abc")[0] is None
+    tr = it.walk(b"abd")[1]
+    assert [t.what for t in tr] == ["commit", "commit", "commit", "end_plain"]
+    # the bit that sends the FIRST byte to the commit pass (nobody holds a membership yet: the gate decides alone), cleared
+    ca = int(it.cmap[ord("a")])
+    assert (it.touchy[it.npos] >> ca) & 1
+    it.touchy[it.npos] &= ~(1 << ca)
+    got, tr = it.walk(b"abc")
+    assert got is not None and tr[0].what == "vector" and it.gate_faults(b"abc")                     # the bit was read, and believed
+
+
+def test_255_atomic_instances_compile_and_the_last_one_commits():
+    with pytest.raises(B.RegexUnsupportedError, match="more than 255 atomic group instances"):
+        B.GpuRegex(ce.instance_pattern(256), engine=B.LC_ENGINE_NFA)
+    rx = B.GpuRegex(ce.instance_pattern(255), engine=B.LC_ENGINE_NFA)
+    it = AtomicNfaInterp(rx)
+    assert rx.atomic_groups() == (255, 0) and it.ninstances == nai.MAX_INSTANCES == 255
+    codes = {code for p in range(it.npos + 1) for path in it.events[p] for code, _ in path if code < nai.ASSERT_EVENT}
+    assert max(codes) == 255 and min(codes) == -255                                                   # instance 254: the top of the key's 8 bits
+    o, plain = OracleRegex(ce.instance_pattern(255)), OracleRegex(ce.instance_pattern(255, plain=True))
+    for line, what in ce.instance_lines():
+        e = o.fullmatch(line)
+        e = None if e is None else [v for be in e[1:] for v in be]
+        assert it.fullmatch(line, capped=False) == e, what
+        for head in range(4):
+            got, trace = it.walk(line, head)
+            assert got == e and exit_of(trace) is None and not it.gate_faults(line, head), (what, head)
+        if what == "commits":                                                                         # only the commit of instance 254 refuses it
+            assert e is None and plain.fullmatch(line) is not None
+            last = [t for t in trace if t.what == "commit" and t.closed][-2:]
+            assert [t.i for t in last] == [len(line) - 2, len(line) - 1]
+        if what == "first":
+            assert e is not None and all(t.what == "commit" for t in trace[:-1]) and len(trace) == len(line) + 1
+
+
+def test_the_length_bound_is_two_short_of_two_to_the_17th():
+    rx = B.GpuRegex(ce.LENGTH_FAMILY.pattern, engine=B.LC_ENGINE_NFA)
+    it = AtomicNfaInterp(rx)
+    o = OracleRegex(ce.LENGTH_FAMILY.pattern)
+    assert rx.atomic_groups() == (1, 0) and it.npos <= 5
+    lines = ce.length_lines()
+    assert len({len(x) % 4 for x in lines}) >= 3
+    for k, line in enumerate(lines):
+        got, trace = it.walk(line, k % 4)
+        e = o.fullmatch(line)
+        if len(line) >= ce.LENGTH_BOUND:
+            assert got == "overflow" and exit_of(trace) == ("long", 0) and e is not None
+        else:
+            assert exit_of(trace) is None and got == (None if e is None else [v for be in e[1:] for v in be]), k
+    assert sum(len(x) >= ce.LENGTH_BOUND for x in lines) == 2 and max(len(x) for x in lines if len(x) < ce.LENGTH_BOUND) == ce.LENGTH_BOUND - 1

@@ -191,8 +191,11 @@ def test_relaxed_screens_never_reject_a_value_the_pattern_matches(monkeypatch, b
 
 
 def test_nfa_tables_with_shortcuts_on_fresh_random_patterns():
-    """tools/fuzz_nfa.py, two seeds of it: fresh random patterns (plain and atomic / possessive), full match and search; the NFA walk
+    """tools/fuzz_nfa.py, three seeds of it: fresh random patterns (plain and atomic / possessive), full match and search; the NFA walk
     WITH the kernel's shortcuts (steady masks, doomed-spawn rows, suffix exit) and after the atomic-elision pass, against the oracle.
+    Atomic programs go through the faithful walk of tests/helpers/nfa_atomic_interp.py -- the atomic kernel's byte loop, touchy gate
+    and overflow exits -- with its gates checked against the full commit pass; some of them carry doomed-spawn rows, and a value that
+    walk gives up is decided by the uncapped commit pass, not dropped.
     (The tool was run over 260 seeds when the shortcuts went in: 58 688 pattern x modes, 626 846 checks.)"""
     import subprocess
     import sys
@@ -202,3 +205,8 @@ def test_nfa_tables_with_shortcuts_on_fresh_random_patterns():
     assert out.returncode == 0 and out.stdout.startswith("ok:"), (out.stdout[-400:], out.stderr[-1500:])
     words = out.stdout.split()
     assert int(words[1]) > 400 and int(out.stdout.split("(")[1].split()[0]) > 100      # patterns x modes; of them with doomed-spawn rows
+    print(out.stdout.strip())
+    before = lambda text: int(out.stdout.split(text)[0].split()[-1])
+    # atomic programs as the generator writes them, and behind a lead field; of them with doomed-spawn rows
+    assert before(" atomic programs bare") >= 10 and before(" behind a lead field") >= 10 and before(" atomic programs with quasi rows") > 0
+    assert " overflows decided by the uncapped walk" in out.stdout

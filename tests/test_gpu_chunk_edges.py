@@ -16,6 +16,12 @@ lc_decide_stats counts exactly the values that had to be sent on.  Rows nfa-ns64
 capture slots, rows runcap-* put the end of a run capture (run_capture_kernel) on a chosen byte for all 16 residues.  The handles of
 lazy-wave and lazy-lane are launched, trained again on their misses and launched once more: a rebuilt automaton behind one handle.
 
+Row nfa-atomic-edges puts the atomic instantiation's ordered commit pass (nfaAtomicStep) on chosen bytes (families alog, acommit, aquasi),
+rows achain-* each of its overflow exits -- the 65th survivor, the vector step's 65th thread, the 7th membership, the 65th closed
+segment, the 11th work entry -- with controls exactly at the cap, as `at_cap` variants or as a sibling family in the same row:
+nfa_decide_kernel takes what is given up, no wide kernel runs, lc_decide_stats counts exactly the values sent on.  Two tests of the
+bounds: values of 2^17 - 3, 2^17 - 2 and 2^17 bytes, and a pattern with 255 atomic instances whose last one commits.
+
 Every launch keeps four sentinel rows in front of and behind the capture table and the status bytes (tests/helpers/guarded_launch.py)
 and runs in both forms: (off, len), where filler gives each line its residue, and off[n + 1] with a separator byte."""
 import json
@@ -29,7 +35,7 @@ import pytest
 
 from loongcollector_amd import binding as B
 from tests.helpers import chunk_edges as ce
-from tests.helpers.chunk_edge_launch import cut as _cut, decide_stats, differing, launch as _launch, make_batches, rows as _rows
+from tests.helpers.chunk_edge_launch import batch_of, cut as _cut, decide_stats, differing, launch as _launch, make_batches, rows as _rows
 from tests.helpers.guarded_launch import STATUS_SENTINEL
 
 pytestmark = pytest.mark.gpu
@@ -78,7 +84,12 @@ def _sent_on(row, family, batch, names, where, listed=None):
         return
     c, fam = batch["corpus"], batch["corpus"].family
     over = [fam.overflows(c.cases[int(i) % batch["n0"]]) for i in (range(batch["n"]) if listed is None else listed)]
-    assert 0 < sum(over) < len(over), where                                    # (overflowing values and controls in every launch)
+    if family in ce.SIBLING:                                                   # (the cap is the pattern's: the controls are the sibling family's)
+        assert sum(over) == len(over), where
+    elif family in ce.SIBLING.values():
+        assert sum(over) == 0, where
+    else:
+        assert 0 < sum(over) < len(over), where                                # (overflowing values and controls in every launch)
     if (row.id, family) in ce.DECIDES:
         assert decide_stats() == (sum(over), 0), (where, decide_stats(), sum(over))
     else:
@@ -217,13 +228,56 @@ def test_a_lazy_automaton_rebuilt_between_two_launches(torch_dev, monkeypatch, b
             assert r["in_use"] == 1 and len(rx.table(B.LC_TABLE_LAZY_TDFA_BLOB, np.uint32)) > words, r
 
 
+def test_the_atomic_instantiation_gives_up_values_of_131070_bytes_and_more(torch_dev, monkeypatch):
+    """nfa_match_kernel<ATOMIC> hands a value of L >= 2^17 - 2 bytes to nfa_decide_kernel before it looks at it (a segment id is
+    (offset << 6 | thread) in 23 bits).  Values of 2^17 - 3, 2^17 - 2 and 2^17 bytes -- a [^;] run and the tail ";12 x" -- among
+    short ones, in both forms: every row is the oracle's, and lc_decide_stats counts exactly the two at or above the bound."""
+    row = next(r for r in ce.ROWS if r.id == "nfa-atomic-edges")
+    ce.set_env(monkeypatch, row)
+    lines = ce.length_lines()
+    assert sorted(len(x) for x in lines)[-3:] == [(1 << 17) - 3, (1 << 17) - 2, 1 << 17] == [ce.LENGTH_BOUND - 1, ce.LENGTH_BOUND, ce.LENGTH_BOUND + 2]
+    assert all(x.endswith(ce.LENGTH_TAIL) and b";" not in x[:-5] for x in lines if len(x) > 1000)
+    batch = batch_of(torch_dev, ce.explicit_corpus(ce.LENGTH_FAMILY, lines))
+    assert batch["status"].sum() >= 7 and (batch["status"] == 0).sum() >= 3    # (the long ones match; some short ones do not)
+    rx = B.GpuRegex(ce.LENGTH_FAMILY.pattern, engine=row.compile_engine)
+    assert rx.atomic_groups()[0] == 1
+    for form in ("len", "sep"):
+        where = "length bound, %s form" % form
+        caps, status, names = _launch(torch_dev, row, rx, batch, form)
+        assert "nfa_match_kernel<atomic>" in names and "nfa_decide_kernel" in names and not [n for n in names if n.startswith("nfa_wide")], names
+        _compare(batch, caps, status, batch["caps"], batch["status"], where)
+        assert decide_stats() == (2, 0), (where, decide_stats())
+
+
+def test_the_255th_atomic_instance_commits(torch_dev, monkeypatch):
+    """A lineage key has 8 bits for the group instance.  A pattern with 255 instances compiles and its last one, index 254, decides:
+    the `commits` value fails only because that group gives nothing back (tests/test_chunk_edges.py says so on the CPU); 256
+    instances are refused.  Every byte of these values is a commit pass."""
+    row = next(r for r in ce.ROWS if r.id == "nfa-atomic-edges")
+    ce.set_env(monkeypatch, row)
+    with pytest.raises(B.RegexUnsupportedError, match="more than 255 atomic group instances"):
+        B.GpuRegex(ce.instance_pattern(256), engine=row.compile_engine)
+    rx = B.GpuRegex(ce.INSTANCE_FAMILY.pattern, engine=row.compile_engine)
+    assert rx.atomic_groups() == (255, 0)
+    lines = [x for x, _ in ce.instance_lines()]
+    batch = batch_of(torch_dev, ce.explicit_corpus(ce.INSTANCE_FAMILY, lines))
+    what = [w for _, w in ce.instance_lines()]
+    assert batch["status"][what.index("first")] == 1 and batch["status"][what.index("commits")] == 0
+    for form in ("len", "sep"):
+        caps, status, names = _launch(torch_dev, row, rx, batch, form)
+        assert "nfa_match_kernel<atomic>" in names, names
+        _compare(batch, caps, status, batch["caps"], batch["status"], "255 instances, %s form" % form)
+        assert "nfa_decide_kernel" not in names or decide_stats() == (0, 0), (names, decide_stats())
+
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_global_memory_nfa_kernel_in_a_process_of_its_own(torch_dev):
     """nfa_match_kernel<..., GLOBAL=true> runs where a program exceeds 52 KB, and LC_NFA_GLOBAL_KB, which moves that bound, is read
     once per process: ONE child process with LC_NFA_GLOBAL_KB=0 (every non-empty batch takes the GLOBAL instantiation) runs rows `nfa`
-    and `nfa-atomic` in both forms, the resumed searches and the result edges on `log`, and rows `nfa-ns64`, `nfa-ns128` and `nfa-ns320`
+    and `nfa-atomic` in both forms, the resumed searches and the result edges on `log`, family `alog` of row `nfa-atomic-edges` and row
+    `achain-kept64` (with lc_decide_stats exact) in both forms, and rows `nfa-ns64`, `nfa-ns128` and `nfa-ns320`
     (64, 128 and 320 capture slots) in both forms (tests/helpers/global_nfa_child.py) and reports
     per launch how many values differ from the oracle's rows.  A child that faults, aborts or runs out of time fails the test with
     its stderr; nothing is started afterwards."""
@@ -241,8 +295,12 @@ def test_global_memory_nfa_kernel_in_a_process_of_its_own(torch_dev):
         wall, res["seconds"]["imports"], res["seconds"]["work"], len(res["launches"])))
     bad = [x for x in res["launches"] if x["differ"] or not x["ran"]]
     assert not bad, "%d of %d launches differ; first: %s" % (len(bad), len(res["launches"]), bad[0])
-    # 4 + 1 families in both forms, 3 search families resumed in both forms, 16 + 2 + 4 result-edge launches, 3 slot widths in both forms
-    assert len(res["launches"]) == 2 * 5 + 2 * 3 + 22 + 2 * 3, len(res["launches"])
+    # 4 + 1 families in both forms, 3 search families resumed in both forms, 16 + 2 + 4 result-edge launches, alog and akept64 in both forms,
+    # 3 slot widths in both forms
+    assert len(res["launches"]) == 2 * 5 + 2 * 3 + 22 + 2 * 2 + 2 * 3, len(res["launches"])
+    assert [x["launch"] for x in res["launches"][-10:-6]] == ["%s, %s, %s form" % (r, f, form) for r, f in (
+        ("nfa-atomic-edges", "alog"), ("achain-kept64", "akept64")) for form in ("len", "sep")]
+    assert "nfa_decide_kernel" in res["kernels"], res["kernels"]         # (the child checks per launch that no wide kernel took part)
     assert [x["launch"] for x in res["launches"][-6:]] == ["%s, %s, %s form" % (r, f, form) for r, f in (
         ("nfa-ns64", "log64"), ("nfa-ns128", "log128"), ("nfa-ns320", "log320")) for form in ("len", "sep")]
     assert "nfa_match_kernel" in res["kernels"] and "nfa_match_kernel<atomic>" in res["kernels"], res["kernels"]
