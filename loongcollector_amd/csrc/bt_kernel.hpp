@@ -60,7 +60,7 @@ __global__ __launch_bounds__(kBtBlock) void bt_match_kernel(const uint8_t* __res
         const int r = btRun(prog, data + o, L, from, mine, sliceWords, budget);
         int32_t* out = caps + size_t(line) * 2 * nGroupsOut;
         for (uint32_t s = 0; s < 2 * nGroupsOut; ++s) out[s] = (r == 1 && s + 2 < nCaps) ? int32_t(mine[s + 2]) : -1;  // (slot 0/1: the whole match)
-        if (r == -2 && !retryPass) {
+        if (r == -2 && !retryPass && sliceWords < kBtRetrySliceWords) {  // (a first pass on the large slice has no second: final)
             status[line] = kBtPending;
             atomicOr(pool, 1u);
         } else {

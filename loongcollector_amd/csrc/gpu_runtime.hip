@@ -1466,7 +1466,9 @@ extern "C" int lc_regex_match_device_from(lc_regex_t* re, int engine, const uint
     if (!re) return LC_ERR_ARG;
     if (n == 0) return LC_OK;
     if (!d_data || !d_off || !d_caps || !d_status) return LC_ERR_ARG;
-    if (d_from && re->nfa.searchPrefix < 0) {
+    // (a handle on the backtracking engine has no automaton to carry the search's prefix position: its syntax flags say what it is)
+    const bool btSearch = re->engine == LC_ENGINE_BT && (re->syntaxFlags & LC_SYNTAX_SEARCH) && !(re->syntaxFlags & LC_SYNTAX_PREFIX);
+    if (d_from && re->nfa.searchPrefix < 0 && !btSearch) {
         tlsError = "resume offsets need a pattern compiled with LC_SYNTAX_SEARCH";
         return LC_ERR_ARG;
     }
