@@ -111,6 +111,9 @@ lc_event_group_t* lc_group_from_lines(const uint8_t* data, const uint32_t* off, 
  * (position = file_offset, n); file_offset_key != NULL sets the group's LOG_FILE_OFFSET_KEY metadata (the splitter then adds the
  * offset content to every line, ProcessorSplitLogStringNative.cpp:151-156) */
 lc_event_group_t* lc_group_from_buffer(const uint8_t* data, size_t n, const char* key, uint64_t file_offset, const char* file_offset_key);
+/* a metadata key of the group by the name the fixture format gives it ("container.type": "1" / "containerd_text" or "2" /
+ * "docker_json-file", "log.file.offset", "has.part.log", ...); LC_ERR_ARG for a name it does not know */
+int lc_group_set_metadata(lc_event_group_t* g, const char* name, const char* value);
 char* lc_group_to_json(const lc_event_group_t* g);
 size_t lc_group_event_count(const lc_event_group_t* g);
 /* the logtail::PipelineEventGroup* inside the fixture wrapper (what processor_interface.process expects) */

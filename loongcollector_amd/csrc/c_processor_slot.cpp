@@ -29,6 +29,9 @@ __attribute__((weak)) void lcTimestampSlotFinalize(void* state);
 __attribute__((weak)) int lcApsaraSlotInit(const char* config_text, void** state);  // processor_parse_apsara_gpu.cpp
 __attribute__((weak)) void lcApsaraSlotProcess(void* state, void* native_group);
 __attribute__((weak)) void lcApsaraSlotFinalize(void* state);
+__attribute__((weak)) int lcContainerLogSlotInit(const char* config_text, void** state);  // processor_parse_container_log_gpu.cpp
+__attribute__((weak)) void lcContainerLogSlotProcess(void* state, void* native_group);
+__attribute__((weak)) void lcContainerLogSlotFinalize(void* state);
 }
 namespace {
 struct SlotEntry {
@@ -42,6 +45,7 @@ const SlotEntry kSlotTable[] = {
     {"processor_parse_delimiter_gpu", "delimiter parser", lcDelimiterSlotInit, lcDelimiterSlotProcess, lcDelimiterSlotFinalize},
     {"processor_parse_timestamp_gpu", "timestamp processor", lcTimestampSlotInit, lcTimestampSlotProcess, lcTimestampSlotFinalize},
     {"processor_parse_apsara_gpu", "Apsara parser", lcApsaraSlotInit, lcApsaraSlotProcess, lcApsaraSlotFinalize},
+    {"processor_parse_container_log_gpu", "container log parser", lcContainerLogSlotInit, lcContainerLogSlotProcess, lcContainerLogSlotFinalize},
 };
 }  // namespace
 
@@ -352,6 +356,9 @@ extern "C" void lc_columnar_free(lc_columnar_t* c) {
     if (tlsColumnarPool.free.size() < ColumnarPool::kKeep) tlsColumnarPool.free.push_back(std::move(st));
 }
 
+extern "C" int lc_group_set_metadata(lc_event_group_t* g, const char* name, const char* value) {
+    return g && name && value && g->group.SetMetadataByName(name, value) ? LC_OK : LC_ERR_ARG;
+}
 extern "C" char* lc_group_to_json(const lc_event_group_t* g) {
     if (!g) return nullptr;
     const std::string s = g->group.ToJsonString();

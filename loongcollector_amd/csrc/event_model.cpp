@@ -16,7 +16,34 @@ const std::pair<const char*, EventGroupMetaKey> kMetaNames[] = {
     {"log.file.offset", EventGroupMetaKey::LOG_FILE_OFFSET_KEY},
     {"has.part.log", EventGroupMetaKey::HAS_PART_LOG},
     {"source.id", EventGroupMetaKey::SOURCE_ID},
+    {"container.type", EventGroupMetaKey::LOG_FORMAT},
 };
+// EventGroupMetaValueToString (core/models/PipelineEventGroup.cpp:363-392): the two container log formats are shown by name.  (The
+// reference renames the value of EVERY key; here only LOG_FORMAT's, so that no other key's output changes.)
+const std::pair<const char*, const char*> kFormatNames[] = {{"1", "containerd_text"}, {"2", "docker_json-file"}};
+std::string metaValueToString(EventGroupMetaKey key, const std::string& value) {
+    if (key == EventGroupMetaKey::LOG_FORMAT)
+        for (const auto& f : kFormatNames)
+            if (value == f.first) return f.second;
+    return value;
+}
+// extension: the reference's FromJson cannot set LOG_FORMAT at all; here the shown name reads back as the value it stands for
+std::string metaValueFromString(EventGroupMetaKey key, const std::string& shown) {
+    if (key == EventGroupMetaKey::LOG_FORMAT)
+        for (const auto& f : kFormatNames)
+            if (shown == f.second) return f.first;
+    return shown;
+}
+}
+
+bool PipelineEventGroup::SetMetadataByName(const std::string& name, const std::string& value) {
+    for (const auto& known : kMetaNames) {
+        if (name == known.first) {
+            SetMetadata(known.second, metaValueFromString(known.second, value));
+            return true;
+        }
+    }
+    return false;
 }
 
 bool PipelineEventGroup::FromJsonString(const std::string& json, std::string* error) {
@@ -28,9 +55,7 @@ bool PipelineEventGroup::FromJsonString(const std::string& json, std::string* er
         return false;
     }
     if (const lcjson::Value* md = root.find("metadata")) {
-        for (const auto& kv : md->obj)
-            for (const auto& name : kMetaNames)
-                if (kv.first == name.first) SetMetadata(name.second, kv.second.str);
+        for (const auto& kv : md->obj) (void)SetMetadataByName(kv.first, kv.second.str);
     }
     if (const lcjson::Value* tags = root.find("tags"))
         for (const auto& kv : tags->obj) SetTag(kv.first, kv.second.str);
@@ -81,7 +106,7 @@ std::string PipelineEventGroup::ToJsonString() const {
         lcjson::Value md = lcjson::Value::makeObject();
         for (const auto& kv : mMetadata)
             for (const auto& name : kMetaNames)
-                if (kv.first == name.second) md.set(name.first, lcjson::Value::makeString(kv.second.to_string()));
+                if (kv.first == name.second) md.set(name.first, lcjson::Value::makeString(metaValueToString(kv.first, kv.second.to_string())));
         root.set("metadata", std::move(md));
     }
     if (!mTags.empty()) {

@@ -165,7 +165,8 @@ enum class EventGroupMetaKey {
     LOG_FILE_INODE,
     LOG_FILE_OFFSET_KEY,
     HAS_PART_LOG,
-    SOURCE_ID
+    SOURCE_ID,
+    LOG_FORMAT  // the container runtime's log format: "1" containerd text, "2" Docker json-file
 };
 using GroupMetadata = std::map<EventGroupMetaKey, StringView>;
 using GroupTags = std::map<StringView, StringView>;
@@ -530,6 +531,8 @@ public:
     // fixture format of the reference unit tests (PipelineEventGroup::FromJsonString / ToJsonString,
     // core/models/PipelineEventGroup.h:140-146, LogEvent.cpp:169-209)
     bool FromJsonString(const std::string& json, std::string* error = nullptr);
+    // a metadata key by the name the fixture format gives it ("container.type", "log.file.offset", ...); false: no such name
+    bool SetMetadataByName(const std::string& name, const std::string& value);
     std::string ToJsonString() const;
 
 private:

@@ -1,4 +1,4 @@
-// parse_processor_shell.hpp -- what processor_parse_delimiter_gpu, processor_parse_timestamp_gpu, processor_parse_json_gpu and processor_parse_apsara_gpu share around
+// parse_processor_shell.hpp -- what processor_parse_delimiter_gpu, processor_parse_timestamp_gpu, processor_parse_json_gpu, processor_parse_apsara_gpu and processor_parse_container_log_gpu share around
 // their own Init, engine call and stitch: the config readers, the counters / alarm sink / tally every parse processor holds, the gather,
 // the ONE second trip for lines wider than the first trip kept, the report of a failed trip, the source-key tail, the in-place
 // compaction, and the C ABI bodies as templates over the handle type.  Header-only; it uses only the event API the stand-in and the

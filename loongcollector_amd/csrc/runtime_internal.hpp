@@ -21,6 +21,7 @@ void lcDelimThreadRelease();                           // delim_device.hip: the 
 void lcTimestampThreadRelease();                       // timestamp_device.hip: the same for the timestamp parser's host entry
 void lcApsaraThreadRelease();                          // apsara_device.hip: the same for the Apsara parser's host entry
 void lcJsonThreadRelease();                            // json_device.hip: the same for the JSON parser's host entry
+void lcClogThreadRelease();                            // clog_device.hip: the same for the container log parser's host entry
 // hipFuncSetAttribute for a launch of `kern` on `dev` that asks for more than 48 KiB of dynamic LDS: once per (thread, kernel, device)
 // and size, grow-only.  The only place the attribute is set.
 int lcAllowLds(const void* kern, int dev, size_t lds);
