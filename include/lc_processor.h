@@ -116,6 +116,8 @@ lc_event_group_t* lc_group_from_buffer(const uint8_t* data, size_t n, const char
 int lc_group_set_metadata(lc_event_group_t* g, const char* name, const char* value);
 char* lc_group_to_json(const lc_event_group_t* g);
 size_t lc_group_event_count(const lc_event_group_t* g);
+/* where log event `event`'s value of `key` lies (tests: a processor that leaves a value alone leaves its VIEW alone); 0: no such content */
+uintptr_t lc_group_content_address(const lc_event_group_t* g, size_t event, const char* key);
 /* the logtail::PipelineEventGroup* inside the fixture wrapper (what processor_interface.process expects) */
 void* lc_group_native(lc_event_group_t* g);
 void lc_group_free(lc_event_group_t* g);

@@ -32,6 +32,9 @@ __attribute__((weak)) void lcApsaraSlotFinalize(void* state);
 __attribute__((weak)) int lcContainerLogSlotInit(const char* config_text, void** state);  // processor_parse_container_log_gpu.cpp
 __attribute__((weak)) void lcContainerLogSlotProcess(void* state, void* native_group);
 __attribute__((weak)) void lcContainerLogSlotFinalize(void* state);
+__attribute__((weak)) int lcDesensitizeSlotInit(const char* config_text, void** state);  // processor_desensitize_gpu.cpp
+__attribute__((weak)) void lcDesensitizeSlotProcess(void* state, void* native_group);
+__attribute__((weak)) void lcDesensitizeSlotFinalize(void* state);
 }
 namespace {
 struct SlotEntry {
@@ -46,6 +49,7 @@ const SlotEntry kSlotTable[] = {
     {"processor_parse_timestamp_gpu", "timestamp processor", lcTimestampSlotInit, lcTimestampSlotProcess, lcTimestampSlotFinalize},
     {"processor_parse_apsara_gpu", "Apsara parser", lcApsaraSlotInit, lcApsaraSlotProcess, lcApsaraSlotFinalize},
     {"processor_parse_container_log_gpu", "container log parser", lcContainerLogSlotInit, lcContainerLogSlotProcess, lcContainerLogSlotFinalize},
+    {"processor_desensitize_gpu", "desensitize processor", lcDesensitizeSlotInit, lcDesensitizeSlotProcess, lcDesensitizeSlotFinalize},
 };
 }  // namespace
 
@@ -368,6 +372,12 @@ extern "C" char* lc_group_to_json(const lc_event_group_t* g) {
 }
 
 extern "C" size_t lc_group_event_count(const lc_event_group_t* g) { return g ? g->group.GetEvents().size() : 0; }
+// where event `event`'s value of `key` lies (tests: a processor that leaves a value alone leaves its VIEW alone); 0: no such content
+extern "C" uintptr_t lc_group_content_address(const lc_event_group_t* g, size_t event, const char* key) {
+    if (!g || !key || event >= g->group.GetEvents().size() || !g->group.GetEvents()[event].Is<logtail::LogEvent>()) return 0;
+    const logtail::LogEvent& ev = g->group.GetEvents()[event].Cast<logtail::LogEvent>();
+    return ev.HasContent(key) ? reinterpret_cast<uintptr_t>(ev.GetContent(key).data()) : 0;
+}
 extern "C" void* lc_group_native(lc_event_group_t* g) { return g ? &g->group : nullptr; }
 extern "C" void lc_group_free(lc_event_group_t* g) { delete g; }
 #endif

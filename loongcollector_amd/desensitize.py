@@ -1,0 +1,199 @@
+"""ctypes binding of the desensitize processor (include/lc_desensitize.h): GpuDesensitize is the engine (the match kernels in rounds,
+desens_collect_kernel, desens_size_kernel, desens_write_kernel over values in device or host memory), DesensitizeProcessor the
+processor_desensitize_gpu plugin over event groups (same shape as processor.Processor).  There is no CPU path: every apply needs a HIP
+device and raises otherwise."""
+import ctypes
+import json
+
+import numpy as np
+
+from . import binding
+from .processor import COUNTER_NAMES, EventGroup, ProcessorInitError, _lib as _processor_lib
+
+LC_DESENS_CONST, LC_DESENS_MD5 = 0, 1
+LC_DESENS_CHANGED, LC_DESENS_GAVE_UP = 1, 2
+LC_ERR_OVERFLOW = 6
+
+
+class LcDesensStats(ctypes.Structure):
+    _fields_ = [("rounds", ctypes.c_uint32), ("pass_through", ctypes.c_uint32), ("searches", ctypes.c_uint64)]
+
+
+class DesensitizeOverflow(RuntimeError):
+    """the output did not fit (or would pass 2^32 - 1 bytes); .needed is the size the call reported"""
+
+    def __init__(self, needed):
+        RuntimeError.__init__(self, "desensitize: the output needs %d bytes" % needed)
+        self.needed = needed
+
+
+def _lib():
+    L = _processor_lib()
+    if not getattr(L, "_lc_desensitize_bound", False):
+        vp, cp, sz, u32, u64, i32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
+        stats = ctypes.POINTER(LcDesensStats)
+        L.lc_desens_create.restype = i32
+        L.lc_desens_create.argtypes = [i32, cp, sz, cp, sz, cp, sz, i32, ctypes.POINTER(vp), ctypes.POINTER(i32), cp, sz]
+        L.lc_desens_free.restype = None
+        L.lc_desens_free.argtypes = [vp]
+        L.lc_desens_regex.restype = vp
+        L.lc_desens_regex.argtypes = [vp]
+        L.lc_desens_apply_device.restype = i32
+        L.lc_desens_apply_device.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, u64, ctypes.POINTER(u64), stats, vp]
+        L.lc_desens_apply_host.restype = i32
+        L.lc_desens_apply_host.argtypes = [vp, vp, vp, u32, vp, vp, ctypes.POINTER(vp), stats]
+        L.lc_desensitize_create.restype = i32
+        L.lc_desensitize_create.argtypes = [cp, ctypes.POINTER(vp), cp, sz]
+        L.lc_desensitize_destroy.restype = None
+        L.lc_desensitize_destroy.argtypes = [vp]
+        L.lc_desensitize_warnings.restype = vp
+        L.lc_desensitize_warnings.argtypes = [vp]
+        L.lc_desensitize_process.restype = i32
+        L.lc_desensitize_process.argtypes = [vp, vp]
+        L.lc_desensitize_counters.restype = i32
+        L.lc_desensitize_counters.argtypes = [vp, ctypes.POINTER(u64)]
+        L.lc_desensitize_set_alarm_sink.restype = None
+        L.lc_desensitize_set_alarm_sink.argtypes = [vp, vp, vp]
+        L.lc_desensitize_engine.restype = vp
+        L.lc_desensitize_engine.argtypes = [vp]
+        L.lc_desensitize_rounds.restype = u64
+        L.lc_desensitize_rounds.argtypes = [vp]
+        L.lc_free.argtypes = [vp]
+        L._lc_desensitize_bound = True
+    return L
+
+
+def _bytes(s):
+    return s.encode("utf-8") if isinstance(s, str) else bytes(s)
+
+
+class GpuDesensitize:
+    """lc_desens_*: method "const" | "md5"; before / content: the two halves of the pattern; replacing: ReplacingString (const)"""
+
+    def __init__(self, method, before, content, replacing=b"", replacing_all=False):
+        self._L = _lib()
+        before, content, replacing = _bytes(before), _bytes(content), _bytes(replacing)
+        h, warning = ctypes.c_void_p(), ctypes.c_int(0)
+        err = ctypes.create_string_buffer(512)
+        rc = self._L.lc_desens_create({"const": LC_DESENS_CONST, "md5": LC_DESENS_MD5}[method], before, len(before), content, len(content),
+                                      replacing, len(replacing), 1 if replacing_all else 0, ctypes.byref(h), ctypes.byref(warning), err, 512)
+        if rc != binding.LC_OK:
+            raise ValueError(err.value.decode("utf-8", "replace"))
+        self._h = h
+        self.pass_through = bool(warning.value)
+
+    def info(self):
+        """lc_regex_info of the compiled search"""
+        out = binding.LcRegexInfo()
+        binding._check(self._L.lc_regex_info(self._L.lc_desens_regex(self._h), ctypes.byref(out)), "lc_regex_info")
+        return {k: getattr(out, k) for k, _ in binding.LcRegexInfo._fields_}
+
+    def apply_device(self, d_data, d_off, d_len, n, d_flags, d_out_off, d_out, stream=0):
+        """d_data uint8, d_off uint32 / int32 [n] (with d_len) or [n + 1] (d_len None), d_flags uint8[n], d_out_off int64[n + 1],
+        d_out uint8 (or None: size query).  -> (needed, stats dict); raises DesensitizeOverflow when d_out is too small."""
+        needed = ctypes.c_uint64(0)
+        stats = LcDesensStats()
+        rc = self._L.lc_desens_apply_device(self._h, d_data.data_ptr(), d_off.data_ptr(), d_len.data_ptr() if d_len is not None else None, n,
+                                            d_flags.data_ptr(), d_out_off.data_ptr(), d_out.data_ptr() if d_out is not None else None,
+                                            d_out.numel() if d_out is not None else 0, ctypes.byref(needed), ctypes.byref(stats), stream)
+        if rc == LC_ERR_OVERFLOW:
+            raise DesensitizeOverflow(int(needed.value))
+        binding._check(rc, "lc_desens_apply_device")
+        return int(needed.value), {"rounds": stats.rounds, "pass_through": stats.pass_through, "searches": int(stats.searches)}
+
+    def apply_host(self, values):
+        """values: list of bytes -> (list of the new value, or None for an unchanged one; flags uint8[n]; stats dict)"""
+        n = len(values)
+        blob = np.frombuffer(b"".join(values) + b"\0", np.uint8).copy()
+        lens = np.array([len(v) for v in values], np.uint32)
+        at = np.zeros(n, np.uint64)
+        if n:
+            at[1:] = np.cumsum(lens[:-1])
+        ptrs = (blob.ctypes.data + at).astype(np.uint64)
+        flags = np.zeros(n, np.uint8)
+        out_off = np.zeros(n + 1, np.uint64)
+        out = ctypes.c_void_p()
+        stats = LcDesensStats()
+        rc = self._L.lc_desens_apply_host(self._h, ptrs.ctypes.data, lens.ctypes.data, n, flags.ctypes.data, out_off.ctypes.data,
+                                          ctypes.byref(out), ctypes.byref(stats))
+        if rc == LC_ERR_OVERFLOW:
+            raise DesensitizeOverflow(0)
+        binding._check(rc, "lc_desens_apply_host")
+        try:
+            new = ctypes.string_at(out, int(out_off[n])) if out.value else b""
+        finally:
+            self._L.lc_free(out)
+        res = [new[int(out_off[i]):int(out_off[i + 1])] if flags[i] & LC_DESENS_CHANGED else None for i in range(n)]
+        return res, flags, {"rounds": stats.rounds, "pass_through": stats.pass_through, "searches": int(stats.searches)}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.lc_desens_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DesensitizeProcessor:
+    """processor_desensitize_gpu; same config keys as processor_desensitize_native"""
+
+    def __init__(self, config):
+        text = config if isinstance(config, str) else json.dumps(config)
+        self._L = _lib()
+        h = ctypes.c_void_p()
+        err = ctypes.create_string_buffer(512)
+        rc = self._L.lc_desensitize_create(text.encode("utf-8"), ctypes.byref(h), err, 512)
+        if rc != binding.LC_OK:
+            raise ProcessorInitError(err.value.decode("utf-8", "replace"))
+        self._h = h
+
+    def warnings(self):
+        p = self._L.lc_desensitize_warnings(self._h)
+        try:
+            return [w for w in ctypes.string_at(p).decode("utf-8").split("\n") if w]
+        finally:
+            self._L.lc_free(p)
+
+    def process(self, group: EventGroup):
+        """raises on a failed trip: the group is then untouched and must not be forwarded"""
+        rc = self._L.lc_desensitize_process(self._h, group._h)
+        if rc == binding.LC_ERR_NO_DEVICE:
+            raise binding.GpuUnavailableError("processor_desensitize_gpu: no usable HIP device (no CPU path)")
+        if rc != binding.LC_OK:
+            raise RuntimeError("lc_desensitize_process rc=%d" % rc)
+
+    def collect_alarms(self):
+        """-> the list that receives (kind, message bytes): kind 1 a search gave up, kind 3 a failed trip"""
+        out = []
+        proto = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
+        self._alarm_cb = proto(lambda user, kind, msg, n: out.append((kind, ctypes.string_at(msg, n))))
+        self._L.lc_desensitize_set_alarm_sink(self._h, ctypes.cast(self._alarm_cb, ctypes.c_void_p), None)
+        return out
+
+    def counters(self):
+        buf = (ctypes.c_uint64 * len(COUNTER_NAMES))()
+        self._L.lc_desensitize_counters(self._h, buf)
+        return dict(zip(COUNTER_NAMES, [int(x) for x in buf]))
+
+    def rounds(self):
+        return int(self._L.lc_desensitize_rounds(self._h))
+
+    def info(self):
+        out = binding.LcRegexInfo()
+        binding._check(self._L.lc_regex_info(self._L.lc_desens_regex(self._L.lc_desensitize_engine(self._h)), ctypes.byref(out)), "lc_regex_info")
+        return {k: getattr(out, k) for k, _ in binding.LcRegexInfo._fields_}
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.lc_desensitize_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -1,0 +1,317 @@
+"""processor_desensitize_gpu on the CPU: the per-value routines of csrc/desens_vm.hpp walked on the host (tests/native/desens_double.cpp:
+every search answered by the oracle's matcher, everything behind it the product's) against the model of tests/helpers/
+desensitize_model.py, on every unit-test vector (tests/golden/desensitize_unittest_vectors.json; how it was made and what the model
+rests on: tests/golden/README_desensitize.md) and every rule and corpus the GPU suite uses; the product's real host code of the processor
+over that double; MD5 against hashlib; Init texts; and the writer under AddressSanitizer + UBSan as a stand-alone program."""
+import ctypes
+import hashlib
+import os
+import subprocess
+
+import pytest
+
+from helpers import desensitize_model as model
+from helpers import desensitize_product as dp
+
+ROOT = dp.ROOT
+METHODS = ("const", "md5")
+
+
+@pytest.fixture(scope="module")
+def L():
+    return dp.double()
+
+
+@pytest.fixture(scope="module")
+def fixtures():
+    return dp.load_fixtures()
+
+
+def corpus_of(name):
+    values = list(dp.RULE_VALUES[name])
+    if name == "edge":
+        values += dp.edge_values()
+    if name == "digest":
+        values += dp.digest_values()
+    if name == "pwd":
+        values += dp.counted_values()
+    return values
+
+
+def test_every_unittest_vector_agrees(fixtures):
+    """the model reproduced every expectation of ProcessorDesensitizeNativeUnittest.cpp when the fixture file was written; only the
+    named defined_only entries stand outside"""
+    assert len(fixtures["cases"]) >= 28
+    assert all(c["unittest_agrees"] is True for c in fixtures["cases"]), [c["name"] for c in fixtures["cases"] if not c["unittest_agrees"]]
+    assert [e["name"] for e in fixtures["defined_only"]] == ["rewrite_bad_escape"]
+    assert {s["kind"] for c in fixtures["cases"] for s in c["stages"]} == {"split", "split_multiline", "merge", "desensitize"}
+
+
+@pytest.mark.parametrize("name", [r[0] for r in dp.RULES])
+def test_host_walk_equals_the_model_on_every_rule(L, name):
+    """collectStep + outLen + writeValue walked value by value, both methods, ReplacingAll off and on: the new value, whether it
+    changed, and how many search rounds the batch takes"""
+    _, before, content, replacing = dp.RULE[name]
+    values = corpus_of(name)
+    for method in METHODS:
+        for replacing_all in (False, True):
+            rule = model.Rule(method, before, content, replacing, replacing_all)
+            got, flags, rounds = dp.Engine(method, before, content, replacing, replacing_all).apply(values)
+            for v, g in zip(values, got):
+                assert g == rule.apply(v), (name, method, replacing_all, v[:80])
+            assert not (flags & dp.GAVE_UP).any()
+            assert rounds == rule.rounds(values), (name, method, replacing_all)
+            if not replacing_all:
+                assert rounds == 1
+
+
+def test_edge_corpus_has_every_position_and_residue():
+    values = dp.edge_values()
+    rule = model.Rule("const", *dp.RULE["edge"][1:], True)
+    begins, ends = set(), set()
+    for v in values:
+        for cut_b, me, _, _ in rule.cuts(v)[0]:
+            begins.add(cut_b)
+            ends.add(me)
+    assert set(dp.POSITIONS) <= begins and set(dp.POSITIONS) - {0} <= ends
+    at, residues = 0, set()
+    for v in values:
+        residues.add(at % 16)
+        at += len(v)
+    assert residues == set(range(16))
+    # a cut that ENDS on byte 0 is the empty match at 0: legal under const, the me == s rule under md5
+    assert model.Rule("const", *dp.RULE["empty"][1:], False).apply(b".") == b"-." and model.Rule("md5", *dp.RULE["empty"][1:], False).apply(b".") is None
+
+
+def test_the_two_disciplines_differ_on_the_anchor_pair(L):
+    """before = "^a", content = "b", value "abab", ReplacingAll: const resumes inside the whole value ('^' sees the bytes in front): one
+    replacement; md5 searches the remaining suffix afresh ('^' matches at its start): two"""
+    digest = hashlib.md5(b"b").hexdigest().upper().encode()
+    assert model.Rule("const", "^a", "b", "X", True).apply(b"abab") == b"aXab"
+    assert model.Rule("md5", "^a", "b", "", True).apply(b"abab") == b"a" + digest + b"a" + digest
+    assert dp.Engine("const", "^a", "b", "X", True).apply([b"abab"])[0] == [b"aXab"]
+    assert dp.Engine("md5", "^a", "b", "", True).apply([b"abab"])[0] == [b"a" + digest + b"a" + digest]
+
+
+def test_md5_is_upper_case_hashlib_for_every_length(L):
+    for n in list(range(131)) + [1000]:
+        data = bytes((i * 131 + n) & 0xFF for i in range(n))
+        raw = ctypes.create_string_buffer(b"\xa5" * 34, 34)
+        L.dd_md5(data, n, raw)
+        assert raw.raw[:32] == hashlib.md5(data).hexdigest().upper().encode(), n
+        assert raw.raw[32:] == b"\xa5\xa5", n
+    assert hashlib.md5(b"").hexdigest().upper() == "D41D8CD98F00B204E9800998ECF8427E"  # (digits A-F: the case matters)
+
+
+def test_me_equals_s_leaves_the_whole_value_unchanged(L):
+    """md5, an empty match at the point of consumption: on the first search, and on a later one -- then earlier replacements go too"""
+    _, before, content, _ = dp.RULE["empty"]
+    rule = model.Rule("md5", before, content, "", True)
+    values = [b"abc", b"xxabc", b"xx", b"ax"]
+    assert [rule.apply(v) for v in values] == [None, None, hashlib.md5(b"xx").hexdigest().upper().encode(), None]
+    assert rule.cuts(b"xxabc") == ([], 2)  # (the rule struck on the SECOND search)
+    got, flags, rounds = dp.Engine("md5", before, content, "", True).apply(values)
+    assert got == [rule.apply(v) for v in values] and rounds == 2 and list(flags) == [0, 0, dp.CHANGED, 0]
+
+
+def test_const_steps_one_byte_behind_an_empty_match(L):
+    """GlobalReplace of x* by "-": an empty match right behind the last replacement is not replaced; the search moves on ONE byte"""
+    _, before, content, replacing = dp.RULE["empty"]
+    want = {b"xaxx": b"-a-", b"abc": b"-a-b-c-", b"": b"-", b"xx": b"-", b"ax": b"-a-"}
+    rule = model.Rule("const", before, content, replacing, True)
+    got = dp.Engine("const", before, content, replacing, True).apply(list(want))[0]
+    for (v, w), g in zip(want.items(), got):
+        assert rule.apply(v) == w and g == w, v
+
+
+def test_rewrite_parser(L):
+    def text(rewrite, groups):
+        p = L.dd_rewrite_text(rewrite, len(rewrite), groups)
+        try:
+            return ctypes.string_at(p).decode()
+        finally:
+            L.dd_free(p)
+
+    assert text(rb"\1***", 1) == "G2 L2a2a2a"             # RE2 group k is engine group k + 1
+    assert text(rb"\0", 1) == "G1"                         # the whole match
+    assert text(rb"\1<\2>", 2) == "G2 L3c G3 L3e"
+    assert text(rb"\1a\5b", 2) == "G2 L6162"               # a number above the group count gives ""
+    assert text(rb"\1\\n", 1) == "G2 L5c6e"                # "\\" is a backslash
+    assert text(rb"\1\x", 1) == "PASS" and text(b"\\1tail\\", 1) == "PASS"
+    assert model.parse_rewrite(rb"\1a\5b", 2) == [1, b"a", b"b"] and model.parse_rewrite(rb"\1\x", 1) is None
+
+
+BASE = {"SourceKey": "cast1", "Method": "const", "ReplacingString": "********", "ContentPatternBeforeReplacedString": "pwd=",
+        "ReplacedContentPattern": "[^,]+", "ReplacingAll": True}
+
+
+def _init_error(config, L=None):
+    with pytest.raises(ValueError) as e:
+        dp.Product(config, L=L)
+    return str(e.value)
+
+
+def _without(key):
+    return {k: v for k, v in BASE.items() if k != key}
+
+
+def test_init_refusals_and_warnings_of_the_real_library():
+    """Init fails exactly where the reference's does, with the readers' messages; the real library compiles the pattern (no device
+    is needed for that), so what the compiler refuses is refused here"""
+    from loongcollector_amd import desensitize
+    R = desensitize._lib()
+    dp.bind(R)
+    for key in ("SourceKey", "Method", "ReplacingString", "ContentPatternBeforeReplacedString", "ReplacedContentPattern"):
+        assert _init_error(_without(key), R) == "mandatory param %s is missing" % key
+        assert _init_error(dict(BASE, **{key: 7}), R) == "param %s is not of type string" % key
+        assert _init_error(dict(BASE, **{key: ""}), R) == "mandatory string param %s is empty" % key
+    assert _init_error(dict(BASE, Method="sha1"), R) == "string param Method is not valid"
+    dp.Product(dict(_without("ReplacingString"), Method="md5"), L=R)  # ReplacingString is mandatory only for const
+    for bad in (r"(\w)\2", r"\p{L}+", r"(?=a)b", r"(?!a)b", r"(?<=a)b", r"(?<!a)b", r"(?>a)b", r"a*+b", r"a{2}+b", "(", "[a"):
+        assert _init_error(dict(BASE, ReplacedContentPattern=bad), R).startswith(
+            "param ContentPatternBeforeReplacedString or ReplacedContentPattern is not a valid regex: "), bad
+    for good in (r"[(?=]+", r"\(\?=a", r"a}+", r"[^,]+"):  # (what only looks like one of them)
+        dp.Product(dict(BASE, ReplacedContentPattern=good), L=R)
+    p = dp.Product(dict(BASE, ReplacingAll="yes"), L=R)
+    assert p.warnings() == ["param ReplacingAll is not of type bool"]
+    assert dp.Product(BASE, L=R).warnings() == []
+    w = dp.Product(dict(BASE, ReplacingString=r"\x"), L=R).warnings()
+    assert len(w) == 1 and "pass through unchanged" in w[0]
+
+
+def test_fixture_groups_through_the_processor(L, fixtures):
+    """the product's host code over every unit-test case, from the group as it reaches the first desensitize stage"""
+    for case in fixtures["cases"]:
+        group = case["at_desensitize"]
+        for stage in case["stages"]:
+            if stage["kind"] != "desensitize":
+                continue
+            p = dp.Product(stage["config"])
+            rc, group = p.process(group)
+            assert rc == 0, case["name"]
+            c = p.counters()
+            for k, v in stage["counters"].items():
+                assert c[k] == v, (case["name"], k)
+            assert c["in_events_total"] == c["out_events_total"] == len(group["events"])
+        got = [{"type": ev.get("type"), "contents": sorted(ev.get("contents", {}).items())} for ev in group["events"]]
+        want = [{"type": ev["type"], "contents": [tuple(kv) for kv in ev["contents"]]} for ev in case["out"]]
+        assert got == want, case["name"]
+
+
+def test_per_event_rules_and_counters(L):
+    group = {"events": [{"type": 1, "timestamp": 1, "contents": {"cast1": "a pwd=x1, pwd=y2,", "other": "pwd=keep,"}},
+                        {"type": 4, "timestamp": 1, "content": "raw pwd=z,"},
+                        {"type": 1, "timestamp": 1, "contents": {"other": "pwd=no-key,"}},
+                        {"type": 1, "timestamp": 1, "contents": {"cast1": ""}},
+                        {"type": 1, "timestamp": 1, "contents": {"cast1": "no secret"}}]}
+    for method in METHODS:
+        config = dict(BASE, Method=method)
+        p = dp.Product(config)
+        rc, out = p.process(group)
+        want, counters = model.process_group(config, group)
+        assert rc == 0 and len(out["events"]) == 5
+        for got_ev, want_ev in zip(out["events"], want["events"]):
+            assert got_ev.get("contents") == want_ev.get("contents") and got_ev.get("content") == want_ev.get("content")
+        c = p.counters()
+        assert counters == {"out_failed_events_total": 2, "out_key_not_found_events_total": 1, "out_successful_events_total": 2,
+                            "discarded_events_total": 0}
+        assert {k: c[k] for k in counters} == counters
+        assert out["events"][0]["contents"]["other"] == "pwd=keep,"
+
+
+def test_unchanged_values_keep_their_view(L):
+    """a value nothing matched in, and a value the me == s rule left alone, still point into the original buffer; a changed one does not"""
+    _, before, content, _ = dp.RULE["empty"]
+    md5 = {"SourceKey": "k", "Method": "md5", "ContentPatternBeforeReplacedString": before, "ReplacedContentPattern": content, "ReplacingAll": True}
+    for value, changed in (("abc", False), ("xxabc", False), ("xx", True)):
+        p = dp.Product(md5)
+        rc, out = p.process({"events": [{"type": 1, "timestamp": 1, "contents": {"k": value}}]})
+        assert rc == 0 and (out["events"][0]["contents"]["k"] != value) == changed
+        assert p.first_view_kept == (not changed), value
+    p = dp.Product(dict(BASE))
+    p.process({"events": [{"type": 1, "timestamp": 1, "contents": {"cast1": "nothing"}}]})
+    assert p.first_view_kept is True
+
+
+def test_failed_trip_leaves_the_group_untouched(L):
+    group = {"events": [{"type": 1, "timestamp": 1, "contents": {"cast1": "pwd=secret,"}}, {"type": 1, "timestamp": 1, "contents": {"cast1": "pwd=b,"}}]}
+    p = dp.Product(dict(BASE))
+    L.dd_fail_next_trips(1)
+    rc, out = p.process(group)
+    assert rc == 4  # LC_ERR_HIP: the caller must not forward the group
+    assert [ev["contents"] for ev in out["events"]] == [ev["contents"] for ev in group["events"]]
+    c = p.counters()
+    assert c["device_failed_events_total"] == 2 and c["out_successful_events_total"] == 0
+    assert len(p.alarms) == 1 and p.alarms[0][0] == 3 and b"2 events left untouched" in p.alarms[0][1]
+    rc, out = p.process(group)
+    assert rc == 0 and out["events"][0]["contents"]["cast1"] == "pwd=********,"
+
+
+def test_gave_up_values_stay_unchanged_and_are_never_silent(L):
+    group = {"events": [{"type": 4, "timestamp": 1, "content": "raw"}] +
+                       [{"type": 1, "timestamp": 1, "contents": {"cast1": "pwd=s%d," % i}} for i in range(4)]}
+    p = dp.Product(dict(BASE))
+    L.dd_give_up_every(2)
+    try:
+        rc, out = p.process(group)
+    finally:
+        L.dd_give_up_every(0)
+    assert rc == 0
+    assert [ev["contents"]["cast1"] for ev in out["events"][1:]] == ["pwd=********,", "pwd=s1,", "pwd=********,", "pwd=s3,"]
+    assert p.counters()["complexity_exceeded_events_total"] == 2 and p.counters()["out_successful_events_total"] == 4
+    assert [a[0] for a in p.alarms] == [1, 1] and b"event 2;" in p.alarms[0][1] and b"event 4;" in p.alarms[1][1]
+
+
+def test_defined_only_pass_through(L, fixtures):
+    entry = fixtures["defined_only"][0]
+    p = dp.Product(entry["config"])
+    assert len(p.warnings()) == 1
+    calls = L.dd_apply_calls()
+    rc, out = p.process(entry["in"])
+    assert rc == 0 and out["events"][0]["contents"] == entry["in"]["events"][0]["contents"]
+    assert p.counters()["out_successful_events_total"] == 1 and p.first_view_kept is True
+    assert L.dd_apply_calls() == calls + 1
+
+
+@pytest.mark.parametrize("method", METHODS)
+def test_model_never_gives_up_on_the_random_batch(method):
+    values, want = dp.random_expected(method)  # (raises where the oracle gives up)
+    assert len(values) == 1 << 16 and min(map(len, values)) >= 32 and max(map(len, values)) <= 700
+    changed = sum(w is not None for w in want)
+    assert len(values) // 2 < changed < len(values)
+
+
+def _job(method, rule, value):
+    cuts, _ = rule.cuts(value)
+    groups = rule.rx.groups + 1
+    rows = " ".join(" ".join("%d %d" % be for be in m) for _, _, _, m in cuts)
+    rewrite = (b"\\1" + dp._b(rule_replacing(rule))).hex() if method == "const" else "-"
+    return "%d %s %d %s %d %d %s" % (0 if method == "const" else 1, rewrite, rule.rx.groups, value.hex() or "-", len(cuts), groups, rows)
+
+
+def rule_replacing(rule):
+    return getattr(rule, "replacing_text", "")
+
+
+def test_sanitized_host_check_program(tmp_path):
+    """tests/native/desens_host_check.cpp under AddressSanitizer + UBSan, as a child process: the writer over the edge corpus, the digest
+    sizes, the counted values and every rule's values, from exactly-sized heap blocks, as one lane and as 64"""
+    exe = str(tmp_path / "desens_host_check")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-w",
+                           "-I", os.path.join(ROOT, "include"), "-o", exe, os.path.join(ROOT, "tests", "native", "desens_host_check.cpp")])
+    jobs, want = [], []
+    for name, before, content, replacing in dp.RULES:
+        for method in METHODS:
+            rule = model.Rule(method, before, content, replacing, True)
+            rule.replacing_text = replacing
+            for v in corpus_of(name):
+                jobs.append(_job(method, rule, v))
+                want.append(rule.apply(v))
+    assert len(jobs) > 400
+    r = subprocess.run([exe], input=("\n".join(jobs) + "\n").encode(), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert r.returncode == 0, r.stderr.decode("utf-8", "replace")[-2000:]
+    out = r.stdout.decode().split("\n")[:-1]
+    assert len(out) == len(jobs)
+    for job, text, w in zip(jobs, out, want):
+        got = None if text == "=" else b"" if text == "-" else bytes.fromhex(text)
+        assert got == w, job[:200]
