@@ -2,16 +2,15 @@
 lines in device or host memory), ApsaraProcessor the processor_parse_apsara_gpu plugin over event groups (same shape as
 processor.Processor).  There is no CPU path: every parse needs a HIP device and raises otherwise."""
 import ctypes
-import json
 
 import numpy as np
 
 from . import binding
-from .processor import COUNTER_NAMES, EventGroup, ProcessorInitError, _lib as _processor_lib
+from .processor import PluginProcessor, bind_plugin, _lib as _processor_lib
+from .timestamp import CLOCK, _ClockedProcessor
 
 LC_APSARA_TIME_OK, LC_APSARA_EPOCH, LC_APSARA_CANON19 = 1, 2, 4
 LC_APSARA_LEVEL, LC_APSARA_THREAD, LC_APSARA_FILE, LC_APSARA_LINE = 0, 1, 2, 3
-CLOCK = ctypes.CFUNCTYPE(ctypes.c_int64, ctypes.c_void_p)
 OUT_KEYS = ("status", "secs", "nanos", "base", "npairs", "pairs")
 
 
@@ -30,25 +29,17 @@ def _lib():
         L.lc_apsara_parse_host.argtypes = [vp, vp, u32, u32, out]
         L.lc_apsara_processor_create_with_clock.restype = i32
         L.lc_apsara_processor_create_with_clock.argtypes = [cp, vp, vp, ctypes.POINTER(vp), cp, sz]
-        L.lc_apsara_processor_destroy.argtypes = [vp]
-        L.lc_apsara_processor_warnings.restype = vp
-        L.lc_apsara_processor_warnings.argtypes = [vp]
         L.lc_apsara_processor_zone_offset.restype = ctypes.c_int32
         L.lc_apsara_processor_zone_offset.argtypes = [vp]
-        L.lc_apsara_processor_process.restype = i32
-        L.lc_apsara_processor_process.argtypes = [vp, vp]
         L.lc_apsara_processor_set_discard.restype = None
         L.lc_apsara_processor_set_discard.argtypes = [vp, i32, ctypes.c_int32]
         L.lc_apsara_processor_set_first_trip_pairs.restype = None
         L.lc_apsara_processor_set_first_trip_pairs.argtypes = [vp, u32]
-        L.lc_apsara_processor_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
         L.lc_apsara_processor_history_failures.restype = ctypes.c_uint64
         L.lc_apsara_processor_history_failures.argtypes = [vp]
         L.lc_apsara_processor_replayed_lines.restype = None
         L.lc_apsara_processor_replayed_lines.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
-        L.lc_apsara_processor_set_alarm_sink.restype = None
-        L.lc_apsara_processor_set_alarm_sink.argtypes = [vp, vp, vp]
-        L.lc_free.argtypes = [vp]
+        bind_plugin(L, "lc_apsara_processor")
         L._lc_apsara_bound = True
     return L
 
@@ -80,66 +71,16 @@ def parse_host(lines, W, fill=None):
     return res
 
 
-class ApsaraProcessor:
-    """processor_parse_apsara_gpu; same config keys as processor_parse_apsara_native.  clock: a callable returning epoch seconds ("now" of
-    Timezone and of the discard rule); default time()."""
-
-    def __init__(self, config, clock=None):
-        text = config if isinstance(config, str) else json.dumps(config)
-        self._L = _lib()
-        h = ctypes.c_void_p()
-        err = ctypes.create_string_buffer(512)
-        self._clock = CLOCK(lambda user: int(clock())) if clock is not None else None
-        rc = self._L.lc_apsara_processor_create_with_clock(
-            text.encode("utf-8"), ctypes.cast(self._clock, ctypes.c_void_p) if self._clock else None, None, ctypes.byref(h), err, 512)
-        if rc != binding.LC_OK:
-            raise ProcessorInitError(err.value.decode())
-        self._h = h
-
-    def warnings(self):
-        p = self._L.lc_apsara_processor_warnings(self._h)
-        try:
-            return [w for w in ctypes.string_at(p).decode("utf-8").split("\n") if w]
-        finally:
-            self._L.lc_free(p)
+class ApsaraProcessor(_ClockedProcessor):
+    """processor_parse_apsara_gpu; same config keys as processor_parse_apsara_native.  clock: "now" of Timezone and of the discard rule.
+    collect_alarms(): kind 0 PARSE_TIME_FAIL_ALARM, kind 1 OUTDATED_LOG_ALARM, kind 3 a failed trip."""
+    PREFIX, PLUGIN = "lc_apsara_processor", "processor_parse_apsara_gpu"
+    _lib = staticmethod(_lib)
 
     def set_discard(self, enabled=True, interval=43200):
         self._L.lc_apsara_processor_set_discard(self._h, int(enabled), interval)
-
-    def process(self, group: EventGroup):
-        rc = self._L.lc_apsara_processor_process(self._h, group._h)
-        if rc == binding.LC_ERR_NO_DEVICE:
-            raise binding.GpuUnavailableError("processor_parse_apsara_gpu: no usable HIP device (no CPU path)")
-        if rc != binding.LC_OK:
-            raise RuntimeError("lc_apsara_processor_process rc=%d" % rc)
-
-    def collect_alarms(self):
-        """-> the list that receives (kind, message bytes): kind 0 PARSE_TIME_FAIL_ALARM, kind 1 OUTDATED_LOG_ALARM, kind 3 a failed trip"""
-        out = []
-        proto = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
-        self._alarm_cb = proto(lambda user, kind, msg, n: out.append((kind, ctypes.string_at(msg, n))))
-        self._L.lc_apsara_processor_set_alarm_sink(self._h, ctypes.cast(self._alarm_cb, ctypes.c_void_p), None)
-        return out
-
-    def counters(self):
-        buf = (ctypes.c_uint64 * len(COUNTER_NAMES))()
-        self._L.lc_apsara_processor_counters(self._h, buf)
-        d = dict(zip(COUNTER_NAMES, [int(x) for x in buf]))
-        d["history_failure_total"] = int(self._L.lc_apsara_processor_history_failures(self._h))
-        return d
 
     def replayed_lines(self):
         s = (ctypes.c_uint64 * 2)()
         self._L.lc_apsara_processor_replayed_lines(self._h, s)
         return int(s[0]), int(s[1])
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.lc_apsara_processor_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -3,12 +3,11 @@
 processor_parse_container_log_gpu plugin over event groups (same shape as processor.Processor).  There is no CPU path: every parse needs
 a HIP device and raises otherwise."""
 import ctypes
-import json
 
 import numpy as np
 
 from . import binding
-from .processor import COUNTER_NAMES, EventGroup, ProcessorInitError, _lib as _processor_lib
+from .processor import EventGroup, PluginProcessor, bind_plugin, _lib as _processor_lib
 
 LC_CLOG_CONTAINERD, LC_CLOG_DOCKER = 1, 2
 LC_CLOG_OK, LC_CLOG_FAIL_TIME, LC_CLOG_FAIL_SOURCE, LC_CLOG_FAIL_STREAM, LC_CLOG_FAIL_JSON = 0, 1, 2, 3, 4
@@ -30,25 +29,15 @@ def _lib():
         L.lc_container_log_parse_device.argtypes = [i32, vp, vp, u32, out, vp, vp]
         L.lc_container_log_parse_host.restype = i32
         L.lc_container_log_parse_host.argtypes = [i32, vp, vp, u32, out, vp, ctypes.POINTER(ctypes.c_uint64)]
-        L.lc_container_log_processor_create.restype = i32
-        L.lc_container_log_processor_create.argtypes = [cp, ctypes.POINTER(vp), cp, sz]
-        L.lc_container_log_processor_destroy.argtypes = [vp]
-        L.lc_container_log_processor_warnings.restype = vp
-        L.lc_container_log_processor_warnings.argtypes = [vp]
         L.lc_container_log_processor_set_config_name.restype = None
         L.lc_container_log_processor_set_config_name.argtypes = [vp, cp]
-        L.lc_container_log_processor_process.restype = i32
-        L.lc_container_log_processor_process.argtypes = [vp, vp]
-        L.lc_container_log_processor_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
         L.lc_container_log_processor_stream_counts.restype = None
         L.lc_container_log_processor_stream_counts.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
         L.lc_container_log_processor_replayed_lines.restype = ctypes.c_uint64
         L.lc_container_log_processor_replayed_lines.argtypes = [vp]
-        L.lc_container_log_processor_set_alarm_sink.restype = None
-        L.lc_container_log_processor_set_alarm_sink.argtypes = [vp, vp, vp]
         L.lc_group_set_metadata.restype = i32
         L.lc_group_set_metadata.argtypes = [vp, cp, cp]
-        L.lc_free.argtypes = [vp]
+        bind_plugin(L, "lc_container_log_processor")
         L._lc_container_log_bound = True
     return L
 
@@ -92,47 +81,18 @@ def parse_host(fmt, lines, fill=None):
     return res
 
 
-class ContainerLogProcessor:
+class ContainerLogProcessor(PluginProcessor):
     """processor_parse_container_log_gpu; same config keys as processor_parse_container_log_native.  The format of a group is its
-    LOG_FORMAT metadata (set_group_format)."""
+    LOG_FORMAT metadata (set_group_format).  collect_alarms(): kind 0 PARSE_LOG_FAIL_ALARM, kind 3 a failed trip."""
+    PREFIX, PLUGIN = "lc_container_log_processor", "processor_parse_container_log_gpu"
+    _lib = staticmethod(_lib)
 
     def __init__(self, config, config_name=""):
-        text = config if isinstance(config, str) else json.dumps(config)
-        self._L = _lib()
-        h = ctypes.c_void_p()
-        err = ctypes.create_string_buffer(512)
-        rc = self._L.lc_container_log_processor_create(text.encode("utf-8"), ctypes.byref(h), err, 512)
-        if rc != binding.LC_OK:
-            raise ProcessorInitError(err.value.decode())
-        self._h = h
+        self._create(config)
         self._L.lc_container_log_processor_set_config_name(self._h, config_name.encode("utf-8"))
 
-    def warnings(self):
-        p = self._L.lc_container_log_processor_warnings(self._h)
-        try:
-            return [w for w in ctypes.string_at(p).decode("utf-8").split("\n") if w]
-        finally:
-            self._L.lc_free(p)
-
-    def process(self, group: EventGroup):
-        rc = self._L.lc_container_log_processor_process(self._h, group._h)
-        if rc == binding.LC_ERR_NO_DEVICE:
-            raise binding.GpuUnavailableError("processor_parse_container_log_gpu: no usable HIP device (no CPU path)")
-        if rc != binding.LC_OK:
-            raise RuntimeError("lc_container_log_processor_process rc=%d" % rc)
-
-    def collect_alarms(self):
-        """-> the list that receives (kind, message bytes): kind 0 PARSE_LOG_FAIL_ALARM, kind 3 a failed trip"""
-        out = []
-        proto = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
-        self._alarm_cb = proto(lambda user, kind, msg, n: out.append((kind, ctypes.string_at(msg, n))))
-        self._L.lc_container_log_processor_set_alarm_sink(self._h, ctypes.cast(self._alarm_cb, ctypes.c_void_p), None)
-        return out
-
     def counters(self):
-        buf = (ctypes.c_uint64 * len(COUNTER_NAMES))()
-        self._L.lc_container_log_processor_counters(self._h, buf)
-        d = dict(zip(COUNTER_NAMES, [int(x) for x in buf]))
+        d = PluginProcessor.counters(self)
         s = (ctypes.c_uint64 * 2)()
         self._L.lc_container_log_processor_stream_counts(self._h, s)
         d["parse_stdout_total"], d["parse_stderr_total"] = int(s[0]), int(s[1])
@@ -140,14 +100,3 @@ class ContainerLogProcessor:
 
     def replayed_lines(self):
         return int(self._L.lc_container_log_processor_replayed_lines(self._h))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.lc_container_log_processor_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -6,8 +6,7 @@
 
 #include "../../include/lc_apsara.h"
 #include "apsara_kernel.hpp"
-#include "runtime_internal.hpp"
-#include "trip_buffers.hpp"
+#include "packed_trip.hpp"
 
 static int launchParse(const uint8_t* d_data, const int32_t* d_off, uint32_t n, uint32_t W, const lc_apsara_out_t& o, hipStream_t st) {
     const dim3 grid((n + lcapsara::kBlock - 1) / lcapsara::kBlock), block(lcapsara::kBlock);
@@ -42,21 +41,7 @@ extern "C" int lc_apsara_parse_device(const uint8_t* d_data, const int32_t* d_of
 
 // ------------------------------------------------------------------------------------------------ host lines
 namespace {
-// per runner thread: a stream, one pinned and one device block each way, the pinned completion word; grow-only
-struct ApsaraThread : TripThread<ApsaraThread> {
-    TripBuf hIn, hOut, dIn, dOut;
-    ApsaraThread() : TripThread(true) { hIn.pinned = hOut.pinned = true; }
-    ~ApsaraThread() {
-        if (live()) release();
-    }
-    void release() { releaseWith({&hIn, &hOut, &dIn, &dOut}); }
-};
-thread_local ApsaraThread tlsApsara;
-
-constexpr size_t kChunkBytes = 32u << 20;    // payload bytes per trip
-constexpr uint32_t kChunkLines = 1u << 18;   // and at most this many lines
-constexpr size_t kChunkResultBytes = 64u << 20;
-constexpr size_t kFixedResultBytes = 32 + 8 + 4 + 4 + 1;  // base, secs, nanos, npairs, status
+thread_local PackedThread<struct ApsaraTag> tlsApsara;
 }  // namespace
 
 void lcApsaraThreadRelease() { tlsApsara.release(); }
@@ -64,62 +49,36 @@ void lcApsaraThreadRelease() { tlsApsara.release(); }
 extern "C" int lc_apsara_parse_host(const uint8_t* const* lines, const uint32_t* len, uint32_t n, uint32_t W, const lc_apsara_out_t* out) {
     if (n == 0) return LC_OK;
     if (!lines || !len || !outComplete(out, W)) return LC_ERR_ARG;
-    ApsaraThread& T = tlsApsara;
+    auto& T = tlsApsara;
     int dev = 0;
     const int rcBegin = lcTripBegin(T, &dev, "no HIP device: the Apsara parser has no CPU path");
     if (rcBegin != LC_OK) return rcBegin;
     const size_t linePairBytes = size_t(W) * sizeof(ApsaraPair);
-    uint32_t next = 0;
-    while (next < n) {
-        // a chunk: the lines back to back, then (64-byte aligned) their n + 1 offsets -- ONE copy up; every result array in one device
-        // block -- ONE copy down
-        uint32_t cnt = 0;
-        size_t bytes = 0;
-        if (!tripCarve(len, next, n, kChunkLines, kChunkBytes, linePairBytes + kFixedResultBytes, kChunkResultBytes, &cnt, &bytes)) {
-            lcSetLastError("lc_apsara_parse_host: a line of 2 GiB or more");
-            return LC_ERR_ARG;
-        }
-        const size_t offAt = tripOffAt(bytes);
-        const size_t inBytes = offAt + (size_t(cnt) + 1) * 4;
-        const size_t baseAt = tripRoundUp(size_t(cnt) * linePairBytes, 64);
-        const size_t secsAt = baseAt + tripRoundUp(size_t(cnt) * 32, 64);
-        const size_t nanosAt = secsAt + tripRoundUp(size_t(cnt) * 8, 64);
-        const size_t npairsAt = nanosAt + tripRoundUp(size_t(cnt) * 4, 64);
-        const size_t statusAt = npairsAt + tripRoundUp(size_t(cnt) * 4, 64);
-        const size_t outBytes = statusAt + tripRoundUp(cnt, 64);
-        LC_HIP_TRY(T.hIn.ensure(inBytes));
-        LC_HIP_TRY(T.dIn.ensure(inBytes));
-        LC_HIP_TRY(T.hOut.ensure(outBytes));
-        LC_HIP_TRY(T.dOut.ensure(outBytes));
-        uint8_t* hIn = static_cast<uint8_t*>(T.hIn.p);
-        reinterpret_cast<int32_t*>(hIn + offAt)[cnt] = int32_t(tripPackLines(hIn, offAt, lines, len, next, cnt));
-        uint8_t* dIn = static_cast<uint8_t*>(T.dIn.p);
-        uint8_t* dOut = static_cast<uint8_t*>(T.dOut.p);
-        LC_HIP_TRY(hipMemcpyAsync(dIn, hIn, inBytes, hipMemcpyHostToDevice, T.stream));
-        const lc_apsara_out_t d{dOut + statusAt, reinterpret_cast<int64_t*>(dOut + secsAt), reinterpret_cast<uint32_t*>(dOut + nanosAt),
-                                reinterpret_cast<int32_t*>(dOut + baseAt), reinterpret_cast<uint32_t*>(dOut + npairsAt),
-                                reinterpret_cast<int32_t*>(dOut)};
-        int rc = launchParse(dIn, reinterpret_cast<const int32_t*>(dIn + offAt), cnt, W, d, T.stream);
-        // (with W short of a line's pairs the pair block is only partly written: the copy down moves it whole, the caller reads
-        // min(npairs, W) entries of a line)
-        if (rc == LC_OK) {
-            const hipError_t e = hipMemcpyAsync(T.hOut.p, dOut, outBytes, hipMemcpyDeviceToHost, T.stream);
-            if (e != hipSuccess) rc = lcHipFail(e, "hipMemcpyAsync(Apsara results)");
-        }
-        rc = T.end(rc);
-        if (rc != LC_OK) return rc;
-        const uint8_t* hOut = static_cast<const uint8_t*>(T.hOut.p);
-        const uint32_t* np = reinterpret_cast<const uint32_t*>(hOut + npairsAt);
-        for (uint32_t i = 0; W && i < cnt; ++i) {  // only what the kernel wrote: the caller's array keeps what it held behind it
-            const uint32_t k = np[i] < W ? np[i] : W;
-            if (k) std::memcpy(out->pairs + (size_t(next) + i) * W * 3, hOut + size_t(i) * linePairBytes, size_t(k) * sizeof(ApsaraPair));
-        }
-        std::memcpy(out->base + size_t(next) * 8, hOut + baseAt, size_t(cnt) * 32);
-        std::memcpy(out->secs + next, hOut + secsAt, size_t(cnt) * 8);
-        std::memcpy(out->nanos + next, hOut + nanosAt, size_t(cnt) * 4);
-        std::memcpy(out->npairs + next, np, size_t(cnt) * 4);
-        std::memcpy(out->status + next, hOut + statusAt, cnt);
-        next += cnt;
-    }
-    return LC_OK;
+    // a chunk: 32 MiB of payload, 2^18 lines, 64 MiB of results; down come pairs, base, secs, nanos, npairs, status
+    const PackedTripSpec spec{"lc_apsara_parse_host", "line", 1u << 18, 32u << 20, linePairBytes + 32 + 8 + 4 + 4 + 1, 64u << 20,
+                              "hipMemcpyAsync(Apsara results)"};
+    enum { kPairs, kBase, kSecs, kNanos, kNpairs, kStatus };
+    return packedTrip(
+        T, spec, lines, len, n, {linePairBytes, 32, 8, 4, 4, 1},
+        [&](const PackedChunk& c) {
+            // (with W short of a line's pairs the pair block is only partly written: the copy down moves it whole, the caller reads
+            // min(npairs, W) entries of a line)
+            const lc_apsara_out_t d{c.dResult<uint8_t>(kStatus), c.dResult<int64_t>(kSecs),    c.dResult<uint32_t>(kNanos),
+                                    c.dResult<int32_t>(kBase),   c.dResult<uint32_t>(kNpairs), c.dResult<int32_t>(kPairs)};
+            return launchParse(c.dIn, reinterpret_cast<const int32_t*>(c.dIn + c.in.offAt), c.cnt, W, d, T.stream);
+        },
+        [&](PackedChunk& c) {
+            const uint32_t* np = reinterpret_cast<const uint32_t*>(c.hResult(kNpairs, 4));
+            const uint8_t* hPairs = c.hResult(kPairs, linePairBytes);
+            for (uint32_t i = 0; W && i < c.cnt; ++i) {  // only what the kernel wrote: the caller's array keeps what it held behind it
+                const uint32_t k = np[i] < W ? np[i] : W;
+                if (k) std::memcpy(out->pairs + (size_t(c.next) + i) * W * 3, hPairs + size_t(i) * linePairBytes, size_t(k) * sizeof(ApsaraPair));
+            }
+            std::memcpy(out->base + size_t(c.next) * 8, c.hResult(kBase, 32), size_t(c.cnt) * 32);
+            std::memcpy(out->secs + c.next, c.hResult(kSecs, 8), size_t(c.cnt) * 8);
+            std::memcpy(out->nanos + c.next, c.hResult(kNanos, 4), size_t(c.cnt) * 4);
+            std::memcpy(out->npairs + c.next, np, size_t(c.cnt) * 4);
+            std::memcpy(out->status + c.next, c.hResult(kStatus, 1), c.cnt);
+            return LC_OK;
+        });
 }

@@ -7,8 +7,7 @@
 
 #include "../../include/lc_delimiter.h"
 #include "delim_kernel.hpp"
-#include "runtime_internal.hpp"
-#include "trip_buffers.hpp"
+#include "packed_trip.hpp"
 
 struct lc_delim {
     DelimConfig cfg;
@@ -53,20 +52,7 @@ extern "C" int lc_delim_split_device(lc_delim_t* d, const uint8_t* d_data, const
 
 // ------------------------------------------------------------------------------------------------ host lines
 namespace {
-// per runner thread: a stream, one pinned and one device block each way, the pinned completion word; grow-only
-struct DelimThread : TripThread<DelimThread> {
-    TripBuf hIn, hOut, dIn, dOut;
-    DelimThread() : TripThread(true) { hIn.pinned = hOut.pinned = true; }
-    ~DelimThread() {
-        if (live()) release();
-    }
-    void release() { releaseWith({&hIn, &hOut, &dIn, &dOut}); }
-};
-thread_local DelimThread tlsDelim;
-
-constexpr size_t kChunkBytes = 32u << 20;    // payload bytes per trip
-constexpr uint32_t kChunkLines = 1u << 18;   // and at most this many lines
-constexpr size_t kChunkSpanBytes = 64u << 20;
+thread_local PackedThread<struct DelimTag> tlsDelim;
 }  // namespace
 
 void lcDelimThreadRelease() { tlsDelim.release(); }
@@ -76,48 +62,24 @@ extern "C" int lc_delim_split_host(lc_delim_t* d, const uint8_t* const* lines, c
     if (!d) return LC_ERR_ARG;
     if (n == 0) return LC_OK;
     if (!lines || !len || !status || !ncols || (W && !spans)) return LC_ERR_ARG;
-    DelimThread& T = tlsDelim;
+    auto& T = tlsDelim;
     int dev = 0;
     const int rcBegin = lcTripBegin(T, &dev, "no HIP device: the delimiter parser has no CPU path");
     if (rcBegin != LC_OK) return rcBegin;
     const size_t lineSpanBytes = size_t(W) * 8;
-    uint32_t next = 0;
-    while (next < n) {
-        // a chunk: the lines back to back, then (64-byte aligned) their n + 1 offsets -- ONE copy up; spans, counts and status bytes
-        // in one device block -- ONE copy down
-        uint32_t cnt = 0;
-        size_t bytes = 0;
-        if (!tripCarve(len, next, n, kChunkLines, kChunkBytes, lineSpanBytes, kChunkSpanBytes, &cnt, &bytes)) {
-            lcSetLastError("lc_delim_split_host: a line of 2 GiB or more");
-            return LC_ERR_ARG;
-        }
-        const size_t offAt = tripOffAt(bytes);
-        const size_t inBytes = offAt + (size_t(cnt) + 1) * 4;
-        const size_t ncolsAt = tripRoundUp(size_t(cnt) * lineSpanBytes, 64);
-        const size_t statusAt = ncolsAt + tripRoundUp(size_t(cnt) * 4, 64);
-        const size_t outBytes = statusAt + tripRoundUp(cnt, 64);
-        LC_HIP_TRY(T.hIn.ensure(inBytes));
-        LC_HIP_TRY(T.dIn.ensure(inBytes));
-        LC_HIP_TRY(T.hOut.ensure(outBytes));
-        LC_HIP_TRY(T.dOut.ensure(outBytes));
-        uint8_t* hIn = static_cast<uint8_t*>(T.hIn.p);
-        reinterpret_cast<int32_t*>(hIn + offAt)[cnt] = int32_t(tripPackLines(hIn, offAt, lines, len, next, cnt));
-        uint8_t* dIn = static_cast<uint8_t*>(T.dIn.p);
-        uint8_t* dOut = static_cast<uint8_t*>(T.dOut.p);
-        LC_HIP_TRY(hipMemcpyAsync(dIn, hIn, inBytes, hipMemcpyHostToDevice, T.stream));
-        int rc = launchSplit(d, dIn, reinterpret_cast<const int32_t*>(dIn + offAt), cnt, W, dOut + statusAt,
-                             reinterpret_cast<uint32_t*>(dOut + ncolsAt), reinterpret_cast<int32_t*>(dOut), T.stream);
-        if (rc == LC_OK) {
-            const hipError_t e = hipMemcpyAsync(T.hOut.p, dOut, outBytes, hipMemcpyDeviceToHost, T.stream);
-            if (e != hipSuccess) rc = lcHipFail(e, "hipMemcpyAsync(delimiter results)");
-        }
-        rc = T.end(rc);
-        if (rc != LC_OK) return rc;
-        const uint8_t* hOut = static_cast<const uint8_t*>(T.hOut.p);
-        if (W) std::memcpy(spans + size_t(next) * W * 2, hOut, size_t(cnt) * lineSpanBytes);
-        std::memcpy(ncols + next, hOut + ncolsAt, size_t(cnt) * 4);
-        std::memcpy(status + next, hOut + statusAt, cnt);
-        next += cnt;
-    }
-    return LC_OK;
+    // a chunk: 32 MiB of payload, 2^18 lines, 64 MiB of spans; down come the spans, the counts and the status bytes
+    const PackedTripSpec spec{"lc_delim_split_host", "line", 1u << 18, 32u << 20, lineSpanBytes, 64u << 20, "hipMemcpyAsync(delimiter results)"};
+    enum { kSpans, kNcols, kStatus };
+    return packedTrip(
+        T, spec, lines, len, n, {lineSpanBytes, 4, 1},
+        [&](const PackedChunk& c) {
+            return launchSplit(d, c.dIn, reinterpret_cast<const int32_t*>(c.dIn + c.in.offAt), c.cnt, W, c.dResult<uint8_t>(kStatus),
+                               c.dResult<uint32_t>(kNcols), c.dResult<int32_t>(kSpans), T.stream);
+        },
+        [&](PackedChunk& c) {
+            if (W) std::memcpy(spans + size_t(c.next) * W * 2, c.hResult(kSpans, lineSpanBytes), size_t(c.cnt) * lineSpanBytes);
+            std::memcpy(ncols + c.next, c.hResult(kNcols, 4), size_t(c.cnt) * 4);
+            std::memcpy(status + c.next, c.hResult(kStatus, 1), c.cnt);
+            return LC_OK;
+        });
 }

@@ -12,8 +12,7 @@
 
 #include "../../include/lc_desensitize.h"
 #include "desens_kernel.hpp"
-#include "runtime_internal.hpp"
-#include "trip_buffers.hpp"
+#include "packed_trip.hpp"
 
 using lcdesens::Batch;
 using lcdesens::kBlock;
@@ -365,24 +364,17 @@ extern "C" int lc_desens_apply_host(lc_desens_t* h, const uint8_t* const* lines,
     if (rcBegin != LC_OK) return rcBegin;
     std::vector<uint8_t> bytes;
     lc_desens_stats_t total{0, 0, 0};
-    uint32_t next = 0;
-    while (next < n) {
-        uint32_t cnt = 0;
-        size_t payload = 0;
-        if (!tripCarve(len, next, n, kChunkLines, kChunkBytes, kLineResultBytes, kChunkResultBytes, &cnt, &payload)) {
-            lcSetLastError("lc_desens_apply_host: a value of 2 GiB or more");
-            return LC_ERR_ARG;
-        }
-        const size_t offAt = tripOffAt(payload);
-        const size_t inBytes = offAt + (size_t(cnt) + 1) * 4;
-        LC_HIP_TRY(T.hIn.ensure(inBytes));
-        LC_HIP_TRY(T.dIn.ensure(inBytes));
+    // the input half of the packed trip alone (packed_trip.hpp): the result sizes are known only once applyOnStream is through
+    const PackedTripSpec spec{"lc_desens_apply_host", "value", kChunkLines, kChunkBytes, kLineResultBytes, kChunkResultBytes, nullptr};
+    PackedChunk c;
+    while (c.next < n) {
+        if (const int rc = packedTripPlan(T, spec, len, n, &c); rc != LC_OK) return rc;
+        const uint32_t next = c.next, cnt = c.cnt;
         LC_HIP_TRY(T.dFlags.ensure(tripRoundUp(cnt, 64)));
         LC_HIP_TRY(T.dOutOff.ensure((size_t(cnt) + 1) * 8));
-        uint8_t* hIn = static_cast<uint8_t*>(T.hIn.p);
-        reinterpret_cast<uint32_t*>(hIn + offAt)[cnt] = uint32_t(tripPackLines(hIn, offAt, lines, len, next, cnt));
-        uint8_t* dIn = static_cast<uint8_t*>(T.dIn.p);
-        LC_HIP_TRY(hipMemcpyAsync(dIn, hIn, inBytes, hipMemcpyHostToDevice, T.stream));
+        if (const int rc = packedTripUpload(T, lines, len, c); rc != LC_OK) return rc;
+        uint8_t* dIn = c.dIn;
+        const size_t offAt = c.in.offAt;
         uint64_t needed = 0;
         lc_desens_stats_t s{0, 0, 0};
         hipError_t roomError = hipSuccess;
@@ -422,7 +414,7 @@ extern "C" int lc_desens_apply_host(lc_desens_t* h, const uint8_t* const* lines,
         bytes.insert(bytes.end(), hOut + bytesAt, hOut + bytesAt + needed);
         total.rounds += s.rounds;
         total.searches += s.searches;
-        next += cnt;
+        c.advance(len);
     }
     if (stats) *stats = total;
     if (!bytes.empty()) {

@@ -9,8 +9,7 @@
 
 #include "../../include/lc_json.h"
 #include "json_kernel.hpp"
-#include "runtime_internal.hpp"
-#include "trip_buffers.hpp"
+#include "packed_trip.hpp"
 
 namespace {
 // the second launch's nesting stacks: one block of kDeepScratchBytes (2 MiB) per (device, stream) that has queued a walk, allocated
@@ -92,10 +91,7 @@ extern "C" int lc_json_walk_device(const uint8_t* d_data, const int32_t* d_off, 
 
 // ------------------------------------------------------------------------------------------------ host lines
 namespace {
-// per runner thread: a stream, pinned and device blocks each way, the pinned completion word; grow-only
-struct JsonThread : TripThread<JsonThread> {
-    TripBuf hIn, hOut, hShadow, dIn, dOut, dShadow;
-    JsonThread() : TripThread(true) { hIn.pinned = hOut.pinned = hShadow.pinned = true; }
+struct JsonThread : PackedShadowBuffers<JsonThread> {
     ~JsonThread() {
         if (live()) release();
     }
@@ -104,15 +100,10 @@ struct JsonThread : TripThread<JsonThread> {
             (void)hipStreamSynchronize(stream);
             deepScratchForget(device, stream);  // (before the stream is destroyed: the block is found by it)
         }
-        releaseWith({&hIn, &hOut, &hShadow, &dIn, &dOut, &dShadow});
+        releaseBuffers();
     }
 };
 thread_local JsonThread tlsJson;
-
-constexpr size_t kChunkBytes = 32u << 20;    // payload bytes per trip
-constexpr uint32_t kChunkLines = 1u << 18;   // and at most this many lines
-constexpr size_t kChunkRecordBytes = 64u << 20;
-constexpr uint32_t kShadowGap = 4096;        // two escaped spans closer than this come down in one copy
 }  // namespace
 
 void lcJsonThreadRelease() { tlsJson.release(); }
@@ -127,106 +118,50 @@ extern "C" int lc_json_walk_host(const uint8_t* const* lines, const uint32_t* le
     const int rcBegin = lcTripBegin(T, &dev, "no HIP device: the JSON parser has no CPU path");
     if (rcBegin != LC_OK) return rcBegin;
     const size_t lineRecordBytes = size_t(W) * sizeof(lc_json_member_t);
-    uint32_t next = 0;
-    size_t shadowAt = 0;  // where line `next`'s part of the caller's shadow begins
-    uint64_t moved = 0;
-    while (next < n) {
-        // a chunk: the lines back to back, then (64-byte aligned) their n + 1 offsets -- ONE copy up; records, counts, error offsets and
-        // status bytes in one device block -- ONE copy down
-        uint32_t cnt = 0;
-        size_t bytes = 0;
-        if (!tripCarve(len, next, n, kChunkLines, kChunkBytes, lineRecordBytes, kChunkRecordBytes, &cnt, &bytes)) {
-            lcSetLastError("lc_json_walk_host: a line of 2 GiB or more");
-            return LC_ERR_ARG;
-        }
-        const size_t offAt = tripOffAt(bytes);
-        const size_t inBytes = offAt + (size_t(cnt) + 1) * 4;
-        const size_t countAt = tripRoundUp(size_t(cnt) * lineRecordBytes, 64);
-        const size_t errAt = countAt + tripRoundUp(size_t(cnt) * 4, 64);
-        const size_t statusAt = errAt + tripRoundUp(size_t(cnt) * 4, 64);
-        const size_t outBytes = statusAt + tripRoundUp(cnt, 64);
-        LC_HIP_TRY(T.hIn.ensure(inBytes));
-        LC_HIP_TRY(T.dIn.ensure(inBytes));
-        LC_HIP_TRY(T.hOut.ensure(outBytes));
-        LC_HIP_TRY(T.dOut.ensure(outBytes));
-        LC_HIP_TRY(T.dShadow.ensure(offAt));
-        uint8_t* hIn = static_cast<uint8_t*>(T.hIn.p);
-        int32_t* hOff = reinterpret_cast<int32_t*>(hIn + offAt);
-        hOff[cnt] = int32_t(tripPackLines(hIn, offAt, lines, len, next, cnt));
-        uint8_t* dIn = static_cast<uint8_t*>(T.dIn.p);
-        uint8_t* dOut = static_cast<uint8_t*>(T.dOut.p);
+    // a chunk: 32 MiB of payload, 2^18 lines, 64 MiB of records; down come records, counts, error offsets and status bytes
+    const PackedTripSpec spec{"lc_json_walk_host", "line", 1u << 18, 32u << 20, lineRecordBytes, 64u << 20, "hipMemcpyAsync(JSON results)"};
+    enum { kRecords, kCount, kErr, kStatus };
+    const auto launch = [&](const PackedChunk& c, bool deep) {
+        const int32_t* dOff = reinterpret_cast<const int32_t*>(c.dIn + c.in.offAt);
         uint8_t* dShadow = static_cast<uint8_t*>(T.dShadow.p);
-        const int32_t* dOff = reinterpret_cast<const int32_t*>(dIn + offAt);
-        uint8_t* dStatus = dOut + statusAt;
-        uint32_t* dCount = reinterpret_cast<uint32_t*>(dOut + countAt);
-        uint32_t* dErr = reinterpret_cast<uint32_t*>(dOut + errAt);
-        lc_json_member_t* dRec = reinterpret_cast<lc_json_member_t*>(dOut);
-        LC_HIP_TRY(hipMemcpyAsync(dIn, hIn, inBytes, hipMemcpyHostToDevice, T.stream));
-        int rc = launchWalk(dIn, dOff, cnt, W, dStatus, dCount, dErr, dRec, dShadow, T.stream);
-        if (rc == LC_OK) {
-            const hipError_t e = hipMemcpyAsync(T.hOut.p, dOut, outBytes, hipMemcpyDeviceToHost, T.stream);
-            if (e != hipSuccess) rc = lcHipFail(e, "hipMemcpyAsync(JSON results)");
-        }
-        rc = T.end(rc);
-        if (rc != LC_OK) return rc;
-        const uint8_t* hOut = static_cast<const uint8_t*>(T.hOut.p);
-        // lines nested deeper than the first launch's registers reach: the second launch, over the chunk that still lies on the device
-        if (std::memchr(hOut + statusAt, LC_JSON_DEEP, cnt)) {
-            rc = launchDeep(dev, dIn, dOff, cnt, W, dStatus, dCount, dErr, dRec, dShadow, T.stream);
-            if (rc == LC_OK) {
-                const hipError_t e = hipMemcpyAsync(T.hOut.p, dOut, outBytes, hipMemcpyDeviceToHost, T.stream);
-                if (e != hipSuccess) rc = lcHipFail(e, "hipMemcpyAsync(JSON results, second launch)");
-            }
-            rc = T.end(rc);
-            if (rc != LC_OK) return rc;
-        }
-        if (W) std::memcpy(records + size_t(next) * W, hOut, size_t(cnt) * lineRecordBytes);
-        std::memcpy(nmembers + next, hOut + countAt, size_t(cnt) * 4);
-        std::memcpy(errpos + next, hOut + errAt, size_t(cnt) * 4);
-        std::memcpy(status + next, hOut + statusAt, cnt);
-        // the unescaped bytes: only the escaped spans' come down, neighbours within kShadowGap in one copy
-        struct Range {
-            size_t b, e;
-        };
-        std::vector<Range> spans, copies;
-        for (uint32_t i = 0; i < cnt; ++i) {
-            if (status[next + i] != LC_JSON_OK) continue;
-            const uint32_t m = nmembers[next + i] < W ? nmembers[next + i] : W;
-            const lc_json_member_t* row = records + size_t(next + i) * W;
-            for (uint32_t k = 0; k < m; ++k) {
-                if (row[k].key_begin & LC_JSON_ESCAPED)
-                    spans.push_back(Range{size_t(hOff[i]) + (row[k].key_begin & ~LC_JSON_ESCAPED), size_t(hOff[i]) + row[k].key_end});
-                if (row[k].type == LC_JSON_STRING && (row[k].val_begin & LC_JSON_ESCAPED))
-                    spans.push_back(Range{size_t(hOff[i]) + (row[k].val_begin & ~LC_JSON_ESCAPED), size_t(hOff[i]) + row[k].val_end});
-            }
-        }
-        if (!spans.empty()) {
-            for (const Range& r : spans) {  // (in ascending order: members come in document order)
-                if (r.e <= r.b) continue;
-                if (!copies.empty() && r.b <= copies.back().e + kShadowGap) copies.back().e = r.e;
-                else copies.push_back(r);
-            }
-            LC_HIP_TRY(T.hShadow.ensure(offAt));
-            uint8_t* hShadow = static_cast<uint8_t*>(T.hShadow.p);
-            rc = LC_OK;
-            for (const Range& c : copies) {
-                const hipError_t e = hipMemcpyAsync(hShadow + c.b, dShadow + c.b, c.e - c.b, hipMemcpyDeviceToHost, T.stream);
-                if (e != hipSuccess) {
-                    rc = lcHipFail(e, "hipMemcpyAsync(JSON unescaped bytes)");
-                    break;
-                }
-                moved += c.e - c.b;
-            }
-            if (!copies.empty()) {
-                rc = T.end(rc);
+        uint8_t* dStatus = c.dResult<uint8_t>(kStatus);
+        uint32_t* dCount = c.dResult<uint32_t>(kCount);
+        uint32_t* dErr = c.dResult<uint32_t>(kErr);
+        lc_json_member_t* dRec = c.dResult<lc_json_member_t>(kRecords);
+        if (deep) return launchDeep(dev, c.dIn, dOff, c.cnt, W, dStatus, dCount, dErr, dRec, dShadow, T.stream);
+        return launchWalk(c.dIn, dOff, c.cnt, W, dStatus, dCount, dErr, dRec, dShadow, T.stream);
+    };
+    return packedTrip(
+        T, spec, lines, len, n, {lineRecordBytes, 4, 4, 1},
+        [&](const PackedChunk& c) {
+            const size_t offAt = c.in.offAt;
+            LC_HIP_TRY(T.dShadow.ensure(offAt));
+            return launch(c, false);
+        },
+        [&](PackedChunk& c) {
+            // lines nested deeper than the first launch's registers reach: the second launch, over the chunk that still lies on the device
+            if (std::memchr(c.hResult(kStatus, 1), LC_JSON_DEEP, c.cnt)) {
+                const int rc = packedTripDown(T, c, launch(c, true), "hipMemcpyAsync(JSON results, second launch)");
                 if (rc != LC_OK) return rc;
             }
-            for (const Range& r : spans)
-                if (r.e > r.b) std::memcpy(shadow + shadowAt + r.b, hShadow + r.b, r.e - r.b);
-        }
-        shadowAt += bytes;
-        next += cnt;
-    }
-    if (shadow_bytes_moved) *shadow_bytes_moved = moved;
-    return LC_OK;
+            if (W) std::memcpy(records + size_t(c.next) * W, c.hResult(kRecords, lineRecordBytes), size_t(c.cnt) * lineRecordBytes);
+            std::memcpy(nmembers + c.next, c.hResult(kCount, 4), size_t(c.cnt) * 4);
+            std::memcpy(errpos + c.next, c.hResult(kErr, 4), size_t(c.cnt) * 4);
+            std::memcpy(status + c.next, c.hResult(kStatus, 1), c.cnt);
+            // the unescaped bytes: only the escaped spans' come down (in ascending order: members come in document order)
+            std::vector<TripRange> spans;
+            for (uint32_t i = 0; i < c.cnt; ++i) {
+                if (status[c.next + i] != LC_JSON_OK) continue;
+                const uint32_t m = nmembers[c.next + i] < W ? nmembers[c.next + i] : W;
+                const lc_json_member_t* row = records + size_t(c.next + i) * W;
+                const size_t at = size_t(c.hOff()[i]);
+                for (uint32_t k = 0; k < m; ++k) {
+                    if (row[k].key_begin & LC_JSON_ESCAPED) spans.push_back(TripRange{at + (row[k].key_begin & ~LC_JSON_ESCAPED), at + row[k].key_end});
+                    if (row[k].type == LC_JSON_STRING && (row[k].val_begin & LC_JSON_ESCAPED))
+                        spans.push_back(TripRange{at + (row[k].val_begin & ~LC_JSON_ESCAPED), at + row[k].val_end});
+                }
+            }
+            return packedShadowDown(T, &c, spans, shadow, "hipMemcpyAsync(JSON unescaped bytes)");
+        },
+        shadow_bytes_moved);
 }

@@ -7,10 +7,9 @@
 #include <string>
 
 #include "../../include/lc_timestamp.h"
-#include "runtime_internal.hpp"
+#include "packed_trip.hpp"
 #include "strptime_kernel.hpp"
 #include "strptime_program.hpp"
-#include "trip_buffers.hpp"
 
 struct lc_strptime {
     StrptimeProgram prog;
@@ -78,18 +77,7 @@ extern "C" int lc_strptime_parse_captures_device(lc_strptime_t* t, const uint8_t
 
 // ------------------------------------------------------------------------------------------------ host values
 namespace {
-struct TimestampThread : TripThread<TimestampThread> {
-    TripBuf hIn, hOut, dIn, dOut;
-    TimestampThread() : TripThread(true) { hIn.pinned = hOut.pinned = true; }
-    ~TimestampThread() {
-        if (live()) release();
-    }
-    void release() { releaseWith({&hIn, &hOut, &dIn, &dOut}); }
-};
-thread_local TimestampThread tlsTimestamp;
-
-constexpr size_t kChunkBytes = 32u << 20;   // value bytes per trip
-constexpr uint32_t kChunkValues = 1u << 20;  // and at most this many values
+thread_local PackedThread<struct TimestampTag> tlsTimestamp;
 }  // namespace
 
 void lcTimestampThreadRelease() { tlsTimestamp.release(); }
@@ -98,65 +86,32 @@ extern "C" int lc_strptime_parse_host(lc_strptime_t* t, const uint8_t* const* va
     if (!t) return LC_ERR_ARG;
     if (n == 0) return LC_OK;
     if (!vals || !len || !outComplete(out)) return LC_ERR_ARG;
-    TimestampThread& T = tlsTimestamp;
+    auto& T = tlsTimestamp;
     int dev = 0;
     const int rcBegin = lcTripBegin(T, &dev, "no HIP device: the timestamp parser has no CPU path");
     if (rcBegin != LC_OK) return rcBegin;
-    uint32_t next = 0;
-    while (next < n) {
-        // a chunk up: the values back to back, then (64-byte aligned) their offsets and (begin, end) pairs -- ONE copy; down: the six
-        // result arrays in one block -- ONE copy.  same_as_prev of a chunk's first value is computed against nothing: the chunk starts
-        // one value early instead (the value before is parsed again and its results are dropped).
-        const uint32_t lead = next ? 1u : 0u;
-        const uint32_t first = next - lead;
-        uint32_t cnt = lead;
-        size_t bytes = lead ? len[first] : 0;
-        if (!tripCarve(len, next, n, kChunkValues, kChunkBytes, 0, 0, &cnt, &bytes)) {
-            lcSetLastError("lc_strptime_parse_host: a value of 2 GiB or more");
-            return LC_ERR_ARG;
-        }
-        const size_t offAt = tripOffAt(bytes);
-        const size_t spanAt = offAt + tripRoundUp(size_t(cnt) * 4, 64);
-        const size_t inBytes = spanAt + size_t(cnt) * 8;
-        const size_t nanosAt = tripRoundUp(size_t(cnt) * 8, 64);
-        const size_t matchedAt = nanosAt + tripRoundUp(size_t(cnt) * 4, 64);
-        const size_t fracAt = matchedAt + tripRoundUp(size_t(cnt) * 4, 64);
-        const size_t statusAt = fracAt + tripRoundUp(size_t(cnt) * 4, 64);
-        const size_t sameAt = statusAt + tripRoundUp(cnt, 64);
-        const size_t outBytes = sameAt + tripRoundUp(cnt, 64);
-        LC_HIP_TRY(T.hIn.ensure(inBytes));
-        LC_HIP_TRY(T.dIn.ensure(inBytes));
-        LC_HIP_TRY(T.hOut.ensure(outBytes));
-        LC_HIP_TRY(T.dOut.ensure(outBytes));
-        uint8_t* hIn = static_cast<uint8_t*>(T.hIn.p);
-        tripPackLines(hIn, offAt, vals, len, first, cnt);
-        int32_t* hSpan = reinterpret_cast<int32_t*>(hIn + spanAt);
-        for (uint32_t i = 0; i < cnt; ++i) {
-            hSpan[2 * i] = 0;
-            hSpan[2 * i + 1] = int32_t(len[first + i]);
-        }
-        uint8_t* dIn = static_cast<uint8_t*>(T.dIn.p);
-        uint8_t* dOut = static_cast<uint8_t*>(T.dOut.p);
-        LC_HIP_TRY(hipMemcpyAsync(dIn, hIn, inBytes, hipMemcpyHostToDevice, T.stream));
-        const lc_ts_out_t dev_out{dOut + statusAt, reinterpret_cast<int64_t*>(dOut), reinterpret_cast<uint32_t*>(dOut + nanosAt),
-                                  reinterpret_cast<int32_t*>(dOut + matchedAt), reinterpret_cast<int32_t*>(dOut + fracAt), dOut + sameAt};
-        const lcts::Values v{dIn, reinterpret_cast<const uint32_t*>(dIn + offAt), reinterpret_cast<const int32_t*>(dIn + spanAt), 2, 0, nullptr, 0};
-        int rc = launchParse(t, v, cnt, &dev_out, T.stream);
-        if (rc == LC_OK) {
-            const hipError_t e = hipMemcpyAsync(T.hOut.p, dOut, outBytes, hipMemcpyDeviceToHost, T.stream);
-            if (e != hipSuccess) rc = lcHipFail(e, "hipMemcpyAsync(timestamp results)");
-        }
-        rc = T.end(rc);
-        if (rc != LC_OK) return rc;
-        const uint8_t* hOut = static_cast<const uint8_t*>(T.hOut.p);
-        const uint32_t got = cnt - lead;
-        std::memcpy(out->secs + next, hOut + size_t(lead) * 8, size_t(got) * 8);
-        std::memcpy(out->nanos + next, hOut + nanosAt + size_t(lead) * 4, size_t(got) * 4);
-        std::memcpy(out->matched + next, hOut + matchedAt + size_t(lead) * 4, size_t(got) * 4);
-        std::memcpy(out->frac_len + next, hOut + fracAt + size_t(lead) * 4, size_t(got) * 4);
-        std::memcpy(out->status + next, hOut + statusAt + lead, got);
-        std::memcpy(out->same_as_prev + next, hOut + sameAt + lead, got);
-        next += got;
-    }
-    return LC_OK;
+    // a chunk: 32 MiB of value bytes, 2^20 values, no cap on the results; up go the values, their offsets and (begin, end) pairs, down
+    // come the six result arrays.  same_as_prev of a chunk's first value is computed against nothing: the chunk starts one value early
+    // instead (leadIn: the value before is parsed again and its results are dropped).
+    PackedTripSpec spec{"lc_strptime_parse_host", "value", 1u << 20, 32u << 20, 0, 0, "hipMemcpyAsync(timestamp results)"};
+    spec.leadIn = spec.pairs = true;
+    enum { kSecs, kNanos, kMatched, kFrac, kStatus, kSame };
+    return packedTrip(
+        T, spec, vals, len, n, {8, 4, 4, 4, 1, 1},
+        [&](const PackedChunk& c) {
+            const lc_ts_out_t dev_out{c.dResult<uint8_t>(kStatus),  c.dResult<int64_t>(kSecs), c.dResult<uint32_t>(kNanos),
+                                      c.dResult<int32_t>(kMatched), c.dResult<int32_t>(kFrac), c.dResult<uint8_t>(kSame)};
+            const lcts::Values v{c.dIn, reinterpret_cast<const uint32_t*>(c.dIn + c.in.offAt), reinterpret_cast<const int32_t*>(c.dIn + c.in.pairAt),
+                                 2, 0, nullptr, 0};
+            return launchParse(t, v, c.cnt, &dev_out, T.stream);
+        },
+        [&](PackedChunk& c) {
+            std::memcpy(out->secs + c.next, c.hResult(kSecs, 8), size_t(c.got()) * 8);
+            std::memcpy(out->nanos + c.next, c.hResult(kNanos, 4), size_t(c.got()) * 4);
+            std::memcpy(out->matched + c.next, c.hResult(kMatched, 4), size_t(c.got()) * 4);
+            std::memcpy(out->frac_len + c.next, c.hResult(kFrac, 4), size_t(c.got()) * 4);
+            std::memcpy(out->status + c.next, c.hResult(kStatus, 1), c.got());
+            std::memcpy(out->same_as_prev + c.next, c.hResult(kSame, 1), c.got());
+            return LC_OK;
+        });
 }

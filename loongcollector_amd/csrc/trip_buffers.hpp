@@ -1,10 +1,13 @@
 // trip_buffers.hpp -- a runner thread's device trips, written once for every owner (delim_device.hip, timestamp_device.hip,
-// json_device.hip, multiline_device.hip, processor_filter_gpu.cpp, processor_pipeline_gpu.cpp):
+// json_device.hip, apsara_device.hip, clog_device.hip, desens_device.hip, multiline_device.hip, processor_filter_gpu.cpp,
+// processor_pipeline_gpu.cpp):
 //   TripBuf       a grow-only pinned / device buffer
 //   TripThread    the thread's stream, its device and its pinned completion word: begin() opens a host entry, end() closes a trip,
 //                 release() gives everything back -- lc_thread_release() calls each owner's lc...ThreadRelease(), and so does the
 //                 owner's destructor when the thread ends
-//   tripCarve / tripPackLines   the parsers' host entries: which lines a trip takes, and their packed staging
+//   tripCarve / tripInLayout / tripPackLines / tripLayout / tripCoalesce   the plan of the parsers' host entries: which lines a trip
+//                 takes, their packed staging, where the result arrays lie, which shadow ranges come down in one copy -- pure
+//                 arithmetic (tests/native/trip_plan_check.cpp); the loop that makes the trips is packed_trip.hpp
 // HIP-light: the host translation units and the tests' host doubles include it as well.
 #pragma once
 
@@ -14,6 +17,7 @@
 #include <cstdint>
 #include <cstring>
 #include <initializer_list>
+#include <vector>
 
 #include "../../include/lc_regex_gpu.h"
 
@@ -123,7 +127,8 @@ struct TripThread {
     }
 };
 
-// ---- the packed-lines trip of the parsers' host entries (lc_delim_split_host, lc_strptime_parse_host, lc_json_walk_host)
+// ---- the plan of a packed-lines trip (packed_trip.hpp): the host entries lc_delim_split_host, lc_strptime_parse_host, lc_json_walk_host,
+// lc_apsara_parse_host, lc_container_log_parse_host and lc_desens_apply_host
 inline size_t tripRoundUp(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // Which lines line `from` and its successors (of n) add to a trip that holds *cnt lines of *bytes payload bytes already: the first always
@@ -154,4 +159,57 @@ inline size_t tripPackLines(uint8_t* hIn, size_t offAt, const uint8_t* const* li
     }
     std::memset(hIn + at, 0, offAt - at);
     return at;
+}
+// (begin, end) = (0, len) of lines [first, first + cnt) at hIn + pairAt: the span pairs a kernel that takes spans reads
+inline void tripPackPairs(uint8_t* hIn, size_t pairAt, const uint32_t* len, uint32_t first, uint32_t cnt) {
+    int32_t* hPair = reinterpret_cast<int32_t*>(hIn + pairAt);
+    for (uint32_t i = 0; i < cnt; ++i) {
+        hPair[2 * i] = 0;
+        hPair[2 * i + 1] = int32_t(len[first + i]);
+    }
+}
+
+// The block that goes up: `payload` bytes, the offsets at offAt, and either their cnt + 1-th entry (pairAt == 0) or, 64-byte aligned
+// behind cnt offsets, the lines' (begin, end) pairs.
+struct TripInLayout {
+    size_t offAt, pairAt, bytes;
+};
+inline TripInLayout tripInLayout(size_t payload, uint32_t cnt, bool pairs) {
+    const size_t offAt = tripOffAt(payload);
+    if (!pairs) return TripInLayout{offAt, 0, offAt + (size_t(cnt) + 1) * 4};
+    const size_t pairAt = offAt + tripRoundUp(size_t(cnt) * 4, 64);
+    return TripInLayout{offAt, pairAt, pairAt + size_t(cnt) * 8};
+}
+
+// The block that comes down: one array of cnt elements per entry of elemBytes, in that order, each 64-byte aligned.
+struct TripLayout {
+    static constexpr size_t kMaxArrays = 8;
+    size_t at[kMaxArrays];
+    size_t bytes;
+};
+inline TripLayout tripLayout(uint32_t cnt, const size_t* elemBytes, size_t arrays) {
+    TripLayout L{};
+    for (size_t k = 0; k < arrays && k < TripLayout::kMaxArrays; ++k) {
+        L.at[k] = L.bytes;
+        L.bytes += tripRoundUp(size_t(cnt) * elemBytes[k], 64);
+    }
+    return L;
+}
+inline TripLayout tripLayout(uint32_t cnt, std::initializer_list<size_t> elemBytes) { return tripLayout(cnt, elemBytes.begin(), elemBytes.size()); }
+
+// The copies that bring the ascending ranges r[0..n) down: empty ranges (e <= b) are skipped, a range that begins within `gap` bytes
+// of the copy before it extends that copy.  Returns the bytes the copies move.
+struct TripRange {
+    size_t b, e;
+};
+inline uint64_t tripCoalesce(const TripRange* r, size_t n, size_t gap, std::vector<TripRange>* copies) {
+    copies->clear();
+    for (size_t i = 0; i < n; ++i) {
+        if (r[i].e <= r[i].b) continue;
+        if (!copies->empty() && r[i].b <= copies->back().e + gap) copies->back().e = r[i].e;
+        else copies->push_back(r[i]);
+    }
+    uint64_t moved = 0;
+    for (const TripRange& c : *copies) moved += c.e - c.b;
+    return moved;
 }

@@ -2,12 +2,11 @@
 device or host memory), DelimiterProcessor the processor_parse_delimiter_gpu plugin over event groups (same shape as
 processor.Processor).  There is no CPU path: every split needs a HIP device and raises otherwise."""
 import ctypes
-import json
 
 import numpy as np
 
 from . import binding
-from .processor import COUNTER_NAMES, EventGroup, ProcessorInitError, _lib as _processor_lib
+from .processor import PluginProcessor, bind_plugin, _lib as _processor_lib
 
 LC_DELIM_FAIL, LC_DELIM_OK, LC_DELIM_BLANK = 0, 1, 2
 LC_DELIM_EXTEND, LC_DELIM_KEEP, LC_DELIM_DISCARD = 0, 1, 2
@@ -27,18 +26,9 @@ def _lib():
         L.lc_delim_split_device.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, vp]
         L.lc_delim_split_host.restype = i32
         L.lc_delim_split_host.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp]
-        L.lc_delimiter_processor_create.restype = i32
-        L.lc_delimiter_processor_create.argtypes = [cp, ctypes.POINTER(vp), cp, sz]
-        L.lc_delimiter_processor_destroy.argtypes = [vp]
-        L.lc_delimiter_processor_warnings.restype = vp
-        L.lc_delimiter_processor_warnings.argtypes = [vp]
-        L.lc_delimiter_processor_process.restype = i32
-        L.lc_delimiter_processor_process.argtypes = [vp, vp]
         L.lc_delimiter_processor_set_first_trip_columns.restype = None
         L.lc_delimiter_processor_set_first_trip_columns.argtypes = [vp, u32]
-        L.lc_delimiter_processor_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
-        L.lc_delimiter_processor_set_alarm_sink.restype = None
-        L.lc_delimiter_processor_set_alarm_sink.argtypes = [vp, vp, vp]
+        bind_plugin(L, "lc_delimiter_processor")
         L._lc_delimiter_bound = True
     return L
 
@@ -92,55 +82,13 @@ class GpuDelimiter:
             pass
 
 
-class DelimiterProcessor:
-    """processor_parse_delimiter_gpu; same config keys as processor_parse_delimiter_native."""
+class DelimiterProcessor(PluginProcessor):
+    """processor_parse_delimiter_gpu; same config keys as processor_parse_delimiter_native.  collect_alarms(): every PARSE_LOG_FAIL_ALARM
+    the reference would raise."""
+    PREFIX, PLUGIN = "lc_delimiter_processor", "processor_parse_delimiter_gpu"
+    _lib = staticmethod(_lib)
 
     def __init__(self, config, first_trip_columns=0):
-        text = config if isinstance(config, str) else json.dumps(config)
-        self._L = _lib()
-        h = ctypes.c_void_p()
-        err = ctypes.create_string_buffer(512)
-        rc = self._L.lc_delimiter_processor_create(text.encode("utf-8"), ctypes.byref(h), err, 512)
-        if rc != binding.LC_OK:
-            raise ProcessorInitError(err.value.decode())
-        self._h = h
+        self._create(config)
         if first_trip_columns:
-            self._L.lc_delimiter_processor_set_first_trip_columns(h, first_trip_columns)
-
-    def warnings(self):
-        p = self._L.lc_delimiter_processor_warnings(self._h)
-        try:
-            return [w for w in ctypes.string_at(p).decode("utf-8").split("\n") if w]
-        finally:
-            self._L.lc_free(p)
-
-    def process(self, group: EventGroup):
-        rc = self._L.lc_delimiter_processor_process(self._h, group._h)
-        if rc == binding.LC_ERR_NO_DEVICE:
-            raise binding.GpuUnavailableError("processor_parse_delimiter_gpu: no usable HIP device (no CPU path)")
-        if rc != binding.LC_OK:
-            raise RuntimeError("lc_delimiter_processor_process rc=%d" % rc)
-
-    def collect_alarms(self):
-        """-> the list that receives (kind, message bytes) for every PARSE_LOG_FAIL_ALARM the reference would raise"""
-        out = []
-        proto = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
-        self._alarm_cb = proto(lambda user, kind, msg, n: out.append((kind, ctypes.string_at(msg, n))))
-        self._L.lc_delimiter_processor_set_alarm_sink(self._h, ctypes.cast(self._alarm_cb, ctypes.c_void_p), None)
-        return out
-
-    def counters(self):
-        buf = (ctypes.c_uint64 * len(COUNTER_NAMES))()
-        self._L.lc_delimiter_processor_counters(self._h, buf)
-        return dict(zip(COUNTER_NAMES, [int(x) for x in buf]))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.lc_delimiter_processor_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+            self._L.lc_delimiter_processor_set_first_trip_columns(self._h, first_trip_columns)

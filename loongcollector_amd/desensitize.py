@@ -3,12 +3,11 @@ desens_collect_kernel, desens_size_kernel, desens_write_kernel over values in de
 processor_desensitize_gpu plugin over event groups (same shape as processor.Processor).  There is no CPU path: every apply needs a HIP
 device and raises otherwise."""
 import ctypes
-import json
 
 import numpy as np
 
 from . import binding
-from .processor import COUNTER_NAMES, EventGroup, ProcessorInitError, _lib as _processor_lib
+from .processor import PluginProcessor, bind_plugin, _lib as _processor_lib
 
 LC_DESENS_CONST, LC_DESENS_MD5 = 0, 1
 LC_DESENS_CHANGED, LC_DESENS_GAVE_UP = 1, 2
@@ -42,23 +41,11 @@ def _lib():
         L.lc_desens_apply_device.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, u64, ctypes.POINTER(u64), stats, vp]
         L.lc_desens_apply_host.restype = i32
         L.lc_desens_apply_host.argtypes = [vp, vp, vp, u32, vp, vp, ctypes.POINTER(vp), stats]
-        L.lc_desensitize_create.restype = i32
-        L.lc_desensitize_create.argtypes = [cp, ctypes.POINTER(vp), cp, sz]
-        L.lc_desensitize_destroy.restype = None
-        L.lc_desensitize_destroy.argtypes = [vp]
-        L.lc_desensitize_warnings.restype = vp
-        L.lc_desensitize_warnings.argtypes = [vp]
-        L.lc_desensitize_process.restype = i32
-        L.lc_desensitize_process.argtypes = [vp, vp]
-        L.lc_desensitize_counters.restype = i32
-        L.lc_desensitize_counters.argtypes = [vp, ctypes.POINTER(u64)]
-        L.lc_desensitize_set_alarm_sink.restype = None
-        L.lc_desensitize_set_alarm_sink.argtypes = [vp, vp, vp]
         L.lc_desensitize_engine.restype = vp
         L.lc_desensitize_engine.argtypes = [vp]
         L.lc_desensitize_rounds.restype = u64
         L.lc_desensitize_rounds.argtypes = [vp]
-        L.lc_free.argtypes = [vp]
+        bind_plugin(L, "lc_desensitize")
         L._lc_desensitize_bound = True
     return L
 
@@ -138,46 +125,14 @@ class GpuDesensitize:
             pass
 
 
-class DesensitizeProcessor:
-    """processor_desensitize_gpu; same config keys as processor_desensitize_native"""
+class DesensitizeProcessor(PluginProcessor):
+    """processor_desensitize_gpu; same config keys as processor_desensitize_native.  collect_alarms(): kind 1 a search gave up, kind 3 a
+    failed trip."""
+    PREFIX, PLUGIN = "lc_desensitize", "processor_desensitize_gpu"
+    _lib = staticmethod(_lib)
 
     def __init__(self, config):
-        text = config if isinstance(config, str) else json.dumps(config)
-        self._L = _lib()
-        h = ctypes.c_void_p()
-        err = ctypes.create_string_buffer(512)
-        rc = self._L.lc_desensitize_create(text.encode("utf-8"), ctypes.byref(h), err, 512)
-        if rc != binding.LC_OK:
-            raise ProcessorInitError(err.value.decode("utf-8", "replace"))
-        self._h = h
-
-    def warnings(self):
-        p = self._L.lc_desensitize_warnings(self._h)
-        try:
-            return [w for w in ctypes.string_at(p).decode("utf-8").split("\n") if w]
-        finally:
-            self._L.lc_free(p)
-
-    def process(self, group: EventGroup):
-        """raises on a failed trip: the group is then untouched and must not be forwarded"""
-        rc = self._L.lc_desensitize_process(self._h, group._h)
-        if rc == binding.LC_ERR_NO_DEVICE:
-            raise binding.GpuUnavailableError("processor_desensitize_gpu: no usable HIP device (no CPU path)")
-        if rc != binding.LC_OK:
-            raise RuntimeError("lc_desensitize_process rc=%d" % rc)
-
-    def collect_alarms(self):
-        """-> the list that receives (kind, message bytes): kind 1 a search gave up, kind 3 a failed trip"""
-        out = []
-        proto = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
-        self._alarm_cb = proto(lambda user, kind, msg, n: out.append((kind, ctypes.string_at(msg, n))))
-        self._L.lc_desensitize_set_alarm_sink(self._h, ctypes.cast(self._alarm_cb, ctypes.c_void_p), None)
-        return out
-
-    def counters(self):
-        buf = (ctypes.c_uint64 * len(COUNTER_NAMES))()
-        self._L.lc_desensitize_counters(self._h, buf)
-        return dict(zip(COUNTER_NAMES, [int(x) for x in buf]))
+        self._create(config)
 
     def rounds(self):
         return int(self._L.lc_desensitize_rounds(self._h))
@@ -186,14 +141,3 @@ class DesensitizeProcessor:
         out = binding.LcRegexInfo()
         binding._check(self._L.lc_regex_info(self._L.lc_desens_regex(self._L.lc_desensitize_engine(self._h)), ctypes.byref(out)), "lc_regex_info")
         return {k: getattr(out, k) for k, _ in binding.LcRegexInfo._fields_}
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.lc_desensitize_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -2,12 +2,11 @@
 JsonProcessor the processor_parse_json_gpu plugin over event groups (same shape as processor.Processor).  There is no CPU path: every
 walk needs a HIP device and raises otherwise."""
 import ctypes
-import json
 
 import numpy as np
 
 from . import binding
-from .processor import COUNTER_NAMES, EventGroup, ProcessorInitError, _lib as _processor_lib
+from .processor import PluginProcessor, bind_plugin, _lib as _processor_lib
 
 LC_JSON_FAIL, LC_JSON_OK, LC_JSON_EMPTY, LC_JSON_DEEP = 0, 1, 2, 3
 LC_JSON_STRING, LC_JSON_INT, LC_JSON_DOUBLE, LC_JSON_TRUE, LC_JSON_FALSE, LC_JSON_NULL, LC_JSON_OBJECT, LC_JSON_ARRAY = range(8)
@@ -24,18 +23,9 @@ def _lib():
         L.lc_json_walk_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp, vp, vp]
         L.lc_json_walk_host.restype = i32
         L.lc_json_walk_host.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_uint64)]
-        L.lc_json_processor_create.restype = i32
-        L.lc_json_processor_create.argtypes = [cp, ctypes.POINTER(vp), cp, sz]
-        L.lc_json_processor_destroy.argtypes = [vp]
-        L.lc_json_processor_warnings.restype = vp
-        L.lc_json_processor_warnings.argtypes = [vp]
-        L.lc_json_processor_process.restype = i32
-        L.lc_json_processor_process.argtypes = [vp, vp]
         L.lc_json_processor_set_first_trip_members.restype = None
         L.lc_json_processor_set_first_trip_members.argtypes = [vp, u32]
-        L.lc_json_processor_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
-        L.lc_json_processor_set_alarm_sink.restype = None
-        L.lc_json_processor_set_alarm_sink.argtypes = [vp, vp, vp]
+        bind_plugin(L, "lc_json_processor")
         L._lc_json_bound = True
     return L
 
@@ -74,55 +64,13 @@ class GpuJson:
         return status, nmembers, errpos, records, shadow, int(moved.value)
 
 
-class JsonProcessor:
-    """processor_parse_json_gpu; same config keys as processor_parse_json_native."""
+class JsonProcessor(PluginProcessor):
+    """processor_parse_json_gpu; same config keys as processor_parse_json_native.  collect_alarms(): every PARSE_LOG_FAIL_ALARM the
+    reference would raise."""
+    PREFIX, PLUGIN = "lc_json_processor", "processor_parse_json_gpu"
+    _lib = staticmethod(_lib)
 
     def __init__(self, config, first_trip_members=0):
-        text = config if isinstance(config, str) else json.dumps(config)
-        self._L = _lib()
-        h = ctypes.c_void_p()
-        err = ctypes.create_string_buffer(512)
-        rc = self._L.lc_json_processor_create(text.encode("utf-8"), ctypes.byref(h), err, 512)
-        if rc != binding.LC_OK:
-            raise ProcessorInitError(err.value.decode())
-        self._h = h
+        self._create(config)
         if first_trip_members:
-            self._L.lc_json_processor_set_first_trip_members(h, first_trip_members)
-
-    def warnings(self):
-        p = self._L.lc_json_processor_warnings(self._h)
-        try:
-            return [w for w in ctypes.string_at(p).decode("utf-8").split("\n") if w]
-        finally:
-            self._L.lc_free(p)
-
-    def process(self, group: EventGroup):
-        rc = self._L.lc_json_processor_process(self._h, group._h)
-        if rc == binding.LC_ERR_NO_DEVICE:
-            raise binding.GpuUnavailableError("processor_parse_json_gpu: no usable HIP device (no CPU path)")
-        if rc != binding.LC_OK:
-            raise RuntimeError("lc_json_processor_process rc=%d" % rc)
-
-    def collect_alarms(self):
-        """-> the list that receives (kind, message bytes) for every PARSE_LOG_FAIL_ALARM the reference would raise"""
-        out = []
-        proto = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
-        self._alarm_cb = proto(lambda user, kind, msg, n: out.append((kind, ctypes.string_at(msg, n))))
-        self._L.lc_json_processor_set_alarm_sink(self._h, ctypes.cast(self._alarm_cb, ctypes.c_void_p), None)
-        return out
-
-    def counters(self):
-        buf = (ctypes.c_uint64 * len(COUNTER_NAMES))()
-        self._L.lc_json_processor_counters(self._h, buf)
-        return dict(zip(COUNTER_NAMES, [int(x) for x in buf]))
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.lc_json_processor_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+            self._L.lc_json_processor_set_first_trip_members(self._h, first_trip_members)

@@ -149,6 +149,77 @@ class EventGroup:
             pass
 
 
+def bind_plugin(L, prefix):
+    """the six prototypes every parse plugin has: <prefix>_create, _destroy, _warnings, _process, _counters, _set_alarm_sink"""
+    vp, cp, sz = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t
+    for name, restype, argtypes in (("create", ctypes.c_int, [cp, ctypes.POINTER(vp), cp, sz]), ("destroy", None, [vp]), ("warnings", vp, [vp]),
+                                    ("process", ctypes.c_int, [vp, vp]), ("counters", ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_uint64)]),
+                                    ("set_alarm_sink", None, [vp, vp, vp])):
+        fn = getattr(L, "%s_%s" % (prefix, name))
+        fn.restype, fn.argtypes = restype, argtypes
+    L.lc_free.argtypes = [vp]
+
+
+class PluginProcessor:
+    """What the plugins over event groups share (same shape as Processor).  A subclass names PREFIX, the C prefix bind_plugin() took,
+    and PLUGIN, the plugin's name; sets _lib to its module's _lib; and opens its handle with _create()."""
+    PREFIX = PLUGIN = None
+    _lib = staticmethod(_lib)
+
+    def _call(self, name, *args):
+        return getattr(self._L, "%s_%s" % (self.PREFIX, name))(*args)
+
+    def _create(self, config, *args, create="create"):
+        """<PREFIX>_<create>(config, *args, &handle, err, 512)"""
+        text = config if isinstance(config, str) else json.dumps(config)
+        self._L = self._lib()
+        h = ctypes.c_void_p()
+        err = ctypes.create_string_buffer(512)
+        rc = self._call(create, text.encode("utf-8"), *args, ctypes.byref(h), err, 512)
+        if rc != binding.LC_OK:
+            raise ProcessorInitError(err.value.decode("utf-8", "replace"))
+        self._h = h
+
+    def warnings(self):
+        p = self._call("warnings", self._h)
+        try:
+            return [w for w in ctypes.string_at(p).decode("utf-8").split("\n") if w]
+        finally:
+            self._L.lc_free(p)
+
+    def process(self, group: EventGroup):
+        """raises on a failed trip: the group is then untouched and must not be forwarded"""
+        rc = self._call("process", self._h, group._h)
+        if rc == binding.LC_ERR_NO_DEVICE:
+            raise binding.GpuUnavailableError("%s: no usable HIP device (no CPU path)" % self.PLUGIN)
+        if rc != binding.LC_OK:
+            raise RuntimeError("%s_process rc=%d" % (self.PREFIX, rc))
+
+    def collect_alarms(self):
+        """-> the list that receives (kind, message bytes) for every alarm the plugin raises"""
+        out = []
+        proto = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
+        self._alarm_cb = proto(lambda user, kind, msg, n: out.append((kind, ctypes.string_at(msg, n))))
+        self._call("set_alarm_sink", self._h, ctypes.cast(self._alarm_cb, ctypes.c_void_p), None)
+        return out
+
+    def counters(self):
+        buf = (ctypes.c_uint64 * len(COUNTER_NAMES))()
+        self._call("counters", self._h, buf)
+        return dict(zip(COUNTER_NAMES, [int(x) for x in buf]))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._call("destroy", self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Processor:
     """processor_parse_regex_gpu; same config keys as processor_parse_regex_native."""
 

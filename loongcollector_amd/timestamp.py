@@ -2,12 +2,11 @@
 host memory, also straight from a parser's capture table), TimestampProcessor the processor_parse_timestamp_gpu plugin over event groups
 (same shape as processor.Processor).  There is no CPU path: every parse needs a HIP device and raises otherwise."""
 import ctypes
-import json
 
 import numpy as np
 
 from . import binding
-from .processor import COUNTER_NAMES, EventGroup, ProcessorInitError, _lib as _processor_lib
+from .processor import PluginProcessor, bind_plugin, _lib as _processor_lib
 
 LC_TS_OK, LC_TS_HAS_YEAR, LC_TS_DST, LC_TS_EPOCH, LC_TS_ABSENT = 1, 2, 4, 8, 0x80
 LC_TS_MAX_PROGRAM = 64
@@ -38,17 +37,10 @@ def _lib():
         L.lc_timestamp_zone_seconds.restype = ctypes.c_int64
         L.lc_timestamp_zone_seconds.argtypes = [ctypes.c_int64, i32]
         L.lc_timestamp_zone_reset.restype = None
-        L.lc_timestamp_processor_create.restype = i32
-        L.lc_timestamp_processor_create.argtypes = [cp, ctypes.POINTER(vp), cp, sz]
         L.lc_timestamp_processor_create_with_clock.restype = i32
         L.lc_timestamp_processor_create_with_clock.argtypes = [cp, vp, vp, ctypes.POINTER(vp), cp, sz]
-        L.lc_timestamp_processor_destroy.argtypes = [vp]
-        L.lc_timestamp_processor_warnings.restype = vp
-        L.lc_timestamp_processor_warnings.argtypes = [vp]
         L.lc_timestamp_processor_zone_offset.restype = ctypes.c_int32
         L.lc_timestamp_processor_zone_offset.argtypes = [vp]
-        L.lc_timestamp_processor_process.restype = i32
-        L.lc_timestamp_processor_process.argtypes = [vp, vp]
         L.lc_timestamp_processor_set_clock.restype = None
         L.lc_timestamp_processor_set_clock.argtypes = [vp, vp, vp]
         L.lc_timestamp_processor_set_discard.restype = None
@@ -57,11 +49,9 @@ def _lib():
         L.lc_timestamp_processor_set_plain_walk.argtypes = [vp, i32]
         L.lc_timestamp_processor_walk_stats.restype = None
         L.lc_timestamp_processor_walk_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
-        L.lc_timestamp_processor_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
         L.lc_timestamp_processor_history_failures.restype = ctypes.c_uint64
         L.lc_timestamp_processor_history_failures.argtypes = [vp]
-        L.lc_timestamp_processor_set_alarm_sink.restype = None
-        L.lc_timestamp_processor_set_alarm_sink.argtypes = [vp, vp, vp]
+        bind_plugin(L, "lc_timestamp_processor")
         L._lc_timestamp_bound = True
     return L
 
@@ -137,61 +127,24 @@ class GpuStrptime:
             pass
 
 
-class TimestampProcessor:
-    """processor_parse_timestamp_gpu; same config keys as processor_parse_timestamp_native.  clock: a callable returning epoch seconds
-    ("now" of the year deduction and of the discard rule); default time()."""
+class _ClockedProcessor(PluginProcessor):
+    """a plugin created with a clock: a callable returning epoch seconds; default time().  Its counters carry history_failure_total."""
 
     def __init__(self, config, clock=None):
-        text = config if isinstance(config, str) else json.dumps(config)
-        self._L = _lib()
-        h = ctypes.c_void_p()
-        err = ctypes.create_string_buffer(512)
         self._clock = CLOCK(lambda user: int(clock())) if clock is not None else None
-        rc = self._L.lc_timestamp_processor_create_with_clock(
-            text.encode("utf-8"), ctypes.cast(self._clock, ctypes.c_void_p) if self._clock else None, None, ctypes.byref(h), err, 512)
-        if rc != binding.LC_OK:
-            raise ProcessorInitError(err.value.decode())
-        self._h = h
+        self._create(config, ctypes.cast(self._clock, ctypes.c_void_p) if self._clock else None, None, create="create_with_clock")
 
-    def warnings(self):
-        p = self._L.lc_timestamp_processor_warnings(self._h)
-        try:
-            return [w for w in ctypes.string_at(p).decode("utf-8").split("\n") if w]
-        finally:
-            self._L.lc_free(p)
+    def counters(self):
+        d = PluginProcessor.counters(self)
+        d["history_failure_total"] = int(self._call("history_failures", self._h))
+        return d
+
+
+class TimestampProcessor(_ClockedProcessor):
+    """processor_parse_timestamp_gpu; same config keys as processor_parse_timestamp_native.  clock: "now" of the year deduction and of
+    the discard rule.  collect_alarms(): kind 0 PARSE_TIME_FAIL_ALARM, kind 1 OUTDATED_LOG_ALARM."""
+    PREFIX, PLUGIN = "lc_timestamp_processor", "processor_parse_timestamp_gpu"
+    _lib = staticmethod(_lib)
 
     def set_discard(self, enabled=True, interval=43200, onetime=False):
         self._L.lc_timestamp_processor_set_discard(self._h, int(enabled), interval, int(onetime))
-
-    def process(self, group: EventGroup):
-        rc = self._L.lc_timestamp_processor_process(self._h, group._h)
-        if rc == binding.LC_ERR_NO_DEVICE:
-            raise binding.GpuUnavailableError("processor_parse_timestamp_gpu: no usable HIP device (no CPU path)")
-        if rc != binding.LC_OK:
-            raise RuntimeError("lc_timestamp_processor_process rc=%d" % rc)
-
-    def collect_alarms(self):
-        """-> the list that receives (kind, message bytes): kind 0 PARSE_TIME_FAIL_ALARM, kind 1 OUTDATED_LOG_ALARM"""
-        out = []
-        proto = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
-        self._alarm_cb = proto(lambda user, kind, msg, n: out.append((kind, ctypes.string_at(msg, n))))
-        self._L.lc_timestamp_processor_set_alarm_sink(self._h, ctypes.cast(self._alarm_cb, ctypes.c_void_p), None)
-        return out
-
-    def counters(self):
-        buf = (ctypes.c_uint64 * len(COUNTER_NAMES))()
-        self._L.lc_timestamp_processor_counters(self._h, buf)
-        d = dict(zip(COUNTER_NAMES, [int(x) for x in buf]))
-        d["history_failure_total"] = int(self._L.lc_timestamp_processor_history_failures(self._h))
-        return d
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.lc_timestamp_processor_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

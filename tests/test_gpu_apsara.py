@@ -227,3 +227,56 @@ def test_64k_random_lines():
     compare(lines, W, got, "random")
     got = apsara.parse_host(lines[:4096], W, fill=SENT)
     compare(lines[:4096], W, got, "random, host entry")
+
+
+# ---------------------------------------------------------------------------------------------- the host entry's chunk limits
+def _host_equals_device(lines, W):
+    """lc_apsara_parse_host against lc_apsara_parse_device over the same packed lines, on every output array; of the pairs the first
+    min(npairs, W) of a line, and behind them the caller's array still holds the fill byte"""
+    torch = _torch()
+    from loongcollector_amd import apsara
+    dev = device_parse(torch, lines, W)
+    got = apsara.parse_host(lines, W, fill=SENT)
+    for k in ("status", "secs", "nanos", "base", "npairs"):
+        assert np.array_equal(got[k].astype(np.int64), dev[k].astype(np.int64) % 2 ** 32 if got[k].dtype == np.uint32 else dev[k]), k
+    live = np.arange(W)[None, :] < np.minimum(got["npairs"], W)[:, None]
+    assert np.array_equal(got["pairs"][live], dev["pairs"][live])
+    assert (got["pairs"][~live].view(np.uint8) == SENT & 0xFF).all(), "a pair behind the count was written"
+    compare(lines[:8] + lines[-8:], W, {k: np.concatenate([v[:8], v[-8:]]) for k, v in got.items()}, "host entry, both ends")
+    return got
+
+
+def test_parse_host_second_chunk_behind_two_to_the_18_lines():
+    n = (1 << 18) + 1
+    lines = [D + b"\t[INFO]\tk:%d" % (i % 1000) if i % 7 else b"[1378972171093]\tm:%d\tn:2\to:3" % (i % 10) for i in range(n)]
+    lines[n - 1] = b"[1378972170425093]\tlast:one\tz:9"           # (the one-line second chunk; W = 4 keeps the result cap out of it)
+    got = _host_equals_device(lines, 4)
+    assert (int(got["status"][n - 1]), int(got["secs"][n - 1]), int(got["nanos"][n - 1]), int(got["npairs"][n - 1])) == (3, 1378972170, 425093000, 2)
+    assert got["pairs"][n - 1][:2].tolist() == [[19, 23, 27], [28, 29, 31]] and (got["base"][n - 1] == -1).all()
+
+
+def test_parse_host_forty_lines_of_one_mib_cross_the_payload_limit():
+    head = D + b"\t[INFO]"
+    lines = []
+    for i in range(40):
+        if i % 2:     # more pairs than W: the count is the true one, W of them come back
+            m = ((1 << 20) - len(head) - 3) // 8
+            body = head + b"\tkk:vvvv" * m
+            body += b"\tp:" + b"x" * ((1 << 20) - len(body) - 3)
+        else:
+            body = head + b"\tk:" + b"v" * ((1 << 20) - len(head) - 3)
+        assert len(body) == 1 << 20
+        lines += [body, D + b"\t[WARN]\ts:%d" % i, b""]
+    got = _host_equals_device(lines, 4)
+    assert [int(c) for c in got["npairs"][:6]] == [1, 1, 0, ((1 << 20) - len(head) - 3) // 8 + 1, 1, 0]
+    assert [int(s) for s in got["status"][:6]] == [5, 5, 0, 5, 5, 0]
+
+
+def test_parse_host_64_mib_of_results_per_chunk_at_w_8192():
+    # a line's results take W * 12 + 49 = 98353 bytes (pairs, base 32, secs 8, nanos 4, npairs 4, status 1): floor(64 MiB / 98353) = 682
+    # lines fill a chunk, line 682 opens the second
+    assert (64 << 20) // (8192 * 12 + 49) == 682
+    lines = [D + b"\t[INFO]" + b"".join(b"\tk%d:v%d" % (c, i) for c in range(1 + i % 5)) for i in range(700)]
+    got = _host_equals_device(lines, 8192)
+    assert [int(c) for c in got["npairs"][678:688]] == [1 + i % 5 for i in range(678, 688)]
+    assert got["pairs"][682][0].tolist() == [36, 38, 43] and got["pairs"][681][0].tolist() == [36, 38, 43]

@@ -329,3 +329,70 @@ def test_64k_random_lines(fmt):
     lines = [uniq[rng.randrange(len(uniq))] for _ in range(65536)]
     compare(fmt, lines, device_parse(torch, fmt, lines), "random")
     compare(fmt, lines[:4096], host_entry(fmt, lines[:4096]), "random, host entry", host_entry=True)
+
+
+# ---------------------------------------------------------------------------------------------- the host entry's chunk limits
+def _host_equals_device(fmt, lines):
+    """lc_container_log_parse_host against lc_container_log_parse_device over the same packed lines, on every output array; of the
+    shadow the host entry brings [rewrite_begin, content end) of every rewritten line that needs no replay, and nothing else"""
+    torch = _torch()
+    from loongcollector_amd import container_log
+    dev = device_parse(torch, fmt, lines)
+    got = container_log.parse_host(fmt, lines, fill=SENT)
+    for k in container_log.OUT_KEYS:
+        assert np.array_equal(got[k], dev[k]), k
+    at = np.concatenate([[0], np.cumsum([len(v) for v in lines])]).astype(np.int64)
+    want = np.full(int(at[-1]), SENT, np.uint8)
+    rewritten = 0
+    if fmt == cp.DOCKER:
+        moves = (got["status"] != cp.FAIL_JSON) & ((got["flags"] & (cp.ESCAPED | cp.REPLAY)) == cp.ESCAPED)
+        for i in np.flatnonzero(moves):
+            b, e = int(got["rewrite_begin"][i]), int(got["spans"][i][2][1])
+            want[at[i] + b:at[i] + e] = np.frombuffer(dev["shadow"][i][b:e], np.uint8)
+            rewritten += max(e - b, 0)
+    assert np.array_equal(got["shadow"], want)
+    assert got["moved"] >= rewritten and (got["moved"] > 0) == (rewritten > 0)
+    return got, at
+
+
+def test_parse_host_containerd_second_chunk_behind_two_to_the_18_lines():
+    n = (1 << 18) + 1
+    lines = [b"2026-10-19T10:00:%02d.5Z %s %sline %d" % (i % 60, b"stderr" if i % 7 == 0 else b"stdout", b"P " if i % 5 == 0 else b"F ", i % 1000)
+             for i in range(n)]
+    lines[n - 1] = b"2026-10-19T10:00:05.000000005Z stdout F line 5"
+    got, _ = _host_equals_device(cp.CONTAINERD, lines)
+    assert (int(got["status"][n - 1]), int(got["flags"][n - 1]), int(got["rewrite_begin"][n - 1])) == (0, 0, 0)
+    assert got["spans"][n - 1].tolist() == [[0, 30], [31, 37], [40, 46]]
+    assert int(got["flags"][n - 5]) == 2 and got["moved"] == 0           # (line 2^18 - 4: partial)
+
+
+def test_parse_host_docker_second_chunk_carries_an_escape_into_the_callers_shadow():
+    n = (1 << 18) + 1
+    lines = [b'{"log":"tab\\t%d\\n","stream":"stdout","time":"2026-10-19T10:00:05.5Z"}' % (i % 1000) if i % 5 == 0 else
+             b'{"log":"plain %d","stream":"stdout","time":"2026-10-19T10:00:05.5Z"}' % (i % 1000) for i in range(n)]
+    lines[n - 1] = b'{"log":"last\\tline\\n","stream":"stderr","time":"2026-10-19T10:00:05.5Z"}'     # (the one-line second chunk)
+    got, at = _host_equals_device(cp.DOCKER, lines)
+    assert (int(got["status"][n - 1]), int(got["flags"][n - 1]), int(got["rewrite_begin"][n - 1])) == (0, cp.ESCAPED | 1, 12)
+    assert got["spans"][n - 1].tolist() == [[48, 70], [32, 38], [8, 18]]
+    assert bytes(got["shadow"][at[n - 1] + 12:at[n - 1] + 18]) == b"\tline\n" and got["moved"] > 0
+    assert int(got["flags"][n - 2]) == 0 and int(got["flags"][n - 5]) == cp.ESCAPED
+
+
+@pytest.mark.parametrize("fmt", [cp.CONTAINERD, cp.DOCKER])
+def test_parse_host_forty_lines_of_one_mib_cross_the_payload_limit(fmt):
+    lines = []
+    for i in range(40):
+        if fmt == cp.CONTAINERD:
+            head = b"2026-10-19T10:00:05.5Z stdout F "
+            body = head + b"v" * ((1 << 20) - len(head))
+            lines += [body, b"2026-10-19T10:00:05.5Z stderr P s%d" % i, b""]
+        else:    # every other 1 MiB line escaped, at its end
+            tail = b'","stream":"stdout","time":"2026-10-19T10:00:05.5Z"}'
+            esc = b"\\t%d\\n" % i if i % 2 else b""
+            body = b'{"log":"' + b"v" * ((1 << 20) - 8 - len(esc) - len(tail)) + esc + tail
+            lines += [body, b'{"log":"s%d","stream":"stderr","time":"2026-10-19T10:00:05.5Z"}' % i, b""]
+        assert len(body) == 1 << 20
+    got, at = _host_equals_device(fmt, lines)
+    assert [int(s) for s in got["status"][:2]] == [0, 0] and int(got["status"][2]) != 0
+    if fmt == cp.DOCKER:
+        assert [int(f) & cp.ESCAPED for f in got["flags"][:6]] == [0, 0, 0, cp.ESCAPED, 0, 0] and got["moved"] > 0

@@ -404,3 +404,74 @@ def test_pass_through_handle():
     assert p.counters()["out_successful_events_total"] == 1
     eng = desensitize.GpuDesensitize("const", "pwd=", "[^,]+", r"\x", True)
     assert eng.pass_through and eng.apply_host([b"pwd=a,", b"b"])[0] == [None, None]
+
+
+# ---------------------------------------------------------------------------------------------- the host entry's chunk limits
+def _host_raw(eng, values):
+    """lc_desens_apply_host itself -> (flags, out_off uint64[n + 1], the output bytes); both arrays hold a sentinel beforehand"""
+    n = len(values)
+    blob = np.frombuffer(b"".join(values) + b"\0", np.uint8).copy()
+    lens = np.array([len(v) for v in values], np.uint32)
+    at = np.zeros(n, np.uint64)
+    at[1:] = np.cumsum(lens[:-1])
+    ptrs = (blob.ctypes.data + at).astype(np.uint64)
+    flags = np.full(n, SENT, np.uint8)
+    out_off = np.full(n + 1, 7, np.uint64)
+    out = ctypes.c_void_p()
+    rc = eng._L.lc_desens_apply_host(eng._h, ptrs.ctypes.data, lens.ctypes.data, n, flags.ctypes.data, out_off.ctypes.data, ctypes.byref(out), None)
+    assert rc == 0
+    try:
+        return flags, out_off, ctypes.string_at(out, int(out_off[n])) if out.value else b""
+    finally:
+        eng._L.lc_free(out)
+
+
+def _host_equals_device(eng, values, want):
+    """lc_desens_apply_host against lc_desens_apply_device over the same packed values (device_apply: into an output of exactly the
+    size `want` gives): the flags, every value's output bytes, and an out_off that is monotone over the whole call"""
+    torch = _torch()
+    dev, dev_flags, _ = device_apply(torch, eng, values, want)
+    flags, out_off, new = _host_raw(eng, values)
+    assert np.array_equal(flags, dev_flags)
+    assert np.array_equal(flags, np.array([dp.CHANGED if w is not None else 0 for w in want], np.uint8)), "the flags are not the model's"
+    assert int(out_off[0]) == 0 and np.array_equal(np.diff(out_off.astype(np.int64)), np.array([len(w) if w is not None else 0 for w in want], np.int64))
+    host = [new[int(out_off[i]):int(out_off[i + 1])] if flags[i] & dp.CHANGED else None for i in np.flatnonzero(flags)]
+    assert host == [dev[i] for i in np.flatnonzero(flags)]
+    return host, out_off
+
+
+@pytest.mark.parametrize("method", METHODS)
+def test_apply_host_second_chunk_behind_two_to_the_18_values(method):
+    from loongcollector_amd import desensitize
+    _, before, content, replacing = dp.RULE["pwd"]
+    rule = model.Rule(method, before, content, replacing, True)
+    eng = desensitize.GpuDesensitize(method, before, content, replacing, True)
+    n = (1 << 18) + 1
+    fill = [b"user=u%d ip=10.0.0.%d" % (k, k) for k in range(16)]
+    values = [fill[i % 16] for i in range(n)]
+    for i in (0, 3, 64, 4097, 200000):           # a handful in the first chunk ...
+        values[i] = b"v%d pwd=one%d, then pwd=two," % (i, i)
+    values[n - 1] = b"last pwd=secret9, and pwd=again"          # ... and the one-value second chunk
+    cache = {v: rule.apply(v) for v in set(values)}
+    want = [cache[v] for v in values]
+    assert [i for i, w in enumerate(want) if w is not None] == [0, 3, 64, 4097, 200000, n - 1]
+    host, out_off = _host_equals_device(eng, values, want)
+    assert host[-1] == want[n - 1] and host[:5] == [want[i] for i in (0, 3, 64, 4097, 200000)]
+    if method == "const":
+        assert host[-1] == b"last pwd=********, and pwd=********"
+    assert int(out_off[n - 1]) == sum(len(want[i]) for i in (0, 3, 64, 4097, 200000)) and int(out_off[n]) == int(out_off[n - 1]) + len(want[n - 1])
+
+
+def test_apply_host_forty_values_of_one_mib_cross_the_payload_limit():
+    from loongcollector_amd import desensitize
+    _, before, content, replacing = dp.RULE["pwd"]
+    eng = desensitize.GpuDesensitize("const", before, content, replacing, True)
+    values, want = [], []
+    for i in range(40):           # every other 1 MiB value with one match near its end
+        tail = b" pwd=topsecret%02d, end" % i if i % 2 else b""
+        body = b"x" * ((1 << 20) - len(tail)) + tail
+        assert len(body) == 1 << 20
+        values += [body, b"s%d pwd=k%d," % (i, i), b""]
+        want += [body.replace(b"topsecret%02d" % i, b"********") if i % 2 else None, b"s%d pwd=********," % i, None]
+    host, out_off = _host_equals_device(eng, values, want)
+    assert len(host) == 60 and int(out_off[-1]) == sum(len(w) for w in want if w is not None)
