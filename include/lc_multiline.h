@@ -63,7 +63,7 @@ void lc_multiline_free_records(lc_ml_record_t* r);
  *   mode      LC_ML_HAS_* of the patterns in use | LC_ML_DISCARD (UnmatchedContentTreatment discard) | LC_ML_FLUSH (the input ends
  *             here: the log under construction is emitted / handed to HandleUnmatchLogs, :288-298)
  *   d_start, d_cont, d_end   status bytes of the three match launches (NULL for a pattern that is not in use)
- *   d_nitems  optional device-side item count (<= max_items)
+ *   d_nitems  optional device-side item count (<= max_items; a larger value is clamped to max_items, both kernels read min of the two)
  *   d_off     the offsets[n+1] + one separator byte table of lc_split_lines_device: records are BYTE ranges of the source value and
  *             carry LC_ML_LAST as CreateNewEvent needs it; NULL: records are ITEM ranges (begin = first item, length = items)
  *   d_flags   max_items bytes of scratch; records / counts may be device or pinned host memory; at most record_cap records are

@@ -82,6 +82,8 @@ int boundsAndFetch(MlThread& T, uint32_t mode, const uint8_t* const status[3], c
         // atomic support -- and come down behind the kernels; the records are plain stores into the pinned block)
         LC_HIP_TRY(T.dSmall.ensure(256));
         uint32_t* dCounts = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(T.dSmall.p) + 128);
+        // (the launch log folds duplicate names: the repeated scan gets a name of its own, so that lc_launched_kernels() shows it)
+        if (attempt == 1) lcNoteKernel("ml_bounds_kernel[second attempt]");
         const int rc = lc_multiline_bounds_device(mode, status[0], status[1], status[2], dN, maxItems, dOff, nbytes,
                                                   static_cast<uint8_t*>(T.dFlags.p), hRecs, cap, dCounts, T.stream);
         if (rc != LC_OK) return rc;

@@ -161,10 +161,27 @@ ML_HAS_START, ML_HAS_CONT, ML_HAS_END, ML_DISCARD, ML_FLUSH = 1, 2, 4, 8, 16
 ML_LAST, ML_RUN = 0x80000000, 2
 
 
-def bounds_model(mode, flags, off=None, nbytes=0):
+def bounds_device(mode, d_start, d_cont, d_end, d_nitems, max_items, d_off, nbytes, d_flags, records, record_cap, counts, stream=None,
+                  check=True):
+    """lc_multiline_bounds_device on torch tensors: three uint8 status tensors, the uint32 item count, the line table and the flag
+    scratch on the device; `records` ((cap, 3) 32-bit words) on the device or in pinned host memory; `counts` (8 words) on the device.
+    Any of them may be None (a NULL pointer).  Asynchronous on `stream`.  -> the status code (check=False: not raised)"""
+    L = binding.load()
+    vp, u32 = ctypes.c_void_p, ctypes.c_uint32
+    L.lc_multiline_bounds_device.restype = ctypes.c_int
+    L.lc_multiline_bounds_device.argtypes = [u32, vp, vp, vp, vp, u32, vp, u32, vp, vp, u32, vp, vp]
+    ptr = lambda t: None if t is None else t.data_ptr()
+    rc = L.lc_multiline_bounds_device(mode, ptr(d_start), ptr(d_cont), ptr(d_end), ptr(d_nitems), max_items, ptr(d_off), nbytes,
+                                      ptr(d_flags), ptr(records), record_cap, ptr(counts), stream)
+    if check:
+        binding._check(rc, "lc_multiline_bounds_device")
+    return rc
+
+
+def bounds_model(mode, flags, off=None, nbytes=0, raw=False):
     """lc_multiline_bounds_model: the device scan's code run on the host, slice by slice.  flags: one byte per item (bit 0 start,
     bit 1 continue, bit 2 end matched); off: the offsets[n+1] + separator table (byte records) or None (item records).
-    -> (records [(begin, length, flags)], counts[8])"""
+    -> (records [(begin, length, flags)], counts[8]); raw=True: both as uint32 arrays ((records, 3) and (8,))"""
     import numpy as np
     L = binding.load()
     L.lc_multiline_bounds_model.restype = ctypes.c_int
@@ -179,4 +196,6 @@ def bounds_model(mode, flags, off=None, nbytes=0):
     rc = L.lc_multiline_bounds_model(mode, fl.ctypes.data if n else None, n, None if o is None else o.ctypes.data, nbytes,
                                      recs.ctypes.data, cap, counts.ctypes.data)
     binding._check(rc, "lc_multiline_bounds_model")
+    if raw:
+        return recs[:int(counts[3])], counts
     return [tuple(int(x) for x in r) for r in recs[:int(counts[3])]], [int(x) for x in counts]

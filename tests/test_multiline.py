@@ -282,22 +282,7 @@ def test_merge_processor_flag_mode():
 from loongcollector_amd import multiline as ML  # noqa: E402
 
 
-def _flags_and_table(o, val):
-    """what the device computes before the scan: the split kernels' line table and the three answers per line (here: the oracle's
-    regexes, line by line)"""
-    lines = val.split(b"\n")
-    if lines and lines[-1] == b"":
-        lines.pop()          # a trailing line feed does not open an empty last line (GetNextLine :382-392)
-    off, at = [], 0
-    for ln in lines:
-        off.append(at)
-        at += len(ln) + 1
-    off.append(at)           # len[i] = off[i+1] - off[i] - 1, also for an unterminated last line
-    hit = lambda rx, ln: 1 if (rx is not None and rx.prefixmatch(ln) is not None) else 0
-    flags = [hit(o.start, ln) | hit(o.cont, ln) << 1 | hit(o.end, ln) << 2 | (8 if not ln else 0) for ln in lines]
-    mode = (ML.ML_HAS_START if o.start else 0) | (ML.ML_HAS_CONT if o.cont else 0) | (ML.ML_HAS_END if o.end else 0) | \
-        (ML.ML_DISCARD if o.discard else 0) | ML.ML_FLUSH
-    return mode, flags, off
+from helpers.multiline_walk import POOL, SCAN_CONFIGS, flags_and_table as _flags_and_table  # noqa: E402  (shared with tests/test_multiline_walk.py)
 
 
 def _scan_equals_the_walk(config, val):
@@ -319,23 +304,6 @@ def _scan_equals_the_walk(config, val):
 def test_scan_model_reproduces_the_reference_unit_test_cases(vectors):
     for c in vectors["cases"]:
         _scan_equals_the_walk(c["config"], _value(vectors, c["in"]))
-
-
-SCAN_CONFIGS = [
-    {"StartPattern": r"\d{4}-\d{2}-\d{2} .*"},
-    {"StartPattern": r"\[\w+\]", "ContinuePattern": r"\s+at\s.*", "UnmatchedContentTreatment": "discard"},
-    {"StartPattern": r"\[\w+\]", "ContinuePattern": r"\s+at\s.*"},
-    {"StartPattern": "BEGIN", "EndPattern": r"END\d*$"},
-    {"StartPattern": "BEGIN", "EndPattern": r"END\d*$", "UnmatchedContentTreatment": "discard"},
-    {"ContinuePattern": r"\s+.*", "EndPattern": r"\}"},
-    {"ContinuePattern": r"\s+.*", "EndPattern": r"\}", "UnmatchedContentTreatment": "discard"},
-    {"EndPattern": ";$", "UnmatchedContentTreatment": "discard"},
-    {"EndPattern": ";$"},
-    {"StartPattern": r"\[\w+\].*", "ContinuePattern": r"\s+at\s.*", "EndPattern": r"\}$"},
-    {"StartPattern": ".*"},
-]
-POOL = [b"2024-01-04 boom", b"  at com.example.A.b(A.java:1)", b"[ERROR] x", b"BEGIN tx", b"END7", b"END", b"END7x", b"}x", b"}", b"{",
-        b"stmt;", b"noise", b"", b"\tcontinued", b"2024-13-99 not checked"]
 
 
 @pytest.mark.parametrize("config", SCAN_CONFIGS)
