@@ -17,7 +17,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -26,6 +25,7 @@
 #include <vector>
 
 #include "grok_kernel.hpp"
+#include "grok_plan_host.hpp"
 #include "grok_plan_kernel.hpp"
 #include "grok_runtime.hpp"
 #include "group_combiner.hpp"
@@ -678,96 +678,263 @@ int grokPlanPhase1(const std::vector<GrokDevicePattern>& patterns, GrokDeviceSta
     return LC_OK;
 }
 
-// host view of one active entry of the batch
-struct PlanEntry {
-    uint32_t p = 0, cand = 0, capsRow = 0, columns = 0, rounds = 0, ran = 0;
-    bool second = false;  // level > 0
-    uint32_t level = 0;   // 0: evaluated at once; L > 0: most of its candidates have an EARLIER candidate entry (of level < L) -- it waits
-                          // for those and only looks at the values none of them has won (a general format behind specific ones)
-    bool queued = false;  // rounds behind the first match were queued for this entry
+static_assert(grokplan::CW_UNANCHORED == GC_UNANCHORED && grokplan::CW_ROUND0 == GC_ROUND0 && grokplan::CW_BOUND == GC_BOUND &&
+                  grokplan::CW_WIDE == GC_WIDE && grokplan::CW_OVERFLOW == GC_OVERFLOW && grokplan::CW_REMAINDER == GC_REMAINDER &&
+                  grokplan::CW_FILTERED == GC_FILTERED && grokplan::CW_WORDS == GC_WORDS,
+              "grok_plan_host.hpp names the counter words of grok_plan_kernel.hpp");
+static_assert(HW_FIRST - HW_CAND == grokplan::PW_FIRST && HW_SHADOW - HW_CAND == grokplan::PW_SHADOW && kPlanWords == grokplan::PW_WORDS &&
+                  kGrokMaxRounds == grokplan::kMaxRounds && uint32_t(kGrokMaxStreams) == grokplan::kMaxStreams,
+              "grok_plan_host.hpp reads the plan words as phase 1 lays them out");
+
+// host view of one active entry of the batch: the planner's part (grok_plan_host.hpp), then the entry's arrays
+struct PlanEntry : grokplan::Entry {
+    uint32_t capsRow = 0, columns = 0;
+    uint32_t ran = 0;        // rounds the entry ran, when it had to go on behind the ones queued for it
     bool wideFirst = false;  // round 0 ran nfa_wide_kernel over every candidate (the entry's history says its values overflow 64 threads)
-    uint32_t seq0 = 0;    // launch sequence of round 0's first-chance kernel (lcMatchSecondChanceOnStream)
-    uint32_t seqS = 0;    // ... and of the search proper's (phase 2c)
+    uint32_t seq0 = 0;       // launch sequence of round 0's first-chance kernel (lcMatchSecondChanceOnStream)
+    uint32_t seqS = 0;       // ... and of the search proper's
     const GrokScreenDev* remainderScreen = nullptr;  // the entry's screen (host copy), walked over what is left behind a first match
-    int stream = 0;
-    double cost = 0, cost0 = 0, cost1 = 0;  // heuristic; measured round 0 / leftovers (ns, 0 = unknown)
-    GrokEntryDev dev{};
-    uint32_t *listA = nullptr, *listB = nullptr, *unanchored = nullptr;
+    GrokEntryDev dev{};      // the entry's row of the device table; its arrays lie in the thread's arena
+    uint32_t* listB = nullptr;
     int32_t* caps = nullptr;
     uint8_t* status = nullptr;
 };
 
-int grokMatchSpeculative(const std::vector<GrokDevicePattern>& patterns, GrokDeviceState* state, const GrokOptions& opts, uint32_t row,
-                         const uint8_t* d_data, const uint32_t* d_off, const uint32_t* d_len, uint32_t n, int32_t* d_pattern,
-                         int32_t* d_first, int32_t* d_extra, uint32_t extraCap, uint32_t* d_nextra, void* d_scratch, hipStream_t st,
-                         int dev) {
-    GrokBatchStats& stats = tlsStats;
-    const uint32_t nP = uint32_t(patterns.size());
-    static const uint32_t envStreams = [] {  // LC_GROK_STREAMS overrides the handle's option (A/B measurements)
-        const char* e = getenv("LC_GROK_STREAMS");
-        return uint32_t(e ? atoi(e) : 0);
-    }();
-    const uint32_t nStreams = std::max(1u, std::min<uint32_t>(envStreams ? envStreams : opts.streams, kGrokMaxStreams));
+// The knobs of the speculative path, read in ONE place.  Per batch -- the GPU tests flip them between batches of one process --
+// except the three at the end.
+grokplan::Knobs grokReadKnobs() {
+    auto text = [](const char* name) { return getenv(name); };
+    auto num = [&](const char* name, int dflt) { return text(name) ? atoi(text(name)) : dflt; };
+    grokplan::Knobs k;
+    k.wideFirst = num("LC_GROK_WIDE_FIRST", 1);
+    k.earlyRounds = num("LC_GROK_EARLY_ROUNDS", 1);
+    k.flat = !(text("LC_GROK_FLAT") && text("LC_GROK_FLAT")[0] == '0');
+    k.remainderLiteral = num("LC_GROK_REMAINDER_LITERAL", 1) != 0;
+    k.remainderWon = num("LC_GROK_REMAINDER_WON", 1) != 0;
+    k.screenScaled = num("LC_GROK_SCREEN_SCALED", 1) != 0;
+    k.fusedStage = text("LC_GROK_FUSED_STAGE") ? (num("LC_GROK_FUSED_STAGE", 0) != 0 ? 1 : 0) : -1;
+    static const uint32_t streams = uint32_t(num("LC_GROK_STREAMS", 0));  // overrides the handle's option (A/B measurements)
+    static const bool trace = text("LC_GROK_TRACE") != nullptr;
+    static const bool remSplit = text("LC_GROK_REM_SPLIT") != nullptr;  // diagnosis: one launch pair per entry (a kernel trace then times each)
+    k.streams = streams;
+    k.trace = trace;
+    k.remSplit = remSplit;
+    return k;
+}
+
+// One batch on the speculative path: what the call was given, the thread's resources, the plan, and one method per phase.
+// grokMatchSpeculative (below) is the sequence of the phases.
+struct GrokBatch {
+    // ---- the call (the arguments of grokMatchSpeculative, in their order)
+    const std::vector<GrokDevicePattern>& patterns;
+    GrokDeviceState* state;
+    const GrokOptions& opts;
+    uint32_t row;
+    const uint8_t* d_data;
+    const uint32_t *d_off, *d_len;
+    uint32_t n;
+    int32_t *d_pattern, *d_first, *d_extra;
+    uint32_t extraCap;
+    uint32_t* d_nextra;
+    void* d_scratch;
+    hipStream_t st;
+    int dev;
+    // ---- the thread's resources, the knobs, the plan
     PlanThread& T = tlsPlan;
-    {
-        int rc = T.ensure(dev, nStreams);
-        if (rc != LC_OK) return rc;
-    }
-    static const bool trace = getenv("LC_GROK_TRACE") != nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
-    auto msNow = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); };
-
-    // ---- phase 1: length order, literal index, all screens, candidate counts (grokPlanPhase1)
+    GrokBatchStats& stats = tlsStats;
+    const grokplan::Knobs K = grokReadKnobs();
+    uint32_t nStreams = 1, used = 1;  // worker streams allowed / in use (min(nStreams, nAct))
     GrokPhase1 P1;
-    {
-        int rc = grokPlanPhase1(patterns, state, T, row, d_data, d_off, d_len, n, d_first, d_nextra, d_scratch, st, dev, 2, &P1);
-        if (rc != LC_OK) return rc;
-    }
-    uint32_t* const winner = P1.winner;
-    uint32_t* const undecided = P1.undecided;
-    uint32_t* const order = P1.order;
-    uint64_t* const masks = P1.masks;
-    const uint32_t* const literalIndex = P1.literalIndex;
-    const uint32_t nScreens = P1.nScreens;
-    const bool small = P1.small;
-    uint32_t* tail = T.dTail;                                        // TW_* (the entries' counters behind them: one block, one copy back)
-    const uint32_t gridAll = (n + kGrokPlanBlock - 1) / kGrokPlanBlock;
-    HIP_TRY(hipMemcpyAsync(T.hostWords + HW_CAND, T.dPlanWords, size_t(kPlanWords) * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(syncCounted(st));  // sync 1: candidates per entry
-    const double tPhase1 = msNow();
+    uint32_t *winner = nullptr, *undecided = nullptr;
+    const uint32_t *remLiteral = nullptr, *remWinner = nullptr;  // what grok_remainder_literal_kernel gets (both nullptr: it is not launched)
+    std::vector<PlanEntry> act;  // the active entries, in the order of the device table
+    uint32_t nAct = 0, nSecond = 0, maxCand = 0;
+    GrokSlotMap map;
+    int32_t* xtmp = nullptr;  // extra rows wanted: [xcap][xstride], at the head of the arena
+    uint32_t xcap = 0, xstride = 0;
+    uint32_t *gate = nullptr, *xcount = nullptr;
+    bool calibrate = false;      // a calibration batch: the entries' launches are timed with events
+    bool aheadLaunched = false;  // the remainder screens went out ahead of sync 2
+    uint8_t order1[grokplan::kMaxEntries] = {};  // the leftovers deal's order: the chains are queued in it
+    grokplan::Chains chains;
+    // (round 6) A worker stream waits for the fork when it first GETS work (W), and only the streams that got any are joined: a
+    // phase forks into sixteen streams and usually uses three, and the thirteen idle ones cost the host 26 calls per fork / join
+    // and the batch's stream thirteen barrier packets that it works through one after the other (0.09 ms between the end of round
+    // 0 and the first kernel behind the join, profiles/round6_grok_timeline.txt).
+    uint32_t waitedMask = 0, touchedMask = 0;
+    std::chrono::steady_clock::time_point t0;
+    double tPhase1 = 0, tPhase3 = 0;
 
-    // ---- the batch's active entries and their arrays
-    std::vector<PlanEntry> act;
-    size_t arenaBytes = 0;
-    auto carve = [&](size_t bytes) {
-        const size_t at = arenaBytes;
-        arenaBytes += alignUp(bytes, 256);
-        return at;
-    };
-    const uint32_t xcap = std::max<uint32_t>(extraCap, n / 4 + 1024);
-    const uint32_t xstride = row + 3;
-    const size_t xtmpAt = carve(size_t(xcap) * xstride * 4);
-    struct Offsets {
-        size_t off, len, line, from, nmatch, first, listA, listB, unanchored, ovList, caps, status;
-    };
-    std::vector<Offsets> offs;
-    uint32_t levelOf[64] = {};
-    for (uint32_t p = 0; p < nP; ++p) {
-        const uint32_t c = T.hostWords[HW_CAND + p];
-        if (!c) continue;
+    double msNow() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+    uint32_t cnt(size_t a, uint32_t word) const { return T.hostWords[HW_CNT + a * GC_WORDS + word]; }
+    static uint32_t grid(uint32_t slots) { return (slots + kGrokPlanBlock - 1) / kGrokPlanBlock; }          // a lane per slot
+    static uint32_t waveGrid(uint32_t slots) { return (slots + kGrokPlanBlock / 64 - 1) / (kGrokPlanBlock / 64); }  // a wavefront per slot
+    lc_regex* firstOf(const PlanEntry& e) const { return patterns[e.p].anchored ? patterns[e.p].anchored : patterns[e.p].re; }  // round 0's automaton
+
+    int fork() {
+        HIP_TRY(hipEventRecord(T.fork, st));
+        waitedMask = 0;  // (everybody waits for THIS fork from now on; what was touched before stays to be joined)
+        return LC_OK;
+    }
+    hipStream_t W(int s) {  // (a failure surfaces at the join: hipGetLastError)
+        const uint32_t bit = 1u << uint32_t(s);
+        if (!(waitedMask & bit)) {
+            (void)hipStreamWaitEvent(T.workers[s], T.fork, 0);
+            waitedMask |= bit;
+        }
+        touchedMask |= bit;
+        return T.workers[s];
+    }
+    int join(int rc) {
+        lcSetDecideSlot(0);
+        if (rc == LC_OK && hipGetLastError() != hipSuccess) rc = lcHipFail(hipGetLastError(), "grok entry launch");
+        if (rc != LC_OK) {
+            for (uint32_t s = 0; s < used; ++s) (void)hipStreamSynchronize(T.workers[s]);
+            return rc;
+        }
+        for (uint32_t s = 0; s < used; ++s) {
+            if (!((touchedMask >> s) & 1u)) continue;
+            HIP_TRY(hipEventRecord(T.join[s], T.workers[s]));
+            HIP_TRY(hipStreamWaitEvent(st, T.join[s], 0));
+        }
+        touchedMask = 0;
+        return LC_OK;
+    }
+    // entry e's candidates as a launch sees them: `bound` of them at most, the count on the device, the list and the resume offsets
+    MatchBatch entryBatch(const PlanEntry& e, uint32_t bound, const uint32_t* count, const uint32_t* list, const uint32_t* resume, hipStream_t ws) const {
+        return MatchBatch{.d_data = d_data, .d_off = e.dev.off, .d_len = e.dev.len, .n = bound,
+                          .d_n = count,
+                          .d_order = list,
+                          .d_resume = resume,
+                          .ngroups = e.capsRow / 2, .d_caps = e.caps, .d_status = e.status, .dev = dev, .stream = ws};
+    }
+    // An entry whose values needed more than 64 threads in recent batches (GC_WIDE, noted behind the batch) goes WIDE FIRST: its
+    // first chance is nfa_wide_kernel over every candidate, and what is left behind it are the decide kernels alone.  Round 4's
+    // timeline: the longest entry's first chance 1.0 ms + its second chance (14 values restarted from byte 0) 1.1 ms, back to back
+    // on the critical path of the batch; now 1.1 ms.
+    bool wantsWideFirst(lc_regex* h) const {
+        if (!K.wideFirst || h->engine != LC_ENGINE_NFA || !lcNfaWideApplies(h)) return false;
+        if (K.wideFirst >= 2) return true;
+        return n <= kGrokWideFirstBatch && h->grokOverflowSeen.load(std::memory_order_relaxed) != 0;
+    }
+    // one engine call of entry e on stream ws: the first-chance kernel ...
+    int runFirst(PlanEntry& e, lc_regex* h, bool wide, const uint32_t* count, const uint32_t* list, bool withFrom, uint32_t* seq, hipStream_t ws) {
+        const MatchBatch b = entryBatch(e, e.cand, count, list, withFrom ? e.dev.from : nullptr, ws);
+        if (wide) return lcMatchWideFirstOnStream(0, h, h->engine, b, seq, e.dev.cnt + GC_WIDE);
+        return lcMatchFirstOnStream(h, h->engine, b, seq);
+    }
+    // ... and what is left behind it (note: the entry's GC_WIDE word, set when the wide kernel had anything to do)
+    int runSecond(PlanEntry& e, lc_regex* h, bool wide, const uint32_t* count, const uint32_t* list, bool withFrom, uint32_t seq, uint32_t* note,
+                  hipStream_t ws) {
+        const MatchBatch b = entryBatch(e, e.cand, count, list, withFrom ? e.dev.from : nullptr, ws);
+        if (wide) return lcMatchWideFirstOnStream(1, h, h->engine, b, &seq, nullptr);
+        lcSetWideNote(note);
+        const int r = lcMatchSecondChanceOnStream(h, h->engine, b, seq);
+        lcSetWideNote(nullptr);
+        return r;
+    }
+    // grok_post_kernel over `rows` entries of the table from `first` on (most: the largest of them): overflowed slots -> the entry's
+    // overflow list, slots the anchored search did not match -> its unanchored list, matches recorded, what is still in play -> listA
+    void post(hipStream_t ws, size_t first, size_t rows, uint32_t most, const uint32_t* in, const uint32_t* inCount, uint32_t flags,
+              unsigned long long skip) {
+        hipLaunchKernelGGL(grok_post_kernel, dim3(grid(most), uint32_t(rows)), dim3(kGrokPlanBlock), 0, ws, T.dEntries, uint32_t(first), in, inCount,
+                           flags, xtmp, xcap, xstride, xcount, skip);
+    }
+    // the values won so far (atomicMin per value: idempotent, the finish runs it again); one: that entry's alone
+    void wonSoFar(hipStream_t ws, uint32_t most, uint32_t rows, uint32_t one) {
+        hipLaunchKernelGGL(grok_entry_finish_kernel, dim3(grid(most), rows), dim3(kGrokPlanBlock), 0, ws, T.dEntries, winner, undecided,
+                           static_cast<const uint32_t*>(nullptr), one);
+    }
+    // The remainder screens of `rows` entries of the table from `first` on: the literal index over the remainders (and the slots of
+    // values an earlier entry has won dropped), then the entries' screens; the survivors are counted onto the gate word.  The other
+    // entries' workgroups leave at once (skip mask).  ahead: queued before the host has read round 0's counts -- the kernels test the
+    // entry's overflow / unanchored counts themselves.
+    void remainderScreens(hipStream_t ws, size_t first, uint32_t rows, uint32_t most, uint32_t lds, unsigned long long skip, bool ahead) {
+        const GrokEntryDev* entries = static_cast<const GrokEntryDev*>(T.dEntries) + first;
+        const uint32_t walk = (P1.small ? 1u : 0u) | (K.screenScaled ? 32u : 0u) | (ahead ? 64u : 0u);
+        if (remLiteral || remWinner) {
+            lcNoteKernel("grok_remainder_literal_kernel");
+            hipLaunchKernelGGL(grok_remainder_literal_kernel, dim3(waveGrid(most), rows), dim3(kGrokPlanBlock), 0, ws, d_data, entries, remLiteral, skip,
+                               remWinner, ahead ? 1u : 0u);
+        }
+        lcNoteKernel("grok_remainder_all_kernel");
+        hipLaunchKernelGGL(grok_remainder_all_kernel, dim3(grid(most), rows), dim3(kGrokPlanBlock), P1.small ? lds : 0, ws, d_data, entries,
+                           static_cast<const GrokScreenDev*>(T.dRemScreens) + first, walk, skip, gate);
+    }
+    void learn(std::atomic<uint32_t>& slot, hipEvent_t b, hipEvent_t e2, uint32_t cand) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, b, e2) != hipSuccess) {
+            (void)hipGetLastError();
+            return;
+        }
+        const uint32_t ns = uint32_t(std::min(4.0e9, std::max(1.0, double(ms) * 1e6 / std::max(1u, cand))));
+        const uint32_t old = slot.load(std::memory_order_relaxed);
+        slot.store(old ? (old + ns) / 2 : ns, std::memory_order_relaxed);
+    }
+
+    // ---- phase 1: length order, literal index, all screens, candidate counts (grokPlanPhase1) -> host (sync 1)
+    int phase1() {
+        nStreams = std::max(1u, std::min<uint32_t>(K.streams ? K.streams : opts.streams, kGrokMaxStreams));
+        if (const int rc = T.ensure(dev, nStreams); rc != LC_OK) return rc;
+        t0 = std::chrono::steady_clock::now();
+        if (const int rc = grokPlanPhase1(patterns, state, T, row, d_data, d_off, d_len, n, d_first, d_nextra, d_scratch, st, dev, 2, &P1); rc != LC_OK)
+            return rc;
+        winner = P1.winner;
+        undecided = P1.undecided;
+        remLiteral = K.remainderLiteral ? P1.literalIndex : nullptr;
+        remWinner = K.remainderWon ? winner : nullptr;
+        gate = T.dTail + TW_GATE;  // TW_* (the entries' counters behind them: one block, one copy back)
+        xcount = T.dTail + TW_XCOUNT;
+        HIP_TRY(hipMemcpyAsync(T.hostWords + HW_CAND, T.dPlanWords, size_t(kPlanWords) * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(syncCounted(st));  // sync 1: candidates per entry
+        tPhase1 = msNow();
+        return LC_OK;
+    }
+
+    // the entry's arrays, carved from the arena at `at` (arena == nullptr: only counted)
+    static void carveEntry(PlanEntry& e, uint8_t* arena, size_t& at) {
+        auto take = [&](size_t bytes) {
+            uint8_t* p = arena ? arena + at : nullptr;
+            at += alignUp(bytes, 256);
+            return p;
+        };
+        auto slots = [&] { return reinterpret_cast<uint32_t*>(take(size_t(e.cand) * 4)); };
+        e.dev.off = slots();
+        e.dev.len = slots();
+        e.dev.line = slots();
+        e.dev.from = slots();
+        e.dev.nmatch = slots();
+        e.dev.listA = slots();
+        e.listB = slots();
+        e.dev.unanchored = slots();
+        e.dev.ovList = slots();
+        e.dev.first = reinterpret_cast<int32_t*>(take(size_t(e.cand) * e.capsRow * 4));
+        e.dev.caps = e.caps = reinterpret_cast<int32_t*>(take(size_t(e.cand) * e.capsRow * 4));
+        e.dev.status = e.status = take(size_t(e.cand) + 16);
+    }
+    // what the planner is told about list entry p with c candidates, and what the launches need of it
+    PlanEntry describe(uint32_t p, uint32_t c) const {
+        const GrokDevicePattern& gp = patterns[p];
         PlanEntry e;
         e.p = p;
         e.cand = c;
-        e.columns = patterns[p].columns;
-        e.capsRow = 2 * (patterns[p].columns + 1);
-        e.rounds = std::max(1u, std::min(kGrokMaxRounds, patterns[p].re->grokRounds.load(std::memory_order_relaxed)));
+        e.columns = gp.columns;
+        e.capsRow = 2 * (gp.columns + 1);
+        // (round 0 is a phase of its own; round 1 reads the screened list)
+        e.rounds = std::max(2u, std::min(kGrokMaxRounds, gp.re->grokRounds.load(std::memory_order_relaxed)));
         for (const GrokScreenDev& sd : state->hostScreens[dev])
             if (sd.bit == p) e.remainderScreen = &sd;
-        e.rounds = std::max(2u, e.rounds);  // (round 0 is a phase of its own; round 1 reads the screened list)
-        const bool nfa = patterns[p].re->engine == LC_ENGINE_NFA;
-        e.cost = double(c) * (nfa ? (patterns[p].anchored ? 8.0 : 40.0) : 1.0);
+        const lc_regex* first = gp.anchored ? gp.anchored : gp.re;
+        e.anchored = gp.anchored != nullptr;
+        e.firstNfa = first->engine == LC_ENGINE_NFA;
+        e.reTdfa = gp.re->engine == LC_ENGINE_TDFA;
+        e.remainderSeen = gp.re->grokRemainderSeen.load(std::memory_order_relaxed) != 0;
+        // round 0 as a table walk: a complete automaton in global memory, or a lazy one (grok_plan_host.hpp assignLevels)
+        if (first->engine == LC_ENGINE_TDFA) e.tableWalk = !first->tdfaL2Blob.empty() && (first->preferWave || !first->hasTdfa);
+        else e.tableWalk = first->engine == LC_ENGINE_NFA && first->lazyReady.load(std::memory_order_acquire);
+        e.cost = double(c) * (gp.re->engine == LC_ENGINE_NFA ? (gp.anchored ? 8.0 : 40.0) : 1.0);
         // (measured, once a calibration batch has run: ns per candidate of round 0 and of the leftovers)
-        const uint32_t c0 = patterns[p].re->grokCost0Ns.load(std::memory_order_relaxed), c1 = patterns[p].re->grokCost1Ns.load(std::memory_order_relaxed);
+        const uint32_t c0 = gp.re->grokCost0Ns.load(std::memory_order_relaxed), c1 = gp.re->grokCost1Ns.load(std::memory_order_relaxed);
         e.cost0 = c0 ? double(c0) * c : 0.0;
         e.cost1 = c1 ? double(c1) * c : 0.0;
         // an automaton that walks its tables in global memory (tdfa_l2_kernel) takes as long as its LONGEST candidate -- one dependent
@@ -777,131 +944,335 @@ int grokMatchSpeculative(const std::vector<GrokDevicePattern>& patterns, GrokDev
         // (small batches only -- measured 6.36 -> 4.02 ms on 1000 values, 5.67 -> 6.34 ms on 16 Ki: the runtime maps the worker streams
         // onto a few hardware queues, and with thousands of candidates per entry the wide thread-list kernels, not these, are the
         // long poles; sharing half of the streams among these entries was worse for both sizes)
-        if (small && (walksGlobalTables(patterns[p].re) || walksGlobalTables(patterns[p].anchored))) e.cost += 1e12;
-        Offsets o;
-        o.off = carve(size_t(c) * 4);
-        o.len = carve(size_t(c) * 4);
-        o.line = carve(size_t(c) * 4);
-        o.from = carve(size_t(c) * 4);
-        o.nmatch = carve(size_t(c) * 4);
-        o.listA = carve(size_t(c) * 4);
-        o.listB = carve(size_t(c) * 4);
-        o.unanchored = carve(size_t(c) * 4);
-        o.ovList = carve(size_t(c) * 4);
-        o.first = carve(size_t(c) * e.capsRow * 4);
-        o.caps = carve(size_t(c) * e.capsRow * 4);
-        o.status = carve(size_t(c) + 16);
-        // second pass: see phase 2
-        const uint32_t shadowed = c - std::min(c, T.hostWords[HW_FIRST + p]);
-        // levels: an entry half of whose candidates have an earlier candidate entry waits for the entries that shadow a quarter of
-        // them or more (SYSLOGLINE behind CRONLOG / HTTPD_ERRORLOG; SHOREWALL behind SYSLOGLINE; COMBINEDAPACHELOG behind
-        // COMMONAPACHELOG): what those win it never looks at.  Results do not depend on the order -- only the work does.
-        // (round 6) ... unless the entry's round 0 is a TABLE WALK (a complete automaton in global memory, or a lazy one): then looking at
-        // values an earlier entry will win costs a few microseconds of a wavefront each, while waiting costs the batch a host round
-        // trip and the entry's longest walk a second time (0.4 ms in phase 2c, profiles/round6_grok_timeline.txt).  LC_GROK_FLAT=0: levels as in round 5.
-        const bool flat = [&] {
-            const char* v = getenv("LC_GROK_FLAT");
-            if (v && v[0] == '0') return false;
-            const lc_regex* first = patterns[p].anchored ? patterns[p].anchored : patterns[p].re;
-            if (first->engine == LC_ENGINE_TDFA) return !first->tdfaL2Blob.empty() && (first->preferWave || !first->hasTdfa);
-            return first->engine == LC_ENGINE_NFA && first->lazyReady.load(std::memory_order_acquire);
-        }();
-        if (shadowed * 2 >= c && !flat) {
-            uint32_t lv = 1;
-            for (uint32_t f = 0; f < p; ++f)
-                if (T.hostWords[HW_SHADOW + p * 64 + f] * 4 >= c) lv = std::max(lv, levelOf[f] + 1);
-            e.level = std::min(lv, 3u);
+        if (P1.small && (walksGlobalTables(gp.re) || walksGlobalTables(gp.anchored))) e.cost += 1e12;
+        return e;
+    }
+    // ---- the batch's active entries, their levels, their arrays in the arena, the device table; the candidates scattered to them
+    int entries() {
+        const uint32_t nP = uint32_t(patterns.size());
+        xcap = std::max<uint32_t>(extraCap, n / 4 + 1024);
+        xstride = row + 3;
+        size_t arenaBytes = alignUp(size_t(xcap) * xstride * 4, 256);  // (xtmp at the head)
+        const size_t entriesAt = arenaBytes;
+        for (uint32_t p = 0; p < nP; ++p) {
+            const uint32_t c = T.hostWords[HW_CAND + p];
+            if (!c) continue;
+            act.push_back(describe(p, c));
+            carveEntry(act.back(), nullptr, arenaBytes);
         }
-        levelOf[p] = e.level;
-        e.second = e.level != 0;
-        offs.push_back(o);
-        act.push_back(e);
-    }
-    // (the device table lists the entries of the first pass first: its finish kernel runs over a prefix of the table)
-    uint32_t nSecond = 0;
-    {
-        std::vector<size_t> idx(act.size());
-        for (size_t a = 0; a < idx.size(); ++a) idx[a] = a;
-        std::stable_sort(idx.begin(), idx.end(), [&](size_t x, size_t y) { return act[x].level < act[y].level; });
-        std::vector<PlanEntry> act2;
-        std::vector<Offsets> offs2;
-        for (size_t a : idx) {
-            act2.push_back(act[a]);
-            offs2.push_back(offs[a]);
-            nSecond += act[a].second;
+        nAct = uint32_t(act.size());
+        used = std::min<uint32_t>(nStreams, nAct);
+        stats.activeEntries = nAct;
+        if (const int rc = T.ensureArena(arenaBytes); rc != LC_OK) return rc;
+        uint8_t* arena = static_cast<uint8_t*>(T.arena);
+        xtmp = reinterpret_cast<int32_t*>(arena);
+        size_t at = entriesAt;
+        for (PlanEntry& e : act) carveEntry(e, arena, at);  // (in list order: the arena's layout does not depend on the levels)
+        grokplan::assignLevels(act.data(), nAct, T.hostWords + HW_CAND, K);
+        nSecond = grokplan::sortByLevel(act);
+        for (auto& a : map.activeOfBit) a = -1;
+        for (size_t a = 0; a < nAct; ++a) {
+            PlanEntry& e = act[a];
+            e.dev.cnt = T.dCnt + a * GC_WORDS;  // (cleared by grok_init_kernel at the start of the batch)
+            e.dev.cand = e.cand;
+            e.dev.capsRow = e.capsRow;
+            e.dev.bit = e.p;
+            e.dev.columns = e.columns;
+            e.dev.anchored = e.anchored ? 1u : 0u;
+            T.hostEntries[a] = e.dev;
+            T.hostRemScreens[a] = e.remainderScreen ? *e.remainderScreen : GrokScreenDev{nullptr, e.p, 0u};
+            map.activeOfBit[e.p] = int8_t(a);
+            maxCand = std::max(maxCand, e.cand);
+            stats.pairs += e.cand;
         }
-        act.swap(act2);
-        offs.swap(offs2);
+        if (!nAct) return LC_OK;
+        // (the entry table and, behind it, the remainder screens: one block)
+        HIP_TRY(hipMemcpyAsync(T.dEntries, T.hostEntries, 64 * sizeof(GrokEntryDev) + nAct * sizeof(GrokScreenDev), hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(grok_scatter_kernel, dim3(grid(n)), dim3(kGrokPlanBlock), 0, st, P1.masks, n, nP, d_off, d_len, map, T.dEntries,
+                           static_cast<const uint32_t*>(P1.order));
+        HIP_TRY(hipGetLastError());
+        return LC_OK;
     }
-    stats.activeEntries = uint32_t(act.size());
-    GrokSlotMap map;
-    for (auto& a : map.activeOfBit) a = -1;
-    {
-        int rc = T.ensureArena(arenaBytes);
-        if (rc != LC_OK) return rc;
+
+    // ---- phase 2 (round 4).  A batch used to queue 14-17 launches per entry -- 560 for the 46 active entries of configs[2] -- most of
+    // them over lists that turn out empty, and the host could not queue them as fast as the device finished them (18 us a launch).
+    // Now:  round0     ONE launch for the table-walk entries, one each for the others (the engine's main kernel, the anchored search
+    //                  where the entry has one), the post step behind each;
+    //       ahead      values won so far, bounds of the shadowed entries, remainder screens of the quiet entries;   counts -> host
+    //       runChains  only the entries that have any: second chance, search proper, shadowed entries; then the entry's remainder
+    //                  screens or its search rounds;
+    //       finish     the first contributing entry per value;   survivors of the screens -> host with the results
+    //       survivors  only the entries with survivors: the search rounds behind the first match, then the finish again.
+    // Calibration batches (the first three of a handle, then every 64th) time every entry's launches with events; the matcher then
+    // deals longest-first to the least loaded stream (grok_plan_host.hpp deal).
+    // ---- round 0 of the entries of level 0 (the shadowed ones wait for them: runChains)
+    int round0() {
+        bool allKnown = true;
+        for (const PlanEntry& e : act) allKnown = allKnown && e.cost0 > 0;
+        const uint32_t seen = patterns[act[0].p].re->grokBatches.fetch_add(1, std::memory_order_relaxed);
+        calibrate = !allKnown || seen < 3 || (seen & 63u) == 0;
+        if (calibrate)
+            for (size_t k = 0; k < 4 * size_t(nAct); ++k)
+                if (!T.tick[k]) HIP_TRY(hipEventCreate(&T.tick[k]));
+        return round0Launches();
     }
-    uint8_t* arena = static_cast<uint8_t*>(T.arena);
-    int32_t* xtmp = reinterpret_cast<int32_t*>(arena + xtmpAt);
-    uint32_t maxCand = 0, nRemScreens = 0, remScreenLds = 0;
-    for (size_t a = 0; a < act.size(); ++a) {
-        PlanEntry& e = act[a];
-        const Offsets& o = offs[a];
-        e.dev.off = reinterpret_cast<uint32_t*>(arena + o.off);
-        e.dev.len = reinterpret_cast<uint32_t*>(arena + o.len);
-        e.dev.line = reinterpret_cast<uint32_t*>(arena + o.line);
-        e.dev.from = reinterpret_cast<uint32_t*>(arena + o.from);
-        e.dev.nmatch = reinterpret_cast<uint32_t*>(arena + o.nmatch);
-        e.dev.first = reinterpret_cast<int32_t*>(arena + o.first);
-        e.dev.cnt = T.dCnt + a * GC_WORDS;
-        e.dev.cand = e.cand;
-        e.dev.capsRow = e.capsRow;
-        e.dev.bit = e.p;
-        e.listA = reinterpret_cast<uint32_t*>(arena + o.listA);
-        e.listB = reinterpret_cast<uint32_t*>(arena + o.listB);
-        e.unanchored = reinterpret_cast<uint32_t*>(arena + o.unanchored);
-        e.caps = reinterpret_cast<int32_t*>(arena + o.caps);
-        e.status = arena + o.status;
-        e.dev.status = e.status;
-        e.dev.caps = e.caps;
-        e.dev.listA = e.listA;
-        e.dev.unanchored = e.unanchored;
-        e.dev.ovList = reinterpret_cast<uint32_t*>(arena + o.ovList);
-        e.dev.columns = e.columns;
-        e.dev.anchored = patterns[e.p].anchored ? 1u : 0u;
-        T.hostEntries[a] = e.dev;
-        T.hostRemScreens[a] = e.remainderScreen ? *e.remainderScreen : GrokScreenDev{nullptr, e.p, 0u};
-        if (e.remainderScreen) {
-            ++nRemScreens;
-            remScreenLds = std::max(remScreenLds, e.remainderScreen->ldsBytes);
-        }
-        map.activeOfBit[e.p] = int8_t(a);
-        maxCand = std::max(maxCand, e.cand);
-        stats.pairs += e.cand;
-    }
-    uint32_t* gate = tail + TW_GATE;
-    uint32_t* xcount = tail + TW_XCOUNT;
-    const uint32_t nAct = uint32_t(act.size());
-    // entry e's candidates as a launch sees them: `bound` of them at most, the count on the device, the list and the resume offsets
-    auto entryBatch = [&](const PlanEntry& e, uint32_t bound, const uint32_t* count, const uint32_t* list, const uint32_t* resume,
-                          hipStream_t ws) {
-        return MatchBatch{.d_data = d_data, .d_off = e.dev.off, .d_len = e.dev.len, .n = bound,
-                          .d_n = count,
-                          .d_order = list,
-                          .d_resume = resume,
-                          .ngroups = e.capsRow / 2, .d_caps = e.caps, .d_status = e.status, .dev = dev, .stream = ws};
+    // Round 6: the entries whose round 0 is a walk of tables in global memory -- a complete tagged DFA, or the LAZY automaton of an
+    // entry that does not determinise -- go in ONE launch (tdfa_wave_multi_kernel) with ONE post launch behind it.  Round 0 used to
+    // be ~46 kernels of 30-100 us each plus their 46 post kernels, and lasted as long as the host needed to queue them: the last one
+    // started 1.4 ms after the first (profiles/round6_grok_timeline_lazy.txt).  LC_GROK_FUSED_ROUND0=0: one launch per entry.
+    struct FusedJobs {
+        std::vector<TdfaWaveJob> jobs;
+        uint32_t blocks = 0, ldsMax = 0;
+        size_t lo = 0, hi = 0;  // the first and the last fused entry of the table
     };
-    // ---- phase 3: the first contributing entry per value; its rows go out.  All of it returns at once when values are still in
-    // play somewhere (gate != 0): the host then finishes those entries and queues it again
-    const uint32_t gridCand = (maxCand + kGrokPlanBlock - 1) / kGrokPlanBlock;
-    auto finishAll = [&](const uint32_t* g) -> int {
-        if (nAct) {
-            hipLaunchKernelGGL(grok_entry_finish_kernel, dim3(gridCand, nAct), dim3(kGrokPlanBlock), 0, st, T.dEntries, winner, undecided, g, 0u);
+    int prepareFused(FusedJobs& F) {
+        // (all entries' candidates together are what the ONE launch walks; LC_GROK_FUSED_STAGE=0/1 forces it: A/B)
+        const bool stagePrograms = K.fusedStage >= 0 ? K.fusedStage != 0 : stats.pairs <= 32768;
+        int rcJob = LC_OK;
+        const bool ok = grokplan::selectFused(act.data(), nAct, K, kTdfaWaveMaxJobs, [&](size_t a) {
+            PlanEntry& e = act[a];
+            TdfaWaveJob j{};
+            uint32_t lds = 0, seq = 0;
+            if (!lcWaveJobPrepare(firstOf(e), dev, e.cand, stagePrograms, &j, &lds, &seq, &rcJob)) return rcJob != LC_OK ? -1 : 0;
+            j.off = e.dev.off;
+            j.len = e.dev.len;
+            j.resume = e.anchored ? nullptr : e.dev.from;
+            j.caps = e.caps;
+            j.status = e.status;
+            j.n = e.cand;
+            j.nGroupsOut = e.capsRow / 2;
+            j.firstBlock = F.blocks;
+            F.blocks += (e.cand + kTdfaWaveValues - 1) / kTdfaWaveValues;
+            F.ldsMax = std::max(F.ldsMax, lds);
+            e.seq0 = seq;  // (a lazy automaton's misses are LC_OVERFLOW under this number: the second chance in the entry's chain takes them)
+            e.wideFirst = false;
+            if (F.jobs.empty()) F.lo = a;
+            F.hi = a;
+            F.jobs.push_back(j);
+            return 1;
+        });
+        return ok ? LC_OK : rcJob;
+    }
+    int launchFused(const FusedJobs& F, hipStream_t ws) {
+        const int rc = lcLaunchWaveJobs(d_data, F.jobs.data(), uint32_t(F.jobs.size()), F.blocks, F.ldsMax, T.hostJobs, T.dJobs, dev, ws);
+        // the post step of the fused entries: ONE launch over their span of the entry table (the entries in between that are not
+        // the fused launch's leave at once: skip mask)
+        if (rc == LC_OK) {
+            unsigned long long skip = 0;
+            uint32_t most = 0;
+            for (size_t a = F.lo; a <= F.hi; ++a) {
+                if (act[a].fused) most = std::max(most, act[a].cand);
+                else skip |= 1ull << a;
+            }
+            post(ws, F.lo, F.hi - F.lo + 1, most, nullptr, nullptr, GP_ANCHORED_PASS, skip);
         }
-        hipLaunchKernelGGL(grok_resolve_kernel, dim3(gridAll), dim3(kGrokPlanBlock), 0, st, n, winner, undecided, d_pattern, g);
+        if (K.trace) fprintf(stderr, "grok plan 2a: %zu entries in one launch (%u workgroups, %u B of LDS)\n", F.jobs.size(), F.blocks, F.ldsMax);
+        return rc;
+    }
+    // round 0 of an entry that keeps a launch of its own, on its stream, its post step right behind its kernel (round 5: the one post
+    // launch for all entries behind the join (0.12 ms) waited for the slowest entry and then stood between it and the host's read of
+    // the counts)
+    int round0Entry(size_t a) {
+        PlanEntry& e = act[a];
+        const GrokDevicePattern& gp = patterns[e.p];
+        lcSetDecideSlot(1 + e.stream);
+        lc_regex* first = firstOf(e);
+        e.wideFirst = wantsWideFirst(first);
+        int rc = LC_OK;
+        // (failures inside the forked region become rc: the workers are always joined)
+        if (calibrate && hipEventRecord(T.tick[2 * a], W(e.stream)) != hipSuccess) rc = lcHipFail(hipGetLastError(), "hipEventRecord(calibration)");
+        if (rc == LC_OK) rc = runFirst(e, first, e.wideFirst, nullptr, nullptr, !gp.anchored, &e.seq0, W(e.stream));
+        if (calibrate) (void)hipEventRecord(T.tick[2 * a + 1], W(e.stream));
+        if (rc == LC_OK) post(W(e.stream), a, 1, e.cand, nullptr, nullptr, GP_ANCHORED_PASS, 0ull);
+        if (K.trace)
+            fprintf(stderr, "grok plan 2a: entry %u cand %u stream %d engine %s%s%s positions %zu slots %d atomic %d | measured round 0 %.3f ms, leftovers %.3f ms\n",
+                    e.p, e.cand, e.stream, first->engine == LC_ENGINE_NFA ? "nfa" : first->hasTdfa ? "tdfa-lds" : "tdfa-l2",
+                    gp.anchored ? " (anchored)" : "", e.wideFirst ? " (wide first)" : "", first->nfa.positions.size(), first->nfa.slotCount(),
+                    first->nfa.atomicCount, e.cost0 * 1e-6, e.cost1 * 1e-6);
+        return rc;
+    }
+    int round0Launches() {
+        FusedJobs F;
+        if (const int rc = prepareFused(F); rc != LC_OK) return rc;
+        bool others = false;
+        for (const PlanEntry& e : act) others = others || (!e.level && !e.fused);
+        int rc = others ? fork() : LC_OK;
+        if (rc != LC_OK) return rc;
+        hipStream_t fusedStream = others ? W(0) : st;
+        if (!F.jobs.empty()) rc = launchFused(F, fusedStream);
+        uint8_t order0[grokplan::kMaxEntries];
+        grokplan::deal(act.data(), nAct, used, false, order0);
+        for (size_t i = 0; i < nAct && rc == LC_OK && others; ++i)
+            if (!act[order0[i]].level && !act[order0[i]].fused) rc = round0Entry(order0[i]);
+        if (others) rc = join(rc);
+        else if (rc == LC_OK && hipGetLastError() != hipSuccess) rc = lcHipFail(hipGetLastError(), "grok round 0");
+        return rc;
+    }
+
+    // ---- round 0's results: the values won so far, the bounds, the remainder screens queued ahead; counts -> host (sync 2)
+    int ahead() {
+        lcNoteKernel("grok_post_kernel");
+        // the values won so far, and for the entries of level >= 1 how many of their slots are still open: an entry all of whose
+        // candidates an entry of level 0 has won (COMBINEDAPACHELOG behind COMMONAPACHELOG on a corpus without referrers) queues nothing
+        // in its chain -- its dozen launches over empty lists were the tail of the phase
+        if (nSecond) {
+            wonSoFar(st, maxCand, nAct, 0u);
+            hipLaunchKernelGGL(grok_bound_kernel, dim3(grid(maxCand), nSecond), dim3(kGrokPlanBlock), 0, st, T.dEntries, nAct - nSecond,
+                               static_cast<const uint32_t*>(winner));  // (the table lists the entries by level)
+        }
+        // (Tried in round 5 and dropped -- profiles/round5_grok_steps.txt: the chains of level 1, and by the entries' history the
+        // leftovers of level 0, queued BEFORE the host reads round 0's counts.  The device has them earlier, but a batch is bound by
+        // the rate at which the host can queue launches, and the extra, mostly empty chains cost more than the earlier start gained:
+        // 16 Ki values 4.76 -> 5.4 ms, 1000 values 3.9 -> 5.2 ms.)
+        // (round 6) The remainder screens, AHEAD of the host's read of round 0's counts.  Queued behind it, that launch pair (0.5 ms: a
+        // few thousand remainders of up to 4 KiB, one lane each) started 0.16 ms after round 0 had ended: a copy, a host round trip and
+        // the host's planning of the chains (profiles/round6_grok_timeline.txt).  Which entries have nothing else to do is a test of
+        // two counters the device has: the launch pair goes out now, on a worker stream beside the copy, and leaves the entries with
+        // overflowed or unanchored slots (and the shadowed ones, and the ones whose search rounds their history queues ahead: `skip`)
+        // to their chains.
+        // (whose rounds are queued ahead is decided ONCE per batch -- another runner thread's batch on the same handle may rewrite that
+        // history between here and the chains)
+        grokplan::decideEarly(act.data(), nAct, K, calibrate);
+        struct {
+            unsigned long long skip = 0;  // the shadowed entries and the ones whose rounds are queued ahead leave the launch
+            uint32_t most = 0;            // the largest entry in it (0: no launch)
+        } h;
+        uint32_t lds = 0;
+        for (size_t a = 0; a < nAct; ++a) {
+            if (act[a].level || act[a].early) h.skip |= 1ull << a;
+            else {
+                h.most = std::max(h.most, act[a].cand);
+                if (act[a].remainderScreen) lds = std::max(lds, act[a].remainderScreen->ldsBytes);
+            }
+        }
+        if (h.most) {
+            if (!nSecond) wonSoFar(st, maxCand, nAct, 0u);  // (the literal pass drops the slots of values an earlier entry has won)
+            if (const int rc = fork(); rc != LC_OK) return rc;
+            hipStream_t gs = W(int(used) - 1);
+            if (!K.remSplit) remainderScreens(gs, 0, nAct, h.most, lds, h.skip, true);
+            for (uint32_t a = 0; a < (K.remSplit ? nAct : 0u); ++a)
+                if (!((h.skip >> a) & 1ull)) remainderScreens(gs, 0, nAct, h.most, lds, ~(1ull << a), true);
+            aheadLaunched = true;
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(T.hostWords + HW_CNT, T.dCnt, size_t(nAct) * GC_WORDS * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(syncCounted(st));  // sync 2
+        for (size_t a = 0; a < nAct; ++a) {
+            std::atomic<uint32_t>& cost0 = patterns[act[a].p].re->grokCost0Ns;
+            if (calibrate && !act[a].level && !act[a].fused) learn(cost0, T.tick[2 * a], T.tick[2 * a + 1], act[a].cand);
+            // (an entry of the fused launch has no kernel of its own to time: a nominal cost keeps the handle "known")
+            if (act[a].fused && cost0.load(std::memory_order_relaxed) == 0) cost0.store(100, std::memory_order_relaxed);
+        }
+        return LC_OK;
+    }
+
+    // ---- the chains: what round 0 left undone on the entries of level 0 (second chance of overflowed slots; the search proper for
+    // what the anchored search did not match -- minus the values an earlier entry has won meanwhile), and, level by level, the shadowed
+    // entries on the values nobody before them has won.  grok_plan_host.hpp builds them as steps; this is the only place that turns
+    // a step into launches.
+    static uint32_t* listOf(const PlanEntry& e, uint8_t sel) {
+        uint32_t* const lists[] = {nullptr, e.dev.listA, e.listB, e.dev.unanchored, e.dev.ovList};  // grokplan::ListSel
+        return lists[sel];
+    }
+    void tick(size_t a, int which, int& rc) {
+        if (!calibrate || !act[a].busy) return;
+        if (hipEventRecord(T.tick[2 * nAct + 2 * a + size_t(which)], W(act[a].stream)) != hipSuccess && rc == LC_OK && which == 0)
+            rc = lcHipFail(hipGetLastError(), "hipEventRecord(calibration)");
+    }
+    void runStep(const grokplan::Step& s, int& rc) {
+        using namespace grokplan;
+        const size_t a = s.entry;
+        PlanEntry& e = act[a];
+        if (s.flags & F_TICK_BEGIN) tick(a, 0, rc);
+        if (s.flags & F_TICK_END) {
+            int ignored = LC_OK;
+            tick(a, 1, ignored);
+        }
+        if (rc != LC_OK || s.kind == S_TICK) return;
+        const GrokDevicePattern& gp = patterns[e.p];
+        lc_regex* first = firstOf(e);
+        hipStream_t ws = W(e.stream);
+        uint32_t* list = listOf(e, s.list);
+        uint32_t* out = listOf(e, s.out);
+        uint32_t* count = e.dev.cnt + s.count;
+        if (s.kind != S_FINISH_SHADOWER && s.kind != S_POST && s.kind != S_REMAINDER) lcSetDecideSlot(1 + e.stream);
+        switch (s.kind) {
+            case S_FINISH_SHADOWER: wonSoFar(ws, act[s.arg].cand, 1, uint32_t(s.arg)); break;
+            case S_SECOND_OVERFLOW: rc = runSecond(e, first, e.wideFirst, count, list, !gp.anchored, e.seq0, e.dev.cnt + GC_WIDE, ws); break;
+            case S_POST: post(ws, a, 1, e.cand, list, count, GP_ANCHORED_PASS | GP_OVERFLOW_FINAL, 0ull); break;
+            case S_SEARCH_FIRST:
+                hipLaunchKernelGGL(grok_filter_won_kernel, dim3(grid(e.cand)), dim3(kGrokPlanBlock), 0, ws, e.dev, static_cast<const uint32_t*>(winner),
+                                   static_cast<const uint32_t*>(list), static_cast<const uint32_t*>(count), out, e.dev.cnt + GC_FILTERED);
+                rc = runFirst(e, gp.re, false, e.dev.cnt + GC_FILTERED, out, true, &e.seqS, ws);
+                break;
+            case S_SEARCH_SECOND_POST:
+                rc = runSecond(e, gp.re, false, count, list, true, e.seqS, nullptr, ws);
+                if (rc == LC_OK) post(ws, a, 1, e.cand, list, count, GP_OVERFLOW_FINAL, 0ull);
+                break;
+            case S_SHADOWED_FIRST:
+                hipLaunchKernelGGL(grok_filter_won_kernel, dim3(grid(e.cand)), dim3(kGrokPlanBlock), 0, ws, e.dev, static_cast<const uint32_t*>(winner),
+                                   static_cast<const uint32_t*>(nullptr), static_cast<const uint32_t*>(nullptr), out, count);
+                e.wideFirst = wantsWideFirst(first);
+                rc = runFirst(e, first, e.wideFirst, count, out, !gp.anchored, &e.seq0, ws);
+                break;
+            case S_SHADOWED_SECOND_POST:
+                rc = runSecond(e, first, e.wideFirst, count, list, !gp.anchored, e.seq0, e.dev.cnt + GC_WIDE, ws);
+                if (rc == LC_OK) post(ws, a, 1, e.cand, list, count, GP_ANCHORED_PASS | GP_OVERFLOW_FINAL, 0ull);
+                break;
+            case S_ROUND:
+                rc = lcMatchOnStream(gp.re, gp.re->engine, entryBatch(e, e.cand, count, list, e.dev.from, ws));
+                if (rc != LC_OK) return;
+                hipLaunchKernelGGL(grok_advance2_kernel, dim3(grid(e.cand)), dim3(kGrokPlanBlock), 0, ws, static_cast<const uint32_t*>(list), e.cand,
+                                   static_cast<const uint32_t*>(count), e.status, e.caps, e.capsRow, e.columns, e.dev, xtmp, xcap, xstride, xcount, out,
+                                   e.dev.cnt + GC_ROUND0 + s.arg, (s.flags & F_GATE) ? gate : static_cast<uint32_t*>(nullptr));
+                break;
+            case S_REMAINDER:  // (grid.y = 1 over a table that begins at this entry)
+                remainderScreens(ws, a, 1, e.cand, e.remainderScreen ? e.remainderScreen->ldsBytes : 0u, 0ull, false);
+                break;
+        }
+    }
+    void traceChains() const {
+        for (size_t i = 0; i < nAct; ++i) {
+            const size_t a = order1[i];
+            const PlanEntry& e = act[a];
+            const char* rounds = e.early ? " + rounds" : "";
+            if (e.level && cnt(a, GC_BOUND) == 0)
+                fprintf(stderr, "grok plan 2c: entry %u level %u cand %u: every value already won\n", e.p, e.level, e.cand);
+            else if (e.level) fprintf(stderr, "grok plan 2c: entry %u level %u cand %u stream %d%s\n", e.p, e.level, e.cand, e.stream, rounds);
+            else if (e.busy || e.early)
+                fprintf(stderr, "grok plan 2c: entry %u overflowed %u unanchored %u%s\n", e.p, cnt(a, GC_OVERFLOW), cnt(a, GC_UNANCHORED), rounds);
+        }
+    }
+    int runChains() {
+        chains = grokplan::buildChains(act.data(), nAct, T.hostWords + HW_CAND, T.hostWords + HW_CNT, used, order1);
+        if (K.trace) traceChains();
+        if (grokplan::longestChain(chains) || aheadLaunched) {
+            if (!nSecond && !aheadLaunched) wonSoFar(st, maxCand, nAct, 0u);
+            int rc = fork();
+            if (rc != LC_OK) return rc;
+            grokplan::forEachQueued(chains, order1, [&](const grokplan::Step& s) { runStep(s, rc); });
+            rc = join(rc);  // (always: a failure inside the forked region must not leave the worker streams unjoined)
+            if (rc != LC_OK) return rc;
+        }
+        HIP_TRY(hipGetLastError());
+        return LC_OK;
+    }
+
+    // ---- the finish: the first contributing entry per value; its rows go out.  All of it returns at once when values are still in
+    // play somewhere (gate != 0): the host then finishes those entries and queues it again.
+    // What is left of phase 2 needs the survivors of the remainder screens -- almost always none.  Round 5: the host no longer waits
+    // to learn that.  The screens add their survivors to the gate word, the finish of the batch is queued behind them (it returns at
+    // once if the gate is up), and the host reads everything in ONE round trip: gate down = done (three host synchronisations per batch
+    // instead of four); gate up = the search rounds of the entries with survivors, then the finish again.
+    int finish(const uint32_t* g) {
         if (nAct) {
-            // (row nAct of the grid: the extra rows of the winners -- grok_commit_extra_kernel's launch until round 6)
-            hipLaunchKernelGGL(grok_commit_kernel, dim3(std::max(gridCand, 64u), nAct + 1), dim3(kGrokPlanBlock), 0, st, T.dEntries, nAct, d_pattern,
-                               d_first, row, g, xtmp, xcount, xcap, xstride, map, d_extra, extraCap, d_nextra, tail + TW_NEXTRA);
+            hipLaunchKernelGGL(grok_entry_finish_kernel, dim3(grid(maxCand), nAct), dim3(kGrokPlanBlock), 0, st, T.dEntries, winner, undecided, g, 0u);
+        }
+        hipLaunchKernelGGL(grok_resolve_kernel, dim3(grid(n)), dim3(kGrokPlanBlock), 0, st, n, winner, undecided, d_pattern, g);
+        if (nAct) {
+            // (row nAct of the grid: the extra rows of the winners)
+            hipLaunchKernelGGL(grok_commit_kernel, dim3(std::max(grid(maxCand), 64u), nAct + 1), dim3(kGrokPlanBlock), 0, st, T.dEntries, nAct, d_pattern,
+                               d_first, row, g, xtmp, xcount, xcap, xstride, map, d_extra, extraCap, d_nextra, T.dTail + TW_NEXTRA);
         }
         HIP_TRY(hipGetLastError());
         // (tail words, the copy of nextra among them, and the entries' counters: one block)
@@ -910,689 +1281,67 @@ int grokMatchSpeculative(const std::vector<GrokDevicePattern>& patterns, GrokDev
             HIP_TRY(hipMemcpyAsync(tlsTail.hPattern, d_pattern, size_t(n) * 4, hipMemcpyDeviceToHost, st));
             HIP_TRY(hipMemcpyAsync(tlsTail.hFirst, d_first, size_t(n) * row * 4, hipMemcpyDeviceToHost, st));
         }
-        HIP_TRY(syncCounted(st));
+        HIP_TRY(syncCounted(st));  // sync 3 = the last one, unless the gate is up
         if (tlsTail.armed) {
             tlsTail.done = true;
             tlsTail.nextra = T.hostWords[HW_TAIL + TW_NEXTRA];
         }
         return LC_OK;
-    };
-    bool finished = false;  // finishAll has run (phase 2 ended with it: see the end of phase 2c)
-    if (nAct) {
-        // (the entry table and, behind it, the remainder screens: one block)
-        HIP_TRY(hipMemcpyAsync(T.dEntries, T.hostEntries, 64 * sizeof(GrokEntryDev) + nAct * sizeof(GrokScreenDev), hipMemcpyHostToDevice, st));
-        (void)nRemScreens;  // (dCnt: cleared by grok_init_kernel at the start of the batch)
-        hipLaunchKernelGGL(grok_scatter_kernel, dim3(gridAll), dim3(kGrokPlanBlock), 0, st, masks, n, nP, d_off, d_len, map, T.dEntries,
-                           static_cast<const uint32_t*>(order));
-        HIP_TRY(hipGetLastError());
-        // ---- phase 2 (round 4).  A batch used to queue 14-17 launches per entry -- 560 for the 46 active entries of configs[2] -- most of
-        // them over lists that turn out empty, and the host could not queue them as fast as the device finished them (18 us a launch).
-        // Now:  2a  round 0, ONE launch per entry (the engine's main kernel, the anchored search where the entry has one), dearest
-        //           entry first, dealt round-robin to the worker streams;
-        //       2b  grok_post_kernel, ONE launch for all entries: overflowed slots -> the entry's overflow list, slots the anchored
-        //           search did not match -> its unanchored list, matches recorded, what is still in play -> listA;   counts -> host
-        //       2c  only the entries that have any: the second chance for the overflowed slots, the search proper for the unanchored
-        //           ones, each followed by a post launch over that list;
-        //       2d  grok_remainder_all_kernel, ONE launch: the remainder of every slot in play against its entry's screen; counts -> host
-        //       2e  only the entries with survivors: the search rounds behind the first match, queued ahead as before.
-        std::vector<size_t> byCost(nAct);
-        for (size_t a = 0; a < nAct; ++a) byCost[a] = a;
-        std::sort(byCost.begin(), byCost.end(), [&](size_t x, size_t y) { return act[x].cost > act[y].cost; });
-        const uint32_t used = std::min<uint32_t>(nStreams, nAct);
-        // (round 6) A worker stream waits for the fork when it first GETS work (W), and only the streams that got any are joined: a
-        // phase forks into sixteen streams and usually uses three, and the thirteen idle ones cost the host 26 calls per fork / join
-        // and the batch's stream thirteen barrier packets that it works through one after the other (0.09 ms between the end of round
-        // 0 and the first kernel behind the join, profiles/round6_grok_timeline.txt).
-        uint32_t waitedMask = 0, touchedMask = 0;
-        auto fork = [&]() -> int {
-            HIP_TRY(hipEventRecord(T.fork, st));
-            waitedMask = 0;  // (everybody waits for THIS fork from now on; what was touched before stays to be joined)
-            return LC_OK;
-        };
-        auto W = [&](int s) -> hipStream_t {  // (a failure surfaces at the join: hipGetLastError)
-            const uint32_t bit = 1u << uint32_t(s);
-            if (!(waitedMask & bit)) {
-                (void)hipStreamWaitEvent(T.workers[s], T.fork, 0);
-                waitedMask |= bit;
-            }
-            touchedMask |= bit;
-            return T.workers[s];
-        };
-        auto join = [&](int rc) -> int {
-            lcSetDecideSlot(0);
-            if (rc == LC_OK && hipGetLastError() != hipSuccess) rc = lcHipFail(hipGetLastError(), "grok entry launch");
-            if (rc != LC_OK) {
-                for (uint32_t s = 0; s < used; ++s) (void)hipStreamSynchronize(T.workers[s]);
-                return rc;
-            }
-            for (uint32_t s = 0; s < used; ++s) {
-                if (!((touchedMask >> s) & 1u)) continue;
-                HIP_TRY(hipEventRecord(T.join[s], T.workers[s]));
-                HIP_TRY(hipStreamWaitEvent(st, T.join[s], 0));
-            }
-            touchedMask = 0;
-            return LC_OK;
-        };
-        auto readCounts = [&]() -> int {
-            HIP_TRY(hipMemcpyAsync(T.hostWords + HW_CNT, T.dCnt, size_t(nAct) * GC_WORDS * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(syncCounted(st));
-            return LC_OK;
-        };
-        auto cnt = [&](size_t a, uint32_t word) { return T.hostWords[HW_CNT + a * GC_WORDS + word]; };
-        // Which stream an entry goes to.  A phase lasts as long as its most loaded stream, and the entries differ by a factor of ten
-        // (an anchored DFA over 300 values: 0.1 ms; the thread-list engine on a format with a free-text field in the middle: 3 ms).
-        // Calibration batches (the first three of a handle, then every 64th) time every entry's launches with events; the matcher
-        // then deals longest-first to the least loaded stream.  Before the first measurement: the static estimate.
-        bool calibrate = false;
-        {
-            bool allKnown = true;
-            for (size_t a = 0; a < nAct; ++a) allKnown = allKnown && act[a].cost0 > 0;
-            const uint32_t seen = patterns[act[0].p].re->grokBatches.fetch_add(1, std::memory_order_relaxed);
-            calibrate = !allKnown || seen < 3 || (seen & 63u) == 0;
-            if (calibrate)
-                for (size_t k = 0; k < 4 * nAct; ++k)
-                    if (!T.tick[k]) HIP_TRY(hipEventCreate(&T.tick[k]));
-        }
-        std::vector<char> busy2c(nAct, 0);  // phase 2c: the entries that have anything to do in it
-        auto deal = [&](bool leftovers) {  // longest first, each to the least loaded stream
-            std::vector<size_t> idx;
-            for (size_t a = 0; a < nAct; ++a) idx.push_back(a);
-            auto costOf = [&](size_t a) {
-                const double known = leftovers ? act[a].cost1 : act[a].cost0;
-                return known > 0 ? known : act[a].cost * 50.0;
-            };
-            std::stable_sort(idx.begin(), idx.end(), [&](size_t x, size_t y) { return costOf(x) > costOf(y); });
-            double load[kGrokMaxStreams] = {};
-            for (size_t a : idx) {
-                if (leftovers ? (!busy2c[a] || act[a].level >= 2) : act[a].level != 0) continue;
-                uint32_t best = 0;
-                for (uint32_t s2 = 1; s2 < used; ++s2)
-                    if (load[s2] < load[best]) best = s2;
-                act[a].stream = int(best);
-                load[best] += costOf(a) + 20000.0;  // (+ a launch)
-            }
-            return idx;
-        };
-        // ---- round 5's plan knobs (each one can be switched off for A/B measurements; read per batch: the GPU tests flip them)
-        auto envInt = [](const char* name, int dflt) {
-            const char* v = getenv(name);
-            return v ? atoi(v) : dflt;
-        };
-        const int wideFirstMode = envInt("LC_GROK_WIDE_FIRST", 1);      // 0 off, 1 by the entry's history, 2 always
-        const bool breadthFirst = envInt("LC_GROK_BREADTH", 1) != 0;    // phase 2c queues the chains' launches round-robin, heavy kernels first
-        const int earlyRoundsMode = envInt("LC_GROK_EARLY_ROUNDS", 1);  // 0 off, 1 by the entry's history, 2 always
-        const bool remainderLiteral = envInt("LC_GROK_REMAINDER_LITERAL", 1) != 0 && literalIndex != nullptr;
-        const bool remainderWon = envInt("LC_GROK_REMAINDER_WON", 1) != 0;      // slots of values an earlier entry has won drop out in front of the screens
-        const bool remainderInChain = envInt("LC_GROK_REMAINDER_INCHAIN", 1) != 0;  // the remainder screens per entry, at the end of its chain in phase 2c
-        const uint32_t remWalk = envInt("LC_GROK_SCREEN_SCALED", 1) != 0 ? 32u : 0u;
-        auto remGrid = [&](uint32_t slots) { return (slots + kGrokPlanBlock - 1) / kGrokPlanBlock; };
-        // (round 5) the host reads the survivors of the remainder screens together with the finish of the batch (three synchronisations
-        // instead of four: see the end of phase 2c).  Round 6: the screens count their survivors onto the gate word themselves.
-        const bool lazy = envInt("LC_GROK_LAZY_SYNC3", 1) != 0;
-        uint32_t* remGate = lazy ? gate : nullptr;
-        // (round 6) the remainder screens of the entries round 0 leaves nothing else to do for are queued BEFORE the host reads round 0's
-        // counts, on a stream beside it (the kernels test the entry's overflow / unanchored counts themselves): see phase 2b
-        const bool remainderAhead = remainderInChain && envInt("LC_GROK_REMAINDER_AHEAD", 1) != 0;
-        const bool postInStream = envInt("LC_GROK_POST_IN_STREAM", 1) != 0;    // round 0's post step behind each entry's kernel, on its stream
-        // An entry whose values needed more than 64 threads in recent batches (GC_WIDE, noted behind the batch) goes WIDE FIRST: its
-        // first chance is nfa_wide_kernel over every candidate, and what is left behind it are the decide kernels alone.  Round 4's
-        // timeline: the longest entry's first chance 1.0 ms + its second chance (14 values restarted from byte 0) 1.1 ms, back to back
-        // on the critical path of the batch; now 1.1 ms.
-        auto wantsWideFirst = [&](lc_regex* h) {
-            if (!wideFirstMode || h->engine != LC_ENGINE_NFA || !lcNfaWideApplies(h)) return false;
-            if (wideFirstMode >= 2) return true;
-            return n <= kGrokWideFirstBatch && h->grokOverflowSeen.load(std::memory_order_relaxed) != 0;
-        };
-        // one engine call of entry e on stream ws: the first-chance kernel ...
-        auto runFirst = [&](PlanEntry& e, lc_regex* h, bool wide, const uint32_t* count, const uint32_t* list, bool withFrom, uint32_t* seq,
-                            hipStream_t ws) -> int {
-            const MatchBatch b = entryBatch(e, e.cand, count, list, withFrom ? e.dev.from : nullptr, ws);
-            if (wide) return lcMatchWideFirstOnStream(0, h, h->engine, b, seq, e.dev.cnt + GC_WIDE);
-            return lcMatchFirstOnStream(h, h->engine, b, seq);
-        };
-        // ... and what is left behind it (note: the entry's GC_WIDE word, set when the wide kernel had anything to do)
-        auto runSecond = [&](PlanEntry& e, lc_regex* h, bool wide, const uint32_t* count, const uint32_t* list, bool withFrom, uint32_t seq,
-                             uint32_t* note, hipStream_t ws) -> int {
-            const MatchBatch b = entryBatch(e, e.cand, count, list, withFrom ? e.dev.from : nullptr, ws);
-            if (wide) return lcMatchWideFirstOnStream(1, h, h->engine, b, &seq, nullptr);
-            lcSetWideNote(note);
-            const int r = lcMatchSecondChanceOnStream(h, h->engine, b, seq);
-            lcSetWideNote(nullptr);
-            return r;
-        };
-        // 2a
-        // Round 6: the entries whose round 0 is a walk of tables in global memory -- a complete tagged DFA, or the LAZY automaton of an
-        // entry that does not determinise -- go in ONE launch (tdfa_wave_multi_kernel) with ONE post launch behind it.  Round 0 used to
-        // be ~46 kernels of 30-100 us each plus their 46 post kernels, and lasted as long as the host needed to queue them: the last one
-        // started 1.4 ms after the first (profiles/round6_grok_timeline_lazy.txt).  LC_GROK_FUSED_ROUND0=0: one launch per entry.
-        std::vector<char> fused(nAct, 0);
-        {
-            std::vector<TdfaWaveJob> jobs;
-            std::vector<size_t> jobEntry;
-            uint32_t blocks = 0, ldsMax = 0;
-            // (all entries' candidates together are what the ONE launch walks; LC_GROK_FUSED_STAGE=0/1 forces it: A/B)
-            const bool stagePrograms = envInt("LC_GROK_FUSED_STAGE", stats.pairs <= 32768 ? 1 : 0) != 0;
-            for (size_t a = 0; a < nAct && jobs.size() < kTdfaWaveMaxJobs; ++a) {
-                PlanEntry& e = act[a];
-                const GrokDevicePattern& gp = patterns[e.p];
-                if (e.level || !e.cand) continue;
-                lc_regex* first = gp.anchored ? gp.anchored : gp.re;
-                if (wideFirstMode >= 2 && first->engine == LC_ENGINE_NFA) continue;  // (the knob forces the wide kernel: A/B, parity tests)
-                TdfaWaveJob j{};
-                uint32_t lds = 0, seq = 0;
-                int rcJob = LC_OK;
-                if (!lcWaveJobPrepare(first, dev, e.cand, stagePrograms, &j, &lds, &seq, &rcJob)) {
-                    if (rcJob != LC_OK) return rcJob;
-                    continue;
-                }
-                j.off = e.dev.off;
-                j.len = e.dev.len;
-                j.resume = gp.anchored ? nullptr : e.dev.from;
-                j.caps = e.caps;
-                j.status = e.status;
-                j.n = e.cand;
-                j.nGroupsOut = e.capsRow / 2;
-                j.firstBlock = blocks;
-                blocks += (e.cand + kTdfaWaveValues - 1) / kTdfaWaveValues;
-                ldsMax = std::max(ldsMax, lds);
-                e.seq0 = seq;        // (a lazy automaton's misses are LC_OVERFLOW under this number: the second chance of phase 2c takes them)
-                e.wideFirst = false;
-                fused[a] = 1;
-                jobs.push_back(j);
-                jobEntry.push_back(a);
-            }
-            bool others = false;
-            for (size_t a = 0; a < nAct; ++a) others = others || (!act[a].level && !fused[a]);
-            int rc = LC_OK;
-            if (others) rc = fork();
-            if (rc != LC_OK) return rc;
-            hipStream_t fusedStream = others ? W(0) : st;
-            if (!jobs.empty()) {
-                rc = lcLaunchWaveJobs(d_data, jobs.data(), uint32_t(jobs.size()), blocks, ldsMax, T.hostJobs, T.dJobs, dev, fusedStream);
-                // the post step of the fused entries: ONE launch over their span of the entry table (the entries in between that are not
-                // the fused launch's leave at once: skip mask)
-                if (rc == LC_OK) {
-                    const size_t lo = jobEntry.front(), hi = jobEntry.back();
-                    unsigned long long skip = 0;
-                    uint32_t most = 0;
-                    for (size_t a = lo; a <= hi; ++a) {
-                        if (fused[a]) most = std::max(most, act[a].cand);
-                        else skip |= 1ull << a;
-                    }
-                    hipLaunchKernelGGL(grok_post_kernel, dim3((most + kGrokPlanBlock - 1) / kGrokPlanBlock, uint32_t(hi - lo + 1)), dim3(kGrokPlanBlock), 0,
-                                       fusedStream, T.dEntries, uint32_t(lo), static_cast<const uint32_t*>(nullptr),
-                                       static_cast<const uint32_t*>(nullptr), uint32_t(GP_ANCHORED_PASS), xtmp, xcap, xstride, xcount, skip);
-                }
-                if (trace) fprintf(stderr, "grok plan 2a: %zu entries in one launch (%u workgroups, %u B of LDS)\n", jobs.size(), blocks, ldsMax);
-            }
-            const std::vector<size_t> order0 = deal(false);
-            for (size_t i = 0; i < nAct && rc == LC_OK && others; ++i) {
-                const size_t a = order0[i];
-                PlanEntry& e = act[a];
-                const GrokDevicePattern& gp = patterns[e.p];
-                if (e.level || fused[a]) continue;  // (level >= 1: waits for the entries that shadow it, phase 2c)
-                lcSetDecideSlot(1 + e.stream);
-                lc_regex* first = gp.anchored ? gp.anchored : gp.re;
-                e.wideFirst = wantsWideFirst(first);
-                // (failures inside the forked region become rc: the workers are always joined below)
-                if (calibrate && hipEventRecord(T.tick[2 * a], W(e.stream)) != hipSuccess) rc = lcHipFail(hipGetLastError(), "hipEventRecord(calibration)");
-                if (rc == LC_OK) rc = runFirst(e, first, e.wideFirst, nullptr, nullptr, !gp.anchored, &e.seq0, W(e.stream));
-                if (calibrate) (void)hipEventRecord(T.tick[2 * a + 1], W(e.stream));
-                // (round 5) the entry's post step right behind its kernel: the one launch for all entries behind the join (0.12 ms) waited
-                // for the slowest entry and then stood between it and the host's read of the counts
-                if (rc == LC_OK && postInStream)
-                    hipLaunchKernelGGL(grok_post_kernel, dim3((e.cand + kGrokPlanBlock - 1) / kGrokPlanBlock, 1), dim3(kGrokPlanBlock), 0,
-                                       W(e.stream), T.dEntries, uint32_t(a), static_cast<const uint32_t*>(nullptr),
-                                       static_cast<const uint32_t*>(nullptr), uint32_t(GP_ANCHORED_PASS), xtmp, xcap, xstride, xcount, 0ull);
-                if (trace)
-                    fprintf(stderr, "grok plan 2a: entry %u cand %u stream %d engine %s%s%s positions %zu slots %d atomic %d | measured round 0 %.3f ms, leftovers %.3f ms\n",
-                            e.p, e.cand, e.stream, first->engine == LC_ENGINE_NFA ? "nfa" : first->hasTdfa ? "tdfa-lds" : "tdfa-l2",
-                            gp.anchored ? " (anchored)" : "", e.wideFirst ? " (wide first)" : "", first->nfa.positions.size(), first->nfa.slotCount(),
-                            first->nfa.atomicCount, e.cost0 * 1e-6, e.cost1 * 1e-6);
-            }
-            if (others) rc = join(rc);
-            else if (rc == LC_OK && hipGetLastError() != hipSuccess) rc = lcHipFail(hipGetLastError(), "grok round 0");
-            if (rc != LC_OK) return rc;
-        }
-        // 2b: round 0's results of the level-0 entries; the values won so far
-        const uint32_t gridCand0 = (maxCand + kGrokPlanBlock - 1) / kGrokPlanBlock;
-        lcNoteKernel("grok_post_kernel");
-        const uint32_t nLevel0 = nAct - nSecond;  // (the table lists the entries by level)
-        if (nLevel0 && !postInStream)
-            for (uint32_t a = 0; a < nLevel0; ++a)  // (the entries of the fused launch have had their post step behind it)
-                if (!fused[a])
-                    hipLaunchKernelGGL(grok_post_kernel, dim3((act[a].cand + kGrokPlanBlock - 1) / kGrokPlanBlock, 1), dim3(kGrokPlanBlock), 0, st,
-                                       T.dEntries, a, static_cast<const uint32_t*>(nullptr), static_cast<const uint32_t*>(nullptr),
-                                       uint32_t(GP_ANCHORED_PASS), xtmp, xcap, xstride, xcount, 0ull);
-        uint32_t maxLevel = 0;
-        for (size_t a = 0; a < nAct; ++a) maxLevel = std::max(maxLevel, act[a].level);
-        // the values won so far, and for the entries of level >= 1 how many of their slots are still open: an entry all of whose
-        // candidates an entry of level 0 has won (COMBINEDAPACHELOG behind COMMONAPACHELOG on a corpus without referrers) queues nothing
-        // in phase 2c -- its dozen launches over empty lists were the tail of the phase
-        const bool boundKnown = nSecond != 0 && envInt("LC_GROK_BOUND", 1) != 0;
-        if (boundKnown) {
-            hipLaunchKernelGGL(grok_entry_finish_kernel, dim3(gridCand0, nAct), dim3(kGrokPlanBlock), 0, st, T.dEntries, winner, undecided,
-                               static_cast<const uint32_t*>(nullptr), 0u);
-            hipLaunchKernelGGL(grok_bound_kernel, dim3(gridCand0, nSecond), dim3(kGrokPlanBlock), 0, st, T.dEntries, nLevel0,
-                               static_cast<const uint32_t*>(winner));
-        }
-        // (Tried in round 5 and dropped -- profiles/round5_grok_steps.txt: the chains of level 1, and by the entries' history the
-        // leftovers of level 0, queued BEFORE the host reads round 0's counts.  The device has them earlier, but a batch is bound by
-        // the rate at which the host can queue launches, and the extra, mostly empty chains cost more than the earlier start gained:
-        // 16 Ki values 4.76 -> 5.4 ms, 1000 values 3.9 -> 5.2 ms.)
-        // (round 6) The remainder screens, AHEAD of the host's read of round 0's counts.  Round 5 queued them behind it -- the entries
-        // with nothing else to do in phase 2c in one launch pair at the fork -- and that pair (0.5 ms: a few thousand remainders of up to
-        // 4 KiB, one lane each) started 0.16 ms after round 0 had ended: a copy, a host round trip and the host's planning of phase 2c
-        // (profiles/round6_grok_timeline.txt).  Which entries those are is a test of two counters the device has: the launch pair goes out
-        // now, on a worker stream beside the copy, and leaves the entries with overflowed or unanchored slots (and the shadowed ones, and
-        // the ones whose search rounds their history queues ahead: `skip`) to their chains.  LC_GROK_REMAINDER_AHEAD=0: as before.
-        // (an entry's search rounds are queued ahead by its history; decided ONCE per batch -- another runner thread's batch on the same
-        // handle may rewrite that history between here and phase 2c)
-        std::vector<char> earlyOf(nAct, 0);
-        for (size_t a = 0; a < nAct; ++a) {
-            const GrokDevicePattern& gp = patterns[act[a].p];
-            earlyOf[a] = (earlyRoundsMode && act[a].rounds >= 2 && gp.re->engine == LC_ENGINE_TDFA &&
-                          (earlyRoundsMode >= 2 || (!calibrate && gp.re->grokRemainderSeen.load(std::memory_order_relaxed) != 0))) ? 1 : 0;
-        }
-        bool aheadLaunched = false;
-        if (remainderAhead && nLevel0) {
-            unsigned long long skip = 0;
-            uint32_t most = 0, ldsAhead = 0;
-            for (size_t a = 0; a < nAct; ++a) {
-                if (act[a].level || earlyOf[a]) skip |= 1ull << a;
-                else {
-                    most = std::max(most, act[a].cand);
-                    if (act[a].remainderScreen) ldsAhead = std::max(ldsAhead, act[a].remainderScreen->ldsBytes);
-                }
-            }
-            if (most) {
-                if (!boundKnown)  // the values won so far (the literal pass drops the slots of values an earlier entry has won)
-                    hipLaunchKernelGGL(grok_entry_finish_kernel, dim3(gridCand0, nAct), dim3(kGrokPlanBlock), 0, st, T.dEntries, winner, undecided,
-                                       static_cast<const uint32_t*>(nullptr), 0u);
-                {
-                    int rcFork = fork();
-                    if (rcFork != LC_OK) return rcFork;
-                }
-                hipStream_t gs = W(int(used) - 1);
-                static const bool splitRem = getenv("LC_GROK_REM_SPLIT") != nullptr;  // diagnosis: one launch pair per entry (a kernel trace then times each)
-                for (uint32_t a1 = 0; a1 < (splitRem ? nAct : 1u); ++a1) {
-                    const unsigned long long skip1 = splitRem ? ~(1ull << a1) : skip;
-                    if (splitRem && ((skip >> a1) & 1ull)) continue;
-                    if (remainderLiteral || remainderWon) lcNoteKernel("grok_remainder_literal_kernel");
-                    lcNoteKernel("grok_remainder_all_kernel");
-                    if (remainderLiteral || remainderWon)
-                        hipLaunchKernelGGL(grok_remainder_literal_kernel, dim3((most + kGrokPlanBlock / 64 - 1) / (kGrokPlanBlock / 64), nAct),
-                                           dim3(kGrokPlanBlock), 0, gs, d_data, T.dEntries,
-                                           remainderLiteral ? literalIndex : static_cast<const uint32_t*>(nullptr), skip1,
-                                           remainderWon ? static_cast<const uint32_t*>(winner) : static_cast<const uint32_t*>(nullptr), 1u);
-                    hipLaunchKernelGGL(grok_remainder_all_kernel, dim3(remGrid(most), nAct), dim3(kGrokPlanBlock), small ? ldsAhead : 0, gs, d_data,
-                                       T.dEntries, static_cast<const GrokScreenDev*>(T.dRemScreens), (small ? 1u : 0u) | remWalk | 64u, skip1, remGate);
-                }
-                aheadLaunched = true;
-            }
-        }
-        HIP_TRY(hipGetLastError());
-        {
-            int rc = readCounts();  // sync 2
-            if (rc != LC_OK) return rc;
-        }
-        auto learn = [&](std::atomic<uint32_t>& slot, hipEvent_t b, hipEvent_t e2, uint32_t cand) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, b, e2) != hipSuccess) {
-                (void)hipGetLastError();
-                return;
-            }
-            const uint32_t ns = uint32_t(std::min(4.0e9, std::max(1.0, double(ms) * 1e6 / std::max(1u, cand))));
-            const uint32_t old = slot.load(std::memory_order_relaxed);
-            slot.store(old ? (old + ns) / 2 : ns, std::memory_order_relaxed);
-        };
+    }
+
+    // ---- behind the finish: what the chains measured, and the search rounds of the entries with survivors
+    void afterCounts() {
         if (calibrate)
             for (size_t a = 0; a < nAct; ++a)
-                if (!act[a].level && !fused[a]) learn(patterns[act[a].p].re->grokCost0Ns, T.tick[2 * a], T.tick[2 * a + 1], act[a].cand);
-        for (size_t a = 0; a < nAct; ++a)  // (an entry of the fused launch has no kernel of its own to time: a nominal cost keeps the handle "known")
-            if (fused[a] && patterns[act[a].p].re->grokCost0Ns.load(std::memory_order_relaxed) == 0)
-                patterns[act[a].p].re->grokCost0Ns.store(100, std::memory_order_relaxed);
-        // 2c: what round 0 left undone on the entries of level 0 (second chance of overflowed slots; the search proper for what the
-        // anchored search did not match -- minus the values an earlier entry has won meanwhile), and, level by level, the shadowed
-        // entries on the values nobody before them has won.  ONE fork for all of it: the leftovers of level 0 and the entries of
-        // level 1 depend on round 0 only; an entry of level 2 or 3 goes behind the chain of the entry that shadows most of its
-        // candidates, on that entry's stream (stream order instead of a barrier per level).
-        //
-        // Round 5: a chain is built as a list of STEPS (one to three launches each) and the steps of all chains are queued round-robin,
-        // dearest chain first.  Round 4 queued chain after chain: a dozen launches each, 15-20 us a launch -- the third shadowed
-        // entry's kernel started 0.8 ms after the fork, behind sixty launches of other entries' mostly empty follow-up steps, and it,
-        // not the second-chance kernel, ended the phase.  And an entry whose remainders mostly pass its screen (by its history:
-        // grokRemainderSeen) gets its search rounds behind the first match queued HERE, at the end of its chain, unscreened: they run
-        // in the shadow of this phase instead of in a phase of their own behind the remainder screens and another host round trip.
-        using Step = std::function<void(int&)>;
-        std::vector<std::vector<Step>> chains(nAct);
-        std::vector<size_t> chainOwner(nAct);  // whose list an entry's steps went to (itself; a level >= 2 entry: its shadower's owner)
-        for (size_t a = 0; a < nAct; ++a) chainOwner[a] = a;
-        unsigned long long earlyMask = 0;  // active entries whose rounds were queued in this phase
-        unsigned long long coveredMask = 0;  // ... whose remainder screens were
-        unsigned long long groupMask = 0;    // ... of those, the entries of level 0 that have nothing else to do in this phase
-        // rounds 1 .. of entry a (FindNextMatch from the end of the previous match; the list lengths stay on the device), one step per
-        // round.  screened: round 1 reads the survivors of the remainder screen (phase 2e); else every slot in play (queued ahead)
-        auto roundSteps = [&](size_t a, bool screened, std::vector<Step>& out) {
-            PlanEntry& e0 = act[a];
-            e0.queued = true;
-            for (uint32_t r = 1; r < e0.rounds; ++r)
-                out.push_back([&, a, r, screened](int& rc) {
-                    if (rc != LC_OK) return;
-                    PlanEntry& e = act[a];
-                    const GrokDevicePattern& gp = patterns[e.p];
-                    hipStream_t ws = W(e.stream);
-                    lcSetDecideSlot(1 + e.stream);
-                    const uint32_t grid = (e.cand + kGrokPlanBlock - 1) / kGrokPlanBlock;
-                    const uint32_t* list = r == 1 ? (screened ? e.unanchored : e.listA) : (r & 1) ? e.listA : e.listB;
-                    uint32_t* out2 = (r & 1) ? e.listB : e.listA;
-                    const uint32_t* countPtr = r == 1 ? e.dev.cnt + (screened ? GC_REMAINDER : GC_ROUND0) : e.dev.cnt + GC_ROUND0 + r - 1;
-                    rc = lcMatchOnStream(gp.re, gp.re->engine, entryBatch(e, e.cand, countPtr, list, e.dev.from, ws));
-                    if (rc != LC_OK) return;
-                    hipLaunchKernelGGL(grok_advance2_kernel, dim3(grid), dim3(kGrokPlanBlock), 0, ws, list, e.cand, countPtr, e.status, e.caps,
-                                       e.capsRow, e.columns, e.dev, xtmp, xcap, xstride, xcount, out2, e.dev.cnt + GC_ROUND0 + r,
-                                       r + 1 == e.rounds ? gate : static_cast<uint32_t*>(nullptr));
-                });
-        };
-        auto buildChain = [&](size_t a) {
-            PlanEntry& e0 = act[a];
-            const uint32_t level = e0.level;
-            const uint32_t ov = level ? 0u : cnt(a, GC_OVERFLOW);
-            const uint32_t un = level ? 0u : cnt(a, GC_UNANCHORED);
-            const bool early = earlyOf[a] != 0;
-            // (round 0 left slots in play: their remainders are screened at the end of this chain, see remainderSteps)
-            const bool inPlay0 = remainderInChain && !level && cnt(a, GC_ROUND0) != 0;
-            if (!level && !ov && !un && !early && !inPlay0) return;
-            if (!level && !ov && !un && !early) {  // nothing but remainders to screen: with the others of its kind, in ONE launch at the fork
-                groupMask |= 1ull << a;
-                coveredMask |= 1ull << a;
-                return;
-            }
-            if (level && boundKnown && cnt(a, GC_BOUND) == 0) {  // nothing left for it (values are only ever won, never lost)
-                busy2c[a] = 0;
-                if (trace) fprintf(stderr, "grok plan 2c: entry %u level %u cand %u: every value already won\n", e0.p, e0.level, e0.cand);
-                return;
-            }
-            size_t owner = a;  // whose list the steps go to
-            if (level >= 2) {  // behind its main shadower
-                uint32_t best = 0, bestF = 0;
-                for (uint32_t f = 0; f < e0.p; ++f)
-                    if (T.hostWords[HW_SHADOW + e0.p * 64 + f] > best && map.activeOfBit[f] >= 0) {
-                        best = T.hostWords[HW_SHADOW + e0.p * 64 + f];
-                        bestF = f;
-                    }
-                if (best) {
-                    const size_t sa = size_t(map.activeOfBit[bestF]);
-                    e0.stream = act[sa].stream;
-                    owner = chainOwner[sa];
-                    chainOwner[a] = owner;
-                    chains[owner].push_back([&, a, sa](int& rc) {
-                        if (rc != LC_OK) return;
-                        hipLaunchKernelGGL(grok_entry_finish_kernel, dim3((act[sa].cand + kGrokPlanBlock - 1) / kGrokPlanBlock, 1), dim3(kGrokPlanBlock),
-                                           0, W(act[a].stream), T.dEntries, winner, undecided, static_cast<const uint32_t*>(nullptr), uint32_t(sa));
-                    });
-                }
-            }
-            std::vector<Step>& out = chains[owner];
-            busy2c[a] = (level || ov || un) ? 1 : 0;
-            if (trace) {
-                if (level) fprintf(stderr, "grok plan 2c: entry %u level %u cand %u stream %d%s\n", e0.p, e0.level, e0.cand, e0.stream, early ? " + rounds" : "");
-                else fprintf(stderr, "grok plan 2c: entry %u overflowed %u unanchored %u%s\n", e0.p, ov, un, early ? " + rounds" : "");
-            }
-            auto post = [&, a](const uint32_t* in, const uint32_t* inCount, uint32_t flags) {
-                PlanEntry& e = act[a];
-                hipLaunchKernelGGL(grok_post_kernel, dim3((e.cand + kGrokPlanBlock - 1) / kGrokPlanBlock, 1), dim3(kGrokPlanBlock), 0, W(e.stream),
-                                   T.dEntries, uint32_t(a), in, inCount, flags, xtmp, xcap, xstride, xcount, 0ull);
-            };
-            auto tick = [&, a](int which, int& rc) {
-                if (!calibrate || !busy2c[a]) return;
-                if (hipEventRecord(T.tick[2 * nAct + 2 * a + size_t(which)], W(act[a].stream)) != hipSuccess && rc == LC_OK && which == 0)
-                    rc = lcHipFail(hipGetLastError(), "hipEventRecord(calibration)");
-            };
-            // the search proper over the slots in `list`, minus the values an earlier entry has won: two steps
-            auto searchProperSteps = [&, a, post](const uint32_t* list, const uint32_t* count) {
-                out.push_back([&, a, list, count](int& rc) {
-                    if (rc != LC_OK) return;
-                    PlanEntry& e = act[a];
-                    const GrokDevicePattern& gp = patterns[e.p];
-                    hipStream_t ws = W(e.stream);
-                    lcSetDecideSlot(1 + e.stream);
-                    hipLaunchKernelGGL(grok_filter_won_kernel, dim3((e.cand + kGrokPlanBlock - 1) / kGrokPlanBlock), dim3(kGrokPlanBlock), 0, ws, e.dev,
-                                       static_cast<const uint32_t*>(winner), list, count, e.listB, e.dev.cnt + GC_FILTERED);
-                    rc = runFirst(e, gp.re, false, e.dev.cnt + GC_FILTERED, e.listB, true, &e.seqS, ws);
-                });
-                out.push_back([&, a, post](int& rc) {
-                    if (rc != LC_OK) return;
-                    PlanEntry& e = act[a];
-                    const GrokDevicePattern& gp = patterns[e.p];
-                    lcSetDecideSlot(1 + e.stream);
-                    rc = runSecond(e, gp.re, false, e.dev.cnt + GC_FILTERED, e.listB, true, e.seqS, nullptr, W(e.stream));
-                    if (rc == LC_OK) post(e.listB, e.dev.cnt + GC_FILTERED, uint32_t(GP_OVERFLOW_FINAL));
-                });
-            };
-            if (level == 0) {
-                if (ov) {  // the second chance of round 0's engine over the overflow list (the longest kernel of the phase: first), then the post step
-                    out.push_back([&, a, tick](int& rc) {
-                        tick(0, rc);
-                        if (rc != LC_OK) return;
-                        PlanEntry& e = act[a];
-                        const GrokDevicePattern& gp = patterns[e.p];
-                        lc_regex* first = gp.anchored ? gp.anchored : gp.re;
-                        lcSetDecideSlot(1 + e.stream);
-                        rc = runSecond(e, first, e.wideFirst, e.dev.cnt + GC_OVERFLOW, e.dev.ovList, !gp.anchored, e.seq0, e.dev.cnt + GC_WIDE,
-                                       W(e.stream));
-                    });
-                    out.push_back([&, a, post](int& rc) {
-                        if (rc != LC_OK) return;
-                        PlanEntry& e = act[a];
-                        post(e.dev.ovList, e.dev.cnt + GC_OVERFLOW, uint32_t(GP_ANCHORED_PASS | GP_OVERFLOW_FINAL));
-                    });
-                } else if (un) {
-                    out.push_back([tick](int& rc) { tick(0, rc); });
-                }
-                // (only when the anchored search left any value unmatched -- the host knows the count)
-                if (patterns[e0.p].anchored && un) searchProperSteps(e0.dev.unanchored, e0.dev.cnt + GC_UNANCHORED);
-            } else {
-                // every slot whose value nobody before has won: the anchored search (or the search) in full, then the rest
-                out.push_back([&, a, tick](int& rc) {
-                    tick(0, rc);
-                    if (rc != LC_OK) return;
-                    PlanEntry& e = act[a];
-                    const GrokDevicePattern& gp = patterns[e.p];
-                    hipStream_t ws = W(e.stream);
-                    lcSetDecideSlot(1 + e.stream);
-                    uint32_t* mine = e.dev.ovList;  // (a level > 0 entry has no first-chance pass: its overflow list is free)
-                    hipLaunchKernelGGL(grok_filter_won_kernel, dim3((e.cand + kGrokPlanBlock - 1) / kGrokPlanBlock), dim3(kGrokPlanBlock), 0, ws, e.dev,
-                                       static_cast<const uint32_t*>(winner), static_cast<const uint32_t*>(nullptr), static_cast<const uint32_t*>(nullptr),
-                                       mine, e.dev.cnt + GC_OVERFLOW);
-                    lc_regex* first = gp.anchored ? gp.anchored : gp.re;
-                    e.wideFirst = wantsWideFirst(first);
-                    rc = runFirst(e, first, e.wideFirst, e.dev.cnt + GC_OVERFLOW, mine, !gp.anchored, &e.seq0, ws);
-                });
-                out.push_back([&, a, post](int& rc) {
-                    if (rc != LC_OK) return;
-                    PlanEntry& e = act[a];
-                    const GrokDevicePattern& gp = patterns[e.p];
-                    lc_regex* first = gp.anchored ? gp.anchored : gp.re;
-                    lcSetDecideSlot(1 + e.stream);
-                    rc = runSecond(e, first, e.wideFirst, e.dev.cnt + GC_OVERFLOW, e.dev.ovList, !gp.anchored, e.seq0, e.dev.cnt + GC_WIDE,
-                                   W(e.stream));
-                    if (rc == LC_OK) post(e.dev.ovList, e.dev.cnt + GC_OVERFLOW, uint32_t(GP_ANCHORED_PASS | GP_OVERFLOW_FINAL));
-                });
-                if (patterns[e0.p].anchored) searchProperSteps(e0.dev.unanchored, e0.dev.cnt + GC_UNANCHORED);
-            }
-            if (busy2c[a]) out.push_back([tick](int& rc) { int ignored = LC_OK; tick(1, ignored); (void)rc; });  // (whichever way the chain ended)
-            if (early) {
-                earlyMask |= 1ull << a;
-                roundSteps(a, false, out);
-            } else if (remainderInChain) {
-                // Round 5: the remainder screens of THIS entry, here -- on its stream, as soon as its own chain is through -- instead of
-                // one launch for all entries behind the join of the phase (that launch, 0.4-0.5 ms for a few hundred 4 KiB remainders of
-                // one shadowed entry, sat between two host round trips on every batch's critical path).  Same kernels, the other
-                // entries' workgroups leave at once (skip mask).
-                coveredMask |= 1ull << a;
-                out.push_back([&, a](int& rc) {
-                    if (rc != LC_OK) return;
-                    PlanEntry& e = act[a];
-                    hipStream_t ws = W(e.stream);
-                    // (grid.y = 1 over a table that begins at this entry)
-                    const GrokEntryDev* mine = static_cast<const GrokEntryDev*>(T.dEntries) + a;
-                    if (remainderLiteral || remainderWon) lcNoteKernel("grok_remainder_literal_kernel");
-                    lcNoteKernel("grok_remainder_all_kernel");
-                    if (remainderLiteral || remainderWon)
-                        hipLaunchKernelGGL(grok_remainder_literal_kernel, dim3((e.cand + kGrokPlanBlock / 64 - 1) / (kGrokPlanBlock / 64), 1),
-                                           dim3(kGrokPlanBlock), 0, ws, d_data, mine,
-                                           remainderLiteral ? literalIndex : static_cast<const uint32_t*>(nullptr), 0ull,
-                                           remainderWon ? static_cast<const uint32_t*>(winner) : static_cast<const uint32_t*>(nullptr), 0u);
-                    const GrokScreenDev* sc = e.remainderScreen;
-                    const uint32_t lds = (small && sc) ? sc->ldsBytes : 0u;
-                    hipLaunchKernelGGL(grok_remainder_all_kernel, dim3(remGrid(e.cand), 1), dim3(kGrokPlanBlock), lds, ws,
-                                       d_data, mine, static_cast<const GrokScreenDev*>(T.dRemScreens) + a, (small ? 1u : 0u) | remWalk, 0ull,
-                                       remGate);
-                });
-            }
-        };
-        bool forked = false;
-        int rc2c = LC_OK;
-        {
-            for (size_t a = 0; a < nAct; ++a)
-                busy2c[a] = act[a].level ? ((boundKnown && cnt(a, GC_BOUND) == 0) ? 0 : 1) : (cnt(a, GC_OVERFLOW) || cnt(a, GC_UNANCHORED)) ? 1 : 0;
-            const std::vector<size_t> order1 = deal(true);
-            for (uint32_t level = 0; level <= maxLevel; ++level)
-                for (size_t i = 0; i < nAct; ++i)
-                    if (act[order1[i]].level == level) buildChain(order1[i]);
-            size_t longest = 0;
-            for (size_t a = 0; a < nAct; ++a) longest = std::max(longest, chains[a].size());
-            if (longest || groupMask || aheadLaunched) {
-                if (!boundKnown && !aheadLaunched)
-                    hipLaunchKernelGGL(grok_entry_finish_kernel, dim3(gridCand0, nAct), dim3(kGrokPlanBlock), 0, st, T.dEntries, winner, undecided,
-                                       static_cast<const uint32_t*>(nullptr), 0u);  // the values won so far (atomicMin per value: idempotent, finishAll runs it again)
-                rc2c = fork();
-                if (rc2c != LC_OK) return rc2c;
-                forked = true;
-                if (groupMask && !aheadLaunched) {  // the entries that only have remainders to screen: one launch pair, beside the chains
-                    hipStream_t gs = W(int(used) - 1);
-                    if (remainderLiteral || remainderWon) lcNoteKernel("grok_remainder_literal_kernel");
-                    lcNoteKernel("grok_remainder_all_kernel");
-                    if (remainderLiteral || remainderWon)
-                        hipLaunchKernelGGL(grok_remainder_literal_kernel, dim3((maxCand + kGrokPlanBlock / 64 - 1) / (kGrokPlanBlock / 64), nAct),
-                                           dim3(kGrokPlanBlock), 0, gs, d_data, T.dEntries,
-                                           remainderLiteral ? literalIndex : static_cast<const uint32_t*>(nullptr), ~groupMask,
-                                           remainderWon ? static_cast<const uint32_t*>(winner) : static_cast<const uint32_t*>(nullptr), 0u);
-                    hipLaunchKernelGGL(grok_remainder_all_kernel, dim3(remGrid(maxCand), nAct), dim3(kGrokPlanBlock), small ? remScreenLds : 0, gs, d_data,
-                                       T.dEntries, static_cast<const GrokScreenDev*>(T.dRemScreens), (small ? 1u : 0u) | remWalk, ~groupMask, remGate);
-                }
-                if (breadthFirst) {
-                    for (size_t k = 0; k < longest; ++k)
-                        for (size_t i = 0; i < nAct; ++i) {
-                            const size_t a = order1[i];
-                            if (k < chains[a].size()) chains[a][k](rc2c);
-                        }
-                } else {
-                    for (size_t i = 0; i < nAct; ++i)
-                        for (Step& s : chains[order1[i]]) s(rc2c);
-                }
-            }
-            if (forked) {
-                rc2c = join(rc2c);  // (always: a failure inside the forked region must not leave the worker streams unjoined)
-                if (rc2c != LC_OK) return rc2c;
-            }
-        }
-        // 2d (LC_GROK_REMAINDER_INCHAIN=0 only: by default every entry that can have a slot in play screened its remainders in its chain)
-        if (!remainderInChain) {
-        if (remainderWon)  // (the values won by now, phase 2c included: a slot in play whose value an earlier entry has won is finished)
-            hipLaunchKernelGGL(grok_entry_finish_kernel, dim3(gridCand0, nAct), dim3(kGrokPlanBlock), 0, st, T.dEntries, winner, undecided,
-                               static_cast<const uint32_t*>(nullptr), 0u);
-        if (remainderLiteral || remainderWon) {
-            lcNoteKernel("grok_remainder_literal_kernel");
-            hipLaunchKernelGGL(grok_remainder_literal_kernel, dim3((maxCand + kGrokPlanBlock / 64 - 1) / (kGrokPlanBlock / 64), nAct), dim3(kGrokPlanBlock),
-                               0, st, d_data, T.dEntries, remainderLiteral ? literalIndex : static_cast<const uint32_t*>(nullptr), earlyMask,
-                               remainderWon ? static_cast<const uint32_t*>(winner) : static_cast<const uint32_t*>(nullptr), 0u);
-        }
-        lcNoteKernel("grok_remainder_all_kernel");
-        hipLaunchKernelGGL(grok_remainder_all_kernel, dim3(remGrid(maxCand), nAct), dim3(kGrokPlanBlock), small ? remScreenLds : 0, st, d_data, T.dEntries,
-                           static_cast<const GrokScreenDev*>(T.dRemScreens), (small ? 1u : 0u) | remWalk, earlyMask, remGate);
-        }
-        HIP_TRY(hipGetLastError());
-        // What is left of phase 2 needs the survivors of the remainder screens -- almost always none.  Round 5: the host no longer waits
-        // to learn that.  A one-wave kernel adds the survivors to the gate word, the finish of the batch is queued behind it (it returns at
-        // once if the gate is up), and the host reads everything in ONE round trip: gate down = done (three host synchronisations per batch
-        // instead of four); gate up = the search rounds of the entries with survivors, then the finish again.  LC_GROK_LAZY_SYNC3=0: as before.
-        auto afterCounts = [&] {
-            if (calibrate)
-                for (size_t a = 0; a < nAct; ++a)
-                    if (busy2c[a]) learn(patterns[act[a].p].re->grokCost1Ns, T.tick[2 * nAct + 2 * a], T.tick[2 * nAct + 2 * a + 1], act[a].cand);
-            if (trace)
-                for (size_t a = 0; a < nAct; ++a)
-                    if (cnt(a, GC_ROUND0))
-                        fprintf(stderr, "grok plan 2d: entry %u in play %u, remainder passes the screen %u%s\n", act[a].p, cnt(a, GC_ROUND0),
-                                cnt(a, GC_REMAINDER), ((earlyMask >> a) & 1ull) ? " (rounds queued ahead)" : "");
-            // (the entries' histories: do most of the slots in play pass the remainder screen?  Judged on the batches that ran the screen
-            // for the entry -- every calibration batch does)
-            for (size_t a = 0; a < nAct; ++a) {
-                if ((earlyMask >> a) & 1ull) continue;
-                const uint32_t inPlay = cnt(a, GC_ROUND0), survivors = cnt(a, GC_REMAINDER);
-                if (inPlay) patterns[act[a].p].re->grokRemainderSeen.store(survivors * 4 >= inPlay * 3 ? 1u : 0u, std::memory_order_relaxed);
-            }
-        };
-        // 2e: the search rounds of the entries with survivors (-> true if there were any)
-        auto rounds2e = [&](bool& ran) -> int {
-            ran = false;
-            bool any = false;
-            for (size_t a = 0; a < nAct; ++a) any = any || (cnt(a, GC_REMAINDER) && !act[a].queued);
-            if (!any) return LC_OK;
-            ran = true;
-            int rc = fork();
-            if (rc != LC_OK) return rc;
-            for (size_t i = 0; i < nAct && rc == LC_OK; ++i) {
-                const size_t a = byCost[i];
-                PlanEntry& e = act[a];
-                if (!cnt(a, GC_REMAINDER) || e.queued) continue;
-                if (trace) fprintf(stderr, "grok plan 2e: entry %u in play %u survivors %u\n", e.p, cnt(a, GC_ROUND0), cnt(a, GC_REMAINDER));
-                std::vector<Step> steps;
-                roundSteps(a, true, steps);
-                for (Step& s2 : steps) s2(rc);
-            }
-            return join(rc);
-        };
-        if (!lazy) {
-            int rc = readCounts();  // sync 3
-            if (rc != LC_OK) return rc;
-            afterCounts();
-            bool ran = false;
-            rc = rounds2e(ran);
-            if (rc != LC_OK) return rc;
-        } else {
-            // (the survivors are on the gate word already: grok_remainder_all_kernel counts them there)
-            int rc = finishAll(gate);  // sync 3 = the last one, unless the gate is up
-            if (rc != LC_OK) return rc;
-            finished = true;
-            afterCounts();
-            if (T.hostWords[HW_TAIL + TW_GATE] != 0) {
-                // (the survivors' share leaves the gate again: what stays up is what the queued rounds left in play)
-                hipLaunchKernelGGL(grok_survivor_gate_kernel, dim3(1), dim3(64), 0, st, static_cast<const GrokEntryDev*>(T.dEntries), nAct, gate, 0u);
-                bool ran = false;
-                rc = rounds2e(ran);
-                if (rc != LC_OK) return rc;
-                if (ran) {
-                    rc = finishAll(gate);
-                    if (rc != LC_OK) return rc;
-                }
-            }
+                if (act[a].busy) learn(patterns[act[a].p].re->grokCost1Ns, T.tick[2 * nAct + 2 * a], T.tick[2 * nAct + 2 * a + 1], act[a].cand);
+        // (the entries' histories: do most of the slots in play pass the remainder screen?  Judged on the batches that ran the screen
+        // for the entry -- every calibration batch does)
+        for (size_t a = 0; a < nAct; ++a) {
+            const bool early = (chains.earlyMask >> a) & 1ull;
+            if (K.trace && cnt(a, GC_ROUND0))
+                fprintf(stderr, "grok plan 2d: entry %u in play %u, remainder passes the screen %u%s\n", act[a].p, cnt(a, GC_ROUND0),
+                        cnt(a, GC_REMAINDER), early ? " (rounds queued ahead)" : "");
+            const int seen = early ? -1 : grokplan::nextRemainderSeen(cnt(a, GC_ROUND0), cnt(a, GC_REMAINDER));
+            if (seen >= 0) patterns[act[a].p].re->grokRemainderSeen.store(uint32_t(seen), std::memory_order_relaxed);
         }
     }
-    if (!finished) {
-        int rc = finishAll(gate);  // the last sync
+    int survivors() {
+        afterCounts();
+        if (T.hostWords[HW_TAIL + TW_GATE] == 0) return LC_OK;
+        // (the survivors' share leaves the gate again: what stays up is what the queued rounds left in play)
+        hipLaunchKernelGGL(grok_survivor_gate_kernel, dim3(1), dim3(64), 0, st, static_cast<const GrokEntryDev*>(T.dEntries), nAct, gate, 0u);
+        bool any = false;
+        for (size_t a = 0; a < nAct; ++a) any = any || (cnt(a, GC_REMAINDER) && !act[a].queued);
+        if (!any) return LC_OK;
+        std::vector<size_t> byCost;  // (dearest first, by the static estimate)
+        for (size_t a = 0; a < nAct; ++a) byCost.push_back(a);
+        std::sort(byCost.begin(), byCost.end(), [&](size_t x, size_t y) { return act[x].cost > act[y].cost; });
+        int rc = fork();
         if (rc != LC_OK) return rc;
+        std::vector<grokplan::Step> steps;
+        for (size_t i = 0; i < nAct && rc == LC_OK; ++i) {
+            const size_t a = byCost[i];
+            PlanEntry& e = act[a];
+            if (!cnt(a, GC_REMAINDER) || e.queued) continue;
+            if (K.trace) fprintf(stderr, "grok plan 2e: entry %u in play %u survivors %u\n", e.p, cnt(a, GC_ROUND0), cnt(a, GC_REMAINDER));
+            steps.clear();
+            grokplan::appendRounds(e, a, true, steps);
+            for (const grokplan::Step& s : steps) runStep(s, rc);
+        }
+        rc = join(rc);
+        return rc != LC_OK ? rc : finish(gate);
     }
-    const double tPhase3 = msNow();
-    if (T.hostWords[HW_TAIL + TW_GATE] != 0) {
-        // values still in play after the last queued round of some entries: those entries go on, a stretch of rounds at a time (as
-        // many again as they had queued, the counts on the device as before), until nothing is left -- an entry pays this once, then
-        // asks for that many rounds ahead
+
+    // ---- values still in play after the last queued round of some entries: those entries go on, a stretch of rounds at a time (as
+    // many again as they had queued, the counts on the device as before), until nothing is left -- an entry pays this once, then
+    // asks for that many rounds ahead
+    int deferred() {
+        tPhase3 = msNow();
+        if (T.hostWords[HW_TAIL + TW_GATE] == 0) return LC_OK;
         for (size_t a = 0; a < nAct; ++a) {
             PlanEntry& e = act[a];
-            uint32_t inPlay = T.hostWords[HW_CNT + a * GC_WORDS + GC_ROUND0 + e.rounds - 1];
+            uint32_t* hostRounds = T.hostWords + HW_CNT + a * GC_WORDS + GC_ROUND0;
+            uint32_t inPlay = hostRounds[e.rounds - 1];
             if (!inPlay) continue;
             ++stats.deferredEntries;
             const GrokDevicePattern& gp = patterns[e.p];
@@ -1602,73 +1351,81 @@ int grokMatchSpeculative(const std::vector<GrokDevicePattern>& patterns, GrokDev
                 // the list of round r was written by round r - 1: (r & 1) ? listA : listB; counters are reused from slot 0
                 HIP_TRY(hipMemsetAsync(e.dev.cnt + GC_ROUND0, 0, size_t(stretch) * 4, st));
                 for (uint32_t k = 0; k < stretch; ++k, ++r) {
-                    const uint32_t* list = (r & 1) ? e.listA : e.listB;
-                    uint32_t* out = (r & 1) ? e.listB : e.listA;
+                    const uint32_t* list = (r & 1) ? e.dev.listA : e.listB;
+                    uint32_t* out = (r & 1) ? e.listB : e.dev.listA;
                     const uint32_t bound = k == 0 ? inPlay : e.cand;
                     const uint32_t* countPtr = k == 0 ? nullptr : e.dev.cnt + GC_ROUND0 + k - 1;
-                    int rc = lcMatchOnStream(gp.re, gp.re->engine, entryBatch(e, bound, countPtr, list, e.dev.from, st));
-                    if (rc != LC_OK) return rc;
-                    hipLaunchKernelGGL(grok_advance2_kernel, dim3((bound + kGrokPlanBlock - 1) / kGrokPlanBlock), dim3(kGrokPlanBlock), 0, st,
-                                       list, bound, countPtr, e.status, e.caps, e.capsRow, e.columns, e.dev, xtmp, xcap, xstride, xcount, out,
-                                       e.dev.cnt + GC_ROUND0 + k, static_cast<uint32_t*>(nullptr));
+                    if (const int rc = lcMatchOnStream(gp.re, gp.re->engine, entryBatch(e, bound, countPtr, list, e.dev.from, st)); rc != LC_OK) return rc;
+                    hipLaunchKernelGGL(grok_advance2_kernel, dim3(grid(bound)), dim3(kGrokPlanBlock), 0, st, list, bound, countPtr, e.status, e.caps,
+                                       e.capsRow, e.columns, e.dev, xtmp, xcap, xstride, xcount, out, e.dev.cnt + GC_ROUND0 + k,
+                                       static_cast<uint32_t*>(nullptr));
                 }
-                HIP_TRY(hipMemcpyAsync(T.hostWords + HW_CNT + a * GC_WORDS + GC_ROUND0, e.dev.cnt + GC_ROUND0, size_t(stretch) * 4,
-                                       hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpyAsync(hostRounds, e.dev.cnt + GC_ROUND0, size_t(stretch) * 4, hipMemcpyDeviceToHost, st));
                 HIP_TRY(syncCounted(st));
-                inPlay = T.hostWords[HW_CNT + a * GC_WORDS + GC_ROUND0 + stretch - 1];
+                inPlay = hostRounds[stretch - 1];
                 if (!inPlay) {  // rounds that had anything to search: up to the first empty list of this stretch
                     uint32_t usedRounds = stretch;
-                    while (usedRounds > 1 && T.hostWords[HW_CNT + a * GC_WORDS + GC_ROUND0 + usedRounds - 2] == 0) --usedRounds;
+                    while (usedRounds > 1 && hostRounds[usedRounds - 2] == 0) --usedRounds;
                     r = r - stretch + usedRounds;
                 }
             }
             e.ran = r;  // (what this batch needed: the hint below)
         }
-        int rc = finishAll(nullptr);
-        if (rc != LC_OK) return rc;
+        return finish(nullptr);
     }
-    // ---- how many rounds each entry should queue ahead next time: what this batch needed, forgotten slowly
-    for (size_t a = 0; a < nAct; ++a) {
-        PlanEntry& e = act[a];
-        {  // did any of its values need more than 64 threads (GC_WIDE: set by the wide kernel)?  seen now = 8, else forgotten a batch at a time
-            lc_regex* first = patterns[e.p].anchored ? patterns[e.p].anchored : patterns[e.p].re;
-            const uint32_t v = first->grokOverflowSeen.load(std::memory_order_relaxed);
-            if (T.hostWords[HW_CNT + a * GC_WORDS + GC_WIDE]) first->grokOverflowSeen.store(8, std::memory_order_relaxed);
-            else if (v) first->grokOverflowSeen.store(v - 1, std::memory_order_relaxed);
-        }
-        uint32_t needed = 1;  // rounds that had any value to search
-        for (uint32_t r = 0; r + 1 < e.rounds && e.ran == 0; ++r)
-            if (T.hostWords[HW_CNT + a * GC_WORDS + GC_ROUND0 + r]) needed = r + 2;
-        lc_regex* re = patterns[e.p].re;
-        const uint32_t hint = re->grokRounds.load(std::memory_order_relaxed);
-        if (e.ran > hint) {
-            re->grokRounds.store(std::min(e.ran, kGrokMaxRounds), std::memory_order_relaxed);
-            re->grokRoundsSlack.store(0, std::memory_order_relaxed);
-        } else if (needed < hint && e.ran == 0) {
-            if (re->grokRoundsSlack.fetch_add(1, std::memory_order_relaxed) + 1 >= 4) {
-                re->grokRounds.store(needed, std::memory_order_relaxed);
-                re->grokRoundsSlack.store(0, std::memory_order_relaxed);
-            }
-        } else {
-            re->grokRoundsSlack.store(0, std::memory_order_relaxed);
+
+    // ---- the entries' histories: wide first next time?  how many rounds to queue ahead?  (grok_plan_host.hpp has the rules)
+    void history() {
+        for (size_t a = 0; a < nAct; ++a) {
+            const PlanEntry& e = act[a];
+            const uint32_t* my = T.hostWords + HW_CNT + a * GC_WORDS;
+            std::atomic<uint32_t>& overflowSeen = firstOf(e)->grokOverflowSeen;
+            const uint32_t seen = overflowSeen.load(std::memory_order_relaxed);
+            if (my[GC_WIDE] || seen) overflowSeen.store(grokplan::nextOverflowSeen(seen, my[GC_WIDE]), std::memory_order_relaxed);
+            lc_regex* re = patterns[e.p].re;
+            const grokplan::RoundsHint now{re->grokRounds.load(std::memory_order_relaxed), re->grokRoundsSlack.load(std::memory_order_relaxed)};
+            const grokplan::RoundsHint next = grokplan::nextRoundsHint(now, e.ran, grokplan::roundsNeeded(my, e.rounds, e.ran));
+            if (next.rounds != now.rounds) re->grokRounds.store(next.rounds, std::memory_order_relaxed);
+            re->grokRoundsSlack.store(next.slack, std::memory_order_relaxed);
         }
     }
-    if (trace)
-        fprintf(stderr, "grok plan: n %u entries %u (second pass %u) pairs %u screens %u | phase1 %.3f ms, entries+finish %.3f ms, total %.3f ms, syncs %u, deferred %u\n",
-                n, nAct, nSecond, stats.pairs, nScreens, tPhase1, tPhase3 - tPhase1, msNow(), stats.hostSyncs, stats.deferredEntries);
-    const uint32_t xWanted = T.hostWords[HW_TAIL + TW_XCOUNT];
-    const uint32_t nextra = T.hostWords[HW_TAIL + TW_NEXTRA];
-    if (xWanted > xcap) {
-        // the temporary rows themselves did not fit: report an upper bound of what is needed (winners' rows <= all rows)
-        HIP_TRY(hipMemcpy(d_nextra, &xWanted, 4, hipMemcpyHostToDevice));
-        lcSetLastError("grok: " + std::to_string(xWanted) + " extra match rows needed, buffer holds " + std::to_string(extraCap));
-        return LC_ERR_OVERFLOW;
+
+    int result() {
+        if (K.trace)
+            fprintf(stderr, "grok plan: n %u entries %u (second pass %u) pairs %u screens %u | phase1 %.3f ms, entries+finish %.3f ms, total %.3f ms, syncs %u, deferred %u\n",
+                    n, nAct, nSecond, stats.pairs, P1.nScreens, tPhase1, tPhase3 - tPhase1, msNow(), stats.hostSyncs, stats.deferredEntries);
+        const uint32_t xWanted = T.hostWords[HW_TAIL + TW_XCOUNT];
+        const uint32_t nextra = T.hostWords[HW_TAIL + TW_NEXTRA];
+        if (xWanted > xcap) {
+            // the temporary rows themselves did not fit: report an upper bound of what is needed (winners' rows <= all rows)
+            HIP_TRY(hipMemcpy(d_nextra, &xWanted, 4, hipMemcpyHostToDevice));
+            lcSetLastError("grok: " + std::to_string(xWanted) + " extra match rows needed, buffer holds " + std::to_string(extraCap));
+            return LC_ERR_OVERFLOW;
+        }
+        if (nextra > extraCap) {
+            lcSetLastError("grok: " + std::to_string(nextra) + " extra match rows needed, buffer holds " + std::to_string(extraCap));
+            return LC_ERR_OVERFLOW;
+        }
+        return LC_OK;
     }
-    if (nextra > extraCap) {
-        lcSetLastError("grok: " + std::to_string(nextra) + " extra match rows needed, buffer holds " + std::to_string(extraCap));
-        return LC_ERR_OVERFLOW;
-    }
-    return LC_OK;
+};
+
+int grokMatchSpeculative(const std::vector<GrokDevicePattern>& patterns, GrokDeviceState* state, const GrokOptions& opts, uint32_t row,
+                         const uint8_t* d_data, const uint32_t* d_off, const uint32_t* d_len, uint32_t n, int32_t* d_pattern,
+                         int32_t* d_first, int32_t* d_extra, uint32_t extraCap, uint32_t* d_nextra, void* d_scratch, hipStream_t st,
+                         int dev) {
+    GrokBatch B{patterns, state, opts, row, d_data, d_off, d_len, n, d_pattern, d_first, d_extra, extraCap, d_nextra, d_scratch, st, dev};
+    int rc = B.phase1();  // sync 1
+    if (rc == LC_OK) rc = B.entries();
+    if (rc == LC_OK && B.nAct) rc = B.round0();
+    if (rc == LC_OK && B.nAct) rc = B.ahead();  // sync 2
+    if (rc == LC_OK && B.nAct) rc = B.runChains();
+    if (rc == LC_OK) rc = B.finish(B.gate);  // sync 3: the last one, unless the gate is up
+    if (rc == LC_OK && B.nAct) rc = B.survivors();
+    if (rc == LC_OK) rc = B.deferred();
+    if (rc != LC_OK) return rc;
+    B.history();
+    return B.result();
 }
 }  // namespace
 
