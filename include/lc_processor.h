@@ -116,6 +116,21 @@ lc_event_group_t* lc_group_from_buffer(const uint8_t* data, size_t n, const char
 int lc_group_set_metadata(lc_event_group_t* g, const char* name, const char* value);
 char* lc_group_to_json(const lc_event_group_t* g);
 size_t lc_group_event_count(const lc_event_group_t* g);
+/* ---- raw events in, metric events out (processor_parse_prom_gpu, lc_prom.h): an empty group; one more RawEvent whose content is a
+ * copy of data[0 .. n) in the group's SourceBuffer; one more LogEvent with one content (an event that is no RawEvent) */
+lc_event_group_t* lc_group_new(void);
+int lc_group_add_raw_event(lc_event_group_t* g, const uint8_t* data, size_t n);
+int lc_group_add_log_event(lc_event_group_t* g, const char* key, const char* value);
+/* PipelineEvent::Type of event `event`: 1 log, 2 metric, 3 span, 4 raw; 0: no such event */
+int lc_group_event_type(const lc_event_group_t* g, size_t event);
+/* the event's timestamp; *has_nanos: whether the nanosecond part is set.  LC_ERR_ARG: no such event */
+int lc_group_event_timestamp(const lc_event_group_t* g, size_t event, int64_t* secs, uint32_t* nanos, int* has_nanos);
+/* a MetricEvent's name (a view, not NUL-terminated), the bits of its UntypedSingleValue, its tags in order.  LC_ERR_ARG: event is no
+ * metric event (or holds no single value / no tag k) */
+int lc_group_metric_name(const lc_event_group_t* g, size_t event, const char** name, size_t* len);
+int lc_group_metric_value_bits(const lc_event_group_t* g, size_t event, uint64_t* bits);
+size_t lc_group_metric_tag_count(const lc_event_group_t* g, size_t event);
+int lc_group_metric_tag(const lc_event_group_t* g, size_t event, size_t k, const char** key, size_t* key_len, const char** value, size_t* value_len);
 /* where log event `event`'s value of `key` lies (tests: a processor that leaves a value alone leaves its VIEW alone); 0: no such content */
 uintptr_t lc_group_content_address(const lc_event_group_t* g, size_t event, const char* key);
 /* the logtail::PipelineEventGroup* inside the fixture wrapper (what processor_interface.process expects) */

@@ -18,8 +18,8 @@ LIB = os.path.join(LIBDIR, "liblc_regex_gpu.so")
 # end_to_end.in_agent_reference_shape_MBps -- what an agent build's event model lets one runner thread do; never the default.
 LIB_REFSHAPE = os.path.join(LIBDIR, "liblc_regex_gpu_refshape.so")
 
-SOURCES = ["regex_parse.cpp", "atomic_elide.cpp", "follow_nfa.cpp", "tdfa.cpp", "table_cache.cpp", "screen_dfa.cpp", "bt_program.cpp", "regex_handle.cpp", "gpu_runtime.hip", "grok_device.hip", "multiline_device.hip", "delim_device.hip", "strptime_program.cpp", "timestamp_device.hip", "json_device.hip", "apsara_device.hip", "clog_device.hip", "desens_device.hip"]
-OPTIONAL_SOURCES = ["event_model.cpp", "processor_parse_regex_gpu.cpp", "grok.cpp", "grok_literal_index.cpp", "processor_grok_gpu.cpp", "processor_filter_gpu.cpp", "processor_go_regex_gpu.cpp", "multiline_gpu.cpp", "multiline_events.cpp", "processor_pipeline_gpu.cpp", "processor_parse_delimiter_gpu.cpp", "processor_parse_timestamp_gpu.cpp", "processor_parse_json_gpu.cpp", "processor_parse_apsara_gpu.cpp", "processor_parse_container_log_gpu.cpp", "processor_desensitize_gpu.cpp", "c_processor_slot.cpp"]
+SOURCES = ["regex_parse.cpp", "atomic_elide.cpp", "follow_nfa.cpp", "tdfa.cpp", "table_cache.cpp", "screen_dfa.cpp", "bt_program.cpp", "regex_handle.cpp", "gpu_runtime.hip", "grok_device.hip", "multiline_device.hip", "delim_device.hip", "strptime_program.cpp", "timestamp_device.hip", "json_device.hip", "apsara_device.hip", "clog_device.hip", "desens_device.hip", "prom_device.hip"]
+OPTIONAL_SOURCES = ["event_model.cpp", "processor_parse_regex_gpu.cpp", "grok.cpp", "grok_literal_index.cpp", "processor_grok_gpu.cpp", "processor_filter_gpu.cpp", "processor_go_regex_gpu.cpp", "multiline_gpu.cpp", "multiline_events.cpp", "processor_pipeline_gpu.cpp", "processor_parse_delimiter_gpu.cpp", "processor_parse_timestamp_gpu.cpp", "processor_parse_json_gpu.cpp", "processor_parse_apsara_gpu.cpp", "processor_parse_container_log_gpu.cpp", "processor_desensitize_gpu.cpp", "processor_parse_prom_gpu.cpp", "c_processor_slot.cpp"]
 
 
 # what the on-disk table cache's stamp is made of: the constructions, the structures they read and write, the cache's own format
@@ -55,6 +55,7 @@ def needs_build():
     deps.append(os.path.join(HERE, "..", "include", "lc_apsara.h"))
     deps.append(os.path.join(HERE, "..", "include", "lc_container_log.h"))
     deps.append(os.path.join(HERE, "..", "include", "lc_desensitize.h"))
+    deps.append(os.path.join(HERE, "..", "include", "lc_prom.h"))
     deps.append(os.path.join(HERE, "data", "grok_default_patterns.txt"))
     return any(os.path.exists(d) and os.path.getmtime(d) > t for d in deps)
 

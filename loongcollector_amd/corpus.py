@@ -182,3 +182,51 @@ def multiline_buffer(target_bytes, seed=SEED + 17, unmatched_head=0):
             out.append(ln)
             size += len(ln) + 1
     return b"\n".join(out) + b"\n"
+
+
+_PROM_WORDS = ("http", "requests", "total", "duration", "seconds", "bucket", "node", "cpu", "memory", "bytes", "container", "network", "receive",
+               "transmit", "errors", "process", "go", "gc", "heap", "alloc", "kube", "pod", "status", "ready", "disk", "io", "time", "queue")
+_PROM_LABELS = ("instance", "job", "namespace", "pod", "container", "device", "mode", "code", "method", "handler", "le", "quantile", "cpu", "id")
+
+
+def prom_exposition_lines(n_lines, seed=SEED + 29, deferred=0.0, failing=0.0):
+    """n Prometheus exposition lines (list of bytes) as a scrape pipeline sees them: names of 10 to 40 bytes, 0 to 8 labels, two lines in
+    three with a millisecond timestamp.  The values are drawn ONLY from the forms the device converts itself (integers and decimals of
+    up to 15 digits, exponents whose decimal exponent stays within +-22, zero, +Inf, NaN) -- except that a fraction `deferred` of the
+    lines carries a value the host has to finish (19-digit mantissas, exponents beyond 22, hex floats) and a fraction `failing` is
+    broken (no value, an open label value, a bad name).  Escaped label values occur in one line in fifty."""
+    import random
+    rng = random.Random(seed)
+    out = []
+    for i in range(n_lines):
+        name = "_".join(rng.choice(_PROM_WORDS) for _ in range(rng.randrange(2, 6)))
+        while len(name) < 10:
+            name += "_" + rng.choice(_PROM_WORDS)
+        name = name[:40].rstrip("_")
+        labels = []
+        for k in rng.sample(_PROM_LABELS, rng.randrange(0, 9)):
+            kind = rng.randrange(4)
+            value = ("10.%d.%d.%d:%d" % (rng.randrange(256), rng.randrange(256), rng.randrange(256), rng.randrange(1024, 65536)) if kind == 0 else
+                     "%s-%x" % (rng.choice(_PROM_WORDS), rng.getrandbits(32)) if kind == 1 else str(rng.randrange(1000)) if kind == 2 else "")
+            if rng.randrange(50) == 0:
+                value += rng.choice(['\\"quoted\\"', "a\\\\b", "line\\nbreak"])
+            labels.append('%s="%s"' % (k, value))
+        form = rng.randrange(8)
+        value = (str(rng.randrange(10 ** rng.randrange(1, 16))) if form < 3 else
+                 "%d.%0*d" % (rng.randrange(10 ** 6), rng.randrange(1, 7), rng.randrange(10)) if form < 5 else
+                 "%d.%de%+03d" % (rng.randrange(1, 10), rng.randrange(10 ** 9), rng.randrange(-10, 11)) if form == 5 else
+                 rng.choice(["0", "+Inf", "NaN", "-0", "1e22", "0.5"]) if form == 6 else "%.6f" % rng.uniform(0, 1000))
+        r = rng.random()
+        if r < failing:
+            broken = rng.randrange(3)
+            line = (name if broken == 0 else '%s{%s="open} %s' % (name, rng.choice(_PROM_LABELS), value) if broken == 1 else "9" + name + " " + value)
+            out.append(line.encode())
+            continue
+        if r < failing + deferred:
+            value = rng.choice(["%d" % rng.randrange(10 ** 18, 10 ** 19), "%d.%de+%d" % (rng.randrange(1, 10), rng.randrange(10 ** 6), rng.randrange(30, 300)),
+                                "0x%x" % rng.getrandbits(20), "0.%d" % rng.randrange(10 ** 17, 10 ** 18)])
+        line = name + ("{" + ",".join(labels) + "}" if labels else "") + " " + value
+        if rng.randrange(3):
+            line += " %d" % (1715829785083 + i)
+        out.append(line.encode())
+    return out

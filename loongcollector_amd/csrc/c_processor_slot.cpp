@@ -35,6 +35,9 @@ __attribute__((weak)) void lcContainerLogSlotFinalize(void* state);
 __attribute__((weak)) int lcDesensitizeSlotInit(const char* config_text, void** state);  // processor_desensitize_gpu.cpp
 __attribute__((weak)) void lcDesensitizeSlotProcess(void* state, void* native_group);
 __attribute__((weak)) void lcDesensitizeSlotFinalize(void* state);
+__attribute__((weak)) int lcPromSlotInit(const char* config_text, void** state);  // processor_parse_prom_gpu.cpp
+__attribute__((weak)) void lcPromSlotProcess(void* state, void* native_group);
+__attribute__((weak)) void lcPromSlotFinalize(void* state);
 }
 namespace {
 struct SlotEntry {
@@ -50,6 +53,7 @@ const SlotEntry kSlotTable[] = {
     {"processor_parse_apsara_gpu", "Apsara parser", lcApsaraSlotInit, lcApsaraSlotProcess, lcApsaraSlotFinalize},
     {"processor_parse_container_log_gpu", "container log parser", lcContainerLogSlotInit, lcContainerLogSlotProcess, lcContainerLogSlotFinalize},
     {"processor_desensitize_gpu", "desensitize processor", lcDesensitizeSlotInit, lcDesensitizeSlotProcess, lcDesensitizeSlotFinalize},
+    {"processor_prom_parse_metric_gpu", "Prometheus line parser", lcPromSlotInit, lcPromSlotProcess, lcPromSlotFinalize},
 };
 }  // namespace
 
@@ -377,6 +381,62 @@ extern "C" uintptr_t lc_group_content_address(const lc_event_group_t* g, size_t 
     if (!g || !key || event >= g->group.GetEvents().size() || !g->group.GetEvents()[event].Is<logtail::LogEvent>()) return 0;
     const logtail::LogEvent& ev = g->group.GetEvents()[event].Cast<logtail::LogEvent>();
     return ev.HasContent(key) ? reinterpret_cast<uintptr_t>(ev.GetContent(key).data()) : 0;
+}
+// ---- raw events in, metric events out (lc_processor.h)
+extern "C" lc_event_group_t* lc_group_new(void) { return new lc_event_group; }
+extern "C" int lc_group_add_raw_event(lc_event_group_t* g, const uint8_t* data, size_t n) {
+    if (!g || (!data && n)) return LC_ERR_ARG;
+    const logtail::StringBuffer b = g->group.GetSourceBuffer()->CopyString(reinterpret_cast<const char*>(data), n);
+    g->group.AddRawEvent()->SetContentNoCopy(logtail::StringView(b.data, b.size));
+    return LC_OK;
+}
+extern "C" int lc_group_add_log_event(lc_event_group_t* g, const char* key, const char* value) {
+    if (!g || !key || !value) return LC_ERR_ARG;
+    g->group.AddLogEvent()->SetContent(std::string(key), std::string(value));
+    return LC_OK;
+}
+extern "C" int lc_group_event_type(const lc_event_group_t* g, size_t event) {
+    return g && event < g->group.GetEvents().size() ? int(g->group.GetEvents()[event]->GetType()) : 0;
+}
+extern "C" int lc_group_event_timestamp(const lc_event_group_t* g, size_t event, int64_t* secs, uint32_t* nanos, int* has_nanos) {
+    if (!g || event >= g->group.GetEvents().size() || !secs || !nanos || !has_nanos) return LC_ERR_ARG;
+    const logtail::PipelineEventPtr& e = g->group.GetEvents()[event];
+    *secs = int64_t(e->GetTimestamp());
+    *has_nanos = e->GetTimestampNanosecond() ? 1 : 0;
+    *nanos = e->GetTimestampNanosecond() ? *e->GetTimestampNanosecond() : 0;
+    return LC_OK;
+}
+static const logtail::MetricEvent* metricEventOf(const lc_event_group_t* g, size_t event) {
+    if (!g || event >= g->group.GetEvents().size() || !g->group.GetEvents()[event].Is<logtail::MetricEvent>()) return nullptr;
+    return &g->group.GetEvents()[event].Cast<logtail::MetricEvent>();
+}
+extern "C" int lc_group_metric_name(const lc_event_group_t* g, size_t event, const char** name, size_t* len) {
+    const logtail::MetricEvent* m = metricEventOf(g, event);
+    if (!m || !name || !len) return LC_ERR_ARG;
+    *name = m->GetName().data();
+    *len = m->GetName().size();
+    return LC_OK;
+}
+extern "C" int lc_group_metric_value_bits(const lc_event_group_t* g, size_t event, uint64_t* bits) {
+    const logtail::MetricEvent* m = metricEventOf(g, event);
+    if (!m || !bits || !m->Is<logtail::UntypedSingleValue>()) return LC_ERR_ARG;
+    std::memcpy(bits, &m->GetValue<logtail::UntypedSingleValue>()->mValue, 8);
+    return LC_OK;
+}
+extern "C" size_t lc_group_metric_tag_count(const lc_event_group_t* g, size_t event) {
+    const logtail::MetricEvent* m = metricEventOf(g, event);
+    return m ? m->TagsSize() : 0;
+}
+extern "C" int lc_group_metric_tag(const lc_event_group_t* g, size_t event, size_t k, const char** key, size_t* key_len, const char** value,
+                                   size_t* value_len) {
+    const logtail::MetricEvent* m = metricEventOf(g, event);
+    if (!m || k >= m->TagsSize() || !key || !key_len || !value || !value_len) return LC_ERR_ARG;
+    const auto& tag = *(m->TagsBegin() + long(k));
+    *key = tag.first.data();
+    *key_len = tag.first.size();
+    *value = tag.second.data();
+    *value_len = tag.second.size();
+    return LC_OK;
 }
 extern "C" void* lc_group_native(lc_event_group_t* g) { return g ? &g->group : nullptr; }
 extern "C" void lc_group_free(lc_event_group_t* g) { delete g; }

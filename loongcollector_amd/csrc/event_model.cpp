@@ -3,6 +3,8 @@
 #include "event_model.hpp"
 
 #include <algorithm>
+#include <cstdio>
+#include <cstring>
 
 #include "json_min.hpp"
 
@@ -18,6 +20,10 @@ const std::pair<const char*, EventGroupMetaKey> kMetaNames[] = {
     {"source.id", EventGroupMetaKey::SOURCE_ID},
     {"container.type", EventGroupMetaKey::LOG_FORMAT},
 };
+// EventGroupMetaKeyToString (core/models/PipelineEventGroup.cpp:367-383) has no name for the scrape timestamp: it is SHOWN as "unknown".
+// extension: the fixture loader reads it under a name of its own (the reference's FromJson cannot set it at all)
+const char* const kScrapeTimestampShown = "unknown";
+const char* const kScrapeTimestampName = "prometheus.scrape.timestamp.millisec";
 // EventGroupMetaValueToString (core/models/PipelineEventGroup.cpp:363-392): the two container log formats are shown by name.  (The
 // reference renames the value of EVERY key; here only LOG_FORMAT's, so that no other key's output changes.)
 const std::pair<const char*, const char*> kFormatNames[] = {{"1", "containerd_text"}, {"2", "docker_json-file"}};
@@ -42,6 +48,10 @@ bool PipelineEventGroup::SetMetadataByName(const std::string& name, const std::s
             SetMetadata(known.second, metaValueFromString(known.second, value));
             return true;
         }
+    }
+    if (name == kScrapeTimestampName) {
+        SetMetadata(EventGroupMetaKey::PROMETHEUS_SCRAPE_TIMESTAMP_MILLISEC, value);
+        return true;
     }
     return false;
 }
@@ -104,9 +114,11 @@ std::string PipelineEventGroup::ToJsonString() const {
     lcjson::Value root = lcjson::Value::makeObject();
     if (!mMetadata.empty()) {
         lcjson::Value md = lcjson::Value::makeObject();
-        for (const auto& kv : mMetadata)
+        for (const auto& kv : mMetadata) {
+            if (kv.first == EventGroupMetaKey::PROMETHEUS_SCRAPE_TIMESTAMP_MILLISEC) md.set(kScrapeTimestampShown, lcjson::Value::makeString(kv.second.to_string()));
             for (const auto& name : kMetaNames)
                 if (kv.first == name.second) md.set(name.first, lcjson::Value::makeString(metaValueToString(kv.first, kv.second.to_string())));
+        }
         root.set("metadata", std::move(md));
     }
     if (!mTags.empty()) {
@@ -130,6 +142,24 @@ std::string PipelineEventGroup::ToJsonString() const {
                     ev.set("fileOffset", lcjson::Value::makeInt(int64_t(le.GetPosition().first)));
                     ev.set("rawSize", lcjson::Value::makeInt(int64_t(le.GetPosition().second)));
                 }
+            } else if (e.Is<MetricEvent>()) {  // MetricEvent::ToJson (MetricEvent.cpp:125-150); the value also as its bit pattern
+                const MetricEvent& me = e.Cast<MetricEvent>();
+                ev.set("name", lcjson::Value::makeString(me.GetName().to_string()));
+                if (const UntypedSingleValue* v = me.GetValue<UntypedSingleValue>()) {
+                    uint64_t bits = 0;
+                    std::memcpy(&bits, &v->mValue, 8);
+                    char hex[17];
+                    std::snprintf(hex, sizeof hex, "%016llx", static_cast<unsigned long long>(bits));
+                    ev.set("valueBits", lcjson::Value::makeString(hex));
+                }
+                lcjson::Value tags = lcjson::Value::makeArray();  // extension: [[key, value], ...] keeps the order
+                for (auto it = me.TagsBegin(); it != me.TagsEnd(); ++it) {
+                    lcjson::Value pair = lcjson::Value::makeArray();
+                    pair.arr.push_back(lcjson::Value::makeString(it->first.to_string()));
+                    pair.arr.push_back(lcjson::Value::makeString(it->second.to_string()));
+                    tags.arr.push_back(std::move(pair));
+                }
+                ev.set("tags", std::move(tags));
             } else {
                 ev.set("content", lcjson::Value::makeString(e.Cast<RawEvent>().GetContent().to_string()));
             }

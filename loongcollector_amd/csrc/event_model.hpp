@@ -3,6 +3,7 @@
 // processor_parse_regex_gpu.cpp compiles unchanged against either this header or the reference's own
 //   core/models/PipelineEventGroup.h:71-158   core/models/LogEvent.h:64-132   core/models/PipelineEventPtr.h:32-96
 //   core/common/StringView.h:25               core/common/memory/SourceBuffer.h:29-181
+//   core/models/MetricEvent.h:30-120 (the subset the Prometheus line parser uses)   core/models/SizedContainer.h:63-104
 // (define LC_USE_REFERENCE_HEADERS in the reference tree).  Written from the interface, not copied: only the
 // observable semantics the reference unit tests pin are reproduced --
 //   * contents are an ordered list of (key,value,alive); lookups scan from the back; delete is a tombstone that keeps
@@ -12,6 +13,7 @@
 //     gives requests of at least half a chunk their own block   (SourceBuffer.h:45-153)
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <iterator>
@@ -25,6 +27,7 @@
 #include <tuple>
 #include <type_traits>
 #include <utility>
+#include <variant>
 #include <vector>
 
 namespace logtail {
@@ -166,7 +169,9 @@ enum class EventGroupMetaKey {
     LOG_FILE_OFFSET_KEY,
     HAS_PART_LOG,
     SOURCE_ID,
-    LOG_FORMAT  // the container runtime's log format: "1" containerd text, "2" Docker json-file
+    LOG_FORMAT,  // the container runtime's log format: "1" containerd text, "2" Docker json-file
+    PROMETHEUS_SCRAPE_TIMESTAMP_MILLISEC  // when the scrape was made: the default timestamp of its samples (shown as "unknown", as the
+                                          // reference's EventGroupMetaKeyToString shows every key it has no name for)
 };
 using GroupMetadata = std::map<EventGroupMetaKey, StringView>;
 using GroupTags = std::map<StringView, StringView>;
@@ -440,6 +445,82 @@ private:
     StringView mContent;
 };
 
+// ---- core/models/MetricValue.h:34-43, SizedContainer.h:63-104, MetricEvent.h -- limited to what processor_parse_prom_gpu calls
+struct UntypedSingleValue {
+    double mValue;
+    constexpr size_t DataSize() const { return sizeof(UntypedSingleValue); }
+};
+using MetricValue = std::variant<std::monostate, UntypedSingleValue>;
+
+// tags in insertion order; a key that is present keeps its position and takes the new value
+class SizedVectorTags {
+public:
+    void Insert(StringView key, StringView val) {
+        auto iter = std::find_if(mInner.begin(), mInner.end(), [key](const auto& item) { return item.first == key; });
+        if (iter != mInner.end()) {
+            mAllocatedSize -= iter->second.size();
+            mAllocatedSize += val.size();
+            iter->second = val;
+        } else {
+            mAllocatedSize += key.size() + val.size();
+            mInner.emplace_back(key, val);
+        }
+    }
+    size_t DataSize() const { return sizeof(decltype(mInner)) + mAllocatedSize; }
+    std::vector<std::pair<StringView, StringView>> mInner;
+
+private:
+    size_t mAllocatedSize = 0;
+};
+
+class MetricEvent : public PipelineEvent {
+public:
+    explicit MetricEvent(PipelineEventGroup* g) : PipelineEvent(Type::METRIC, g) {}
+    StringView GetName() const { return mName; }
+    void SetNameNoCopy(StringView name) { mName = name; }
+    template <typename T>
+    bool Is() const {
+        return std::holds_alternative<T>(mValue);
+    }
+    template <typename T>
+    constexpr std::add_pointer_t<const T> GetValue() const noexcept {
+        return std::get_if<T>(&mValue);
+    }
+    template <typename T>
+    void SetValue(const T& value) {
+        mValue = value;
+    }
+    template <typename T, typename... Args>
+    void SetValue(Args&&... args) {
+        mValue = T{std::forward<Args>(args)...};
+    }
+    StringView GetTag(StringView key) const {
+        for (const auto& t : mTags.mInner)
+            if (t.first == key) return t.second;
+        return StringView();
+    }
+    bool HasTag(StringView key) const {
+        for (const auto& t : mTags.mInner)
+            if (t.first == key) return true;
+        return false;
+    }
+    void SetTag(StringView key, StringView val);  // copies both into the group's SourceBuffer
+    void SetTag(const std::string& key, const std::string& val) { SetTag(StringView(key), StringView(val)); }
+    void SetTagNoCopy(StringView key, StringView val) { mTags.Insert(key, val); }
+    std::vector<std::pair<StringView, StringView>>::const_iterator TagsBegin() const { return mTags.mInner.begin(); }
+    std::vector<std::pair<StringView, StringView>>::const_iterator TagsEnd() const { return mTags.mInner.end(); }
+    size_t TagsSize() const { return mTags.mInner.size(); }
+    size_t DataSize() const override {
+        return PipelineEvent::DataSize() + mName.size() + (Is<UntypedSingleValue>() ? sizeof(UntypedSingleValue) : 0) + mTags.DataSize() +
+               sizeof(std::map<StringView, StringView>);  // (MetricEvent.cpp:119-122; the per-event metadata map is always empty here)
+    }
+
+private:
+    StringView mName;
+    MetricValue mValue;
+    SizedVectorTags mTags;
+};
+
 class PipelineEventPtr {
 public:
     PipelineEventPtr() = default;
@@ -469,6 +550,10 @@ template <>
 inline bool PipelineEventPtr::Is<RawEvent>() const {
     return mData && mData->GetType() == PipelineEvent::Type::RAW;
 }
+template <>
+inline bool PipelineEventPtr::Is<MetricEvent>() const {
+    return mData && mData->GetType() == PipelineEvent::Type::METRIC;
+}
 
 using EventsContainer = std::vector<PipelineEventPtr>;
 
@@ -492,6 +577,14 @@ public:
     RawEvent* AddRawEvent() {
         auto e = std::make_unique<RawEvent>(this);
         RawEvent* raw = e.get();
+        mEvents.emplace_back(std::move(e));
+        return raw;
+    }
+    std::unique_ptr<RawEvent> CreateRawEvent(bool = false) { return std::make_unique<RawEvent>(this); }
+    std::unique_ptr<MetricEvent> CreateMetricEvent(bool = false) { return std::make_unique<MetricEvent>(this); }
+    MetricEvent* AddMetricEvent() {
+        auto e = std::make_unique<MetricEvent>(this);
+        MetricEvent* raw = e.get();
         mEvents.emplace_back(std::move(e));
         return raw;
     }
@@ -550,6 +643,10 @@ inline LogEvent::LogEvent(PipelineEventGroup* g)
     : PipelineEvent(Type::LOG, g),
       mContents(g ? g->GetSourceBuffer().get() : nullptr) {}
 #endif
+inline void MetricEvent::SetTag(StringView key, StringView val) {
+    StringBuffer k = GetSourceBuffer()->CopyString(key), v = GetSourceBuffer()->CopyString(val);
+    SetTagNoCopy(StringView(k.data, k.size), StringView(v.data, v.size));
+}
 inline void LogEvent::SetContent(StringView key, StringView val) {
     StringBuffer k = GetSourceBuffer()->CopyString(key), v = GetSourceBuffer()->CopyString(val);
     SetContentNoCopy(StringView(k.data, k.size), StringView(v.data, v.size));

@@ -2041,6 +2041,7 @@ extern "C" void lc_thread_release(void) {
     lcJsonThreadRelease();
     lcClogThreadRelease();
     lcDesensThreadRelease();
+    lcPromThreadRelease();
 }
 
 extern "C" void lc_nfa_set_dfs(int on) { gNfaDfsMode.store(on < 0 ? -1 : (on ? 1 : 0), std::memory_order_relaxed); }

@@ -22,6 +22,7 @@ void lcTimestampThreadRelease();                       // timestamp_device.hip: 
 void lcApsaraThreadRelease();                          // apsara_device.hip: the same for the Apsara parser's host entry
 void lcJsonThreadRelease();                            // json_device.hip: the same for the JSON parser's host entry
 void lcClogThreadRelease();                            // clog_device.hip: the same for the container log parser's host entry
+void lcPromThreadRelease();                            // prom_device.hip: the same for the Prometheus line parser's host entry
 void lcDesensThreadRelease();                          // desens_device.hip: the same for the desensitize engine's scratch and host entry
 // hipFuncSetAttribute for a launch of `kern` on `dev` that asks for more than 48 KiB of dynamic LDS: once per (thread, kernel, device)
 // and size, grow-only.  The only place the attribute is set.

@@ -183,7 +183,7 @@ inline TripInLayout tripInLayout(size_t payload, uint32_t cnt, bool pairs) {
 
 // The block that comes down: one array of cnt elements per entry of elemBytes, in that order, each 64-byte aligned.
 struct TripLayout {
-    static constexpr size_t kMaxArrays = 8;
+    static constexpr size_t kMaxArrays = 12;
     size_t at[kMaxArrays];
     size_t bytes;
 };
