@@ -6,42 +6,15 @@ import ctypes
 import numpy as np
 
 from . import binding
-from .processor import PluginProcessor, bind_plugin, _lib as _processor_lib
-from .timestamp import CLOCK, _ClockedProcessor
+from .abi import APSARA_OUT_KEYS as OUT_KEYS, LcApsaraOut  # noqa: F401
+from .timestamp import _ClockedProcessor
 
 LC_APSARA_TIME_OK, LC_APSARA_EPOCH, LC_APSARA_CANON19 = 1, 2, 4
 LC_APSARA_LEVEL, LC_APSARA_THREAD, LC_APSARA_FILE, LC_APSARA_LINE = 0, 1, 2, 3
-OUT_KEYS = ("status", "secs", "nanos", "base", "npairs", "pairs")
-
-
-class LcApsaraOut(ctypes.Structure):
-    _fields_ = [(k, ctypes.c_void_p) for k in OUT_KEYS]
 
 
 def _lib():
-    L = _processor_lib()
-    if not getattr(L, "_lc_apsara_bound", False):
-        vp, cp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
-        out = ctypes.POINTER(LcApsaraOut)
-        L.lc_apsara_parse_device.restype = i32
-        L.lc_apsara_parse_device.argtypes = [vp, vp, u32, u32, out, vp]
-        L.lc_apsara_parse_host.restype = i32
-        L.lc_apsara_parse_host.argtypes = [vp, vp, u32, u32, out]
-        L.lc_apsara_processor_create_with_clock.restype = i32
-        L.lc_apsara_processor_create_with_clock.argtypes = [cp, vp, vp, ctypes.POINTER(vp), cp, sz]
-        L.lc_apsara_processor_zone_offset.restype = ctypes.c_int32
-        L.lc_apsara_processor_zone_offset.argtypes = [vp]
-        L.lc_apsara_processor_set_discard.restype = None
-        L.lc_apsara_processor_set_discard.argtypes = [vp, i32, ctypes.c_int32]
-        L.lc_apsara_processor_set_first_trip_pairs.restype = None
-        L.lc_apsara_processor_set_first_trip_pairs.argtypes = [vp, u32]
-        L.lc_apsara_processor_history_failures.restype = ctypes.c_uint64
-        L.lc_apsara_processor_history_failures.argtypes = [vp]
-        L.lc_apsara_processor_replayed_lines.restype = None
-        L.lc_apsara_processor_replayed_lines.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
-        bind_plugin(L, "lc_apsara_processor")
-        L._lc_apsara_bound = True
-    return L
+    return binding.load()
 
 
 def parse_device(d_data, d_off, n, W, d_out, stream=0):
@@ -75,7 +48,6 @@ class ApsaraProcessor(_ClockedProcessor):
     """processor_parse_apsara_gpu; same config keys as processor_parse_apsara_native.  clock: "now" of Timezone and of the discard rule.
     collect_alarms(): kind 0 PARSE_TIME_FAIL_ALARM, kind 1 OUTDATED_LOG_ALARM, kind 3 a failed trip."""
     PREFIX, PLUGIN = "lc_apsara_processor", "processor_parse_apsara_gpu"
-    _lib = staticmethod(_lib)
 
     def set_discard(self, enabled=True, interval=43200):
         self._L.lc_apsara_processor_set_discard(self._h, int(enabled), interval)

@@ -9,6 +9,9 @@ import os
 
 import numpy as np
 
+from . import abi
+from .abi import LcMatchJob, LcRegexInfo, LcSpanFilter  # noqa: F401  (their names here are part of the module)
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LC_REGEX_GPU_LIB", os.path.join(_HERE, "lib", "liblc_regex_gpu.so"))
 
@@ -25,12 +28,6 @@ LC_SYNTAX_PREFIX = 128
  LC_TABLE_TDFA_WIDE_BLOB, LC_TABLE_TDFA_L2_BLOB) = range(12)
 LC_TABLE_LAZY_TDFA_BLOB = 12
 LC_TABLE_BT_BLOB = 13
-
-
-class LcRegexInfo(ctypes.Structure):
-    _fields_ = [("engine", ctypes.c_int), ("mark_count", ctypes.c_int), ("positions", ctypes.c_uint32),
-                ("states", ctypes.c_uint32), ("classes", ctypes.c_uint32), ("registers", ctypes.c_uint32),
-                ("table_bytes", ctypes.c_uint32)]
 
 
 class RegexSyntaxError(ValueError):
@@ -71,52 +68,7 @@ def load(path=None):
     if _lib is not None and path is None:
         return _lib
     _share_torch_hip_runtime()
-    L = ctypes.CDLL(path or LIB_PATH)
-    vp, cp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
-    L.lc_regex_compile.restype = i32
-    L.lc_regex_compile.argtypes = [cp, sz, u32, i32, ctypes.POINTER(vp), cp, sz]
-    L.lc_regex_free.argtypes = [vp]
-    L.lc_regex_mark_count.argtypes = [vp]
-    L.lc_regex_group_name.restype = cp
-    L.lc_regex_group_name.argtypes = [vp, i32]
-    L.lc_regex_info.argtypes = [vp, ctypes.POINTER(LcRegexInfo)]
-    L.lc_regex_table.argtypes = [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(sz)]
-    L.lc_device_count.restype = i32
-    L.lc_regex_match_device.restype = i32
-    L.lc_regex_match_device.argtypes = [vp, vp, vp, vp, u32, u32, u32, vp, vp, vp]
-    L.lc_regex_match_device_engine.restype = i32
-    L.lc_regex_match_device_engine.argtypes = [vp, i32, vp, vp, vp, u32, u32, u32, vp, vp, vp]
-    L.lc_regex_match_device_dyn.restype = i32
-    L.lc_regex_match_device_dyn.argtypes = [vp, i32, vp, vp, u32, vp, u32, u32, vp, vp, vp]
-    L.lc_sched_scratch_bytes.restype = sz
-    L.lc_sched_scratch_bytes.argtypes = [u32]
-    L.lc_regex_match_device_ragged.restype = i32
-    L.lc_regex_match_device_ragged.argtypes = [vp, i32, vp, vp, vp, u32, u32, vp, u32, vp, vp, vp, sz, vp]
-    L.lc_regex_compile_screen.restype = vp
-    L.lc_regex_compile_screen.argtypes = [ctypes.c_char_p, sz, u32, u32, sz]
-    L.lc_regex_compile_relaxed_screen.restype = vp
-    L.lc_regex_compile_relaxed_screen.argtypes = [ctypes.c_char_p, sz, u32, u32, sz]
-    L.lc_regex_screen_device.restype = i32
-    L.lc_regex_screen_device.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, vp]
-    L.lc_regex_required_literal.restype = vp
-    L.lc_regex_required_literal.argtypes = [vp, ctypes.POINTER(sz)]
-    L.lc_regex_run_captures.restype = i32
-    L.lc_regex_run_captures.argtypes = [vp, vp, vp, i32]
-    L.lc_regex_match_device_from.restype = i32
-    L.lc_regex_match_device_from.argtypes = [vp, i32, vp, vp, vp, u32, u32, vp, vp, vp, u32, vp, vp, vp]
-    L.lc_split_scratch_bytes.restype = sz
-    L.lc_split_scratch_bytes.argtypes = [ctypes.c_uint64]
-    L.lc_split_lines_device.restype = i32
-    L.lc_split_lines_device.argtypes = [vp, ctypes.c_uint64, ctypes.c_uint8, vp, u32, vp, vp, sz, vp]
-    L.lc_regex_prepare_span_filter.restype = i32
-    L.lc_regex_prepare_span_filter.argtypes = [vp]
-    L.lc_span_filter_device.restype = i32
-    L.lc_span_filter_device.argtypes = [vp, u32, vp, vp, u32, vp, u32, u32, vp, vp, vp, u32, vp, vp]
-    L.lc_upload_pinned.restype = i32
-    L.lc_upload_pinned.argtypes = [vp, vp, sz, vp]
-    L.lc_regex_match_host.restype = i32
-    L.lc_regex_match_host.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp]
-    L.lc_last_error.restype = cp
+    L = abi.bind(ctypes.CDLL(path or LIB_PATH))
     if path is None:
         _lib = L
     return L
@@ -129,16 +81,6 @@ def _check(rc, what):
         raise GpuUnavailableError("%s: no usable HIP device (the engine has no CPU path)" % what)
     msg = load().lc_last_error()
     raise RuntimeError("%s failed: rc=%d %s" % (what, rc, msg.decode() if msg else ""))
-
-
-class LcSpanFilter(ctypes.Structure):
-    _fields_ = [("re", ctypes.c_void_p), ("group", ctypes.c_uint32)]
-
-
-class LcMatchJob(ctypes.Structure):
-    _fields_ = [("re", ctypes.c_void_p), ("d_data", ctypes.c_void_p), ("d_off", ctypes.c_void_p), ("d_len", ctypes.c_void_p),
-                ("sep_bytes", ctypes.c_uint32), ("n", ctypes.c_uint32), ("ngroups", ctypes.c_uint32),
-                ("d_caps", ctypes.c_void_p), ("d_status", ctypes.c_void_p)]
 
 
 def make_jobs(jobs):
@@ -154,8 +96,6 @@ def make_jobs(jobs):
 def match_device_multi(job_array, stream=None):
     """lc_regex_match_device_multi: several batches, each with its own regex, packed into one kernel launch."""
     L = load()
-    L.lc_regex_match_device_multi.restype = ctypes.c_int
-    L.lc_regex_match_device_multi.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
     _check(L.lc_regex_match_device_multi(ctypes.cast(job_array, ctypes.c_void_p), len(job_array), ctypes.c_void_p(stream or 0)),
            "lc_regex_match_device_multi")
 
@@ -163,8 +103,6 @@ def match_device_multi(job_array, stream=None):
 def launched_kernels():
     """Names of the match kernels this thread has launched since the last call (lc_launched_kernels)."""
     L = load()
-    L.lc_launched_kernels.restype = ctypes.c_size_t
-    L.lc_launched_kernels.argtypes = [ctypes.c_char_p, ctypes.c_size_t]
     buf = ctypes.create_string_buffer(1024)
     L.lc_launched_kernels(buf, 1024)
     return buf.value.decode()
@@ -229,8 +167,6 @@ class GpuRegex:
     def atomic_groups(self):
         """-> (kept, elided): atomic group instances the engines honour / groups made plain at compile time (atomic_elide.cpp)"""
         k, e = ctypes.c_uint32(), ctypes.c_uint32()
-        self._L.lc_regex_atomic_groups.restype = None
-        self._L.lc_regex_atomic_groups.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
         self._L.lc_regex_atomic_groups(self._h, ctypes.byref(k), ctypes.byref(e))
         return int(k.value), int(e.value)
 
@@ -254,8 +190,6 @@ class GpuRegex:
             off[1:n] = np.cumsum(length[:-1], dtype=np.uint64).astype(np.uint32)
         data = np.frombuffer(b"".join(values) + b"\0" * 16, dtype=np.uint8).copy()
         out = (ctypes.c_uint64 * 5)()
-        self._L.lc_regex_lazy_train.restype = ctypes.c_int
-        self._L.lc_regex_lazy_train.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_uint32, ctypes.c_void_p]
         _check(self._L.lc_regex_lazy_train(self._h, data.ctypes.data, off.ctypes.data, length.ctypes.data, n, ctypes.cast(out, ctypes.c_void_p)),
                "lc_regex_lazy_train")
         return dict(zip(("states", "transitions", "sample", "sample_misses", "in_use"), (int(x) for x in out)))
@@ -292,8 +226,6 @@ class GpuRegex:
 
     def prefer_wave_tdfa(self):
         """lc_regex_prefer_wave_tdfa: small batches of this handle take tdfa_wave_kernel (and the handle gets its global-memory tables)"""
-        self._L.lc_regex_prefer_wave_tdfa.restype = ctypes.c_int
-        self._L.lc_regex_prefer_wave_tdfa.argtypes = [ctypes.c_void_p]
         return bool(self._L.lc_regex_prefer_wave_tdfa(self._h))
 
     def prepare_span_filter(self, check=True):
@@ -412,47 +344,32 @@ def device_count():
 LC_BIND_INHERIT, LC_BIND_ROUND_ROBIN, LC_BIND_FIXED = 0, 1, 2
 
 
-def _bind_lib():
-    L = load()
-    L.lc_runtime_set_bind_policy.restype = ctypes.c_int
-    L.lc_runtime_set_bind_policy.argtypes = [ctypes.c_int, ctypes.c_int]
-    L.lc_runtime_bind_policy.restype = ctypes.c_int
-    L.lc_runtime_bind_thread.restype = ctypes.c_int
-    L.lc_runtime_bind_thread.argtypes = [ctypes.c_int]
-    L.lc_runtime_set_thread_device.restype = ctypes.c_int
-    L.lc_runtime_set_thread_device.argtypes = [ctypes.c_int]
-    L.lc_runtime_thread_device.restype = ctypes.c_int
-    L.lc_runtime_device_for_ordinal.restype = ctypes.c_int
-    L.lc_runtime_device_for_ordinal.argtypes = [ctypes.c_uint32, ctypes.c_int]
-    return L
-
-
 def set_bind_policy(policy, device=0):
     """Process-wide placement of the threads that enter the library through its HOST entry points (processors, match_host ...):
     LC_BIND_ROUND_ROBIN (library default: thread ordinal % visible devices), LC_BIND_FIXED (every thread -> `device`; what a
     process that owns ONE GPU -- a rank of bench.py -- says), LC_BIND_INHERIT (never switch)."""
-    _check(_bind_lib().lc_runtime_set_bind_policy(policy, device), "lc_runtime_set_bind_policy")
+    _check(load().lc_runtime_set_bind_policy(policy, device), "lc_runtime_set_bind_policy")
 
 
 def bind_policy():
-    return _bind_lib().lc_runtime_bind_policy()
+    return load().lc_runtime_bind_policy()
 
 
 def bind_thread(policy=-1):
     """Bind the calling thread now; returns its device."""
-    d = _bind_lib().lc_runtime_bind_thread(policy)
+    d = load().lc_runtime_bind_thread(policy)
     if d < 0:
         _check(-d, "lc_runtime_bind_thread")
     return d
 
 
 def set_thread_device(device):
-    _check(_bind_lib().lc_runtime_set_thread_device(device), "lc_runtime_set_thread_device")
+    _check(load().lc_runtime_set_thread_device(device), "lc_runtime_set_thread_device")
 
 
 def thread_device():
-    return _bind_lib().lc_runtime_thread_device()
+    return load().lc_runtime_thread_device()
 
 
 def device_for_ordinal(ordinal, ndevices):
-    return _bind_lib().lc_runtime_device_for_ordinal(ordinal, ndevices)
+    return load().lc_runtime_device_for_ordinal(ordinal, ndevices)

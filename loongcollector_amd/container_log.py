@@ -7,39 +7,17 @@ import ctypes
 import numpy as np
 
 from . import binding
-from .processor import EventGroup, PluginProcessor, bind_plugin, _lib as _processor_lib
+from .abi import CLOG_OUT_KEYS as OUT_KEYS, LcClogOut  # noqa: F401
+from .processor import EventGroup, PluginProcessor
 
 LC_CLOG_CONTAINERD, LC_CLOG_DOCKER = 1, 2
 LC_CLOG_OK, LC_CLOG_FAIL_TIME, LC_CLOG_FAIL_SOURCE, LC_CLOG_FAIL_STREAM, LC_CLOG_FAIL_JSON = 0, 1, 2, 3, 4
 LC_CLOG_STDERR, LC_CLOG_PARTIAL, LC_CLOG_ESCAPED, LC_CLOG_REPLAY = 1, 2, 4, 8
 LC_CLOG_SPAN_TIME, LC_CLOG_SPAN_SOURCE, LC_CLOG_SPAN_CONTENT = 0, 1, 2
-OUT_KEYS = ("status", "flags", "spans", "rewrite_begin")
-
-
-class LcClogOut(ctypes.Structure):
-    _fields_ = [(k, ctypes.c_void_p) for k in OUT_KEYS]
 
 
 def _lib():
-    L = _processor_lib()
-    if not getattr(L, "_lc_container_log_bound", False):
-        vp, cp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
-        out = ctypes.POINTER(LcClogOut)
-        L.lc_container_log_parse_device.restype = i32
-        L.lc_container_log_parse_device.argtypes = [i32, vp, vp, u32, out, vp, vp]
-        L.lc_container_log_parse_host.restype = i32
-        L.lc_container_log_parse_host.argtypes = [i32, vp, vp, u32, out, vp, ctypes.POINTER(ctypes.c_uint64)]
-        L.lc_container_log_processor_set_config_name.restype = None
-        L.lc_container_log_processor_set_config_name.argtypes = [vp, cp]
-        L.lc_container_log_processor_stream_counts.restype = None
-        L.lc_container_log_processor_stream_counts.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
-        L.lc_container_log_processor_replayed_lines.restype = ctypes.c_uint64
-        L.lc_container_log_processor_replayed_lines.argtypes = [vp]
-        L.lc_group_set_metadata.restype = i32
-        L.lc_group_set_metadata.argtypes = [vp, cp, cp]
-        bind_plugin(L, "lc_container_log_processor")
-        L._lc_container_log_bound = True
-    return L
+    return binding.load()
 
 
 def set_group_format(group: EventGroup, fmt):
@@ -85,10 +63,9 @@ class ContainerLogProcessor(PluginProcessor):
     """processor_parse_container_log_gpu; same config keys as processor_parse_container_log_native.  The format of a group is its
     LOG_FORMAT metadata (set_group_format).  collect_alarms(): kind 0 PARSE_LOG_FAIL_ALARM, kind 3 a failed trip."""
     PREFIX, PLUGIN = "lc_container_log_processor", "processor_parse_container_log_gpu"
-    _lib = staticmethod(_lib)
 
-    def __init__(self, config, config_name=""):
-        self._create(config)
+    def __init__(self, config, config_name="", lib=None):
+        self._create(config, lib=lib)
         self._L.lc_container_log_processor_set_config_name(self._h, config_name.encode("utf-8"))
 
     def counters(self):

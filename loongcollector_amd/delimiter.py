@@ -6,7 +6,7 @@ import ctypes
 import numpy as np
 
 from . import binding
-from .processor import PluginProcessor, bind_plugin, _lib as _processor_lib
+from .processor import PluginProcessor
 
 LC_DELIM_FAIL, LC_DELIM_OK, LC_DELIM_BLANK = 0, 1, 2
 LC_DELIM_EXTEND, LC_DELIM_KEEP, LC_DELIM_DISCARD = 0, 1, 2
@@ -15,22 +15,7 @@ MODES = {"extend": LC_DELIM_EXTEND, "keep": LC_DELIM_KEEP, "discard": LC_DELIM_D
 
 
 def _lib():
-    L = _processor_lib()
-    if not getattr(L, "_lc_delimiter_bound", False):
-        vp, cp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
-        L.lc_delim_create.restype = i32
-        L.lc_delim_create.argtypes = [cp, u32, ctypes.c_uint8, i32, u32, ctypes.POINTER(vp)]
-        L.lc_delim_destroy.argtypes = [vp]
-        L.lc_delim_uses_quote.argtypes = [vp]
-        L.lc_delim_split_device.restype = i32
-        L.lc_delim_split_device.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp, vp]
-        L.lc_delim_split_host.restype = i32
-        L.lc_delim_split_host.argtypes = [vp, vp, vp, u32, u32, vp, vp, vp]
-        L.lc_delimiter_processor_set_first_trip_columns.restype = None
-        L.lc_delimiter_processor_set_first_trip_columns.argtypes = [vp, u32]
-        bind_plugin(L, "lc_delimiter_processor")
-        L._lc_delimiter_bound = True
-    return L
+    return binding.load()
 
 
 class GpuDelimiter:
@@ -86,9 +71,8 @@ class DelimiterProcessor(PluginProcessor):
     """processor_parse_delimiter_gpu; same config keys as processor_parse_delimiter_native.  collect_alarms(): every PARSE_LOG_FAIL_ALARM
     the reference would raise."""
     PREFIX, PLUGIN = "lc_delimiter_processor", "processor_parse_delimiter_gpu"
-    _lib = staticmethod(_lib)
 
-    def __init__(self, config, first_trip_columns=0):
-        self._create(config)
+    def __init__(self, config, first_trip_columns=0, lib=None):
+        self._create(config, lib=lib)
         if first_trip_columns:
             self._L.lc_delimiter_processor_set_first_trip_columns(self._h, first_trip_columns)

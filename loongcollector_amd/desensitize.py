@@ -7,15 +7,12 @@ import ctypes
 import numpy as np
 
 from . import binding
-from .processor import PluginProcessor, bind_plugin, _lib as _processor_lib
+from .abi import LcDesensStats  # noqa: F401
+from .processor import PluginProcessor
 
 LC_DESENS_CONST, LC_DESENS_MD5 = 0, 1
 LC_DESENS_CHANGED, LC_DESENS_GAVE_UP = 1, 2
 LC_ERR_OVERFLOW = 6
-
-
-class LcDesensStats(ctypes.Structure):
-    _fields_ = [("rounds", ctypes.c_uint32), ("pass_through", ctypes.c_uint32), ("searches", ctypes.c_uint64)]
 
 
 class DesensitizeOverflow(RuntimeError):
@@ -27,27 +24,7 @@ class DesensitizeOverflow(RuntimeError):
 
 
 def _lib():
-    L = _processor_lib()
-    if not getattr(L, "_lc_desensitize_bound", False):
-        vp, cp, sz, u32, u64, i32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
-        stats = ctypes.POINTER(LcDesensStats)
-        L.lc_desens_create.restype = i32
-        L.lc_desens_create.argtypes = [i32, cp, sz, cp, sz, cp, sz, i32, ctypes.POINTER(vp), ctypes.POINTER(i32), cp, sz]
-        L.lc_desens_free.restype = None
-        L.lc_desens_free.argtypes = [vp]
-        L.lc_desens_regex.restype = vp
-        L.lc_desens_regex.argtypes = [vp]
-        L.lc_desens_apply_device.restype = i32
-        L.lc_desens_apply_device.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, u64, ctypes.POINTER(u64), stats, vp]
-        L.lc_desens_apply_host.restype = i32
-        L.lc_desens_apply_host.argtypes = [vp, vp, vp, u32, vp, vp, ctypes.POINTER(vp), stats]
-        L.lc_desensitize_engine.restype = vp
-        L.lc_desensitize_engine.argtypes = [vp]
-        L.lc_desensitize_rounds.restype = u64
-        L.lc_desensitize_rounds.argtypes = [vp]
-        bind_plugin(L, "lc_desensitize")
-        L._lc_desensitize_bound = True
-    return L
+    return binding.load()
 
 
 def _bytes(s):
@@ -57,8 +34,8 @@ def _bytes(s):
 class GpuDesensitize:
     """lc_desens_*: method "const" | "md5"; before / content: the two halves of the pattern; replacing: ReplacingString (const)"""
 
-    def __init__(self, method, before, content, replacing=b"", replacing_all=False):
-        self._L = _lib()
+    def __init__(self, method, before, content, replacing=b"", replacing_all=False, lib=None):
+        self._L = lib or _lib()
         before, content, replacing = _bytes(before), _bytes(content), _bytes(replacing)
         h, warning = ctypes.c_void_p(), ctypes.c_int(0)
         err = ctypes.create_string_buffer(512)
@@ -129,10 +106,6 @@ class DesensitizeProcessor(PluginProcessor):
     """processor_desensitize_gpu; same config keys as processor_desensitize_native.  collect_alarms(): kind 1 a search gave up, kind 3 a
     failed trip."""
     PREFIX, PLUGIN = "lc_desensitize", "processor_desensitize_gpu"
-    _lib = staticmethod(_lib)
-
-    def __init__(self, config):
-        self._create(config)
 
     def rounds(self):
         return int(self._L.lc_desensitize_rounds(self._h))

@@ -13,50 +13,7 @@ class GrokInitError(ValueError):
 
 
 def _lib():
-    L = binding.load()
-    if not getattr(L, "_lc_grok_bound", False):
-        vp, cp, sz, i32, u32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_uint32
-        L.lc_grok_create.restype = i32
-        L.lc_grok_create.argtypes = [cp, sz, ctypes.POINTER(vp), cp, sz]
-        L.lc_grok_free.argtypes = [vp]
-        L.lc_grok_wait_ready.restype = None
-        L.lc_grok_wait_ready.argtypes = [vp]
-        for name in ("lc_grok_match_count", "lc_grok_key_count", "lc_grok_row_ints"):
-            getattr(L, name).restype = i32
-            getattr(L, name).argtypes = [vp]
-        L.lc_grok_expanded.restype = cp
-        L.lc_grok_expanded.argtypes = [vp, i32]
-        L.lc_grok_processed.restype = cp
-        L.lc_grok_processed.argtypes = [vp, cp]
-        L.lc_grok_denormalize.restype = vp
-        L.lc_grok_denormalize.argtypes = [vp, cp, cp, sz]
-        L.lc_grok_engine.restype = i32
-        L.lc_grok_engine.argtypes = [vp, i32]
-        L.lc_grok_key.restype = cp
-        L.lc_grok_key.argtypes = [vp, i32]
-        L.lc_grok_column_count.restype = i32
-        L.lc_grok_column_count.argtypes = [vp, i32]
-        L.lc_grok_column_key.restype = i32
-        L.lc_grok_column_key.argtypes = [vp, i32, i32]
-        L.lc_grok_scratch_bytes.restype = sz
-        L.lc_grok_scratch_bytes.argtypes = [vp, u32]
-        L.lc_grok_match_device.restype = i32
-        L.lc_grok_match_device.argtypes = [vp, vp, vp, vp, u32, vp, vp, vp, u32, vp, vp, sz, vp]
-        L.lc_grok_match_host.restype = i32
-        L.lc_grok_match_host.argtypes = [vp, vp, vp, vp, u32, vp, ctypes.POINTER(vp)]
-        L.lc_grok_result_arrays.argtypes = [vp] + [ctypes.POINTER(vp)] * 4
-        L.lc_grok_result_free.argtypes = [vp]
-        L.lc_grok_process_logs_json.restype = i32
-        L.lc_grok_process_logs_json.argtypes = [vp, cp, sz, ctypes.POINTER(vp)]
-        L.lc_grok_free_string.argtypes = [vp]
-        L.lc_grok_plan_masks_device.restype = i32
-        L.lc_grok_plan_masks_device.argtypes = [vp, vp, vp, vp, u32, i32, vp, vp, vp, sz, vp]
-        L.lc_grok_screen_blob.restype = i32
-        L.lc_grok_screen_blob.argtypes = [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(u32)]
-        L.lc_grok_last_batch_stats.restype = None
-        L.lc_grok_last_batch_stats.argtypes = [vp]
-        L._lc_grok_bound = True
-    return L
+    return binding.load()
 
 
 class Grok:
@@ -85,8 +42,6 @@ class Grok:
         import numpy as np
         words = ctypes.c_void_p()
         n = ctypes.c_size_t()
-        self._L.lc_grok_literal_index.restype = ctypes.c_int
-        self._L.lc_grok_literal_index.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
         rc = self._L.lc_grok_literal_index(self._h, ctypes.byref(words), ctypes.byref(n))
         if rc != 0 or not words.value:
             return None
@@ -186,19 +141,16 @@ class Grok:
 
     def lazy_settle(self, timeout_ms=60000):
         """block until the lazy automata's trainer has nothing to do (include/lc_grok.h); -> True if it settled in time"""
-        self._L.lc_grok_lazy_settle.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
         return self._L.lc_grok_lazy_settle(self._h, timeout_ms) == 0
 
     def lazy_stats(self):
         w = (ctypes.c_uint64 * 5)()
-        self._L.lc_grok_lazy_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         self._L.lc_grok_lazy_stats(self._h, ctypes.cast(w, ctypes.c_void_p))
         return dict(zip(("automata_in_use", "builds", "values_offered", "values_kept", "batches_taken"), (int(x) for x in w)))
 
     def combiner_stats(self):
         """the group commit behind match_host (csrc/group_combiner.hpp) since the handle was created"""
         w = (ctypes.c_uint64 * 11)()
-        self._L.lc_grok_combiner_stats.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         self._L.lc_grok_combiner_stats(self._h, ctypes.cast(w, ctypes.c_void_p))
         out = {"batches": int(w[0]), "groups": int(w[1]), "values": int(w[2]), "largest_batch_groups": int(w[3]), "linger_expired": int(w[4])}
         out["worker_us"] = dict(zip(("idle", "linger", "place", "gather", "run", "take_out"), (int(x) for x in w[5:11])))
@@ -228,15 +180,6 @@ class GoRegex:
 
     def __init__(self, **config):
         L = self._L = binding.load()
-        if not getattr(L, "_lc_goregex_bound", False):
-            vp, cp, sz = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t
-            L.lc_goregex_create.restype = ctypes.c_int
-            L.lc_goregex_create.argtypes = [cp, sz, ctypes.POINTER(vp), cp, sz]
-            L.lc_goregex_free.argtypes = [vp]
-            L.lc_goregex_process_logs_json.restype = ctypes.c_int
-            L.lc_goregex_process_logs_json.argtypes = [vp, cp, sz, ctypes.POINTER(vp)]
-            L.lc_goregex_free_string.argtypes = [vp]
-            L._lc_goregex_bound = True
         text = json.dumps(config).encode("utf-8")
         h = ctypes.c_void_p()
         err = ctypes.create_string_buffer(512)

@@ -6,7 +6,7 @@ import ctypes
 import numpy as np
 
 from . import binding
-from .processor import PluginProcessor, bind_plugin, _lib as _processor_lib
+from .processor import PluginProcessor
 
 LC_JSON_FAIL, LC_JSON_OK, LC_JSON_EMPTY, LC_JSON_DEEP = 0, 1, 2, 3
 LC_JSON_STRING, LC_JSON_INT, LC_JSON_DOUBLE, LC_JSON_TRUE, LC_JSON_FALSE, LC_JSON_NULL, LC_JSON_OBJECT, LC_JSON_ARRAY = range(8)
@@ -16,18 +16,7 @@ MEMBER = np.dtype([("kb", "<u4"), ("ke", "<u4"), ("vb", "<u4"), ("ve", "<u4"), (
 
 
 def _lib():
-    L = _processor_lib()
-    if not getattr(L, "_lc_json_bound", False):
-        vp, cp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
-        L.lc_json_walk_device.restype = i32
-        L.lc_json_walk_device.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp, vp, vp]
-        L.lc_json_walk_host.restype = i32
-        L.lc_json_walk_host.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_uint64)]
-        L.lc_json_processor_set_first_trip_members.restype = None
-        L.lc_json_processor_set_first_trip_members.argtypes = [vp, u32]
-        bind_plugin(L, "lc_json_processor")
-        L._lc_json_bound = True
-    return L
+    return binding.load()
 
 
 class GpuJson:
@@ -68,9 +57,8 @@ class JsonProcessor(PluginProcessor):
     """processor_parse_json_gpu; same config keys as processor_parse_json_native.  collect_alarms(): every PARSE_LOG_FAIL_ALARM the
     reference would raise."""
     PREFIX, PLUGIN = "lc_json_processor", "processor_parse_json_gpu"
-    _lib = staticmethod(_lib)
 
-    def __init__(self, config, first_trip_members=0):
-        self._create(config)
+    def __init__(self, config, first_trip_members=0, lib=None):
+        self._create(config, lib=lib)
         if first_trip_members:
             self._L.lc_json_processor_set_first_trip_members(self._h, first_trip_members)

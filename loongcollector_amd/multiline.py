@@ -3,42 +3,16 @@ import ctypes
 import json
 
 from . import binding
+from .abi import LcMlRecord as _Record
 
 
 class MultilineInitError(ValueError):
     pass
 
 
-class _Record(ctypes.Structure):
-    _fields_ = [("begin", ctypes.c_uint32), ("length", ctypes.c_uint32), ("matched", ctypes.c_uint32)]
-
-
 class Multiline:
     def __init__(self, **config):
         L = self._L = binding.load()
-        if not getattr(L, "_lc_multiline_bound", False):
-            vp, cp, sz = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t
-            L.lc_multiline_create.restype = ctypes.c_int
-            L.lc_multiline_create.argtypes = [cp, sz, ctypes.POINTER(vp), cp, sz]
-            L.lc_multiline_free.argtypes = [vp]
-            L.lc_multiline_is_multiline.argtypes = [vp]
-            L.lc_multiline_patterns.argtypes = [vp]
-            L.lc_multiline_warnings.restype = cp
-            L.lc_multiline_warnings.argtypes = [vp]
-            L.lc_multiline_split_host.restype = ctypes.c_int
-            L.lc_multiline_split_host.argtypes = [vp, cp, ctypes.c_uint32, ctypes.POINTER(ctypes.POINTER(_Record)),
-                                                  ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]
-            L.lc_multiline_free_records.argtypes = [ctypes.POINTER(_Record)]
-            L.lc_multiline_process_group.restype = ctypes.c_int
-            L.lc_multiline_process_group.argtypes = [vp, vp]
-            L.lc_multiline_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
-            L.lc_merge_multiline_create.restype = ctypes.c_int
-            L.lc_merge_multiline_create.argtypes = [cp, sz, ctypes.POINTER(vp), cp, sz]
-            L.lc_merge_multiline_free.argtypes = [vp]
-            L.lc_merge_multiline_process_group.restype = ctypes.c_int
-            L.lc_merge_multiline_process_group.argtypes = [vp, vp]
-            L.lc_merge_multiline_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
-            L._lc_multiline_bound = True
         text = json.dumps(config).encode("utf-8")
         h = ctypes.c_void_p()
         err = ctypes.create_string_buffer(512)
@@ -142,12 +116,9 @@ class MergeMultiline:
     def patterns(self):
         """bit 0 start, bit 1 continue, bit 2 end: the patterns the processor matches with -- MultilineOptions' own regexes (a trailing
         '$' and ".*"s stripped, ContinuePattern dropped when all three are given), not the splitter's reading; 0 in flag mode"""
-        self._L.lc_merge_multiline_patterns.argtypes = [ctypes.c_void_p]
         return int(self._L.lc_merge_multiline_patterns(self._h))
 
     def warnings(self):
-        self._L.lc_merge_multiline_warnings.restype = ctypes.c_char_p
-        self._L.lc_merge_multiline_warnings.argtypes = [ctypes.c_void_p]
         return self._L.lc_merge_multiline_warnings(self._h).decode("utf-8", "replace")
 
     def counters(self):
@@ -167,9 +138,6 @@ def bounds_device(mode, d_start, d_cont, d_end, d_nitems, max_items, d_off, nbyt
     scratch on the device; `records` ((cap, 3) 32-bit words) on the device or in pinned host memory; `counts` (8 words) on the device.
     Any of them may be None (a NULL pointer).  Asynchronous on `stream`.  -> the status code (check=False: not raised)"""
     L = binding.load()
-    vp, u32 = ctypes.c_void_p, ctypes.c_uint32
-    L.lc_multiline_bounds_device.restype = ctypes.c_int
-    L.lc_multiline_bounds_device.argtypes = [u32, vp, vp, vp, vp, u32, vp, u32, vp, vp, u32, vp, vp]
     ptr = lambda t: None if t is None else t.data_ptr()
     rc = L.lc_multiline_bounds_device(mode, ptr(d_start), ptr(d_cont), ptr(d_end), ptr(d_nitems), max_items, ptr(d_off), nbytes,
                                       ptr(d_flags), ptr(records), record_cap, ptr(counts), stream)
@@ -184,9 +152,6 @@ def bounds_model(mode, flags, off=None, nbytes=0, raw=False):
     -> (records [(begin, length, flags)], counts[8]); raw=True: both as uint32 arrays ((records, 3) and (8,))"""
     import numpy as np
     L = binding.load()
-    L.lc_multiline_bounds_model.restype = ctypes.c_int
-    L.lc_multiline_bounds_model.argtypes = [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32,
-                                            ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]
     fl = np.ascontiguousarray(np.asarray(flags, dtype=np.uint8))
     n = int(fl.size)
     cap = n + 2

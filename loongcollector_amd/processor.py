@@ -4,6 +4,7 @@ import ctypes
 import json
 
 from . import binding
+from .abi import ALARM_SINK, LcColumnar  # noqa: F401
 
 COUNTER_NAMES = ["discarded_events_total", "out_failed_events_total", "out_key_not_found_events_total",
                  "out_successful_events_total", "in_events_total", "out_events_total", "in_size_bytes",
@@ -11,69 +12,12 @@ COUNTER_NAMES = ["discarded_events_total", "out_failed_events_total", "out_key_n
                  "device_failed_events_total"]
 
 
-class LcColumnar(ctypes.Structure):
-    _fields_ = [("n_events", ctypes.c_uint32), ("n_keys", ctypes.c_uint32), ("keys", ctypes.POINTER(ctypes.c_char_p)),
-                ("key_len", ctypes.POINTER(ctypes.c_uint32)), ("base", ctypes.POINTER(ctypes.c_void_p)),
-                ("base_len", ctypes.POINTER(ctypes.c_uint32)), ("spans", ctypes.POINTER(ctypes.c_int32)),
-                ("state", ctypes.POINTER(ctypes.c_uint8)), ("content_bytes", ctypes.POINTER(ctypes.c_uint64))]
-
-
 class ProcessorInitError(ValueError):
     pass
 
 
 def _lib():
-    L = binding.load()
-    if not getattr(L, "_lc_processor_bound", False):
-        vp, cp, sz = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t
-        L.lc_processor_create.restype = ctypes.c_int
-        L.lc_processor_create.argtypes = [cp, ctypes.POINTER(vp), cp, sz]
-        L.lc_processor_destroy.argtypes = [vp]
-        L.lc_processor_key_count.argtypes = [vp]
-        L.lc_processor_key.restype = cp
-        L.lc_processor_key.argtypes = [vp, ctypes.c_int]
-        L.lc_processor_process.restype = ctypes.c_int
-        L.lc_processor_process.argtypes = [vp, vp]
-        L.lc_processor_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
-        L.lc_processor_set_alarm_sink.restype = None
-        L.lc_processor_set_alarm_sink.argtypes = [vp, vp, vp]
-        L.lc_filter_create.restype = ctypes.c_int
-        L.lc_filter_create.argtypes = [cp, ctypes.POINTER(vp), cp, sz]
-        L.lc_filter_destroy.argtypes = [vp]
-        L.lc_filter_mode.argtypes = [vp]
-        L.lc_filter_process.restype = ctypes.c_int
-        L.lc_filter_process.argtypes = [vp, vp]
-        L.lc_filter_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
-        L.lc_filter_none_utf8.restype = ctypes.c_int
-        L.lc_filter_none_utf8.argtypes = [cp, sz, ctypes.c_int]
-        L.lc_group_native.restype = vp
-        L.lc_group_native.argtypes = [vp]
-        L.lc_group_from_json.restype = vp
-        L.lc_group_from_json.argtypes = [cp, cp, sz]
-        L.lc_processor_parse_columnar.restype = ctypes.c_int
-        L.lc_processor_parse_columnar.argtypes = [vp, vp, ctypes.POINTER(ctypes.POINTER(LcColumnar))]
-        L.lc_columnar_free.argtypes = [ctypes.POINTER(LcColumnar)]
-        L.lc_group_from_lines.restype = vp
-        L.lc_group_from_lines.argtypes = [vp, vp, vp, ctypes.c_uint32, cp]
-        L.lc_group_to_json.restype = vp
-        L.lc_group_to_json.argtypes = [vp]
-        L.lc_group_event_count.restype = sz
-        L.lc_group_event_count.argtypes = [vp]
-        L.lc_group_free.argtypes = [vp]
-        L.lc_free.argtypes = [vp]
-        L.lc_group_from_buffer.restype = vp
-        L.lc_group_from_buffer.argtypes = [vp, sz, cp, ctypes.c_uint64, cp]
-        L.lc_pipeline_create.restype = ctypes.c_int
-        L.lc_pipeline_create.argtypes = [cp, ctypes.POINTER(vp), cp, sz]
-        L.lc_pipeline_destroy.argtypes = [vp]
-        L.lc_pipeline_is_fused.restype = ctypes.c_int
-        L.lc_pipeline_is_fused.argtypes = [vp]
-        L.lc_pipeline_process.restype = ctypes.c_int
-        L.lc_pipeline_process.argtypes = [vp, vp]
-        L.lc_pipeline_counters.restype = ctypes.c_int
-        L.lc_pipeline_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
-        L._lc_processor_bound = True
-    return L
+    return binding.load()
 
 
 class EventGroup:
@@ -149,30 +93,23 @@ class EventGroup:
             pass
 
 
-def bind_plugin(L, prefix):
-    """the six prototypes every parse plugin has: <prefix>_create, _destroy, _warnings, _process, _counters, _set_alarm_sink"""
-    vp, cp, sz = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t
-    for name, restype, argtypes in (("create", ctypes.c_int, [cp, ctypes.POINTER(vp), cp, sz]), ("destroy", None, [vp]), ("warnings", vp, [vp]),
-                                    ("process", ctypes.c_int, [vp, vp]), ("counters", ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_uint64)]),
-                                    ("set_alarm_sink", None, [vp, vp, vp])):
-        fn = getattr(L, "%s_%s" % (prefix, name))
-        fn.restype, fn.argtypes = restype, argtypes
-    L.lc_free.argtypes = [vp]
-
-
 class PluginProcessor:
-    """What the plugins over event groups share (same shape as Processor).  A subclass names PREFIX, the C prefix bind_plugin() took,
-    and PLUGIN, the plugin's name; sets _lib to its module's _lib; and opens its handle with _create()."""
+    """What the plugins over event groups share (same shape as Processor).  A subclass names PREFIX, the C prefix of its
+    entry points, and PLUGIN, the plugin's name, and opens its handle with _create(); lib: another library that exports the same entry points
+    (a host double) in place of the product."""
     PREFIX = PLUGIN = None
     _lib = staticmethod(_lib)
 
     def _call(self, name, *args):
         return getattr(self._L, "%s_%s" % (self.PREFIX, name))(*args)
 
-    def _create(self, config, *args, create="create"):
+    def __init__(self, config, lib=None):
+        self._create(config, lib=lib)
+
+    def _create(self, config, *args, create="create", lib=None):
         """<PREFIX>_<create>(config, *args, &handle, err, 512)"""
         text = config if isinstance(config, str) else json.dumps(config)
-        self._L = self._lib()
+        self._L = lib or self._lib()
         h = ctypes.c_void_p()
         err = ctypes.create_string_buffer(512)
         rc = self._call(create, text.encode("utf-8"), *args, ctypes.byref(h), err, 512)
@@ -198,8 +135,7 @@ class PluginProcessor:
     def collect_alarms(self):
         """-> the list that receives (kind, message bytes) for every alarm the plugin raises"""
         out = []
-        proto = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
-        self._alarm_cb = proto(lambda user, kind, msg, n: out.append((kind, ctypes.string_at(msg, n))))
+        self._alarm_cb = ALARM_SINK(lambda user, kind, msg, n: out.append((kind, ctypes.string_at(msg, n))))
         self._call("set_alarm_sink", self._h, ctypes.cast(self._alarm_cb, ctypes.c_void_p), None)
         return out
 
@@ -223,9 +159,9 @@ class PluginProcessor:
 class Processor:
     """processor_parse_regex_gpu; same config keys as processor_parse_regex_native."""
 
-    def __init__(self, config):
+    def __init__(self, config, lib=None):
         text = config if isinstance(config, str) else json.dumps(config)
-        self._L = _lib()
+        self._L = lib or _lib()
         h = ctypes.c_void_p()
         err = ctypes.create_string_buffer(512)
         rc = self._L.lc_processor_create(text.encode("utf-8"), ctypes.byref(h), err, 512)
@@ -303,8 +239,7 @@ class Processor:
         """lc_processor_set_alarm_sink: -> the list that receives (kind, message bytes) for every REGEX_MATCH_ALARM the
         reference would raise (ProcessorParseRegexNative.cpp:196-244)"""
         out = []
-        proto = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
-        self._alarm_cb = proto(lambda user, kind, msg, n: out.append((kind, ctypes.string_at(msg, n))))
+        self._alarm_cb = ALARM_SINK(lambda user, kind, msg, n: out.append((kind, ctypes.string_at(msg, n))))
         self._L.lc_processor_set_alarm_sink(self._h, ctypes.cast(self._alarm_cb, ctypes.c_void_p), None)
         return out
 

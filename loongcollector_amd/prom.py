@@ -7,7 +7,8 @@ import ctypes
 import numpy as np
 
 from . import binding
-from .processor import EventGroup, PluginProcessor, bind_plugin, _lib as _processor_lib
+from .abi import PROM_OUT_KEYS as OUT_KEYS, LcPromOut  # noqa: F401
+from .processor import EventGroup, PluginProcessor
 
 LC_PROM_OK = 0
 (LC_PROM_FAIL_NAME, LC_PROM_FAIL_NAME_END, LC_PROM_FAIL_EQUAL, LC_PROM_FAIL_LABEL_NAME, LC_PROM_FAIL_QUOTE, LC_PROM_FAIL_LABEL_VALUE_END,
@@ -16,12 +17,7 @@ LC_PROM_OK = 0
 LC_PROM_VALUE_HOST, LC_PROM_TIME_HOST, LC_PROM_HAS_TIME, LC_PROM_ANY_ESCAPE = 1, 2, 4, 8
 LC_PROM_LABEL_ESCAPED = 0x80000000
 LC_PROM_DEFAULT_LABELS = 16
-OUT_KEYS = ("status", "flags", "name", "value", "value_span", "time_span", "secs", "nanos", "nlabels", "labels")
 SCRAPE_TIMESTAMP = "prometheus.scrape.timestamp.millisec"  # the name lc_group_set_metadata knows the scrape timestamp by
-
-
-class LcPromOut(ctypes.Structure):
-    _fields_ = [(k, ctypes.c_void_p) for k in OUT_KEYS]
 
 
 def out_shapes(n, W):
@@ -32,45 +28,7 @@ def out_shapes(n, W):
 
 
 def _lib():
-    L = _processor_lib()
-    if not getattr(L, "_lc_prom_bound", False):
-        vp, cp, sz, u32, i32, u64 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int, ctypes.c_uint64
-        out = ctypes.POINTER(LcPromOut)
-        L.lc_prom_parse_device.restype = i32
-        L.lc_prom_parse_device.argtypes = [i32, vp, vp, u32, out, u32, vp]
-        L.lc_prom_parse_host.restype = i32
-        L.lc_prom_parse_host.argtypes = [i32, vp, vp, u32, out, u32, ctypes.POINTER(u64)]
-        L.lc_prom_processor_set_config_name.restype = None
-        L.lc_prom_processor_set_config_name.argtypes = [vp, cp]
-        L.lc_prom_processor_deferred_tokens.restype = u64
-        L.lc_prom_processor_deferred_tokens.argtypes = [vp]
-        L.lc_prom_processor_mop_up_lines.restype = u64
-        L.lc_prom_processor_mop_up_lines.argtypes = [vp]
-        L.lc_prom_processor_set_first_trip_labels.restype = None
-        L.lc_prom_processor_set_first_trip_labels.argtypes = [vp, u32]
-        L.lc_group_set_metadata.restype = i32
-        L.lc_group_set_metadata.argtypes = [vp, cp, cp]
-        L.lc_group_new.restype = vp
-        L.lc_group_new.argtypes = []
-        L.lc_group_add_raw_event.restype = i32
-        L.lc_group_add_raw_event.argtypes = [vp, cp, sz]
-        L.lc_group_add_log_event.restype = i32
-        L.lc_group_add_log_event.argtypes = [vp, cp, cp]
-        L.lc_group_event_type.restype = i32
-        L.lc_group_event_type.argtypes = [vp, sz]
-        L.lc_group_event_timestamp.restype = i32
-        L.lc_group_event_timestamp.argtypes = [vp, sz, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(u32), ctypes.POINTER(i32)]
-        L.lc_group_metric_name.restype = i32
-        L.lc_group_metric_name.argtypes = [vp, sz, ctypes.POINTER(vp), ctypes.POINTER(sz)]
-        L.lc_group_metric_value_bits.restype = i32
-        L.lc_group_metric_value_bits.argtypes = [vp, sz, ctypes.POINTER(u64)]
-        L.lc_group_metric_tag_count.restype = sz
-        L.lc_group_metric_tag_count.argtypes = [vp, sz]
-        L.lc_group_metric_tag.restype = i32
-        L.lc_group_metric_tag.argtypes = [vp, sz, sz, ctypes.POINTER(vp), ctypes.POINTER(sz), ctypes.POINTER(vp), ctypes.POINTER(sz)]
-        bind_plugin(L, "lc_prom_processor")
-        L._lc_prom_bound = True
-    return L
+    return binding.load()
 
 
 class RawGroup(EventGroup):
@@ -145,10 +103,9 @@ class PromProcessor(PluginProcessor):
     """processor_prom_parse_metric_gpu; the config keys of processor_prom_parse_metric_native that bear on it (job_name, honor_timestamps;
     lc_prom.h).  collect_alarms(): kind 1 an unparsable scrape timestamp, kind 3 a failed trip."""
     PREFIX, PLUGIN = "lc_prom_processor", "processor_prom_parse_metric_gpu"
-    _lib = staticmethod(_lib)
 
-    def __init__(self, config, config_name=""):
-        self._create(config)
+    def __init__(self, config, config_name="", lib=None):
+        self._create(config, lib=lib)
         self._L.lc_prom_processor_set_config_name(self._h, config_name.encode("utf-8"))
 
     def deferred_tokens(self):

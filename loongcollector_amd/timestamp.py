@@ -6,54 +6,15 @@ import ctypes
 import numpy as np
 
 from . import binding
-from .processor import PluginProcessor, bind_plugin, _lib as _processor_lib
+from .abi import CLOCK, LcTsOut  # noqa: F401
+from .processor import PluginProcessor
 
 LC_TS_OK, LC_TS_HAS_YEAR, LC_TS_DST, LC_TS_EPOCH, LC_TS_ABSENT = 1, 2, 4, 8, 0x80
 LC_TS_MAX_PROGRAM = 64
-CLOCK = ctypes.CFUNCTYPE(ctypes.c_int64, ctypes.c_void_p)
-
-
-class LcTsOut(ctypes.Structure):
-    _fields_ = [("status", ctypes.c_void_p), ("secs", ctypes.c_void_p), ("nanos", ctypes.c_void_p), ("matched", ctypes.c_void_p),
-                ("frac_len", ctypes.c_void_p), ("same_as_prev", ctypes.c_void_p)]
 
 
 def _lib():
-    L = _processor_lib()
-    if not getattr(L, "_lc_timestamp_bound", False):
-        vp, cp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
-        out = ctypes.POINTER(LcTsOut)
-        L.lc_strptime_create.restype = i32
-        L.lc_strptime_create.argtypes = [cp, ctypes.POINTER(vp), cp, sz]
-        L.lc_strptime_destroy.argtypes = [vp]
-        L.lc_strptime_program.restype = u32
-        L.lc_strptime_program.argtypes = [vp, ctypes.POINTER(u32)]
-        L.lc_strptime_parse_spans_device.restype = i32
-        L.lc_strptime_parse_spans_device.argtypes = [vp, vp, vp, vp, u32, out, vp]
-        L.lc_strptime_parse_captures_device.restype = i32
-        L.lc_strptime_parse_captures_device.argtypes = [vp, vp, vp, vp, u32, u32, vp, u32, u32, out, vp]
-        L.lc_strptime_parse_host.restype = i32
-        L.lc_strptime_parse_host.argtypes = [vp, vp, vp, u32, out]
-        L.lc_timestamp_zone_seconds.restype = ctypes.c_int64
-        L.lc_timestamp_zone_seconds.argtypes = [ctypes.c_int64, i32]
-        L.lc_timestamp_zone_reset.restype = None
-        L.lc_timestamp_processor_create_with_clock.restype = i32
-        L.lc_timestamp_processor_create_with_clock.argtypes = [cp, vp, vp, ctypes.POINTER(vp), cp, sz]
-        L.lc_timestamp_processor_zone_offset.restype = ctypes.c_int32
-        L.lc_timestamp_processor_zone_offset.argtypes = [vp]
-        L.lc_timestamp_processor_set_clock.restype = None
-        L.lc_timestamp_processor_set_clock.argtypes = [vp, vp, vp]
-        L.lc_timestamp_processor_set_discard.restype = None
-        L.lc_timestamp_processor_set_discard.argtypes = [vp, i32, ctypes.c_int32, i32]
-        L.lc_timestamp_processor_set_plain_walk.restype = None
-        L.lc_timestamp_processor_set_plain_walk.argtypes = [vp, i32]
-        L.lc_timestamp_processor_walk_stats.restype = None
-        L.lc_timestamp_processor_walk_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
-        L.lc_timestamp_processor_history_failures.restype = ctypes.c_uint64
-        L.lc_timestamp_processor_history_failures.argtypes = [vp]
-        bind_plugin(L, "lc_timestamp_processor")
-        L._lc_timestamp_bound = True
-    return L
+    return binding.load()
 
 
 class GpuStrptime:
@@ -130,9 +91,9 @@ class GpuStrptime:
 class _ClockedProcessor(PluginProcessor):
     """a plugin created with a clock: a callable returning epoch seconds; default time().  Its counters carry history_failure_total."""
 
-    def __init__(self, config, clock=None):
+    def __init__(self, config, clock=None, lib=None):
         self._clock = CLOCK(lambda user: int(clock())) if clock is not None else None
-        self._create(config, ctypes.cast(self._clock, ctypes.c_void_p) if self._clock else None, None, create="create_with_clock")
+        self._create(config, ctypes.cast(self._clock, ctypes.c_void_p) if self._clock else None, None, create="create_with_clock", lib=lib)
 
     def counters(self):
         d = PluginProcessor.counters(self)
@@ -144,7 +105,6 @@ class TimestampProcessor(_ClockedProcessor):
     """processor_parse_timestamp_gpu; same config keys as processor_parse_timestamp_native.  clock: "now" of the year deduction and of
     the discard rule.  collect_alarms(): kind 0 PARSE_TIME_FAIL_ALARM, kind 1 OUTDATED_LOG_ALARM."""
     PREFIX, PLUGIN = "lc_timestamp_processor", "processor_parse_timestamp_gpu"
-    _lib = staticmethod(_lib)
 
     def set_discard(self, enabled=True, interval=43200, onetime=False):
         self._L.lc_timestamp_processor_set_discard(self._h, int(enabled), interval, int(onetime))

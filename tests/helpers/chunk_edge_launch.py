@@ -83,7 +83,6 @@ def launch(torch, row, rx, batch, form, ngroups=None, caps_shift=0, n=None, line
     stream = torch.cuda.current_stream().cuda_stream
     i32 = lambda a: None if a is None else torch.from_numpy(np.asarray(a, np.uint32).view(np.int32).copy()).to(dev)
     L = B.load()
-    L.lc_nfa_set_dfs.argtypes = [ctypes.c_int]
     B.launched_kernels()
     try:
         if row.dfs:

@@ -4,79 +4,33 @@ the product's flag-mode merge behind a host model of its line split for the stdo
 import ctypes
 import json
 import os
-import subprocess
 
 import numpy as np
 
+from helpers import plugin_double
+from helpers.native_build import load_double, oracle_link
+
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-_LIB = None
-CNT = 12
 OUT_FAILED = 1  # LC_CNT_OUT_FAILED_EVENTS
 CONTAINERD, DOCKER = 1, 2
 OK, FAIL_TIME, FAIL_SOURCE, FAIL_STREAM, FAIL_JSON = 0, 1, 2, 3, 4
 STDERR, PARTIAL, ESCAPED, REPLAY = 1, 2, 4, 8
-SINK = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
 FORMAT_NAMES = {"1": "containerd_text", "2": "docker_json-file"}
 
 
-def bind_processor(L):
-    vp, cp, sz = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t
-    L.lc_container_log_processor_create.argtypes = [cp, ctypes.POINTER(vp), cp, sz]
-    L.lc_container_log_processor_destroy.argtypes = [vp]
-    L.lc_container_log_processor_warnings.restype = vp
-    L.lc_container_log_processor_warnings.argtypes = [vp]
-    L.lc_container_log_processor_set_config_name.restype = None
-    L.lc_container_log_processor_set_config_name.argtypes = [vp, cp]
-    L.lc_container_log_processor_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
-    L.lc_container_log_processor_stream_counts.restype = None
-    L.lc_container_log_processor_stream_counts.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
-    L.lc_container_log_processor_replayed_lines.restype = ctypes.c_uint64
-    L.lc_container_log_processor_replayed_lines.argtypes = [vp]
-    L.lc_container_log_processor_set_alarm_sink.restype = None
-    L.lc_container_log_processor_set_alarm_sink.argtypes = [vp, vp, vp]
-    L.lc_free.restype = None
-    L.lc_free.argtypes = [vp]
-    L.lc_merge_multiline_create.argtypes = [cp, sz, ctypes.POINTER(vp), cp, sz]
-    L.lc_merge_multiline_free.argtypes = [vp]
-
-
 def double():
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle")])
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libcontainer_log_double.so")
-    csrc = os.path.join(ROOT, "loongcollector_amd", "csrc")
-    native = os.path.join(ROOT, "tests", "native")
-    srcs = [os.path.join(native, "container_log_double.cpp"), os.path.join(native, "multiline_double.cpp")] + [os.path.join(csrc, f) for f in (
-        "processor_parse_container_log_gpu.cpp", "multiline_events.cpp", "multiline_gpu.cpp", "event_model.cpp")]
-    deps = srcs + [os.path.join(csrc, h) for h in ("clog_vm.hpp", "processor_parse_container_log_gpu.hpp", "processor_parse_regex_gpu.hpp",
-                                                   "parse_processor_shell.hpp", "event_model.hpp", "json_min.hpp", "multiline_gpu.hpp",
-                                                   "multiline_scan.hpp")]
-    deps.append(os.path.join(ROOT, "include", "lc_container_log.h"))
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-w", "-I", os.path.join(ROOT, "include"), "-I", csrc,
-                               "-o", so] + srcs + ["-L" + os.path.join(ROOT, "oracle"), "-loracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"),
-                                                   "-Wl,--no-undefined", "-Wl,-Bsymbolic"])
-    L = ctypes.CDLL(so)
-    bind_processor(L)
-    vp, cp, sz, u32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32
-    L.cd_process_json_rc.restype = vp
-    L.cd_process_json_rc.argtypes = [vp, cp, ctypes.POINTER(ctypes.c_int), cp, sz]
-    L.cd_chain_json.restype = vp
-    L.cd_chain_json.argtypes = [vp, vp, cp, cp, sz, ctypes.POINTER(ctypes.c_int), cp, sz]
-    L.cd_fail_next_trips.argtypes = [ctypes.c_int]
-    L.cd_free.argtypes = [vp]
-    L.cd_parse_one.restype = None
-    L.cd_parse_one.argtypes = [ctypes.c_int, cp, u32, u32, cp, u32, vp, vp, vp, vp, vp, vp]
-    L.cd_parse_resident.restype = None
-    L.cd_parse_resident.argtypes = [ctypes.c_int, vp, vp, u32, vp, vp]
-    L.cd_parse_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
-    _LIB = L
-    return L
+    vp, cp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
+    return load_double("container_log_double", ("container_log_double.cpp", "multiline_double.cpp", "processor_parse_container_log_gpu.cpp",
+                                                "multiline_events.cpp", "multiline_gpu.cpp", "event_model.cpp"), {
+        "cd_process_json_rc": (vp, [vp, cp, ctypes.POINTER(i32), cp, sz]),
+        "cd_chain_json": (vp, [vp, vp, cp, cp, sz, ctypes.POINTER(i32), cp, sz]),
+        "cd_fail_next_trips": (i32, [i32]),
+        "cd_free": (i32, [vp]),
+        "cd_parse_one": (None, [i32, cp, u32, u32, cp, u32, vp, vp, vp, vp, vp, vp]),
+        "cd_parse_resident": (None, [i32, vp, vp, u32, vp, vp]),
+        "cd_parse_stats": (i32, [ctypes.POINTER(ctypes.c_uint64)]),
+    }, extra=oracle_link())
 
 
 def host_parse(fmt, line, head=0, tail=b"", in_place=False):
@@ -105,40 +59,23 @@ def _events_of(out_json):
     return events, dict(d.get("metadata", []))
 
 
-class Product:
+class Product(plugin_double.Product):
     """processor_parse_container_log_gpu of library L (the double by default).  process: (product, group JSON bytes) -> (rc, group
     JSON) and chain: (product, format, read buffer bytes) -> (rc, group JSON), for a library that has no cd_process_json_rc /
     cd_chain_json (the real one goes through lc_group_from_json, and lc_split_lines_device + lc_group_from_lines)"""
+    PREFIX = "lc_container_log_processor"
 
     def __init__(self, config, L=None, process=None, chain=None):
-        self.L = L or double()
-        self.h = ctypes.c_void_p()
-        err = ctypes.create_string_buffer(512)
-        rc = self.L.lc_container_log_processor_create(json.dumps(config).encode(), ctypes.byref(self.h), err, 512)
-        if rc != 0:
-            self.h = None
-            raise ValueError(err.value.decode("utf-8", "replace"))
+        plugin_double.Product.__init__(self, config, L or double())
         self.L.lc_container_log_processor_set_config_name(self.h, b"test_config")
-        self.alarms = []
-        self._cb = SINK(lambda user, kind, msg, n: self.alarms.append((kind, ctypes.string_at(msg, n).decode("latin-1"))))
-        self.L.lc_container_log_processor_set_alarm_sink(self.h, ctypes.cast(self._cb, ctypes.c_void_p), None)
         self._process, self._chain = process, chain
         self._merge = None
 
     def __del__(self):
-        if getattr(self, "h", None):
-            self.L.lc_container_log_processor_destroy(self.h)
-            self.h = None
+        plugin_double.Product.__del__(self)
         if getattr(self, "_merge", None):
             self.L.lc_merge_multiline_free(self._merge)
             self._merge = None
-
-    def warnings(self):
-        p = self.L.lc_container_log_processor_warnings(self.h)
-        try:
-            return [w for w in ctypes.string_at(p).decode().split("\n") if w]
-        finally:
-            self.L.lc_free(p)
 
     def merge_handle(self):
         """the product's flag-mode merge"""
@@ -187,11 +124,9 @@ class Product:
 
     def counters(self):
         """out_failed, parse_stdout_total, parse_stderr_total"""
-        c = (ctypes.c_uint64 * CNT)()
-        self.L.lc_container_log_processor_counters(self.h, c)
         s = (ctypes.c_uint64 * 2)()
         self.L.lc_container_log_processor_stream_counts(self.h, s)
-        return [int(c[OUT_FAILED]), int(s[0]), int(s[1])]
+        return [self.counter_values()[OUT_FAILED], int(s[0]), int(s[1])]
 
     def replayed(self):
         return int(self.L.lc_container_log_processor_replayed_lines(self.h))

@@ -5,155 +5,56 @@ import ctypes
 import json
 import os
 import random
-import subprocess
+
+from helpers import plugin_double
+from helpers.native_build import load_double, oracle_link
+from loongcollector_amd.desensitize import GpuDesensitize
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-_LIB = None
-CNT = 12
-COUNTER_NAMES = ["discarded_events_total", "out_failed_events_total", "out_key_not_found_events_total", "out_successful_events_total",
-                 "in_events_total", "out_events_total", "in_size_bytes", "out_size_bytes", "total_process_time_us",
-                 "complexity_exceeded_events_total", "undecided_events_total", "device_failed_events_total"]
-SINK = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
 CONST, MD5 = 0, 1
 CHANGED, GAVE_UP = 1, 2
 
 
-class Stats(ctypes.Structure):
-    _fields_ = [("rounds", ctypes.c_uint32), ("pass_through", ctypes.c_uint32), ("searches", ctypes.c_uint64)]
-
-
-def bind(L):
-    vp, cp, sz, u32, u64, i32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
-    L.lc_desens_create.restype = i32
-    L.lc_desens_create.argtypes = [i32, cp, sz, cp, sz, cp, sz, i32, ctypes.POINTER(vp), ctypes.POINTER(i32), cp, sz]
-    L.lc_desens_free.restype = None
-    L.lc_desens_free.argtypes = [vp]
-    L.lc_desens_apply_host.restype = i32
-    L.lc_desens_apply_host.argtypes = [vp, vp, vp, u32, vp, vp, ctypes.POINTER(vp), ctypes.POINTER(Stats)]
-    L.lc_desensitize_create.restype = i32
-    L.lc_desensitize_create.argtypes = [cp, ctypes.POINTER(vp), cp, sz]
-    L.lc_desensitize_destroy.restype = None
-    L.lc_desensitize_destroy.argtypes = [vp]
-    L.lc_desensitize_warnings.restype = vp
-    L.lc_desensitize_warnings.argtypes = [vp]
-    L.lc_desensitize_counters.restype = i32
-    L.lc_desensitize_counters.argtypes = [vp, ctypes.POINTER(u64)]
-    L.lc_desensitize_set_alarm_sink.restype = None
-    L.lc_desensitize_set_alarm_sink.argtypes = [vp, vp, vp]
-    L.lc_desensitize_rounds.restype = u64
-    L.lc_desensitize_rounds.argtypes = [vp]
-    L.lc_free.restype = None
-    L.lc_free.argtypes = [vp]
-
-
 def double():
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle")])
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libdesens_double.so")
-    csrc = os.path.join(ROOT, "loongcollector_amd", "csrc")
-    native = os.path.join(ROOT, "tests", "native")
-    srcs = [os.path.join(native, "desens_double.cpp")] + [os.path.join(csrc, f) for f in ("processor_desensitize_gpu.cpp", "event_model.cpp")]
-    deps = srcs + [os.path.join(csrc, h) for h in ("desens_vm.hpp", "processor_desensitize_gpu.hpp", "processor_parse_regex_gpu.hpp",
-                                                   "parse_processor_shell.hpp", "event_model.hpp", "json_min.hpp")]
-    deps.append(os.path.join(ROOT, "include", "lc_desensitize.h"))
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-w", "-I", os.path.join(ROOT, "include"), "-I", csrc,
-                               "-o", so] + srcs + ["-L" + os.path.join(ROOT, "oracle"), "-loracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"),
-                                                   "-Wl,--no-undefined", "-Wl,-Bsymbolic"])
-    L = ctypes.CDLL(so)
-    bind(L)
-    vp, cp, sz, u32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32
-    L.dd_md5.restype = None
-    L.dd_md5.argtypes = [cp, u32, cp]
-    L.dd_rewrite_text.restype = vp
-    L.dd_rewrite_text.argtypes = [cp, sz, ctypes.c_int]
-    L.dd_fail_next_trips.argtypes = [ctypes.c_int]
-    L.dd_give_up_every.argtypes = [ctypes.c_int]
-    L.dd_apply_calls.restype = ctypes.c_uint64
-    L.dd_process_json_rc.restype = vp
-    L.dd_process_json_rc.argtypes = [vp, cp, cp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), cp, sz]
-    L.dd_free.argtypes = [vp]
-    L.dd_write_resident.restype = ctypes.c_uint64
-    L.dd_write_resident.argtypes = [vp, vp, vp, u32, vp, vp, u32, vp, ctypes.POINTER(ctypes.c_double)]
-    _LIB = L
-    return L
+    vp, cp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
+    return load_double("desens_double", ("desens_double.cpp", "processor_desensitize_gpu.cpp", "event_model.cpp"), {
+        "dd_md5": (None, [cp, u32, cp]),
+        "dd_rewrite_text": (vp, [cp, sz, i32]),
+        "dd_fail_next_trips": (i32, [i32]),
+        "dd_give_up_every": (i32, [i32]),
+        "dd_apply_calls": (ctypes.c_uint64, []),
+        "dd_process_json_rc": (vp, [vp, cp, cp, ctypes.POINTER(i32), ctypes.POINTER(i32), cp, sz]),
+        "dd_free": (i32, [vp]),
+        "dd_write_resident": (ctypes.c_uint64, [vp, vp, vp, u32, vp, vp, u32, vp, ctypes.POINTER(ctypes.c_double)]),
+    }, extra=oracle_link())
 
 
 def _b(s):
     return s.encode("utf-8") if isinstance(s, str) else bytes(s)
 
 
-class Engine:
+class Engine(GpuDesensitize):
     """lc_desens_* of library L (the double by default): apply(values) -> (new value or None per value, flags, rounds)"""
 
     def __init__(self, method, before, content, replacing=b"", replacing_all=False, L=None):
-        self.L = L or double()
-        before, content, replacing = _b(before), _b(content), _b(replacing)
-        self.h, warning = ctypes.c_void_p(), ctypes.c_int(0)
-        err = ctypes.create_string_buffer(512)
-        rc = self.L.lc_desens_create(MD5 if method == "md5" else CONST, before, len(before), content, len(content), replacing, len(replacing),
-                                     1 if replacing_all else 0, ctypes.byref(self.h), ctypes.byref(warning), err, 512)
-        if rc != 0:
-            self.h = None
-            raise ValueError(err.value.decode("utf-8", "replace"))
-        self.pass_through = bool(warning.value)
+        GpuDesensitize.__init__(self, method, before, content, replacing, replacing_all, lib=L or double())
 
     def apply(self, values):
-        import numpy as np
-        n = len(values)
-        blob = np.frombuffer(b"".join(values) + b"\0", np.uint8).copy()
-        lens = np.array([len(v) for v in values], np.uint32)
-        at = np.zeros(n, np.uint64)
-        if n:
-            at[1:] = np.cumsum(lens[:-1])
-        ptrs = (blob.ctypes.data + at).astype(np.uint64)
-        flags = np.zeros(n, np.uint8)
-        out_off = np.zeros(n + 1, np.uint64)
-        out = ctypes.c_void_p()
-        stats = Stats()
-        rc = self.L.lc_desens_apply_host(self.h, ptrs.ctypes.data, lens.ctypes.data, n, flags.ctypes.data, out_off.ctypes.data, ctypes.byref(out),
-                                         ctypes.byref(stats))
-        assert rc == 0, rc
-        new = ctypes.string_at(out, int(out_off[n])) if out.value else b""
-        self.L.lc_free(out)
-        return [new[int(out_off[i]):int(out_off[i + 1])] if flags[i] & CHANGED else None for i in range(n)], flags, stats.rounds
-
-    def __del__(self):
-        if getattr(self, "h", None):
-            self.L.lc_desens_free(self.h)
-            self.h = None
+        new, flags, stats = self.apply_host(values)
+        return new, flags, stats["rounds"]
 
 
-class Product:
+class Product(plugin_double.Product):
     """processor_desensitize_gpu of library L (the double by default).  process: (product, group JSON bytes) -> (rc, group JSON text)
     for a library that has no dd_process_json_rc (the real one goes through lc_group_from_json)"""
+    PREFIX, ALARM_TEXT = "lc_desensitize", None
 
     def __init__(self, config, L=None, process=None):
-        self.L = L or double()
-        self.h = ctypes.c_void_p()
-        err = ctypes.create_string_buffer(512)
-        rc = self.L.lc_desensitize_create(json.dumps(config).encode(), ctypes.byref(self.h), err, 512)
-        if rc != 0:
-            self.h = None
-            raise ValueError(err.value.decode("utf-8", "replace"))
+        plugin_double.Product.__init__(self, config, L or double())
         self.key = config.get("SourceKey", "")
         self._process = process
-        self.alarms = []
-        self._cb = SINK(lambda user, kind, msg, n: self.alarms.append((kind, ctypes.string_at(msg, n))))
-        self.L.lc_desensitize_set_alarm_sink(self.h, ctypes.cast(self._cb, ctypes.c_void_p), None)
         self.first_view_kept = None
-
-    def warnings(self):
-        p = self.L.lc_desensitize_warnings(self.h)
-        try:
-            return [w for w in ctypes.string_at(p).decode("utf-8").split("\n") if w]
-        finally:
-            self.L.lc_free(p)
 
     def process(self, group):
         """group: fixture dict -> (rc, the group afterwards as a dict)"""
@@ -172,18 +73,8 @@ class Product:
         self.first_view_kept = bool(kept.value)
         return rc.value, json.loads(out)
 
-    def counters(self):
-        buf = (ctypes.c_uint64 * CNT)()
-        assert self.L.lc_desensitize_counters(self.h, buf) == 0
-        return dict(zip(COUNTER_NAMES, [int(x) for x in buf]))
-
     def rounds(self):
         return int(self.L.lc_desensitize_rounds(self.h))
-
-    def __del__(self):
-        if getattr(self, "h", None):
-            self.L.lc_desensitize_destroy(self.h)
-            self.h = None
 
 
 # ---------------------------------------------------------------------------------------------- the rules of the issue's list

@@ -9,10 +9,13 @@ import subprocess
 
 import numpy as np
 
+from helpers import plugin_double
+from helpers.native_build import load_double
+from loongcollector_amd import abi
+from loongcollector_amd.abi import PROM_OUT_KEYS as OUT_KEYS, LcPromOut  # noqa: F401  (tests and tools read them here)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-_LIB = None
-CNT = 12
 DISCARDED, OUT_FAILED, OUT_SUCCESSFUL, DEVICE_FAILED = 0, 1, 3, 11  # LC_CNT_*
 OK = 0
 STATUS = {name: i + 1 for i, name in enumerate(
@@ -20,13 +23,7 @@ STATUS = {name: i + 1 for i, name in enumerate(
      "TIMESTAMP", "TIMESTAMP_OVERFLOW", "TIMESTAMP_SMALL", "TIMESTAMP_NAN"])}
 VALUE_HOST, TIME_HOST, HAS_TIME, ANY_ESCAPE = 1, 2, 4, 8
 LABEL_ESCAPED = 0x80000000
-OUT_KEYS = ("status", "flags", "name", "value", "value_span", "time_span", "secs", "nanos", "nlabels", "labels")
-SINK = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
 NUMBER_CHARS = set(b"0123456789.-+eEINFTYinftyXxAa")
-
-
-class LcPromOut(ctypes.Structure):
-    _fields_ = [(k, ctypes.c_void_p) for k in OUT_KEYS]
 
 
 def out_arrays(n, W, fill=0):
@@ -39,35 +36,13 @@ def out_arrays(n, W, fill=0):
     return res
 
 
-def bind_processor(L):
-    vp, cp, sz = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t
-    L.lc_prom_processor_create.argtypes = [cp, ctypes.POINTER(vp), cp, sz]
-    L.lc_prom_processor_destroy.argtypes = [vp]
-    L.lc_prom_processor_warnings.restype = vp
-    L.lc_prom_processor_warnings.argtypes = [vp]
-    L.lc_prom_processor_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
-    L.lc_prom_processor_deferred_tokens.restype = ctypes.c_uint64
-    L.lc_prom_processor_deferred_tokens.argtypes = [vp]
-    L.lc_prom_processor_mop_up_lines.restype = ctypes.c_uint64
-    L.lc_prom_processor_mop_up_lines.argtypes = [vp]
-    L.lc_prom_processor_set_first_trip_labels.restype = None
-    L.lc_prom_processor_set_first_trip_labels.argtypes = [vp, ctypes.c_uint32]
-    L.lc_prom_processor_set_alarm_sink.restype = None
-    L.lc_prom_processor_set_alarm_sink.argtypes = [vp, vp, vp]
-    L.lc_free.restype = None
-    L.lc_free.argtypes = [vp]
-
-
-def _bind_routines(L):
+def _routines():
+    """the per-line routines of tests/native/prom_double.cpp, which the double and a mutant of it export"""
     vp, cp, u32, i32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_int
     out = ctypes.POINTER(LcPromOut)
-    L.pd_parse_one.restype = u32
-    L.pd_parse_one.argtypes = [cp, u32, u32, cp, u32, i32, u32, out, i32]
-    L.pd_parse_resident.restype = ctypes.c_uint64
-    L.pd_parse_resident.argtypes = [i32, vp, vp, u32, out, u32, i32]
-    L.pd_unescape.restype = u32
-    L.pd_unescape.argtypes = [cp, ctypes.c_int32, ctypes.c_int32, vp]
-    return L
+    return {"pd_parse_one": (u32, [cp, u32, u32, cp, u32, i32, u32, out, i32]),
+            "pd_parse_resident": (ctypes.c_uint64, [i32, vp, vp, u32, out, u32, i32]),
+            "pd_unescape": (u32, [cp, ctypes.c_int32, ctypes.c_int32, vp])}
 
 
 def mutated_routines(tmp_dir, old, new):
@@ -88,35 +63,17 @@ def mutated_routines(tmp_dir, old, new):
     so = os.path.join(tree, "libprom_mutant.so")
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-w", "-DLC_PROM_DOUBLE_ROUTINES_ONLY", "-o", so,
                            os.path.join(tree, "tests", "native", "prom_double.cpp")])
-    return _bind_routines(ctypes.CDLL(so))
+    return abi.bind(ctypes.CDLL(so), _routines())
 
 
 def double():
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libprom_double.so")
-    csrc = os.path.join(ROOT, "loongcollector_amd", "csrc")
-    srcs = [os.path.join(ROOT, "tests", "native", "prom_double.cpp")] + [os.path.join(csrc, f) for f in ("processor_parse_prom_gpu.cpp", "event_model.cpp")]
-    deps = srcs + [os.path.join(csrc, h) for h in ("prom_vm.hpp", "processor_parse_prom_gpu.hpp", "processor_parse_regex_gpu.hpp", "parse_processor_shell.hpp",
-                                                   "event_model.hpp", "json_min.hpp")]
-    deps.append(os.path.join(ROOT, "include", "lc_prom.h"))
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-w", "-I", os.path.join(ROOT, "include"), "-I", csrc, "-o", so] + srcs +
-                              ["-Wl,--no-undefined", "-Wl,-Bsymbolic"])
-    L = ctypes.CDLL(so)
-    bind_processor(L)
     vp, cp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
-    _bind_routines(L)
-    L.pd_fail_next_trips.argtypes = [i32]
-    L.pd_parse_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
-    L.pd_process.restype = vp
-    L.pd_process.argtypes = [vp, vp, vp, cp, u32, cp, ctypes.POINTER(i32), ctypes.POINTER(sz)]
-    L.pd_free.argtypes = [vp]
-    _LIB = L
-    return L
+    return load_double("prom_double", ("prom_double.cpp", "processor_parse_prom_gpu.cpp", "event_model.cpp"), dict(_routines(), **{
+        "pd_fail_next_trips": (i32, [i32]),
+        "pd_parse_stats": (i32, [ctypes.POINTER(ctypes.c_uint64)]),
+        "pd_process": (vp, [vp, vp, vp, cp, u32, cp, ctypes.POINTER(i32), ctypes.POINTER(sz)]),
+        "pd_free": (i32, [vp]),
+    }))
 
 
 def load_fixtures():
@@ -269,20 +226,12 @@ def unpack_events(raw):
     return out
 
 
-class Product:
+class Product(plugin_double.Product):
     """processor_prom_parse_metric_gpu of the double.  process(lines, scrape): lines is a list of bytes (a RawEvent) or None (a LogEvent)"""
+    PREFIX = "lc_prom_processor"
 
     def __init__(self, config):
-        self.L = double()
-        self.h = ctypes.c_void_p()
-        err = ctypes.create_string_buffer(512)
-        rc = self.L.lc_prom_processor_create(config if isinstance(config, bytes) else json.dumps(config).encode(), ctypes.byref(self.h), err, 512)
-        if rc != 0:
-            self.h = None
-            raise ValueError(err.value.decode("utf-8", "replace"))
-        self.alarms = []
-        self._cb = SINK(lambda user, kind, msg, n: self.alarms.append((kind, ctypes.string_at(msg, n).decode("latin-1"))))
-        self.L.lc_prom_processor_set_alarm_sink(self.h, ctypes.cast(self._cb, ctypes.c_void_p), None)
+        plugin_double.Product.__init__(self, config, double())
 
     def process(self, lines, scrape="1700000000123"):
         n = len(lines)
@@ -298,9 +247,7 @@ class Product:
         return rc.value, unpack_events(raw)
 
     def counters(self):
-        c = (ctypes.c_uint64 * CNT)()
-        self.L.lc_prom_processor_counters(self.h, c)
-        return [int(x) for x in c]
+        return self.counter_values()
 
     def deferred_tokens(self):
         return int(self.L.lc_prom_processor_deferred_tokens(self.h))
@@ -310,11 +257,6 @@ class Product:
 
     def set_first_trip_labels(self, W):
         self.L.lc_prom_processor_set_first_trip_labels(self.h, W)
-
-    def __del__(self):
-        if getattr(self, "h", None):
-            self.L.lc_prom_processor_destroy(self.h)
-            self.h = None
 
 
 def expected_events(lines, honor, scrape_ms, W=64):

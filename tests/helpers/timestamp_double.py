@@ -2,82 +2,25 @@
 processor_parse_timestamp_gpu with the device calls answered by the __host__ instantiation of the per-value routine."""
 import ctypes
 import json
-import os
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-_LIB = None
-CNT = 12
+from helpers import plugin_double
+from helpers.native_build import load_double
+
 INT_MIN = -2 ** 31
 LC_TS_OK, LC_TS_HAS_YEAR, LC_TS_DST, LC_TS_EPOCH, LC_TS_ABSENT = 1, 2, 4, 8, 0x80
-CLOCK = ctypes.CFUNCTYPE(ctypes.c_int64, ctypes.c_void_p)
-SINK = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
-
-
-def bind_processor(L):
-    vp, cp, sz = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t
-    L.lc_timestamp_processor_create.argtypes = [cp, ctypes.POINTER(vp), cp, sz]
-    L.lc_timestamp_processor_create_with_clock.argtypes = [cp, vp, vp, ctypes.POINTER(vp), cp, sz]
-    L.lc_timestamp_processor_destroy.argtypes = [vp]
-    L.lc_timestamp_processor_warnings.restype = vp
-    L.lc_timestamp_processor_warnings.argtypes = [vp]
-    L.lc_timestamp_processor_zone_offset.restype = ctypes.c_int32
-    L.lc_timestamp_processor_zone_offset.argtypes = [vp]
-    L.lc_timestamp_processor_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
-    L.lc_timestamp_processor_history_failures.restype = ctypes.c_uint64
-    L.lc_timestamp_processor_history_failures.argtypes = [vp]
-    L.lc_timestamp_processor_set_alarm_sink.restype = None
-    L.lc_timestamp_processor_set_alarm_sink.argtypes = [vp, vp, vp]
-    L.lc_timestamp_processor_set_clock.restype = None
-    L.lc_timestamp_processor_set_clock.argtypes = [vp, vp, vp]
-    L.lc_timestamp_processor_set_discard.restype = None
-    L.lc_timestamp_processor_set_discard.argtypes = [vp, ctypes.c_int, ctypes.c_int32, ctypes.c_int]
-    L.lc_timestamp_processor_set_plain_walk.restype = None
-    L.lc_timestamp_processor_set_plain_walk.argtypes = [vp, ctypes.c_int]
-    L.lc_timestamp_processor_walk_stats.restype = None
-    L.lc_timestamp_processor_walk_stats.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
-    L.lc_timestamp_zone_seconds.restype = ctypes.c_int64
-    L.lc_timestamp_zone_seconds.argtypes = [ctypes.c_int64, ctypes.c_int]
-    L.lc_timestamp_zone_reset.restype = None
-    L.lc_free.restype = None
-    L.lc_free.argtypes = [vp]
-    L.lc_strptime_create.argtypes = [cp, ctypes.POINTER(vp), cp, sz]
-    L.lc_strptime_destroy.argtypes = [vp]
-    L.lc_strptime_program.restype = ctypes.c_uint32
-    L.lc_strptime_program.argtypes = [vp, ctypes.POINTER(ctypes.c_uint32)]
 
 
 def double():
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libtimestamp_double.so")
-    csrc = os.path.join(ROOT, "loongcollector_amd", "csrc")
-    srcs = [os.path.join(ROOT, "tests", "native", "timestamp_double.cpp")] + [os.path.join(csrc, f) for f in (
-        "processor_parse_timestamp_gpu.cpp", "strptime_program.cpp", "event_model.cpp")]
-    deps = srcs + [os.path.join(csrc, h) for h in ("strptime_vm.hpp", "strptime_program.hpp", "processor_parse_timestamp_gpu.hpp",
-                                                   "processor_parse_regex_gpu.hpp", "parse_processor_shell.hpp", "event_model.hpp", "json_min.hpp")]
-    deps.append(os.path.join(ROOT, "include", "lc_timestamp.h"))
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-w", "-I", os.path.join(ROOT, "include"), "-I", csrc,
-                               "-o", so] + srcs + ["-Wl,--no-undefined", "-Wl,-Bsymbolic"])
-    L = ctypes.CDLL(so)
-    bind_processor(L)
-    vp, cp, sz, u32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32
-    L.td_process_json.restype = vp
-    L.td_process_json.argtypes = [vp, cp, cp, sz]
-    L.td_process_json_rc.restype = vp
-    L.td_process_json_rc.argtypes = [vp, cp, ctypes.POINTER(ctypes.c_int), cp, sz]
-    L.td_fail_next_trips.argtypes = [ctypes.c_int]
-    L.td_fail_after.argtypes = [ctypes.c_int]
-    L.td_free.argtypes = [vp]
-    L.td_parse_one.restype = None
-    L.td_parse_one.argtypes = [vp, cp, u32, vp, vp, vp, vp, vp]
-    L.td_parse_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
-    _LIB = L
-    return L
+    vp, cp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
+    return load_double("timestamp_double", ("timestamp_double.cpp", "processor_parse_timestamp_gpu.cpp", "strptime_program.cpp", "event_model.cpp"), {
+        "td_process_json": (vp, [vp, cp, cp, sz]),
+        "td_process_json_rc": (vp, [vp, cp, ctypes.POINTER(i32), cp, sz]),
+        "td_fail_next_trips": (i32, [i32]),
+        "td_fail_after": (i32, [i32]),
+        "td_free": (i32, [vp]),
+        "td_parse_one": (None, [vp, cp, u32, vp, vp, vp, vp, vp]),
+        "td_parse_stats": (i32, [ctypes.POINTER(ctypes.c_uint64)]),
+    })
 
 
 class Format:
@@ -108,36 +51,13 @@ class Format:
             self.h = None
 
 
-class Product:
+class Product(plugin_double.Product):
     """processor_parse_timestamp_gpu of library L (the double by default) with a fixed clock"""
+    PREFIX = "lc_timestamp_processor"
 
     def __init__(self, config, now=None, L=None, process=None):
-        self.L = L or double()
-        self.h = ctypes.c_void_p()
-        err = ctypes.create_string_buffer(512)
-        self.now = now
-        self._clock = CLOCK(lambda user: self.now) if now is not None else None
-        self.rc = self.L.lc_timestamp_processor_create_with_clock(
-            json.dumps(config).encode(), ctypes.cast(self._clock, ctypes.c_void_p) if self._clock else None, None, ctypes.byref(self.h), err, 512)
-        if self.rc != 0:
-            self.h = None
-            raise ValueError(err.value.decode("utf-8", "replace"))
-        self.alarms = []
-        self._cb = SINK(lambda user, kind, msg, n: self.alarms.append((kind, ctypes.string_at(msg, n).decode("latin-1"))))
-        self.L.lc_timestamp_processor_set_alarm_sink(self.h, ctypes.cast(self._cb, ctypes.c_void_p), None)
+        plugin_double.Product.__init__(self, config, L or double(), *plugin_double.clock_arg(self, now), create="create_with_clock")
         self._process = process
-
-    def __del__(self):
-        if getattr(self, "h", None):
-            self.L.lc_timestamp_processor_destroy(self.h)
-            self.h = None
-
-    def warnings(self):
-        p = self.L.lc_timestamp_processor_warnings(self.h)
-        try:
-            return [w for w in ctypes.string_at(p).decode().split("\n") if w]
-        finally:
-            self.L.lc_free(p)
 
     def zone_offset(self):
         return self.L.lc_timestamp_processor_zone_offset(self.h)
@@ -186,10 +106,7 @@ class Product:
         return out
 
     def counters(self):
-        c = (ctypes.c_uint64 * CNT)()
-        self.L.lc_timestamp_processor_counters(self.h, c)
-        names = ["discarded", "out_failed", "key_not_found", "out_successful"]
-        d = dict(zip(names, [int(x) for x in c][:4]))
+        d = dict(zip(["discarded", "out_failed", "key_not_found", "out_successful"], self.counter_values()))
         d["history_failure"] = int(self.L.lc_timestamp_processor_history_failures(self.h))
         return d
 

@@ -126,7 +126,6 @@ assert libc.getenv(b"GPU_MAX_HW_QUEUES") is None, "library load changed the envi
 g = grok.Grok(Match=["%{WORD:w} %{NUMBER:n}"], SourceKey="content")
 rx = B.GpuRegex(r"(\w+) (\d+)")
 assert libc.getenv(b"GPU_MAX_HW_QUEUES") is None, "creating processors changed the environment"
-L.lc_runtime_prefer_hw_queues.restype = ctypes.c_int; L.lc_runtime_prefer_hw_queues.argtypes = [ctypes.c_int]
 assert L.lc_runtime_prefer_hw_queues(0) != 0 and L.lc_runtime_prefer_hw_queues(1000) != 0
 assert libc.getenv(b"GPU_MAX_HW_QUEUES") is None
 assert L.lc_runtime_prefer_hw_queues(16) == 0 and libc.getenv(b"GPU_MAX_HW_QUEUES") == b"16"

@@ -170,9 +170,7 @@ def test_failed_trip_leaves_the_group_untouched(L):
     rc, events, metadata = p.process_group_rc(group, "2")
     assert rc != 0 and events == [ev["contents"] for ev in group["events"]]
     assert [k for k, _ in p.alarms] == [3] and p.counters() == [0, 0, 0]
-    c = (cp.ctypes.c_uint64 * cp.CNT)()
-    L.lc_container_log_processor_counters(p.h, c)
-    assert int(c[11]) == 1  # LC_CNT_DEVICE_FAILED_EVENTS
+    assert p.counter_values()[11] == 1  # LC_CNT_DEVICE_FAILED_EVENTS
     rc, events, _ = p.process_group_rc(group, "2")
     assert rc == 0 and events[0] == [["content", "a\nb"], ["_time_", "t"], ["_source_", "stdout"]]
 

@@ -7,85 +7,36 @@ import ctypes
 import json
 import os
 import random
-import subprocess
 
 import pytest
 
+from helpers import plugin_double
 from helpers.delimiter_model import Engine
+from helpers.native_build import load_double
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_LIB = None
-CNT = 12
 
 
 def _double():
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libdelimiter_double.so")
-    csrc = os.path.join(ROOT, "loongcollector_amd", "csrc")
-    srcs = [os.path.join(ROOT, "tests", "native", "delimiter_double.cpp")] + [os.path.join(csrc, f) for f in (
-        "processor_parse_delimiter_gpu.cpp", "processor_parse_regex_gpu.cpp", "event_model.cpp")]
-    deps = srcs + [os.path.join(csrc, h) for h in ("delim_vm.hpp", "processor_parse_delimiter_gpu.hpp", "processor_parse_regex_gpu.hpp", "parse_processor_shell.hpp",
-                                                   "event_model.hpp", "json_min.hpp")] + [os.path.join(ROOT, "include", "lc_delimiter.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-w", "-I", os.path.join(ROOT, "include"), "-I", csrc,
-                               "-o", so] + srcs + ["-Wl,--no-undefined", "-Wl,-Bsymbolic"])
-    L = ctypes.CDLL(so)
-    vp, cp, sz, u32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32
-    L.lc_delimiter_processor_create.argtypes = [cp, ctypes.POINTER(vp), cp, sz]
-    L.lc_delimiter_processor_destroy.argtypes = [vp]
-    L.lc_delimiter_processor_warnings.restype = vp
-    L.lc_delimiter_processor_warnings.argtypes = [vp]
-    L.lc_delimiter_processor_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
-    L.lc_delimiter_processor_set_alarm_sink.restype = None
-    L.lc_delimiter_processor_set_alarm_sink.argtypes = [vp, vp, vp]
-    L.lc_delimiter_processor_set_first_trip_columns.restype = None
-    L.lc_delimiter_processor_set_first_trip_columns.argtypes = [vp, u32]
-    L.dd_process_json.restype = vp
-    L.dd_process_json.argtypes = [vp, cp, cp, sz]
-    L.dd_process_json_rc.restype = vp
-    L.dd_process_json_rc.argtypes = [vp, cp, ctypes.POINTER(ctypes.c_int), cp, sz]
-    L.dd_fail_next_trips.argtypes = [ctypes.c_int]
-    L.dd_fail_after.argtypes = [ctypes.c_int]
-    L.dd_free.argtypes = [vp]
-    L.lc_delim_create.argtypes = [cp, u32, ctypes.c_uint8, ctypes.c_int, u32, ctypes.POINTER(vp)]
-    L.lc_delim_destroy.argtypes = [vp]
-    L.dd_split_line.restype = None
-    L.dd_split_line.argtypes = [vp, cp, u32, u32, u32, vp, vp, vp]
-    L.dd_split_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
-    _LIB = L
-    return L
+    vp, cp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
+    return load_double("delimiter_double", ("delimiter_double.cpp", "processor_parse_delimiter_gpu.cpp", "processor_parse_regex_gpu.cpp", "event_model.cpp"), {
+        "dd_process_json": (vp, [vp, cp, cp, sz]),
+        "dd_process_json_rc": (vp, [vp, cp, ctypes.POINTER(i32), cp, sz]),
+        "dd_fail_next_trips": (i32, [i32]),
+        "dd_fail_after": (i32, [i32]),
+        "dd_free": (i32, [vp]),
+        "dd_split_line": (None, [vp, cp, u32, u32, u32, vp, vp, vp]),
+        "dd_split_stats": (i32, [ctypes.POINTER(ctypes.c_uint64)]),
+    })
 
 
-class Product:
+class Product(plugin_double.Product):
+    PREFIX, FREE = "lc_delimiter_processor", "dd_free"
+
     def __init__(self, config, first_trip_columns=0):
-        self.L = _double()
-        self.h = ctypes.c_void_p()
-        err = ctypes.create_string_buffer(512)
-        if self.L.lc_delimiter_processor_create(json.dumps(config).encode(), ctypes.byref(self.h), err, 512) != 0:
-            self.h = None
-            raise ValueError(err.value.decode("utf-8", "replace"))
+        plugin_double.Product.__init__(self, config, _double())
         if first_trip_columns:
             self.L.lc_delimiter_processor_set_first_trip_columns(self.h, first_trip_columns)
-        self.alarms = []
-        proto = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
-        self._cb = proto(lambda user, kind, msg, n: self.alarms.append((kind, ctypes.string_at(msg, n).decode("latin-1"))))
-        self.L.lc_delimiter_processor_set_alarm_sink(self.h, ctypes.cast(self._cb, vp_t), None)
-
-    def __del__(self):
-        if getattr(self, "h", None):
-            self.L.lc_delimiter_processor_destroy(self.h)
-            self.h = None
-
-    def warnings(self):
-        p = self.L.lc_delimiter_processor_warnings(self.h)
-        try:
-            return [w for w in ctypes.string_at(p).decode().split("\n") if w]
-        finally:
-            self.L.dd_free(p)
 
     def process_group(self, group):
         """fixture group in -> the events that are left, each a dict with its contents as an ordered list of pairs"""
@@ -120,12 +71,7 @@ class Product:
         return [ev["contents"] for ev in self.process_group({"events": events})]
 
     def counters(self):
-        c = (ctypes.c_uint64 * CNT)()
-        self.L.lc_delimiter_processor_counters(self.h, c)
-        return [int(x) for x in c]
-
-
-vp_t = ctypes.c_void_p
+        return self.counter_values()
 
 
 def _cases(golden_dir):

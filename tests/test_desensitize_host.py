@@ -160,7 +160,6 @@ def test_init_refusals_and_warnings_of_the_real_library():
     is needed for that), so what the compiler refuses is refused here"""
     from loongcollector_amd import desensitize
     R = desensitize._lib()
-    dp.bind(R)
     for key in ("SourceKey", "Method", "ReplacingString", "ContentPatternBeforeReplacedString", "ReplacedContentPattern"):
         assert _init_error(_without(key), R) == "mandatory param %s is missing" % key
         assert _init_error(dict(BASE, **{key: 7}), R) == "param %s is not of type string" % key

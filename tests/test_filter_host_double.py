@@ -10,45 +10,22 @@ import ctypes
 import json
 import os
 import random
-import subprocess
 
 import pytest
 
+from helpers.native_build import load_double, oracle_link
 from test_reference_neighbours import RefPlugin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference/core"
 pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference tree (/root/reference): its filter is compiled from there")
 
-_LIB = None
-
 
 def _double():
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle")])
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libfilter_double.so")
-    csrc = os.path.join(ROOT, "loongcollector_amd", "csrc")
-    srcs = [os.path.join(ROOT, "tests", "native", "filter_double.cpp"), os.path.join(csrc, "processor_filter_gpu.cpp"), os.path.join(csrc, "event_model.cpp")]
-    deps = srcs + [os.path.join(csrc, h) for h in ("event_model.hpp", "processor_filter_gpu.hpp", "json_min.hpp", "trip_buffers.hpp")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-w", "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include",
-                               "-I", os.path.join(ROOT, "include"), "-I", csrc, "-o", so] + srcs +
-                              ["-L" + os.path.join(ROOT, "oracle"), "-loracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-Wl,--no-undefined", "-Wl,-Bsymbolic"])
-    L = ctypes.CDLL(so)
     vp, cp, sz = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t
-    L.lc_filter_create.argtypes = [cp, ctypes.POINTER(vp), cp, sz]
-    L.lc_filter_destroy.argtypes = [vp]
-    L.lc_filter_mode.argtypes = [vp]
-    L.lc_filter_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
-    L.fd_process_json.restype = vp
-    L.fd_process_json.argtypes = [vp, cp, cp, sz]
-    L.fd_free.argtypes = [vp]
-    _LIB = L
-    return L
+    return load_double("filter_double", ("filter_double.cpp", "processor_filter_gpu.cpp", "event_model.cpp"),
+                       {"fd_process_json": (vp, [vp, cp, cp, sz]), "fd_free": (ctypes.c_int, [vp])},
+                       extra=["-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include"] + oracle_link())
 
 
 def _whole(text):

@@ -2,7 +2,6 @@
 lc_apsara_parse_host against the per-line routine compiled for the host, the processor over every fixture group against the recorded
 output of the reference's own processor, the edges of the stage walk at the smallest shapes that can break, sentinel-guarded outputs,
 and 64 Ki seeded random lines."""
-import ctypes
 import os
 import random
 
@@ -102,7 +101,6 @@ def test_fixture_groups_equal_the_reference(fixtures, zone):
     from loongcollector_amd.processor import EventGroup
     ref, unit = fixtures
     L = apsara._lib()
-    ad.bind_processor(L)
 
     def run(p, text):
         g = EventGroup(text.decode("latin-1"))

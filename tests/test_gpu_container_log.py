@@ -125,10 +125,6 @@ def _real_library():
     from loongcollector_amd import container_log
     from loongcollector_amd.processor import EventGroup
     L = container_log._lib()
-    cp.bind_processor(L)
-    L.lc_merge_multiline_process_group.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    L.lc_group_native.restype = ctypes.c_void_p
-    L.lc_group_native.argtypes = [ctypes.c_void_p]
     return L, EventGroup, container_log
 
 

@@ -194,8 +194,6 @@ def test_depth_first_first_pass_gives_the_same_results(torch_dev):
     import ctypes
     import torch
     L = B.load()
-    L.lc_nfa_set_dfs.argtypes = [ctypes.c_int]
-    L.lc_dfs_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(5)
     cases = [(corpus.REGEX_B, 0), (r"(\d+)-(\w+)", B.LC_SYNTAX_SEARCH), (r"((?>a+)b|a+c)(x*)", 0)]

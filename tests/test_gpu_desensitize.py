@@ -243,8 +243,6 @@ def _real():
     from loongcollector_amd import desensitize
     from loongcollector_amd.processor import EventGroup
     L = desensitize._lib()
-    L.lc_group_content_address.restype = ctypes.c_size_t
-    L.lc_group_content_address.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_char_p]
     return L, EventGroup, desensitize
 
 
@@ -378,8 +376,6 @@ def test_slot_builds_the_desensitize_processor():
     cfg = json.dumps(dict(BASE, Type="processor_desensitize_gpu")).encode()
     assert iface.init(ctypes.byref(ins), ctypes.c_char_p(cfg), None) == 0
     g = EventGroup({"events": [{"contents": {"cast1": "x pwd=abc, y"}, "timestamp": 1, "type": 1}]})
-    L.lc_group_native.restype = ctypes.c_void_p
-    L.lc_group_native.argtypes = [ctypes.c_void_p]
     iface.process(ins.plugin_state, L.lc_group_native(g._h))
     assert _contents(g) == [{"cast1": "x pwd=********, y"}]
     iface.finalize(ins.plugin_state)

@@ -137,8 +137,6 @@ def test_dlsym_slot_end_to_end():
     assert iface.init(ctypes.addressof(ins), ctypes.c_char_p(cfg), None) == 0
     g = EventGroup({"events": [{"contents": {"content": "value1\tvalue2"}, "timestamp": 1, "type": 1}]})
     L = _lib()
-    L.lc_group_native.restype = ctypes.c_void_p
-    L.lc_group_native.argtypes = [ctypes.c_void_p]
     iface.process(ins.plugin_state, L.lc_group_native(g._h))
     assert g.contents() == [[("key1", "value1"), ("key2", "value2")]]
     iface.finalize(ins.plugin_state)

@@ -13,7 +13,7 @@ import pytest
 
 from helpers import fresh_thread
 from helpers import timestamp_model as model
-from helpers.timestamp_double import INT_MIN, LC_TS_ABSENT, LC_TS_EPOCH, LC_TS_HAS_YEAR, LC_TS_OK, Product, bind_processor, check_vector
+from helpers.timestamp_double import INT_MIN, LC_TS_ABSENT, LC_TS_EPOCH, LC_TS_HAS_YEAR, LC_TS_OK, Product, check_vector
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -98,8 +98,6 @@ def test_processor_groups_on_device(zone):
     from loongcollector_amd import timestamp
     from loongcollector_amd.processor import EventGroup
     L = timestamp._lib()
-    bind_processor(L)
-    L.lc_free.argtypes = [ctypes.c_void_p]
 
     def run(p, group):
         g = EventGroup(group)
@@ -281,8 +279,6 @@ def test_slot_builds_the_timestamp_processor():
     assert iface.init(ctypes.byref(ins), ctypes.c_char_p(cfg), None) == 0
     now = int(time.time())
     g = EventGroup({"events": [{"contents": {"time": str(now - 5)}, "timestamp": 1, "type": 1}]})
-    L.lc_group_native.restype = ctypes.c_void_p
-    L.lc_group_native.argtypes = [ctypes.c_void_p]
     iface.process(ins.plugin_state, L.lc_group_native(g._h))
     assert json.loads(g.to_json())["events"][0]["timestamp"] == now - 5
     iface.finalize(ins.plugin_state)

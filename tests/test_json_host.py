@@ -5,61 +5,29 @@ rules, counters, alarms) with tests/native/json_double.cpp standing in for the d
 import ctypes
 import itertools
 import json
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from helpers import json_cases as jc
 from helpers import json_model as jm
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_LIB = None
-CNT = 12
-vp_t = ctypes.c_void_p
+from helpers import plugin_double
+from helpers.native_build import load_double
 
 
 def _double():
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libjson_double.so")
-    csrc = os.path.join(ROOT, "loongcollector_amd", "csrc")
-    srcs = [os.path.join(ROOT, "tests", "native", f) for f in ("json_double.cpp", "json_host_check.cpp")] + [os.path.join(csrc, f) for f in (
-        "processor_parse_json_gpu.cpp", "processor_parse_regex_gpu.cpp", "event_model.cpp")]
-    deps = srcs + [os.path.join(csrc, h) for h in ("json_vm.hpp", "processor_parse_json_gpu.hpp", "processor_parse_regex_gpu.hpp", "parse_processor_shell.hpp",
-                                                   "event_model.hpp", "json_min.hpp")] + [os.path.join(ROOT, "include", "lc_json.h")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-w", "-I", os.path.join(ROOT, "include"), "-I", csrc,
-                               "-o", so] + srcs + ["-Wl,--no-undefined", "-Wl,-Bsymbolic"])
-    L = ctypes.CDLL(so)
-    vp, cp, sz, u32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32
-    L.lc_json_processor_create.argtypes = [cp, ctypes.POINTER(vp), cp, sz]
-    L.lc_json_processor_destroy.argtypes = [vp]
-    L.lc_json_processor_warnings.restype = vp
-    L.lc_json_processor_warnings.argtypes = [vp]
-    L.lc_json_processor_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64)]
-    L.lc_json_processor_set_alarm_sink.restype = None
-    L.lc_json_processor_set_alarm_sink.argtypes = [vp, vp, vp]
-    L.lc_json_processor_set_first_trip_members.restype = None
-    L.lc_json_processor_set_first_trip_members.argtypes = [vp, u32]
-    L.jd_process_json.restype = vp
-    L.jd_process_json.argtypes = [vp, cp, ctypes.POINTER(ctypes.c_int), cp, sz]
-    L.jd_free.argtypes = [vp]
-    L.jd_walk_stats.argtypes = [ctypes.POINTER(ctypes.c_uint64)]
-    L.jd_fail_next_trips.argtypes = [ctypes.c_int]
-    L.jd_fail_after.argtypes = [ctypes.c_int]
-    L.jh_walk_line.restype = None
-    L.jh_walk_line.argtypes = [cp, u32, u32, u32, vp, vp, vp, vp, vp, ctypes.POINTER(ctypes.c_int)]
-    L.jh_walk_line_first.restype = None
-    L.jh_walk_line_first.argtypes = [cp, u32, u32, u32, vp, vp, vp, vp, vp]
-    L.jh_walk_batch.restype = None
-    L.jh_walk_batch.argtypes = [vp, vp, u32, u32, vp, vp, vp, vp, vp]
-    _LIB = L
-    return L
+    vp, cp, sz, u32, i32 = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
+    return load_double("json_double", ("json_double.cpp", "json_host_check.cpp", "processor_parse_json_gpu.cpp", "processor_parse_regex_gpu.cpp",
+                                       "event_model.cpp"), {
+        "jd_process_json": (vp, [vp, cp, ctypes.POINTER(i32), cp, sz]),
+        "jd_free": (i32, [vp]),
+        "jd_walk_stats": (i32, [ctypes.POINTER(ctypes.c_uint64)]),
+        "jd_fail_next_trips": (i32, [i32]),
+        "jd_fail_after": (i32, [i32]),
+        "jh_walk_line": (None, [cp, u32, u32, u32, vp, vp, vp, vp, vp, ctypes.POINTER(i32)]),
+        "jh_walk_line_first": (None, [cp, u32, u32, u32, vp, vp, vp, vp, vp]),
+        "jh_walk_batch": (None, [vp, vp, u32, u32, vp, vp, vp, vp, vp]),
+    })
 
 
 def walk_line(line, head, W, first_only=False):
@@ -132,33 +100,14 @@ def test_only_the_bytes_of_escaped_texts_are_written_to_the_shadow():
     assert written and written <= allowed
 
 
-class Product:
+class Product(plugin_double.Product):
+    PREFIX, FREE, ALARM_TEXT = "lc_json_processor", "jd_free", None
+
     def __init__(self, config, first_trip_members=0):
-        self.L = _double()
-        self.h = ctypes.c_void_p()
-        err = ctypes.create_string_buffer(512)
-        if self.L.lc_json_processor_create(json.dumps(config).encode(), ctypes.byref(self.h), err, 512) != 0:
-            self.h = None
-            raise ValueError(err.value.decode("utf-8", "replace"))
+        plugin_double.Product.__init__(self, config, _double())
         if first_trip_members:
             self.L.lc_json_processor_set_first_trip_members(self.h, first_trip_members)
-        self.alarms = []
-        proto = ctypes.CFUNCTYPE(None, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_char), ctypes.c_size_t)
-        self._cb = proto(lambda user, kind, msg, n: self.alarms.append((kind, ctypes.string_at(msg, n))))
-        self.L.lc_json_processor_set_alarm_sink(self.h, ctypes.cast(self._cb, vp_t), None)
         self.rc = 0
-
-    def __del__(self):
-        if getattr(self, "h", None):
-            self.L.lc_json_processor_destroy(self.h)
-            self.h = None
-
-    def warnings(self):
-        p = self.L.lc_json_processor_warnings(self.h)
-        try:
-            return [w for w in ctypes.string_at(p).decode().split("\n") if w]
-        finally:
-            self.L.jd_free(p)
 
     def process_group(self, group):
         """fixture group (latin-1 text: one character per byte) -> the events that are left, contents as dicts of bytes"""
@@ -180,9 +129,7 @@ class Product:
         return [{k.encode("latin-1"): v.encode("latin-1") for k, v in ev.get("contents", {}).items()} for ev in self.process_group(group)]
 
     def counters(self):
-        c = (ctypes.c_uint64 * CNT)()
-        self.L.lc_json_processor_counters(self.h, c)
-        return [int(x) for x in c]
+        return self.counter_values()
 
 
 def _model_run(config, events):

@@ -12,55 +12,27 @@ import ctypes
 import json
 import os
 import random
-import subprocess
 
 import pytest
 
+from helpers.native_build import load_double, oracle_link
 from test_reference_neighbours import RefPlugin
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference/core"
 pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference tree (/root/reference): its processors are compiled from there")
 
-_LIB = None
-
 
 def _double():
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle")])
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    so = os.path.join(out_dir, "libpipeline_double.so")
-    csrc = os.path.join(ROOT, "loongcollector_amd", "csrc")
-    native = os.path.join(ROOT, "tests", "native")
-    srcs = [os.path.join(native, "pipeline_double.cpp")] + [os.path.join(csrc, f) for f in (
-        "c_processor_slot.cpp", "processor_pipeline_gpu.cpp", "processor_parse_regex_gpu.cpp", "processor_filter_gpu.cpp", "event_model.cpp")]
-    deps = srcs + [os.path.join(native, "filter_double.cpp")] + [os.path.join(csrc, h) for h in (
-        "event_model.hpp", "processor_pipeline_gpu.hpp", "processor_parse_regex_gpu.hpp", "processor_filter_gpu.hpp", "json_min.hpp", "trip_buffers.hpp")]
-    if not os.path.exists(so) or any(os.path.getmtime(d) > os.path.getmtime(so) for d in deps):
-        from loongcollector_amd import build as native_build
-        objdir = os.path.join(ROOT, "loongcollector_amd", "lib", "obj")
-        if not os.path.exists(os.path.join(objdir, "grok_defaults.inc")):
-            native_build.build_native()
-        subprocess.check_call(["g++", "-O2", "-g", "-std=c++17", "-fPIC", "-shared", "-w", "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include",
-                               "-I", os.path.join(ROOT, "include"), "-I", csrc, "-I", objdir, "-o", so] + srcs +
-                              ["-L" + os.path.join(ROOT, "oracle"), "-loracle", "-Wl,-rpath," + os.path.join(ROOT, "oracle"), "-Wl,--no-undefined", "-Wl,-Bsymbolic"])
-    L = ctypes.CDLL(so)
     vp, cp, sz = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t
-    L.lc_pipeline_create.argtypes = [cp, ctypes.POINTER(vp), cp, sz]
-    L.lc_pipeline_destroy.argtypes = [vp]
-    L.lc_pipeline_is_fused.argtypes = [vp]
-    L.lc_pipeline_counters.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
-    L.pd_process_json.restype = vp
-    L.pd_process_json.argtypes = [vp, cp, cp, sz]
-    L.lc_free.argtypes = [vp]
-    R = RefPlugin.lib()
-    R.refp_process_chain4_json.restype = vp
-    R.refp_process_chain4_json.argtypes = [vp, vp, vp, vp, cp, cp, sz]
-    _LIB = L
-    return L
+    objdir = os.path.join(ROOT, "loongcollector_amd", "lib", "obj")
+    if not os.path.exists(os.path.join(objdir, "grok_defaults.inc")):
+        from loongcollector_amd import build as native_build
+        native_build.build_native()
+    return load_double("pipeline_double", ("pipeline_double.cpp", "c_processor_slot.cpp", "processor_pipeline_gpu.cpp", "processor_parse_regex_gpu.cpp",
+                                           "processor_filter_gpu.cpp", "event_model.cpp"),
+                       {"pd_process_json": (vp, [vp, cp, cp, sz])},
+                       extra=["-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", objdir] + oracle_link())
 
 
 def _whole(text):
@@ -124,6 +96,9 @@ class ProductPipeline:
 
 def _ref_chain(handles, fixture):
     R = RefPlugin.lib()
+    vp, cp = ctypes.c_void_p, ctypes.c_char_p
+    R.refp_process_chain4_json.restype = vp
+    R.refp_process_chain4_json.argtypes = [vp, vp, vp, vp, cp, cp, ctypes.c_size_t]
     err = ctypes.create_string_buffer(512)
     hs = [h.h if h is not None else None for h in handles] + [None] * (4 - len(handles))
     p = R.refp_process_chain4_json(hs[0], hs[1], hs[2], hs[3], json.dumps(fixture).encode(), err, 512)

@@ -166,7 +166,7 @@ def main():
             secs = ctypes.c_double(0)
             runs = []
             for _ in range(5):
-                wrote = D.dd_write_resident(eng.h, data.ctypes.data, off.ctypes.data, h, counts.ctypes.data, rows.ctypes.data, 2, out.ctypes.data,
+                wrote = D.dd_write_resident(eng._h, data.ctypes.data, off.ctypes.data, h, counts.ctypes.data, rows.ctypes.data, 2, out.ctypes.data,
                                             ctypes.byref(secs))
                 runs.append(secs.value * 1e3)
             r = rates(spread(runs), h, LINE_BYTES)

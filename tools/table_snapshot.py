@@ -20,10 +20,6 @@ if len(sys.argv) == 4 and sys.argv[1] == "--diff":
 if len(sys.argv) > 2: os.environ["LC_REGEX_GPU_LIB"] = sys.argv[2]
 from loongcollector_amd import binding as B, corpus
 L = B.load()
-L.lc_regex_compile.restype = ctypes.c_int
-L.lc_regex_compile.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.c_char_p, ctypes.c_size_t]
-L.lc_regex_table.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t)]
-L.lc_regex_free.argtypes = [ctypes.c_void_p]
 SEARCH, NAMED, NODOT, NOML, RE2, PREFIX = 1<<5, 1<<4, 1<<1, 1<<2, 1<<6, 1<<7
 GROK = SEARCH|NAMED|NODOT|NOML|RE2
 jobs = []

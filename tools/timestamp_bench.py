@@ -89,8 +89,6 @@ def main():
         f = Format(fmt)
         m = min(args.n, 1 << 16)
         L = f.L
-        L.lc_strptime_parse_host.restype = ctypes.c_int
-        L.lc_strptime_parse_host.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_uint32, ctypes.c_void_p]
         ptrs = (data.ctypes.data + off[:m].astype(np.int64)).astype(np.uint64)
         hl = lens[:m].astype(np.uint32)
         res = {"status": np.zeros(m, np.uint8), "secs": np.zeros(m, np.int64), "nanos": np.zeros(m, np.uint32), "matched": np.zeros(m, np.int32),
