@@ -319,6 +319,21 @@ PROTOTYPES = {
     "lc_timestamp_processor_set_alarm_sink": (None, [vp, vp, vp]),
 }
 
+# liblc_kvsplit.so (include/kvsplit/lc_kvsplit.h): a table of its own, for a library that stands beside liblc_regex_gpu.so;
+# tests/test_kv_abi.py holds it to its header and to that library's exports
+KVSPLIT_PROTOTYPES = {
+    "lc_kvsplit_create": (i32, [cp, sz, P(vp), cp, sz]),
+    "lc_kvsplit_free": (None, [vp]),
+    "lc_kvsplit_device": (i32, [vp, vp, vp, u32, u32, vp, vp, vp, vp]),
+    "lc_kvsplit_host": (i32, [vp, vp, vp, u32, u32, vp, vp, vp]),
+    "lc_kvsplit_process_logs_json": (i32, [vp, cp, sz, P(vp)]),
+    "lc_kvsplit_free_string": (None, [vp]),
+    "lc_kvsplit_counters": (i32, [vp, P(u64)]),
+    "lc_kvsplit_set_alarm_sink": (None, [vp, vp, vp]),
+    "lc_kvsplit_set_first_trip_pairs": (None, [vp, u32]),
+    "lc_kvsplit_thread_release": (None, []),
+}
+
 
 def bind(L, extra=None):
     """restype / argtypes of every table entry (and of `extra`, a table of the same form) that L exports; -> L"""
