@@ -334,6 +334,20 @@ KVSPLIT_PROTOTYPES = {
     "lc_kvsplit_thread_release": (None, []),
 }
 
+# liblc_csv.so (include/csv/lc_csv.h): the same again for the CSV decoder; tests/test_csv_abi.py holds it to its header and exports
+CSV_PROTOTYPES = {
+    "lc_csv_create": (i32, [cp, sz, P(vp), cp, sz]),
+    "lc_csv_free": (None, [vp]),
+    "lc_csv_device": (i32, [vp, vp, vp, u32, u32, vp, vp, vp, vp]),
+    "lc_csv_host": (i32, [vp, vp, vp, u32, u32, vp, vp, vp]),
+    "lc_csv_process_logs_json": (i32, [vp, cp, sz, P(vp)]),
+    "lc_csv_free_string": (None, [vp]),
+    "lc_csv_counters": (i32, [vp, P(u64)]),
+    "lc_csv_set_alarm_sink": (None, [vp, vp, vp]),
+    "lc_csv_set_first_trip_fields": (None, [vp, u32]),
+    "lc_csv_thread_release": (None, []),
+}
+
 
 def bind(L, extra=None):
     """restype / argtypes of every table entry (and of `extra`, a table of the same form) that L exports; -> L"""

@@ -21,6 +21,10 @@ LIB_REFSHAPE = os.path.join(LIBDIR, "liblc_regex_gpu_refshape.so")
 # the key-value splitter (include/kvsplit/lc_kvsplit.h): a library of its own beside LIB, linked against it; LIB's ABI does not grow
 LIB_KV = os.path.join(LIBDIR, "liblc_kvsplit.so")
 KV_SOURCES = ["kv_device.hip", "processor_split_key_value_gpu.cpp"]
+# the CSV decoder (include/csv/lc_csv.h): the same again, a third library beside the two
+LIB_CSV = os.path.join(LIBDIR, "liblc_csv.so")
+CSV_SOURCES = ["csv_device.hip", "processor_csv_gpu.cpp"]
+SIDE_SOURCES = KV_SOURCES + CSV_SOURCES
 
 SOURCES = ["regex_parse.cpp", "atomic_elide.cpp", "follow_nfa.cpp", "tdfa.cpp", "table_cache.cpp", "screen_dfa.cpp", "bt_program.cpp", "regex_handle.cpp", "gpu_runtime.hip", "grok_device.hip", "multiline_device.hip", "delim_device.hip", "strptime_program.cpp", "timestamp_device.hip", "json_device.hip", "apsara_device.hip", "clog_device.hip", "desens_device.hip", "prom_device.hip"]
 OPTIONAL_SOURCES = ["event_model.cpp", "processor_parse_regex_gpu.cpp", "grok.cpp", "grok_literal_index.cpp", "processor_grok_gpu.cpp", "processor_filter_gpu.cpp", "processor_go_regex_gpu.cpp", "multiline_gpu.cpp", "multiline_events.cpp", "processor_pipeline_gpu.cpp", "processor_parse_delimiter_gpu.cpp", "processor_parse_timestamp_gpu.cpp", "processor_parse_json_gpu.cpp", "processor_parse_apsara_gpu.cpp", "processor_parse_container_log_gpu.cpp", "processor_desensitize_gpu.cpp", "processor_parse_prom_gpu.cpp", "c_processor_slot.cpp"]
@@ -40,12 +44,12 @@ def _hipcc():
 def sources():
     out = [os.path.join(CSRC, s) for s in SOURCES]
     out += [os.path.join(CSRC, s) for s in OPTIONAL_SOURCES if os.path.exists(os.path.join(CSRC, s))]
-    out += [os.path.join(CSRC, s) for s in KV_SOURCES]
+    out += [os.path.join(CSRC, s) for s in SIDE_SOURCES]
     return out
 
 
 def needs_build():
-    if not os.path.exists(LIB) or not os.path.exists(LIB_KV):
+    if not os.path.exists(LIB) or not os.path.exists(LIB_KV) or not os.path.exists(LIB_CSV):
         return True
     t = os.path.getmtime(LIB)
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)]
@@ -62,6 +66,7 @@ def needs_build():
     deps.append(os.path.join(HERE, "..", "include", "lc_desensitize.h"))
     deps.append(os.path.join(HERE, "..", "include", "lc_prom.h"))
     deps.append(os.path.join(HERE, "..", "include", "kvsplit", "lc_kvsplit.h"))
+    deps.append(os.path.join(HERE, "..", "include", "csv", "lc_csv.h"))
     deps.append(os.path.join(HERE, "data", "grok_default_patterns.txt"))
     return any(os.path.exists(d) and os.path.getmtime(d) > t for d in deps)
 
@@ -134,17 +139,20 @@ def build_native(force=False, verbose=False, force_sources=()):
         if verbose and out:
             print(out.decode(), file=sys.stderr)
     kv_objs = [o for o in objs if os.path.basename(o)[:-2] in KV_SOURCES]
-    objs = [o for o in objs if o not in kv_objs]
+    csv_objs = [o for o in objs if os.path.basename(o)[:-2] in CSV_SOURCES]
+    objs = [o for o in objs if o not in kv_objs and o not in csv_objs]
     # (the SONAME: liblc_kvsplit.so names this library as needed, and a process that has it loaded already -- from a file a later build has
     # replaced -- must get THAT copy, not a second one)
     cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,-soname,liblc_regex_gpu.so", "-o", LIB] + objs
     subprocess.check_call(cmd)
     subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_KV] + kv_objs +
                           ["-L" + LIBDIR, "-llc_regex_gpu", "-Wl,-rpath,$ORIGIN"])
+    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_CSV] + csv_objs +
+                          ["-L" + LIBDIR, "-llc_regex_gpu", "-Wl,-rpath,$ORIGIN"])
     # the reference-shaped variant: only the host translation units that see the event model are compiled again (with the switch);
     # the regex compilers and every gfx950 object are the ones just linked above
     shape_objs, procs = [], []
-    for src, obj in zip([s for s in sources() if os.path.basename(s) not in KV_SOURCES], objs):
+    for src, obj in zip([s for s in sources() if os.path.basename(s) not in SIDE_SOURCES], objs):
         base = os.path.basename(src)
         if base not in OPTIONAL_SOURCES:
             shape_objs.append(obj)
