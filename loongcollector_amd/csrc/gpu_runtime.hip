@@ -645,11 +645,14 @@ static int launchDecide(lc_regex* re, const void* dBlob, const MatchBatch& b, ui
     if (pool.used && pool.lastStream != stream) HIP_TRY(hipStreamWaitEvent(stream, pool.lastUse, 0));
     const DecideShape shape{re->decideClosedCap, re->decideMaxEnter};
     const uint32_t nPos = uint32_t(re->nfa.positions.size());
+    uint64_t budgetNoMemo = kDecideBudgetNoMemo;
+    if (const char* e = getenv("LC_DECIDE_BUDGET")) budgetNoMemo = strtoull(e, nullptr, 10);  // (read per launch: tests)
     noteKernel("nfa_decide_kernel");
     hipLaunchKernelGGL(nfa_decide_plan_kernel, dim3(1), dim3(256), 0, stream, b.d_off, b.d_len, b.sep, b.n, b.d_n, b.d_order, b.d_resume, nPos,
-                       shape, b.d_status, overflowFlag, seq, pool.p, uint64_t(pool.bytes));
+                       shape, b.ngroups, b.d_caps, b.d_status, overflowFlag, seq, pool.p, uint64_t(pool.bytes));
     hipLaunchKernelGGL(nfa_decide_kernel, dim3(kDecideWorkers), dim3(64), 0, stream, b.d_data, b.d_off, b.d_len, b.sep, b.d_resume,
-                       static_cast<const uint32_t*>(dBlob), shape, b.ngroups, b.d_caps, b.d_status, overflowFlag, seq, pool.p);
+                       static_cast<const uint32_t*>(dBlob), shape, b.ngroups, b.d_caps, b.d_status, overflowFlag, seq, pool.p,
+                       budgetNoMemo);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(pool.lastUse, stream));
     pool.lastStream = stream;

@@ -40,7 +40,7 @@ constexpr uint32_t kDecideNodeWords = 3;
 constexpr uint32_t kDecideExhausted = 0x80000000u;
 constexpr uint32_t kDecideNone = 0xFFFFFFFFu;
 constexpr uint64_t kDecideBudgetMemo = uint64_t(1) << 28;    // steps; with the memo the walk is bounded by paths x length anyway
-constexpr uint64_t kDecideBudgetNoMemo = uint64_t(1) << 22;  // plain backtracking: give up like boost's complexity guard
+constexpr uint64_t kDecideBudgetNoMemo = uint64_t(1) << 22;  // plain backtracking: give up like boost's complexity guard (LC_DECIDE_BUDGET)
 
 struct DecidePlan {
     uint32_t count;       // residue lines in the list
@@ -85,7 +85,8 @@ __global__ __launch_bounds__(256) void nfa_decide_plan_kernel(const uint32_t* __
                                                               const uint32_t* __restrict__ nLinesPtr,
                                                               const uint32_t* __restrict__ order,
                                                               const uint32_t* __restrict__ resume, uint32_t nPos,
-                                                              DecideShape shape, uint8_t* __restrict__ status,
+                                                              DecideShape shape, uint32_t nGroupsOut,
+                                                              int32_t* __restrict__ caps, uint8_t* __restrict__ status,
                                                               const uint32_t* __restrict__ overflowFlag, uint32_t launchSeq,
                                                               uint8_t* __restrict__ pool, uint64_t poolBytes) {
     DecidePlan* plan = reinterpret_cast<DecidePlan*>(pool);
@@ -111,6 +112,8 @@ __global__ __launch_bounds__(256) void nfa_decide_plan_kernel(const uint32_t* __
             if (status[line] != LC_OVERFLOW) continue;
             const uint32_t idx = atomicAdd(&sCount, 1u);
             if (idx >= listCap) {  // more undecided lines than the pool can even list: reported, never guessed
+                int32_t* out = caps + size_t(line) * 2 * nGroupsOut;  // (the row a given-up line has behind the workers too)
+                for (uint32_t s = 0; s < 2 * nGroupsOut; ++s) out[s] = -1;
                 status[line] = LC_GAVE_UP;
                 atomicAdd(&sGaveUp, 1u);
                 continue;
@@ -142,8 +145,10 @@ __global__ __launch_bounds__(256) void nfa_decide_plan_kernel(const uint32_t* __
             const uint64_t fit = avail / withMemo;
             if (fit >= 1) workers = uint32_t(fit < workers ? fit : workers);
             else {
+                // not even one frame stack of the longest line fits: one worker with the whole rest of the pool, which gives up
+                // the lines whose own stack exceeds it and decides the others (never workers = 0: that would give up them all)
                 const uint64_t fitPlain = avail / fixed;
-                workers = uint32_t(fitPlain < workers ? fitPlain : workers);  // 0: not even one frame stack fits
+                workers = fitPlain >= 1 ? uint32_t(fitPlain < workers ? fitPlain : workers) : 1u;
             }
         }
         slice = workers ? (avail / workers) & ~uint64_t(255) : 0;
@@ -378,7 +383,7 @@ __global__ __launch_bounds__(64) void nfa_decide_kernel(const uint8_t* __restric
                                                         uint32_t nGroupsOut, int32_t* __restrict__ caps,
                                                         uint8_t* __restrict__ status,
                                                         const uint32_t* __restrict__ overflowFlag, uint32_t launchSeq,
-                                                        uint8_t* __restrict__ pool) {
+                                                        uint8_t* __restrict__ pool, uint64_t budgetNoMemo) {
     if (__atomic_load_n(overflowFlag, __ATOMIC_RELAXED) < launchSeq) return;  // the thread-list kernels decided every line
     DecidePlan* plan = reinterpret_cast<DecidePlan*>(pool);
     const uint32_t count = plan->count;
@@ -386,14 +391,7 @@ __global__ __launch_bounds__(64) void nfa_decide_kernel(const uint8_t* __restric
     const uint32_t* list = reinterpret_cast<const uint32_t*>(pool + kDecideHeaderBytes);
     const uint32_t lane = threadIdx.x;
     const uint32_t workers = plan->workers;
-    if (workers == 0) {  // the pool cannot hold one frame stack for the longest line: report, never guess
-        for (uint32_t idx = blockIdx.x * 64 + lane; idx < count; idx += gridDim.x * 64) {
-            status[list[idx]] = LC_GAVE_UP;
-            atomicAdd(&plan->gaveUp, 1u);
-        }
-        return;
-    }
-    if (blockIdx.x >= workers) return;
+    if (blockIdx.x >= workers) return;  // (a launch with a list has at least one worker)
     uint8_t* slice = pool + plan->slicesAt + uint64_t(blockIdx.x) * plan->sliceBytes;
     const uint64_t sliceBytes = plan->sliceBytes;
 
@@ -444,7 +442,7 @@ __global__ __launch_bounds__(64) void nfa_decide_kernel(const uint8_t* __restric
             waveLdsSync();
             if (lane == 0)
                 verdict = decideLine(t, w, data + o, L, from, nGroupsOut, caps + size_t(line) * 2 * nGroupsOut,
-                                     w.memo ? kDecideBudgetMemo : kDecideBudgetNoMemo);
+                                     w.memo ? kDecideBudgetMemo : budgetNoMemo);
         }
         if (lane == 0) {
             if (verdict != LC_MATCH) {

@@ -310,7 +310,11 @@ def test_split_host_after_thread_release_gives_the_same_answer():
         return first, dl.split_host(data, off, 4), binding.load().lc_last_error()
 
     first, second, error = fresh_thread.run(body)
-    assert all(np.array_equal(a, b) for a, b in zip(first, second)) and list(first[1]) == [2, 2, 0, 1]
+    assert np.array_equal(first[0], second[0]) and np.array_equal(first[1], second[1]) and list(first[1]) == [2, 2, 0, 1]
+    # the spans that count: columns from ncols[i] on are written by nobody (include/lc_delimiter.h), and the staging the second call
+    # allocates need not hold what the first one's held
+    live = np.arange(4)[None, :] < first[1][:, None]
+    assert np.array_equal(first[2][live], second[2][live]) and first[2][live].tolist() == [[0, 1], [2, 3], [1, 4], [6, 7], [0, 1]]
     assert not error
 
 
