@@ -348,6 +348,22 @@ CSV_PROTOTYPES = {
     "lc_csv_thread_release": (None, []),
 }
 
+# liblc_sls.so (include/sls/lc_sls.h): the same again for the SLS encoder; tests/test_sls_abi.py holds it to its header and exports
+SLS_PROTOTYPES = {
+    "lc_sls_plan_create": (i32, [P(cp), P(u32), u32, P(u32), u32, P(u32), u32, P(vp), cp, sz]),
+    "lc_sls_plan_free": (None, [vp]),
+    "lc_sls_scratch_bytes": (sz, [u32]),
+    "lc_sls_encode_device": (i32, [vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, i32, vp, u64, vp, vp, sz, vp]),
+    "lc_sls_match_encode_host": (i32, [vp, vp, vp, vp, u32, vp, vp, i32, P(vp), P(sz), vp, vp]),
+    "lc_sls_append_tags": (i32, [P(cp), P(u32), P(cp), P(u32), u32, vp, sz, P(sz)]),
+    "lc_sls_thread_release": (None, []),
+    "lc_sls_processor_create": (i32, [cp, P(vp), cp, sz]),
+    "lc_sls_processor_destroy": (None, [vp]),
+    "lc_sls_processor_serialize": (i32, [vp, vp, i32, P(vp), P(sz), P(i32)]),
+    "lc_sls_serialize_group_host": (i32, [vp, i32, P(vp), P(sz)]),
+    "lc_sls_processor_counters": (i32, [vp, P(u64), P(u64)]),
+}
+
 
 def bind(L, extra=None):
     """restype / argtypes of every table entry (and of `extra`, a table of the same form) that L exports; -> L"""

@@ -53,9 +53,11 @@ struct GpuCommonParserOptions {
 };
 
 class ProcessorPipelineGpu;
+class ProcessorSlsGpu;
 
 class ProcessorParseRegexGpu {
     friend class ProcessorPipelineGpu;  // the fused split -> parse -> filter trip stitches with this class's own code
+    friend class ProcessorSlsGpu;       // processor_sls_gpu.cpp (liblc_sls.so) reads its plan off a probe event stitched by it
 
 public:
     static const std::string sName;  // "processor_parse_regex_gpu" (new Type name; static names win in PluginRegistry)
