@@ -364,6 +364,21 @@ SLS_PROTOTYPES = {
     "lc_sls_processor_counters": (i32, [vp, P(u64), P(u64)]),
 }
 
+# liblc_anchor.so (include/anchor/lc_anchor.h): the same again for the anchor processor; tests/test_anchor_abi.py holds it to its header
+# and exports
+ANCHOR_PROTOTYPES = {
+    "lc_anchor_create": (i32, [cp, sz, P(vp), cp, sz]),
+    "lc_anchor_free": (None, [vp]),
+    "lc_anchor_stride": (u32, [vp]),
+    "lc_anchor_locate_device": (i32, [vp, vp, vp, u32, vp, vp]),
+    "lc_anchor_locate_host": (i32, [vp, vp, vp, u32, vp]),
+    "lc_anchor_process_logs_json": (i32, [vp, cp, sz, P(vp)]),
+    "lc_anchor_free_string": (None, [vp]),
+    "lc_anchor_counters": (i32, [vp, P(u64)]),
+    "lc_anchor_set_alarm_sink": (None, [vp, vp, vp]),
+    "lc_anchor_thread_release": (None, []),
+}
+
 
 def bind(L, extra=None):
     """restype / argtypes of every table entry (and of `extra`, a table of the same form) that L exports; -> L"""
