@@ -379,6 +379,19 @@ ANCHOR_PROTOTYPES = {
     "lc_anchor_thread_release": (None, []),
 }
 
+# liblc_lz4.so (include/lz4/lc_lz4.h): the same again for the LZ4 block writer; tests/test_lz4_abi.py holds it to its header and exports
+LZ4_PROTOTYPES = {
+    "lc_lz4_create": (i32, [u32, P(vp), cp, sz]),
+    "lc_lz4_free": (None, [vp]),
+    "lc_lz4_chunk_bytes": (u32, [vp]),
+    "lc_lz4_bound": (u64, [u64]),
+    "lc_lz4_scratch_bytes": (sz, [vp, u64, u32]),
+    "lc_lz4_compress_device": (i32, [vp, vp, vp, vp, u32, vp, u64, vp, vp, sz, vp]),
+    "lc_lz4_compress_host": (i32, [vp, vp, vp, u32, P(vp), vp]),
+    "lc_lz4_match_encode_compress_host": (i32, [vp, vp, vp, vp, vp, u32, vp, vp, i32, vp, u32, P(vp), P(sz), P(u64), vp, vp]),
+    "lc_lz4_thread_release": (None, []),
+}
+
 
 def bind(L, extra=None):
     """restype / argtypes of every table entry (and of `extra`, a table of the same form) that L exports; -> L"""
