@@ -392,6 +392,23 @@ LZ4_PROTOTYPES = {
     "lc_lz4_thread_release": (None, []),
 }
 
+# liblc_jsonl.so (include/jsonl/lc_jsonl.h): the same again for the JSON-lines encoder; tests/test_jsonl_abi.py holds it to its header and
+# exports
+JSONL_PROTOTYPES = {
+    "lc_jsonl_plan_create": (i32, [P(cp), P(u32), u32, P(u32), u32, P(u32), u32, P(vp), cp, sz]),
+    "lc_jsonl_plan_free": (None, [vp]),
+    "lc_jsonl_head": (i32, [P(cp), P(u32), P(cp), P(u32), u32, vp, sz, P(sz)]),
+    "lc_jsonl_scratch_bytes": (sz, [vp, u32]),
+    "lc_jsonl_encode_device": (i32, [vp, vp, vp, vp, u32, u32, u32, vp, vp, vp, vp, u32, vp, u64, vp, vp, sz, vp]),
+    "lc_jsonl_match_encode_host": (i32, [vp, vp, vp, vp, u32, vp, vp, u32, P(vp), P(sz), vp, vp]),
+    "lc_jsonl_thread_release": (None, []),
+    "lc_jsonl_processor_create": (i32, [cp, P(vp), cp, sz]),
+    "lc_jsonl_processor_destroy": (None, [vp]),
+    "lc_jsonl_processor_serialize": (i32, [vp, vp, P(vp), P(sz), P(i32)]),
+    "lc_jsonl_serialize_group_host": (i32, [vp, P(vp), P(sz)]),
+    "lc_jsonl_processor_counters": (i32, [vp, P(u64), P(u64)]),
+}
+
 
 def bind(L, extra=None):
     """restype / argtypes of every table entry (and of `extra`, a table of the same form) that L exports; -> L"""

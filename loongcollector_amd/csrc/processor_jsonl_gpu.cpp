@@ -1,25 +1,25 @@
-// processor_sls_gpu.cpp -- the processor level of the SLS encoder (include/sls/lc_sls.h): processor_parse_regex_native followed by
-// SLSEventGroupSerializer, as one call that leaves the group alone.  The parser is ProcessorParseRegexGpu itself; what an event
-// becomes on the wire is READ OFF that class by the probe events of parse_probe_items.hpp: the contents that are left, in their order,
-// are the plan's two item lists.
-// No HIP here: the tests build this file on a host double of lc_sls_match_encode_host.
+// processor_jsonl_gpu.cpp -- the processor level of the JSON-lines encoder (include/jsonl/lc_jsonl.h): processor_parse_regex_native
+// followed by JsonEventGroupSerializer, as one call that leaves the group alone.  The parser is ProcessorParseRegexGpu itself; what an
+// event becomes is READ OFF that class by the probe events of parse_probe_items.hpp, as ProcessorSlsGpu does.  The head of every
+// record is built per call from the group's tags (lc_jsonl_head).
+// No HIP here: the tests build this file on a host double of lc_jsonl_match_encode_host.
 #include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
 
-#include "../../include/sls/lc_sls.h"
+#include "../../include/jsonl/lc_jsonl.h"
+#include "jsonl_vm.hpp"
 #include "parse_probe_items.hpp"
 #include "parse_processor_shell.hpp"
-#include "sls_vm.hpp"
 
 namespace logtail {
 
-class ProcessorSlsGpu {
+class ProcessorJsonlGpu {
 public:
-    ~ProcessorSlsGpu() { lc_sls_plan_free(mPlan); }
+    ~ProcessorJsonlGpu() { lc_jsonl_plan_free(mPlan); }
     bool Init(const lcjson::Value& config, std::string& error);
-    int Serialize(PipelineEventGroup& group, bool enableNs, const uint8_t** out, size_t* outLen, int* fused);
+    int Serialize(PipelineEventGroup& group, const uint8_t** out, size_t* outLen, int* fused);
 
     ProcessorParseRegexGpu mParse;
     std::atomic<uint64_t> mGroupsDevice{0}, mGroupsHost{0}, mFailedTrips{0}, mBytes{0};
@@ -27,70 +27,68 @@ public:
 private:
     using Tally = ProcessorParseRegexGpu::Tally;
     bool DevicePathServes(const PipelineEventGroup& group) const;
-    int SerializeOnDevice(PipelineEventGroup& group, bool enableNs, const uint8_t** out, size_t* outLen, bool* undecided);
-    void SerializeOnHost(PipelineEventGroup& group, bool enableNs, const uint8_t** out, size_t* outLen);
+    int SerializeOnDevice(PipelineEventGroup& group, const uint8_t** out, size_t* outLen, bool* undecided);
+    void SerializeOnHost(PipelineEventGroup& group, const uint8_t** out, size_t* outLen);
 
-    lc_sls_plan_t* mPlan = nullptr;  // null: no device path for this configuration
-    Tally mFailedTally;              // what FinishEvent books for ONE line the parser did not match
+    lc_jsonl_plan_t* mPlan = nullptr;  // null: no device path for this configuration
+    Tally mFailedTally;                // what FinishEvent books for ONE line the parser did not match
 };
 
 namespace {
-// one runner thread's scratch: the gather of the device path, the bytes of the host path
-struct SlsScratch {
+// one runner thread's scratch: the gather of the device path, the head, the bytes of the host path
+struct JsonlScratch {
     std::vector<const uint8_t*> linePtr;
     std::vector<uint32_t> lineLen, time;
-    std::vector<int32_t> timeNs;
-    std::vector<uint8_t> status, bytes;
+    std::vector<uint8_t> status, head, bytes;
 };
-thread_local SlsScratch tlsScratch;
+thread_local JsonlScratch tlsScratch;
 
-void putVarint(std::vector<uint8_t>& out, uint32_t v) {
-    while (v >= 0x80u) {
-        out.push_back(uint8_t(v | 0x80u));
-        v >>= 7;
+// the group's head into `head`; false (bounded only): beyond LC_JSONL_MAX_HEAD_BYTES, which the device path does not take
+bool groupHead(const PipelineEventGroup& group, std::vector<uint8_t>& head, bool bounded) {
+    std::vector<const char*> kp, vp;
+    std::vector<uint32_t> kl, vl;
+    for (const auto& kv : group.GetTags()) {
+        kp.push_back(kv.first.data());
+        kl.push_back(uint32_t(kv.first.size()));
+        vp.push_back(kv.second.data());
+        vl.push_back(uint32_t(kv.second.size()));
     }
-    out.push_back(uint8_t(v));
+    size_t need = 0;
+    (void)lc_jsonl_head(kp.data(), kl.data(), vp.data(), vl.data(), uint32_t(kp.size()), nullptr, 0, &need);
+    if (bounded && need > LC_JSONL_MAX_HEAD_BYTES) return false;
+    head.resize(need);
+    return lc_jsonl_head(kp.data(), kl.data(), vp.data(), vl.data(), uint32_t(kp.size()), head.data(), head.size(), &need) == LC_OK;
 }
-size_t stringSize(size_t n) { return 1 + lcsls::varintSize(uint32_t(n)) + n; }
 
-// the two passes of SLSEventGroupSerializer over the log events of a group as they are (CalculateLogEventSize + SerializeLogEvent)
-void writeLogEvents(const PipelineEventGroup& group, bool enableNs, std::vector<uint8_t>& bytes) {
+// JsonEventGroupSerializer over the log events of a group as they are; an event that is not a log event is skipped
+void writeLogEvents(const PipelineEventGroup& group, std::vector<uint8_t>& bytes) {
     bytes.clear();
+    std::vector<uint8_t> head;
+    if (!groupHead(group, head, false)) return;
     for (const PipelineEventPtr& e : group.GetEvents()) {
         if (!e.Is<LogEvent>()) continue;
         const LogEvent& ev = e.Cast<LogEvent>();
         if (ev.Empty()) continue;
-        const bool ns = enableNs && ev.GetTimestampNanosecond();
-        size_t logSZ = 6 + (ns ? 5 : 0);
+        bytes.insert(bytes.end(), head.begin(), head.end());
+        const std::string t = std::to_string(uint32_t(ev.GetTimestamp()));
+        bytes.insert(bytes.end(), t.begin(), t.end());
         for (const auto& kv : ev) {
-            const size_t inner = stringSize(kv.first.size()) + stringSize(kv.second.size());
-            logSZ += 1 + lcsls::varintSize(uint32_t(inner)) + inner;
+            bytes.push_back(',');
+            bytes.push_back('"');
+            lcjsonl::appendEscaped(bytes, reinterpret_cast<const uint8_t*>(kv.first.data()), kv.first.size());
+            bytes.push_back('"');
+            bytes.push_back(':');
+            bytes.push_back('"');
+            lcjsonl::appendEscaped(bytes, reinterpret_cast<const uint8_t*>(kv.second.data()), kv.second.size());
+            bytes.push_back('"');
         }
-        bytes.push_back(0x0A);
-        putVarint(bytes, uint32_t(logSZ));
-        bytes.push_back(0x08);
-        const uint32_t t = uint32_t(ev.GetTimestamp());
-        putVarint(bytes, t < lcsls::kMinLogTime ? lcsls::kMinLogTime : t);
-        for (const auto& kv : ev) {
-            bytes.push_back(0x12);
-            putVarint(bytes, uint32_t(stringSize(kv.first.size()) + stringSize(kv.second.size())));
-            bytes.push_back(0x0A);
-            putVarint(bytes, uint32_t(kv.first.size()));
-            bytes.insert(bytes.end(), kv.first.begin(), kv.first.end());
-            bytes.push_back(0x12);
-            putVarint(bytes, uint32_t(kv.second.size()));
-            bytes.insert(bytes.end(), kv.second.begin(), kv.second.end());
-        }
-        if (ns) {
-            bytes.push_back(0x25);
-            const uint32_t v = *ev.GetTimestampNanosecond();
-            for (int j = 0; j < 4; ++j) bytes.push_back(uint8_t(v >> (8 * j)));
-        }
+        bytes.push_back('}');
+        bytes.push_back('\n');
     }
 }
 }  // namespace
 
-bool ProcessorSlsGpu::Init(const lcjson::Value& config, std::string& error) {
+bool ProcessorJsonlGpu::Init(const lcjson::Value& config, std::string& error) {
     if (!mParse.Init(config, error)) return false;
     if (!ParseProbe::serves(mParse)) return true;
     std::vector<std::string> keys;
@@ -104,32 +102,30 @@ bool ProcessorSlsGpu::Init(const lcjson::Value& config, std::string& error) {
     }
     char err[256];
     // (a plan beyond its bounds is refused: the processor then takes its host path for every group)
-    if (lc_sls_plan_create(keyPtr.data(), keyLen.data(), uint32_t(keys.size()), items[0].data(), uint32_t(items[0].size() / 2), items[1].data(),
-                           uint32_t(items[1].size() / 2), &mPlan, err, sizeof err) != LC_OK)
+    if (lc_jsonl_plan_create(keyPtr.data(), keyLen.data(), uint32_t(keys.size()), items[0].data(), uint32_t(items[0].size() / 2), items[1].data(),
+                             uint32_t(items[1].size() / 2), &mPlan, err, sizeof err) != LC_OK)
         mPlan = nullptr;
     return true;
 }
 
 // the groups ProcessorPipelineGpu::ProcessFused would serve
-bool ProcessorSlsGpu::DevicePathServes(const PipelineEventGroup& group) const {
+bool ProcessorJsonlGpu::DevicePathServes(const PipelineEventGroup& group) const {
     if (!mPlan || mParse.AlarmsWanted()) return false;
     for (const PipelineEventPtr& e : group.GetEvents()) {
         if (!e.Is<LogEvent>()) return false;
         const LogEvent& ev = e.Cast<LogEvent>();
         if (ev.Size() != 1 || !ev.HasContent(mParse.mSourceKey)) return false;
-        if (ev.GetTimestampNanosecond() && *ev.GetTimestampNanosecond() > 0x7FFFFFFFu) return false;
     }
     return true;
 }
 
-int ProcessorSlsGpu::SerializeOnDevice(PipelineEventGroup& group, bool enableNs, const uint8_t** out, size_t* outLen, bool* undecided) {
-    SlsScratch& S = tlsScratch;
+int ProcessorJsonlGpu::SerializeOnDevice(PipelineEventGroup& group, const uint8_t** out, size_t* outLen, bool* undecided) {
+    JsonlScratch& S = tlsScratch;
     const EventsContainer& events = group.GetEvents();
     const uint32_t n = uint32_t(events.size());
     S.linePtr.resize(n);
     S.lineLen.resize(n);
     S.time.resize(n);
-    S.timeNs.resize(n);
     S.status.resize(n);
     for (uint32_t i = 0; i < n; ++i) {
         const LogEvent& ev = events[i].Cast<LogEvent>();
@@ -137,10 +133,9 @@ int ProcessorSlsGpu::SerializeOnDevice(PipelineEventGroup& group, bool enableNs,
         S.linePtr[i] = reinterpret_cast<const uint8_t*>(raw.data());
         S.lineLen[i] = uint32_t(raw.size());
         S.time[i] = uint32_t(ev.GetTimestamp());
-        S.timeNs[i] = ev.GetTimestampNanosecond() ? int32_t(*ev.GetTimestampNanosecond()) : -1;
     }
-    const int rc = lc_sls_match_encode_host(mPlan, mParse.mReg, S.linePtr.data(), S.lineLen.data(), n, S.time.data(), S.timeNs.data(), enableNs ? 1 : 0,
-                                            out, outLen, nullptr, S.status.data());
+    const int rc = lc_jsonl_match_encode_host(mPlan, mParse.mReg, S.linePtr.data(), S.lineLen.data(), n, S.time.data(), S.head.data(),
+                                              uint32_t(S.head.size()), out, outLen, nullptr, S.status.data());
     if (rc != LC_OK) {
         mParse.ReportDeviceFailure(rc, n);
         mParse.mDeviceFailedEventsTotal += n;
@@ -165,10 +160,11 @@ int ProcessorSlsGpu::SerializeOnDevice(PipelineEventGroup& group, bool enableNs,
     return LC_OK;
 }
 
-// the parser's own Process on a copy of the events (views into the same buffers), then the two passes of SLSEventGroupSerializer
-void ProcessorSlsGpu::SerializeOnHost(PipelineEventGroup& group, bool enableNs, const uint8_t** out, size_t* outLen) {
+// the parser's own Process on a copy of the events (views into the same buffers), then the host writer
+void ProcessorJsonlGpu::SerializeOnHost(PipelineEventGroup& group, const uint8_t** out, size_t* outLen) {
     PipelineEventGroup copy(std::make_shared<SourceBuffer>());
     for (const auto& kv : group.GetAllMetadata()) copy.SetMetadataNoCopy(kv.first, kv.second);
+    for (const auto& kv : group.GetTags()) copy.SetTag(kv.first.to_string(), kv.second.to_string());
     for (const PipelineEventPtr& e : group.GetEvents()) {
         if (e.Is<LogEvent>()) {
             const LogEvent& ev = e.Cast<LogEvent>();
@@ -183,19 +179,19 @@ void ProcessorSlsGpu::SerializeOnHost(PipelineEventGroup& group, bool enableNs, 
         }
     }
     mParse.Process(copy);
-    writeLogEvents(copy, enableNs, tlsScratch.bytes);
+    writeLogEvents(copy, tlsScratch.bytes);
     *out = tlsScratch.bytes.data();
     *outLen = tlsScratch.bytes.size();
 }
 
-int ProcessorSlsGpu::Serialize(PipelineEventGroup& group, bool enableNs, const uint8_t** out, size_t* outLen, int* fused) {
+int ProcessorJsonlGpu::Serialize(PipelineEventGroup& group, const uint8_t** out, size_t* outLen, int* fused) {
     *out = nullptr;
     *outLen = 0;
     *fused = 0;
     if (group.GetEvents().empty()) return LC_OK;
-    if (DevicePathServes(group)) {
+    if (DevicePathServes(group) && groupHead(group, tlsScratch.head, true)) {
         bool undecided = false;
-        const int rc = SerializeOnDevice(group, enableNs, out, outLen, &undecided);
+        const int rc = SerializeOnDevice(group, out, outLen, &undecided);
         if (rc != LC_OK) {
             ++mFailedTrips;
             *out = nullptr;
@@ -210,7 +206,7 @@ int ProcessorSlsGpu::Serialize(PipelineEventGroup& group, bool enableNs, const u
         }
     }
     const uint64_t failedBefore = mParse.mDeviceFailedEventsTotal;
-    SerializeOnHost(group, enableNs, out, outLen);
+    SerializeOnHost(group, out, outLen);
     if (mParse.mDeviceFailedEventsTotal != failedBefore) {  // the parser's trip failed: its events went on unparsed, nothing to hand out
         ++mFailedTrips;
         *out = nullptr;
@@ -224,17 +220,16 @@ int ProcessorSlsGpu::Serialize(PipelineEventGroup& group, bool enableNs, const u
 
 }  // namespace logtail
 
-struct lc_sls_processor {
-    logtail::ProcessorSlsGpu impl;
+struct lc_jsonl_processor {
+    logtail::ProcessorJsonlGpu impl;
 };
 
-extern "C" int lc_sls_processor_create(const char* config_json, lc_sls_processor_t** out, char* err, size_t errcap) {
+extern "C" int lc_jsonl_processor_create(const char* config_json, lc_jsonl_processor_t** out, char* err, size_t errcap) {
     return logtail::createHandle(config_json, out, err, errcap);
 }
-extern "C" void lc_sls_processor_destroy(lc_sls_processor_t* p) { delete p; }
+extern "C" void lc_jsonl_processor_destroy(lc_jsonl_processor_t* p) { delete p; }
 
-extern "C" int lc_sls_processor_serialize(lc_sls_processor_t* p, lc_event_group_t* group, int enable_ns, const uint8_t** out, size_t* out_len,
-                                          int* fused) {
+extern "C" int lc_jsonl_processor_serialize(lc_jsonl_processor_t* p, lc_event_group_t* group, const uint8_t** out, size_t* out_len, int* fused) {
     if (!p || !group || !out || !out_len || !fused) return LC_ERR_ARG;
     logtail::PipelineEventGroup& g = *static_cast<logtail::PipelineEventGroup*>(lc_group_native(group));
     // a group that needs the device must not be half-processed when there is none: check first, fail loudly (lc_processor_process)
@@ -242,19 +237,19 @@ extern "C" int lc_sls_processor_serialize(lc_sls_processor_t* p, lc_event_group_
         for (const auto& e : g.GetEvents())
             if (e.Is<logtail::LogEvent>() && e.Cast<logtail::LogEvent>().HasContent(p->impl.mParse.mSourceKey)) return LC_ERR_NO_DEVICE;
     }
-    return p->impl.Serialize(g, enable_ns != 0, out, out_len, fused);
+    return p->impl.Serialize(g, out, out_len, fused);
 }
 
-extern "C" int lc_sls_serialize_group_host(lc_event_group_t* group, int enable_ns, const uint8_t** out, size_t* out_len) {
+extern "C" int lc_jsonl_serialize_group_host(lc_event_group_t* group, const uint8_t** out, size_t* out_len) {
     if (!group || !out || !out_len) return LC_ERR_ARG;
     std::vector<uint8_t>& bytes = logtail::tlsScratch.bytes;
-    logtail::writeLogEvents(*static_cast<logtail::PipelineEventGroup*>(lc_group_native(group)), enable_ns != 0, bytes);
+    logtail::writeLogEvents(*static_cast<logtail::PipelineEventGroup*>(lc_group_native(group)), bytes);
     *out = bytes.data();
     *out_len = bytes.size();
     return LC_OK;
 }
 
-extern "C" int lc_sls_processor_counters(const lc_sls_processor_t* p, uint64_t parse[LC_CNT_COUNT], uint64_t own[LC_SLS_CNT_COUNT]) {
+extern "C" int lc_jsonl_processor_counters(const lc_jsonl_processor_t* p, uint64_t parse[LC_CNT_COUNT], uint64_t own[LC_JSONL_CNT_COUNT]) {
     if (!p || !parse || !own) return LC_ERR_ARG;
     for (int i = 0; i < LC_CNT_COUNT; ++i) parse[i] = 0;
     const logtail::ProcessorParseRegexGpu& parser = p->impl.mParse;
@@ -265,9 +260,9 @@ extern "C" int lc_sls_processor_counters(const lc_sls_processor_t* p, uint64_t p
     parse[LC_CNT_COMPLEXITY_EXCEEDED] = parser.mComplexityExceededEventsTotal;
     parse[LC_CNT_UNDECIDED_EVENTS] = parser.mUndecidedEventsTotal;
     parse[LC_CNT_DEVICE_FAILED_EVENTS] = parser.mDeviceFailedEventsTotal;
-    own[LC_SLS_CNT_GROUPS_DEVICE] = p->impl.mGroupsDevice;
-    own[LC_SLS_CNT_GROUPS_HOST] = p->impl.mGroupsHost;
-    own[LC_SLS_CNT_FAILED_TRIPS] = p->impl.mFailedTrips;
-    own[LC_SLS_CNT_BYTES] = p->impl.mBytes;
+    own[LC_JSONL_CNT_GROUPS_DEVICE] = p->impl.mGroupsDevice;
+    own[LC_JSONL_CNT_GROUPS_HOST] = p->impl.mGroupsHost;
+    own[LC_JSONL_CNT_FAILED_TRIPS] = p->impl.mFailedTrips;
+    own[LC_JSONL_CNT_BYTES] = p->impl.mBytes;
     return LC_OK;
 }

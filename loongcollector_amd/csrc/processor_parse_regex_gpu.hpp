@@ -58,6 +58,8 @@ class ProcessorSlsGpu;
 class ProcessorParseRegexGpu {
     friend class ProcessorPipelineGpu;  // the fused split -> parse -> filter trip stitches with this class's own code
     friend class ProcessorSlsGpu;       // processor_sls_gpu.cpp (liblc_sls.so) reads its plan off a probe event stitched by it
+    friend class ProcessorJsonlGpu;     // processor_jsonl_gpu.cpp (liblc_jsonl.so): the same
+    friend struct ParseProbe;           // parse_probe_items.hpp: the probe events of those two
 
 public:
     static const std::string sName;  // "processor_parse_regex_gpu" (new Type name; static names win in PluginRegistry)
