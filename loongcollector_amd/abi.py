@@ -409,6 +409,20 @@ JSONL_PROTOTYPES = {
     "lc_jsonl_processor_counters": (i32, [vp, P(u64), P(u64)]),
 }
 
+# liblc_strrep.so (include/strrep/lc_strrep.h): the same again for the string-replace processor; tests/test_strrep_abi.py holds it to its
+# header and exports
+STRREP_PROTOTYPES = {
+    "lc_strrep_create": (i32, [cp, sz, P(vp), cp, sz]),
+    "lc_strrep_free": (None, [vp]),
+    "lc_strrep_apply_device": (i32, [vp, vp, vp, u32, vp, vp, vp, u64, P(u64), vp]),
+    "lc_strrep_apply_host": (i32, [vp, vp, vp, u32, vp, vp, P(vp)]),
+    "lc_strrep_process_logs_json": (i32, [vp, cp, sz, P(vp)]),
+    "lc_strrep_free_string": (None, [vp]),
+    "lc_strrep_counters": (i32, [vp, P(u64)]),
+    "lc_strrep_set_alarm_sink": (None, [vp, vp, vp]),
+    "lc_strrep_thread_release": (None, []),
+}
+
 
 def bind(L, extra=None):
     """restype / argtypes of every table entry (and of `extra`, a table of the same form) that L exports; -> L"""
