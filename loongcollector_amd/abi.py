@@ -423,6 +423,21 @@ STRREP_PROTOTYPES = {
     "lc_strrep_thread_release": (None, []),
 }
 
+# liblc_codec.so (include/codec/lc_codec.h): the same again for the field codecs (base64 encode / decode, MD5); tests/test_codec_abi.py
+# holds it to its header and exports
+CODEC_PROTOTYPES = {
+    "lc_codec_create": (i32, [cp, sz, P(vp), cp, sz]),
+    "lc_codec_free": (None, [vp]),
+    "lc_codec_apply_device": (i32, [vp, vp, vp, u32, vp, vp, vp, vp, vp, u64, P(u64), vp]),
+    "lc_codec_apply_host": (i32, [vp, vp, vp, u32, vp, vp, vp, vp, P(vp)]),
+    "lc_codec_set_trip_bytes": (u64, [sz]),
+    "lc_codec_process_logs_json": (i32, [vp, cp, sz, P(vp)]),
+    "lc_codec_free_string": (None, [vp]),
+    "lc_codec_counters": (i32, [vp, P(u64)]),
+    "lc_codec_set_alarm_sink": (None, [vp, vp, vp]),
+    "lc_codec_thread_release": (None, []),
+}
+
 
 def bind(L, extra=None):
     """restype / argtypes of every table entry (and of `extra`, a table of the same form) that L exports; -> L"""

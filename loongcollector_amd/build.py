@@ -39,7 +39,10 @@ JSONL_SOURCES = ["jsonl_device.hip", "jsonl_plan.cpp", "processor_jsonl_gpu.cpp"
 # the string-replace processor (include/strrep/lc_strrep.h): an eighth library, linked against the main one as the anchor processor's is
 LIB_STRREP = os.path.join(LIBDIR, "liblc_strrep.so")
 STRREP_SOURCES = ["strrep_device.hip", "processor_string_replace_gpu.cpp"]
-SIDE_SOURCES = KV_SOURCES + CSV_SOURCES + SLS_SOURCES + ANCHOR_SOURCES + LZ4_SOURCES + JSONL_SOURCES + STRREP_SOURCES
+# the field codecs (include/codec/lc_codec.h: base64 encode / decode, MD5): a ninth library, linked against the main one
+LIB_CODEC = os.path.join(LIBDIR, "liblc_codec.so")
+CODEC_SOURCES = ["codec_device.hip", "processor_codec_gpu.cpp"]
+SIDE_SOURCES = KV_SOURCES + CSV_SOURCES + SLS_SOURCES + ANCHOR_SOURCES + LZ4_SOURCES + JSONL_SOURCES + STRREP_SOURCES + CODEC_SOURCES
 
 SOURCES = ["regex_parse.cpp", "atomic_elide.cpp", "follow_nfa.cpp", "tdfa.cpp", "table_cache.cpp", "screen_dfa.cpp", "bt_program.cpp", "regex_handle.cpp", "gpu_runtime.hip", "grok_device.hip", "multiline_device.hip", "delim_device.hip", "strptime_program.cpp", "timestamp_device.hip", "json_device.hip", "apsara_device.hip", "clog_device.hip", "desens_device.hip", "prom_device.hip"]
 OPTIONAL_SOURCES = ["event_model.cpp", "processor_parse_regex_gpu.cpp", "grok.cpp", "grok_literal_index.cpp", "processor_grok_gpu.cpp", "processor_filter_gpu.cpp", "processor_go_regex_gpu.cpp", "multiline_gpu.cpp", "multiline_events.cpp", "processor_pipeline_gpu.cpp", "processor_parse_delimiter_gpu.cpp", "processor_parse_timestamp_gpu.cpp", "processor_parse_json_gpu.cpp", "processor_parse_apsara_gpu.cpp", "processor_parse_container_log_gpu.cpp", "processor_desensitize_gpu.cpp", "processor_parse_prom_gpu.cpp", "c_processor_slot.cpp"]
@@ -65,7 +68,8 @@ def sources():
 
 def needs_build():
     if not os.path.exists(LIB) or not os.path.exists(LIB_KV) or not os.path.exists(LIB_CSV) or not os.path.exists(LIB_SLS) or \
-            not os.path.exists(LIB_ANCHOR) or not os.path.exists(LIB_LZ4) or not os.path.exists(LIB_JSONL) or not os.path.exists(LIB_STRREP):
+            not os.path.exists(LIB_ANCHOR) or not os.path.exists(LIB_LZ4) or not os.path.exists(LIB_JSONL) or not os.path.exists(LIB_STRREP) or \
+            not os.path.exists(LIB_CODEC):
         return True
     t = os.path.getmtime(LIB)
     deps = [os.path.join(CSRC, f) for f in os.listdir(CSRC)]
@@ -88,6 +92,7 @@ def needs_build():
     deps.append(os.path.join(HERE, "..", "include", "lz4", "lc_lz4.h"))
     deps.append(os.path.join(HERE, "..", "include", "jsonl", "lc_jsonl.h"))
     deps.append(os.path.join(HERE, "..", "include", "strrep", "lc_strrep.h"))
+    deps.append(os.path.join(HERE, "..", "include", "codec", "lc_codec.h"))
     deps.append(os.path.join(HERE, "data", "grok_default_patterns.txt"))
     return any(os.path.exists(d) and os.path.getmtime(d) > t for d in deps)
 
@@ -166,8 +171,9 @@ def build_native(force=False, verbose=False, force_sources=()):
     lz4_objs = [o for o in objs if os.path.basename(o)[:-2] in LZ4_SOURCES]
     jsonl_objs = [o for o in objs if os.path.basename(o)[:-2] in JSONL_SOURCES]
     strrep_objs = [o for o in objs if os.path.basename(o)[:-2] in STRREP_SOURCES]
+    codec_objs = [o for o in objs if os.path.basename(o)[:-2] in CODEC_SOURCES]
     objs = [o for o in objs if o not in kv_objs and o not in csv_objs and o not in sls_objs and o not in anchor_objs and o not in lz4_objs
-            and o not in jsonl_objs and o not in strrep_objs]
+            and o not in jsonl_objs and o not in strrep_objs and o not in codec_objs]
     # (the SONAME: liblc_kvsplit.so names this library as needed, and a process that has it loaded already -- from a file a later build has
     # replaced -- must get THAT copy, not a second one)
     cmd = [_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,-soname,liblc_regex_gpu.so", "-o", LIB] + objs
@@ -185,6 +191,8 @@ def build_native(force=False, verbose=False, force_sources=()):
     subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_JSONL] + jsonl_objs +
                           ["-L" + LIBDIR, "-llc_regex_gpu", "-Wl,-rpath,$ORIGIN"])
     subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_STRREP] + strrep_objs +
+                          ["-L" + LIBDIR, "-llc_regex_gpu", "-Wl,-rpath,$ORIGIN"])
+    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB_CODEC] + codec_objs +
                           ["-L" + LIBDIR, "-llc_regex_gpu", "-Wl,-rpath,$ORIGIN"])
     # the reference-shaped variant: only the host translation units that see the event model are compiled again (with the switch);
     # the regex compilers and every gfx950 object are the ones just linked above
